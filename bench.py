@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- layered-model dispersion forward solves/sec (20 periods) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload forward|grid|mcmc|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload forward|grid|mcmc|c5] [--dump-outputs DIR]
     (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+--dump-outputs DIR (forward headline only): after the timed region, rank 0 writes what the LAST timed step returned to its
+caller (BatchPlan.run -> c, u, status of rank 0's whole batch, 65 536 x 20) as DIR/c.npy, DIR/u.npy (float32, km/s) and
+DIR/status.npy (the int32 status codes as float32), 10.7 MB in all.  The inputs are seeded (synth.synth_models, seed = rank),
+so two builds run with the same arguments can be compared output for output.
 
 Default workload `forward` (BASELINE.json configs[1], the configuration the metric is quoted on): a batch of
 65 536 MCMC-perturbed 10-layer stacks per GPU, Rayleigh phase + group velocity at 20 periods, synthetic inputs of
@@ -104,6 +109,26 @@ def cpu_baseline(per, c_gpu, u_gpu):
 
 
 # ------------------------------------------------------------------------------------------------ helpers
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tensors):
+    """{name: device tensor} -> out_dir/<name>.npy: floating arrays as float32, integer codes as float32 (exact below
+    2**24).  Called outside every timed region."""
+    arrays = {}
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        if not np.issubdtype(a.dtype, np.floating):
+            assert np.abs(a).max(initial=0) < (1 << 24), f"{name}: integer codes not exact in float32"
+        arrays[name] = a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment: this process is only a launcher.  It
     starts N rank processes through torch.distributed.run (one per GPU, 127.0.0.1 rendezvous on a free port) as a CHILD
@@ -313,6 +338,9 @@ def workload_forward(rt, args):
     steps(args.steps, NFLIGHT)                             # THE timed region of `value`
     rt.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:                    # before the fast-scan region below reuses the plans
+        last = plans[(args.steps - 1) % NFLIGHT]
+        dump_outputs(args.dump_outputs, {"c": last.c, "u": last.u, "status": last.status})
     # beside the headline: the same workload with the opt-in count-guided scan (SURFDISP_FASTSCAN, include/surfdisp.h)
     steps(args.warmup, NFLIGHT, fast_scan=True)
     rt.barrier()
@@ -639,7 +667,13 @@ def main():
                          "configs[3]) x 50 chains is dealt to the ranks in contiguous blocks (1 GPU: all of it, 8 GPUs: 512 "
                          "points each); every point has the same observations and every chain the same random stream whatever "
                          "the rank count.  0 (default): weak scaling, 512 points per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="forward headline: write what the last timed step returned (rank 0's c, u, status) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in ("all", "forward"):
+        ap.error("--dump-outputs writes the forward headline's outputs: use --workload forward or all")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # self-launch: this process stays a plain launcher (no torch, no HIP); see launch_ranks

@@ -95,3 +95,37 @@ def test_strong_scaling_grid_leg_on_one_gpu():
         assert d["scaling"] == "strong" and d["n_gpus"] == n and d["config"]["total_points"] == 128
         assert d["config"]["points_per_gpu"] == 128 // n and d["config"]["chains_per_gpu"] == 128 // n * 8
         assert abs(d["value"] - 128 * 8 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 1e-6
+
+
+def test_bench_rejects_zero_steps_and_a_dump_of_a_side_leg(tmp_path):
+    for extra in (("--steps", "0"), ("--workload", "grid", "--dump-outputs", str(tmp_path))):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *extra],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr[-2000:])
+    assert not os.listdir(tmp_path)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step():
+    """`bench.py --workload forward --dump-outputs DIR`: the line counts exactly --steps timed steps, and DIR holds what the
+    last one returned - c, u, status of rank 0's whole seeded batch, float32 - which the CPU oracle reproduces."""
+    import tempfile
+    import numpy as np
+    from oracle import cport
+    from pysurfinv_amd import synth
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "forward", "--steps", "2",
+                            "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", d], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        out = {n: np.load(os.path.join(d, f"{n}.npy")) for n in ("c", "u", "status")}
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 65536 * 2 / (line["ms_per_step"] * 2e-3)) / line["value"] < 1e-6
+    assert out["c"].shape == out["u"].shape == (65536, 20) and out["status"].shape == (65536,)
+    assert all(a.dtype == np.float32 for a in out.values())
+    assert (out["status"] >= 0).all() and (out["status"] == np.round(out["status"])).all()
+    n = 256
+    co, uo, _ = cport.forward_batch(synth.synth_models(65536, 10, seed=0)[:n], synth.default_periods(20), 2, nthreads=4)
+    assert np.array_equal(out["c"][:n] > 0, co > 0)
+    ok = co > 0
+    assert np.abs(out["c"][:n][ok] / co[ok] - 1).max() < 1e-4 and np.abs(out["u"][:n][ok] / uo[ok] - 1).max() < 1e-4
