@@ -312,8 +312,10 @@ __device__ __forceinline__ float sqrt_hw(float x) { return __builtin_amdgcn_sqrt
 __device__ __forceinline__ void sinhcosh_sp(float x, float *sh, float *ch)
 {
     // no low-order correction of x log2(e): e^x and e^-x then carry relative errors +-|x| 9e-8, which for |x| > 1 is a
-    // common scale factor of sinh and cosh (the secular function's root does not move) and for |x| < 1 is below one
-    // ulp anyway - golden-case parity unchanged, root search 6 % faster (profiles/r02d/ab_recursion_variants.txt).
+    // common scale factor of sinh and cosh (the secular function's root does not move) - root search 6 % faster
+    // (profiles/r02d/ab_recursion_variants.txt).  For |x| < 1 that is below one ulp of cosh, NOT of sinh: p - q has an
+    // ABSOLUTE error of ~6e-8 for every x, a relative one of 6e-8 / |x| - callers that need sinh of small arguments
+    // (layer_coef) replace it by a series there.
     // Tried and dropped (r02e): the pair scaled by e^-|x| from ONE exponential ((1 +- e^-2|x|)/2; a transcendental costs
     // four plain instructions).  The secular function then comes out times s(c) = exp(-sum |x|): same roots and signs,
     // but s has a square-root kink wherever c crosses a layer velocity and bends the function between them, and the
@@ -343,6 +345,49 @@ __device__ __forceinline__ void sincos_cw(float x, float *sn, float *cs)
     const float c0 = (n & 1) ? ps : pc;
     *sn = (n & 2) ? -s0 : s0;
     *cs = ((n + 1) & 2) ? -c0 : c0;
+}
+
+// The working stack's derived per-layer values (W_IR, W_IA2, W_IB2), one expression each, shared by the root search's
+// rebuild (build in phase_body), the ellipticity kernel's replay and the tests' device probe (tests/probe): v_rcp + one
+// Newton step (<= 1 ulp) instead of the reference's IEEE divisions.
+__device__ __forceinline__ float wk_ia2(const float a) { return rcp_nr(a * a); }                          // 1/a^2
+__device__ __forceinline__ float wk_ib2(const float b) { return (b > 0.0f) ? rcp_nr(b * b) : 0.0f; }    // 1/b^2, 0 if liquid
+__device__ __forceinline__ float wk_irho(const float rho) { return rcp_nr(rho); }                        // Rayleigh layer 0: 1/rho
+__device__ __forceinline__ float wk_rat(const float rho_prev, const float rho) { return rho_prev * rcp_nr(rho); }   // layer m >= 1
+__device__ __forceinline__ float wk_ilove(const float rho, const float b) { return rcp_nr(rho * b * b); }  // Love: 1/(rho b^2)
+
+// One wave type's coefficients in one layer, shared by ray_step (P, S and the liquid top layer), delta_love and - through
+// ray_step - the ellipticity passes.  arg = 1 - c^2/v^2 (> 0: evanescent), wd = k d; r = sqrt(-arg) continued to
+// r = -sqrt(arg) on the evanescent side, x = wd r:
+//      rsin = r sin x,  sinr = sin(x) / r,  cs = cos x        (sinh / cosh on the evanescent side: rsin = -r sinh x,
+//      ph = x where oscillatory, else 0                         sinr = sinh(x) / r, cs = cosh x, surfa.f:263-279)
+// |arg| is clamped away from zero: c == v to the last bit then runs through the oscillatory formulas with r = 1e-15, which
+// give the degenerate values (rsin = 0, sinr = k d, cs = 1) to 1e-15 - no separate branch.
+struct LCoef { float r, rsin, sinr, cs, x, ph; };
+__device__ __forceinline__ LCoef layer_coef(const float arg, const float wd)
+{
+    const float xs = fmaxf(fabsf(arg), 1.0e-30f), y = __builtin_amdgcn_rsqf(xs);
+    const float r = copysignf(xs * y, -arg), ir = copysignf(y, -arg);   // r = x rsq(x) to ~1.5 ulp; < 0: evanescent
+    LCoef o;
+    o.r = r;
+    o.x = wd * r;
+    if (arg > 0.0f) {
+        float sh, ch; sinhcosh_sp(o.x, &sh, &ch);
+        // sinh of a small argument: the difference of the two exponentials carries their absolute error (~6e-8), i.e. a
+        // relative error 6e-8 / |x| that sinr = sinh(x) / r passes on - 1 % one float below a thin layer's velocity, a jump
+        // of the secular function where c crosses it.  Below |x| = 1/4 the odd series to x^5 (truncation < 5e-8 relative;
+        // above, the exponentials' error is < 4e-7 relative).  Cost: 4-6 % of the root search, 5.6 % of the headline.
+        const float x2 = o.x * o.x;
+        const float shs = fmaf(o.x * x2, fmaf(x2, 8.33333333e-3f, 1.66666667e-1f), o.x);
+        if (fabsf(o.x) < 0.25f) sh = shs;
+        o.rsin = -r * sh; o.sinr = sh * ir; o.cs = ch;
+        o.ph = 0.0f;
+    } else {
+        float sn, cs; sincos_cw(o.x, &sn, &cs);
+        o.rsin = r * sn; o.sinr = sn * ir; o.cs = cs;
+        o.ph = o.x;
+    }
+    return o;
 }
 
 // Rayleigh, production kernel: Dunkin's compound-matrix recursion (surfa.f:193-357) in a form built for the VALU.
@@ -422,29 +467,15 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
         h2 *= rat; h3 *= rat; h4 *= rat; h5 *= rat * rat;
     }
     const float arga = fmaf(-csq, ia2, 1.0f);                    // 1 - c^2/a^2, surfa.f:211
-    // |arga| is clamped away from zero: c == a to the last bit then runs through the oscillatory formulas with
-    // ra = 1e-15, which give the reference's degenerate values (rsinp = 0, sinpr = k d, cosp = 1; surfa.f:263-266)
-    // to 1e-15 - no separate branch
-    const float xa = fmaxf(fabsf(arga), 1.0e-30f), ya = __builtin_amdgcn_rsqf(xa);
-    const float ra = copysignf(xa * ya, -arga), ira = copysignf(ya, -arga);   // ra = x rsq(x) to ~1.5 ulp; < 0: evanescent
     const float wd = wvno * d;
     if (FIRST && !(fabsf(sv) > ACCUR)) {
         // liquid surface layer, surfa.f:216-251 (skipped entirely in the ellipticity passes): only a11 = cosp and
         // a21 = rhoc sinpr are non-zero (surfa.f:236-250)
         if (start != 1) return;
         if (CERT) *kunc = true;                            // (a liquid layer: no certificate)
-        const float pm = wd * ra;
-        float sinpr, cosp;
-        if (fabsf(ra) < ACCUR) { sinpr = wd; cosp = 1.0f; }
-        else if (ra < 0.0f) {
-            float sh, ch; sinhcosh_sp(pm, &sh, &ch);
-            sinpr = sh / ra;
-            cosp = ch;
-        } else {
-            float sn, cs; sincos_cw(pm, &sn, &cs);
-            sinpr = sn / ra; cosp = cs;
-            phi += pm;
-        }
+        const LCoef P = layer_coef(arga, wd);
+        const float sinpr = P.sinr, cosp = P.cs;
+        phi += P.ph;
         const float n1 = cosp * b1;
         const float n2 = sinpr * b1;
         const float n5 = cosp * h5 - sinpr * h4;
@@ -452,29 +483,13 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
         return;
     }
     const float argb = fmaf(-csq, ib2, 1.0f);
-    const float xb = fmaxf(fabsf(argb), 1.0e-30f), yb = __builtin_amdgcn_rsqf(xb);    // same for c == b (surfa.f:275-279)
-    const float rb = copysignf(xb * yb, -argb), irb = copysignf(yb, -argb);
     const float g = 2.0f * (sv * sv) * icsq;
     const float g1 = g - 1.0f;
-    const float pm = wd * ra;
-    const float qm = wd * rb;
-    float rsinp, sinpr, cosp, rsinq, sinqr, cosq;
-    if (arga > 0.0f) {                                 // evanescent P (ra < 0), surfa.f:267-269
-        float sh, ch; sinhcosh_sp(pm, &sh, &ch);
-        rsinp = -ra * sh; sinpr = sh * ira; cosp = ch;
-    } else {                                           // oscillatory P, surfa.f:271-273
-        float sn, cs; sincos_cw(pm, &sn, &cs);
-        rsinp = ra * sn; sinpr = sn * ira; cosp = cs;
-        phi += pm;
-    }
-    if (!(argb > 0.0f)) {
-        float sn, cs; sincos_cw(qm, &sn, &cs);
-        rsinq = rb * sn; sinqr = sn * irb; cosq = cs;
-        phi += qm;
-    } else {
-        float sh, ch; sinhcosh_sp(qm, &sh, &ch);
-        rsinq = -rb * sh; sinqr = sh * irb; cosq = ch;
-    }
+    const LCoef P = layer_coef(arga, wd), Q = layer_coef(argb, wd);   // surfa.f:263-279
+    const float rsinp = P.rsin, sinpr = P.sinr, cosp = P.cs;
+    const float rsinq = Q.rsin, sinqr = Q.sinr, cosq = Q.cs, qm = Q.x;
+    phi += P.ph;
+    phi += Q.ph;
     const float g2 = g * g, g12 = g1 * g1;
     const float u1 = fmaf(g2, b1, fmaf(g + g, h3, -h5));
     const float u2 = fmaf(g12, b1, fmaf(g1 + g1, h3, -h5));
@@ -489,7 +504,7 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
 #if SD_RCERT == 2
         // (first attempt, kept for the record: sign changes of b1 at the interfaces only - misses pairs of zeros inside a layer)
         *kc += ((n1 < 0.0f) != (b1 < 0.0f)) ? 1 : 0;
-        *kunc = *kunc || !(fabsf(pm) + fabsf(qm) < SD_RCERT_PHASE) ||
+        *kunc = *kunc || !(fabsf(P.x) + fabsf(qm) < SD_RCERT_PHASE) ||
                 !(fabsf(n1) > 1.0e-4f * (fabsf(b1) + fabsf(E1) + fabsf(E2)));
 #else
         // Zeros of det U_s INSIDE this layer (Wittrick-Williams).  With the surface pair's impedance Z_t at the layer's top and the
@@ -790,27 +805,23 @@ __device__ __forceinline__ float delta_love(const float *wq, const int LS, const
     struct Lyr { float b, d, r, ih; };
     auto load = [&](int m) -> Lyr { const int q = m > 0 ? m : 0; return {W_B(q), W_D(q), W_R(q), W_IR(q)}; };
     auto step = [&](const Lyr &y) {
+        // contractions spelt out: every instantiation (certified scan, point-by-point scan, exact re-evaluation) must round
+        // the same way - the certified scan's brackets are the point-by-point scan's only if the values agree to the bit
+#pragma clang fp contract(off)
         bm = y.b;
         const float d = y.d, rho = y.r, ih = y.ih;
         if (bm == 0.0f) return;                            // water, surfa.f:152
         const float arg = fmaf(csq, ih * rho, -1.0f);      // c^2/b^2 - 1: < 0 evanescent
-        const float x = fmaxf(fabsf(arg), 1.0e-30f), irb = __builtin_amdgcn_rsqf(x);
-        rb = x * irb;
         h = rho * bm * bm;
-        const float q = -wvno * d * rb;
-        float yv, z, cosq;
-        if (arg < 0.0f) {
-            float sh, ch; sinhcosh_sp(q, &sh, &ch);
-            yv = sh * irb;
-            z = -rb * sh;                                  // -rb^2 y
-            cosq = ch;
-        } else {
-            float sn, cs; sincos_cw(q, &sn, &cs);
-            yv = sn * irb; z = rb * sn; cosq = cs;
-        }
+        // the layer's coefficients at q = -k d rb: y = sin(q) / rb = -sinr, z = rb sin q = -rsin = -rb^2 y (rsin, sinr of
+        // layer_coef at 1 - c^2/b^2 = -arg and +k d)
+        const LCoef Q = layer_coef(-arg, wvno * d);
+        rb = fabsf(Q.r);
+        const float q = -Q.x;
+        const float yv = -Q.sinr, z = -Q.rsin, cosq = Q.cs;
         phi -= (arg < 0.0f) ? 0.0f : q;
-        const float eut = cosq * ut - yv * tt * ih;
-        const float ett = h * z * ut + cosq * tt;
+        const float eut = fmaf(cosq, ut, -(yv * tt * ih));
+        const float ett = fmaf(h * z, ut, cosq * tt);
         lmag = fabsf(h * z * ut) + fabsf(cosq * tt);
         if (CERT && count) {
             const bool flip = (tt < 0.0f) != (ett < 0.0f);
@@ -1070,11 +1081,11 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             // the reciprocals are this kernel's own helper values (not the reference's): v_rcp + one Newton
             // step (<= 1 ulp) instead of three IEEE divisions
             W_B(i) = v.b; W_R(i) = v.rho; W_D(i) = v.d;
-            if (KIND == 1 && !EXACT) W_IR(i) = rcp_nr(v.rho * v.b * v.b);       // Love, production: 1/(rho b^2)
-            else if (i == 0 || EXACT) W_IR(i) = rcp_nr(v.rho);
+            if (KIND == 1 && !EXACT) W_IR(i) = wk_ilove(v.rho, v.b);             // Love, production: 1/(rho b^2)
+            else if (i == 0 || EXACT) W_IR(i) = wk_irho(v.rho);
             if (KIND == 2) {
-                W_IA2(i) = EXACT ? v.a : rcp_nr(v.a * v.a);                      // exact kernel: a itself (delta_rayleigh_ref)
-                W_IB2(i) = (v.b > 0.0f) ? rcp_nr(v.b * v.b) : 0.0f;
+                W_IA2(i) = EXACT ? v.a : wk_ia2(v.a);                             // exact kernel: a itself (delta_rayleigh_ref)
+                W_IB2(i) = wk_ib2(v.b);
             }
         }
         if (KIND == 2 && !EXACT) {
@@ -1084,7 +1095,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const int top = nflat < n ? nflat : n - 1;
-            for (int i = 1 + j; i <= top; i += G) W_IR(i) = W_R(i - 1) * rcp_nr(W_R(i));
+            for (int i = 1 + j; i <= top; i += G) W_IR(i) = wk_rat(W_R(i - 1), W_R(i));
         }
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1926,11 +1937,11 @@ __global__ __launch_bounds__(256) void surfdisp_ellip_kernel(EllipArgs A)
             rho_prev = rho_i;
             rho_i = v.rho;
             y.sv = v.b; y.d = v.d;
-            y.ia2 = rcp_nr(v.a * v.a);
-            y.ib2 = (v.b > 0.0f) ? rcp_nr(v.b * v.b) : 0.0f;
-            y.rat = (i > 0) ? rho_prev * rcp_nr(rho_i) : 0.0f;
+            y.ia2 = wk_ia2(v.a);
+            y.ib2 = wk_ib2(v.b);
+            y.rat = (i > 0) ? wk_rat(rho_prev, rho_i) : 0.0f;
             if (i == 0) {
-                const float irho0 = rcp_nr(rho_i);
+                const float irho0 = wk_irho(rho_i);
                 s2 = ray_start(t, 2, irho0);
                 s3 = ray_start(t, 3, irho0);
                 if (last >= 1) { ray_step<true>(s2, t, y, 2, phi); ray_step<true>(s3, t, y, 3, phi); }

@@ -954,8 +954,12 @@ def test_soak_offender_fixture_every_team_size(hip):
     |Delta| ~ 1e20 (the refinement's reciprocals flushed to zero and the bracket's low end came back), and Love overtones
     1e-3 km/s apart (several roots per bracket, invisible to a small team's subdivision).  Every stack whose roots are
     DEFINED by the reference's formulas (its FMA build and two other roundings of exp / flattening agree to 2e-5) must come
-    back on the reference's roots - zero pattern equal, c within 1e-4 - for every team size, and at most one of them may
-    miss for any team size (the soak's residual rate on such stacks is 1e-6)."""
+    back on the reference's roots - zero pattern equal, c within 1e-4 - for every team size, with one named exception:
+    stack 42 (Rayleigh, a 1.3 km water layer over 39 solid layers, periods 4.4 / 66 s).  At 66 s every team size returns
+    3.48345 where the reference and the oracle's variants 1-3 return 3.48513 (4.8e-4): the same value the r03 library
+    returned, and the same before and after the small-argument sinh fix of layer_coef (measured on the GPU), so it is neither
+    a team-size effect nor the velocity-crossing discontinuity; what makes the production recursion land on that value
+    is not established yet."""
     from pysurfinv_amd import _lib
     f = np.load(os.path.join(GOLDEN, "ref_offenders.npz"))
     nst = len(f["nlay"])
@@ -979,4 +983,4 @@ def test_soak_offender_fixture_every_team_size(hip):
             if not ok:
                 bad.setdefault(q, []).append(team)
     assert r03_bad == nst                                      # (the fixture is what it says: every stack was off in r03)
-    assert len(bad) <= 1, bad
+    assert set(bad) <= {42}, bad
