@@ -32,7 +32,8 @@
 extern "C" {
 #endif
 
-#define SURFDISP_ABI_VERSION 4      /* 4 (r04): + SURFDISP_KERN_REFCOORD, surfdisp_workspace_counters, surfdisp_prior_device, surfdisp_mcmc_propose_masked_device; every ABI-3 symbol kept */
+#define SURFDISP_ABI_VERSION 4      /* 4 (r04): + SURFDISP_KERN_REFCOORD, surfdisp_workspace_counters, surfdisp_prior_device, surfdisp_mcmc_propose_masked_device; every ABI-3 symbol kept;
+                                       additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -196,6 +197,31 @@ int surfdisp_forward_kernels_device(void *stream, int B, int Lmax, const int *nl
                                     float *c, float *u, int *status,
                                     float *dcdb, float *dcda, float *dcdr,
                                     void *workspace, size_t workspace_bytes);
+
+/* ---- (5c) ... and the analytic partials of the GROUP velocity (fundamental mode), added within ABI 4.  Differentiating
+ *          U = d omega / dk at fixed omega (Rodi et al. 1975):
+ *              dU/dm = (U/c) (2 - U/c) dc/dm  -  (U/c)^2 d(dc/dm)/d ln T,
+ *          with dc/dm the mean of the phase partials at T (1 - dlnT_frac) and T (1 + dlnT_frac) and d(dc/dm)/d ln T
+ *          their central difference.  After the launches of (5b) - c, u, status, dcdb, dcda, dcdr come out bit-identical
+ *          to surfdisp_forward_kernels_device on the same inputs - every solved (stack, period) unit's root at the two
+ *          shifted periods is found from the first-order prediction c (1 +- dlnT_frac (c/U - 1)) in a bounded window (no
+ *          scan), the phase partials are formed there (attenuation correction and chain factors at the shifted period) and
+ *          combined: dudb / duda / dudr [B][P][Lmax] = dU(period) / d(Vs | Vp | rho) of input layer i, caller's
+ *          coordinates.  The toolkit's own rule (GRV_SENS_KERNEL.f:99-108) is the same except for a wrong sign of the
+ *          frequency term of dU/drho; this library uses the derived sign for all three.
+ *          Rows: zeros where dcdb's row is zero (unsolved periods, bad stacks); every entry NaN for a solved unit whose
+ *          shifted root failed (no bracket within the search budget, more than one sign change in the window, a non-finite
+ *          secular function) - *n_shift_failed (device int, may be NULL) counts those units.  duda, dudr (and dcda, dcdr)
+ *          may be NULL; Love has no duda (zeros if given).  dlnT_frac in [1e-3, 0.05] (0.01: the toolkit's T x 0.99 / 1.01);
+ *          SURFDISP_PHASE_ONLY and SURFDISP_KERN_REFCOORD are rejected (SURFDISP_ERR_INVALID).  Workspace:
+ *          surfdisp_group_kernels_workspace_bytes (that of (5b) plus a second layer-major scratch). */
+size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P);
+int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind, float dlnT_frac,
+                                          float *c, float *u, int *status,
+                                          float *dcdb, float *dcda, float *dcdr,
+                                          float *dudb, float *duda, float *dudr, int *n_shift_failed,
+                                          void *workspace, size_t workspace_bytes);
 
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:
  *          Model1D.seisPropLayers, models.py:72-102 + layers.py:139-284) for models with a static

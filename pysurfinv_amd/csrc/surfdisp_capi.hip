@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <stdint.h>
 #include <atomic>
 #include "surfdisp_internal.h"
 
@@ -273,6 +274,48 @@ size_t surfdisp_kernels_workspace_bytes(int B, int Lmax, int P)
            2 * align_up((size_t)P * B * sizeof(float));
 }
 
+// workspace of surfdisp_forward_group_kernels_device: that of the kernels entry (whose layer-major scratch, free once the
+// phase partials are transposed, takes the T (1 - dfrac) partials), a second scratch for T (1 + dfrac), and per shift and
+// unit the root, ellipticity, group velocity, factor, deepest layer and failure flag
+struct GCarve {
+    float *kscr_p, *ksc, *cs, *ratio, *us, *pers;
+    int *khs;
+    unsigned char *fail;
+    size_t total;
+};
+static GCarve gcarve(void *base, int B, int Lmax, int P)
+{
+    char *p = static_cast<char *>(base);
+    const size_t PB = (size_t)P * B;
+    size_t off = align_up(surfdisp_kernels_workspace_bytes(B, Lmax, P));
+    GCarve g;
+    g.kscr_p = reinterpret_cast<float *>(p + off);  off += align_up((size_t)3 * Lmax * PB * sizeof(float));
+    g.ksc = reinterpret_cast<float *>(p + off);     off += align_up(2 * PB * sizeof(float));
+    g.khs = reinterpret_cast<int *>(p + off);       off += align_up(2 * PB * sizeof(int));
+    g.cs = reinterpret_cast<float *>(p + off);      off += align_up(2 * PB * sizeof(float));
+    g.ratio = reinterpret_cast<float *>(p + off);   off += align_up(2 * PB * sizeof(float));
+    g.us = reinterpret_cast<float *>(p + off);      off += align_up(2 * PB * sizeof(float));
+    g.pers = reinterpret_cast<float *>(p + off);    off += align_up((size_t)2 * P * sizeof(float));
+    g.fail = reinterpret_cast<unsigned char *>(p + off);  off += align_up(2 * PB);
+    g.total = off;
+    return g;
+}
+
+size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    return gcarve(nullptr, B, Lmax, P).total;
+}
+
+// developer / test read-out (not in include/surfdisp.h): byte offset, inside that workspace, of the shifted roots
+// [2][P][B] (float; T (1 - dfrac) first) of the last surfdisp_forward_group_kernels_device call on it
+size_t surfdisp_group_kernels_shift_offset(int B, int Lmax, int P)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    const GCarve g = gcarve(nullptr, B, Lmax, P);
+    return (size_t)reinterpret_cast<uintptr_t>(g.cs);
+}
+
 // introspection: how many stacks (or (stack, period) units in independent mode) the last solve that used this
 // workspace handed to the exact fallback kernel.  Waits for `stream`.
 int surfdisp_workspace_fallback_count(void *stream, const void *workspace, int B, int Lmax, int P, int *count)
@@ -450,6 +493,61 @@ int surfdisp_forward_kernels_device(void *stream, int B, int Lmax, const int *nl
     }
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
                                workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr);
+}
+
+// The same launches, then the analytic partials of the GROUP velocity (K4 in surfdisp_kernels.hip): the roots at
+// T (1 -+ dlnT_frac), the phase partials there, and their combination.  c, u, status, dc* are those of
+// surfdisp_forward_kernels_device, bit for bit.
+int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind, float dlnT_frac,
+                                          float *c, float *u, int *status,
+                                          float *dcdb, float *dcda, float *dcdr,
+                                          float *dudb, float *duda, float *dudr, int *n_shift_failed,
+                                          void *workspace, size_t workspace_bytes)
+{
+    if (!dcdb || !dudb) { set_err("surfdisp_forward_group_kernels_device: dcdb or dudb is NULL"); return SURFDISP_ERR_INVALID; }
+    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
+        set_err("surfdisp_forward_group_kernels_device: no PHASE_ONLY, no KERN_REFCOORD");
+        return SURFDISP_ERR_INVALID;
+    }
+    if (!(dlnT_frac >= 1.0e-3f && dlnT_frac <= 0.05f)) {
+        set_err("surfdisp_forward_group_kernels_device: dlnT_frac outside [1e-3, 0.05]");
+        return SURFDISP_ERR_INVALID;
+    }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < surfdisp_group_kernels_workspace_bytes(B, Lmax, P)) {
+        set_err("workspace too small (surfdisp_group_kernels_workspace_bytes)");
+        return SURFDISP_ERR_WORKSPACE;
+    }
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int wave = kind & ~SD_KIND_FLAGS;
+    const EnvKnobs &kn = knobs();
+    const Carve w = carve(workspace, B, Lmax, P);
+    const size_t PB = (size_t)P * B;
+    char *q = static_cast<char *>(workspace) + align_up(w.total);
+    float *kscr = reinterpret_cast<float *>(q);                                  // forward_device_impl's scratch ...
+    float *kscale0 = reinterpret_cast<float *>(q + align_up((size_t)3 * Lmax * PB * sizeof(float)));   // ... and factors
+    const GCarve g = gcarve(workspace, B, Lmax, P);
+    if (n_shift_failed) SD_HIP(hipMemsetAsync(n_shift_failed, 0, sizeof(int), s));
+    sd::ShiftArgs sa{B, Lmax, P, wave, w.mdl, w.nl, per, w.ct, w.ut, w.nsolved, dlnT_frac, g.pers, g.cs,
+                     wave == SURFDISP_KIND_RAYLEIGH ? g.ratio : nullptr, g.fail, kn.ell_ambig, kn.ell_gmax, w.ovf};
+    SD_HIP(sd::launch_shift(s, sa));
+    for (int sg = 0; sg < 2; ++sg) {
+        // (kb / ka / kr only say which partials are wanted: on the scratch route the kernel writes the scratch alone)
+        sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB, w.nsolved,
+                         g.us + sg * PB, nullptr, dudb, wave == SURFDISP_KIND_RAYLEIGH ? duda : nullptr, dudr,
+                         sg ? g.kscr_p : kscr, g.ksc + sg * PB, g.khs + sg * PB, 0, 0, 0, kn.group_order};
+        SD_HIP(sd::launch_group(s, wave, ga));
+    }
+    const float inv_dlnT = (float)(1.0 / log((1.0 + (double)dlnT_frac) / (1.0 - (double)dlnT_frac)));
+    sd::GroupCombineArgs ca{B, P, Lmax, wave, kscr, g.kscr_p, g.ksc, g.ksc + PB, g.khs, g.khs + PB, kscale0, g.fail,
+                            w.ct, w.ut, inv_dlnT, dudb, duda, dudr, n_shift_failed};
+    SD_HIP(sd::launch_group_combine(s, ca));
+    return SURFDISP_SUCCESS;
 }
 
 // Parameters -> layer stacks on the device for a static-structure model; the

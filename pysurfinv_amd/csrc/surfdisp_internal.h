@@ -92,6 +92,39 @@ struct KernTransposeArgs {
     float *kb, *ka, *kr;  // the caller's [B][P][Lmax] rows (ka, kr may be nullptr)
 };
 
+// group-velocity kernels (surfdisp_forward_group_kernels_device): the fundamental-mode roots at the shifted periods
+// T (1 -+ dfrac) of every solved (stack, period) unit, found from the first-order prediction without a scan
+struct ShiftArgs {
+    int B, Lmax, P, kind;
+    const float *mdl;     // SoA staged fields
+    const int *nl;
+    const float *per;     // [P] the solve's periods
+    const float *c, *u;   // [P][B] the solve's roots and group velocities (period-major)
+    const int *nsolved;   // [B]
+    float dfrac;          // relative period shift
+    float *pers;          // [2][P] out: the shifted periods T (1 - dfrac), T (1 + dfrac)
+    float *cs;            // [2][P][B] out: the roots there; the unit's own c where the unit is unsolved or failed
+    float *ratio;         // [2][P][B] out (Rayleigh): the ellipticity at the shifted root, formed as surfdisp_ellip_kernel does
+    unsigned char *fail;  // [2][P][B] out: 1 = no unique root inside the search budget (or a non-finite value)
+    float ell_ambig, ell_gmax;   // see EllipArgs
+    const float *ovf;     // [3][B] prep statistics
+};
+hipError_t launch_shift(hipStream_t s, const ShiftArgs &a);
+// dU/d(Vs, Vp, rho) from the partials at the two shifted periods (layer-major scratches, as KernTransposeArgs) and c, U
+struct GroupCombineArgs {
+    int B, P, Lmax, kind;
+    const float *kscr_m, *kscr_p;       // [3][Lmax][P][B] unscaled shares at T (1 - dfrac) and T (1 + dfrac)
+    const float *ksc_m, *ksc_p;         // [P][B] their factors 1 / (dL/dk)
+    const int *khs_m, *khs_p;           // [P][B] their deepest layers
+    const float *ksc0;                  // [P][B] the factor of the unshifted unit: 0 = no partials (unsolved), rows of zeros
+    const unsigned char *fail;          // [2][P][B] see ShiftArgs
+    const float *c, *u;                 // [P][B] c and U at T
+    float inv_dlnT;                     // 1 / ln((1 + dfrac) / (1 - dfrac))
+    float *ub, *ua, *ur;                // the caller's [B][P][Lmax] rows (ua, ur may be nullptr)
+    int *n_failed;                      // nullptr, or [1]: solved units whose shifted pass failed (NaN rows)
+};
+hipError_t launch_group_combine(hipStream_t s, const GroupCombineArgs &a);
+
 struct EllipArgs {
     int B, Lmax, P;
     const float *mdl;     // SoA staged fields

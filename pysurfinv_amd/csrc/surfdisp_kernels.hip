@@ -31,6 +31,9 @@
 //                               for Rayleigh as in the reference (surfa.f:717-722); the KERN
 //                               instantiation also writes the analytic partials dc/d(Vs, Vp, rho).
 //   K3 surfdisp_finish_kernel : period-major internal results -> the caller's [B][P] arrays.
+//   K4 (surfdisp_forward_group_kernels_device only) surfdisp_shift_kernel + K2 + surfdisp_group_combine_kernel: roots at
+//                               T (1 -+ d) from the first-order prediction, the phase partials there, and the analytic
+//                               group-velocity partials formed from them (see K4 below).
 // No MFMA: the products are 5x5 / 4x4 / 2x2.  Algorithmic HBM traffic is one read of the model array and one
 // write of c/U (the staged copies and period-major intermediates make it 138 MB per 65 536-stack batch against
 // 24 MB); everything else is VALU + transcendental work.
@@ -2785,6 +2788,227 @@ __global__ __launch_bounds__(256) void surfdisp_kern_transpose_kernel(KernTransp
     }
 }
 
+// ====================================================================== K4: group-velocity kernels
+// surfdisp_forward_group_kernels_device, behind the forward + partials launches (whose outputs it leaves as they are).
+// Differentiating U = d omega / dk at fixed omega (Rodi et al. 1975):
+//      dU/dm = (U/c) (2 - U/c) dc/dm - (U/c)^2 d(dc/dm)/d ln T,
+// with dc/dm the mean of the phase partials at T (1 - dfrac) and T (1 + dfrac) and d(dc/dm)/d ln T their central difference.
+// K4a surfdisp_shift_kernel: one lane per (shift, period, stack) unit finds the fundamental-mode root at the shifted period
+//   from the first-order prediction c' = c (1 +- dfrac (c/U - 1))  ((omega/c) dc/domega = 1 - c/U), WITHOUT a scan: a window
+//   around c' is sampled at five points; exactly one sign change brackets the root, none widens the window (at most
+//   SD_SHIFT_WIDEN times), more than one - or a non-finite value - fails the unit (a mode osculation, a layer velocity in
+//   between, an overflow: a failure flag, not a guess).  A sign change that disappears with the layer dropping frozen at the
+//   bracket's upper end (the refine passes' rule) was a jump of the dropping, not a root: failed too.  The bracket is then
+//   bisected to fp32 resolution.  The secular function is the production recursion (ray_step / ray_close; the step of
+//   delta_love) on layer values rebuilt in registers from the staged fields: a freshly built stack at the shifted period, as
+//   SURFDISP_INDEPENDENT builds one.  Rayleigh: also the ellipticity at the root, as surfdisp_ellip_kernel forms it.
+// K4b surfdisp_group_kernel<KIND, true> at the shifted periods and roots (chain factors at those periods).
+// K4c surfdisp_group_combine_kernel: the rule above on the two layer-major scratches -> the caller's rows.
+#ifndef SD_SHIFT_WIDEN
+#define SD_SHIFT_WIDEN 6
+#endif
+struct ShiftStack { const float *mdl; size_t fs; int B, b, n; float T, lnT; };
+__device__ __forceinline__ LayerV shift_layer(const ShiftStack &q, int i)
+{
+    return layer_at(q.mdl, q.fs, (size_t)i * q.B + q.b, q.lnT, i == q.n - 1);
+}
+// drop_layers on the rebuilt stack
+__device__ __forceinline__ int shift_drop(const ShiftStack &q, float c)
+{
+    const float dmax = FACT * c * q.T;
+    int cnt = 0;
+    float sum = 0.0f;
+    for (int ii = 0; ii < q.n; ++ii) {
+        const LayerV v = shift_layer(q, ii);
+        sum = sum + ((c < v.b) ? v.d : 0.0f);
+        cnt += (sum > dmax) ? 0 : 1;
+    }
+    const int mm = (cnt < q.n) ? cnt + 1 : q.n;
+    return mm < 2 ? 2 : mm;
+}
+// delta_rayleigh on the rebuilt stack (the ellipticity kernel's loop): start 1 dispersion, 2 / 3 the ellipticity passes
+__device__ __forceinline__ float shift_delta_rayleigh(const ShiftStack &q, float c, int mm, int start, float *mag = nullptr)
+{
+    const RTrial t = ray_trial(c, q.T);
+    RState s{};
+    float phi = 0.0f, rho_prev = 0.0f, rho_i = 0.0f;
+    RLyr y{};
+    const int last = mm - 1;
+    for (int i = 0; i <= last; ++i) {
+        const LayerV v = shift_layer(q, i);
+        rho_prev = rho_i;
+        rho_i = v.rho;
+        y.sv = v.b; y.d = v.d;
+        y.ia2 = wk_ia2(v.a);
+        y.ib2 = wk_ib2(v.b);
+        y.rat = (i > 0) ? wk_rat(rho_prev, rho_i) : 0.0f;
+        if (i == 0) {
+            s = ray_start(t, start, (start == 1) ? 0.0f : wk_irho(rho_i));
+            if (last >= 1) ray_step<true>(s, t, y, start, phi);
+        } else if (i < last) {
+            ray_step<false>(s, t, y, start, phi);
+        }
+    }
+    return ray_close(s, t, y, rho_i, (last >= 1) ? rho_prev : 0.0f, start, mag, mag != nullptr);
+}
+// delta_love on the rebuilt stack (its step, without the certificate)
+__device__ __forceinline__ float shift_delta_love(const ShiftStack &q, float c, int mm)
+{
+#pragma clang fp contract(off)
+    const float wvno = 6.2831853f * rcp_nr(c * q.T);
+    const float csq = c * c;
+    const int mh = mm - 1;
+    const LayerV vh = shift_layer(q, mh);
+    const float h0 = vh.rho * vh.b * vh.b;
+    const float rb0 = sqrt_hw(fabsf(fmaf(csq, wk_ilove(vh.rho, vh.b) * vh.rho, -1.0f)));
+    float ut = 1.0f, tt = h0 * rb0;
+    for (int m = mh - 1; m >= 0; --m) {
+        const LayerV v = shift_layer(q, m);
+        if (v.b == 0.0f) continue;                         // water, surfa.f:152
+        const float ih = wk_ilove(v.rho, v.b);
+        const float arg = fmaf(csq, ih * v.rho, -1.0f);
+        const float h = v.rho * v.b * v.b;
+        const LCoef Q = layer_coef(-arg, wvno * v.d);
+        const float yv = -Q.sinr, z = -Q.rsin, cosq = Q.cs;
+        const float eut = fmaf(cosq, ut, -(yv * tt * ih));
+        const float ett = fmaf(h * z, ut, cosq * tt);
+        ut = eut; tt = ett;
+    }
+    return -tt;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void surfdisp_shift_kernel(ShiftArgs A)
+{
+    const int B = A.B, P = A.P;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // [2][P][B]: a wavefront = 64 stacks, one period
+    if (idx >= (size_t)2 * P * B) return;
+    const int b = (int)(idx % B), k = (int)((idx / B) % P), sg = (int)(idx / ((size_t)P * B));
+    const float T = A.per[k];
+    const float Ts = T * (sg ? 1.0f + A.dfrac : 1.0f - A.dfrac);
+    if (b == 0) A.pers[sg * P + k] = Ts;
+    const size_t o = (size_t)k * B + b;
+    const float c0 = A.c[o];
+    float root = c0, ell = 0.0f;
+    unsigned char bad = 0;
+    const int n = A.nl[b];
+    if (n >= 2 && k < A.nsolved[b]) {
+        bad = 1;
+        const float u0 = A.u[o];
+        const ShiftStack q{A.mdl, (size_t)A.Lmax * B, B, b, n, Ts, logf(1.0f / Ts)};
+        auto delta = [&](float c, int mm) { return KIND == 2 ? shift_delta_rayleigh(q, c, mm, 1) : shift_delta_love(q, c, mm); };
+        const float pred = c0 * (1.0f + (sg ? A.dfrac : -A.dfrac) * (c0 / u0 - 1.0f));
+        float lo = 0.0f, hi = 0.0f, flo = 0.0f, fhi = 0.0f;
+        bool found = false, broken = !(u0 > 0.0f) || !(pred > 0.0f) || !fin(pred);
+        float hw = 0.25f * fabsf(pred - c0) + 1.0e-4f * c0;   // the prediction's error is second order in dfrac
+        for (int it = 0; it <= SD_SHIFT_WIDEN && !found && !broken; ++it, hw *= 2.0f) {
+            int changes = 0;
+            float xp = 0.0f, fp = 0.0f;
+            for (int j = 0; j < 5; ++j) {
+                const float x = pred + (0.5f * (float)(j - 2)) * hw;
+                if (!(x > 0.0f)) { broken = true; break; }
+                const float f = delta(x, shift_drop(q, x));      // idrop = 0, as a scan trial
+                if (!fin(f)) { broken = true; break; }
+                if (j > 0 && ((f < 0.0f) != (fp < 0.0f))) { ++changes; lo = xp; flo = fp; hi = x; fhi = f; }
+                xp = x; fp = f;
+            }
+            if (!broken && changes > 1) broken = true;
+            found = !broken && changes == 1;
+        }
+        if (found) {
+            const int mm = shift_drop(q, hi);                    // frozen, as the refine passes see it
+            flo = delta(lo, mm);
+            if (!fin(flo) || ((flo < 0.0f) == (fhi < 0.0f))) found = false;
+            for (int it = 0; found && it < 48; ++it) {
+                const float mid = 0.5f * (lo + hi);
+                if (!(mid > lo && mid < hi)) break;
+                const float f = delta(mid, mm);
+                if (!fin(f)) { found = false; break; }
+                if ((f < 0.0f) == (flo < 0.0f)) { lo = mid; flo = f; } else { hi = mid; fhi = f; }
+            }
+            if (found) {
+                float r = lo - flo * ((hi - lo) / (fhi - flo));
+                if (!(r >= lo && r <= hi)) r = 0.5f * (lo + hi);
+                root = r;
+                bad = 0;
+                if (KIND == 2) {
+                    float m2 = 0.0f, m3 = 0.0f;
+                    float v2 = shift_delta_rayleigh(q, root, mm, 2, &m2), v3 = shift_delta_rayleigh(q, root, mm, 3, &m3);
+                    const float b2max = A.ovf ? 0.5f * __expf(0.25f * A.ovf[2 * (size_t)B + b]) : 0.0f;
+                    if ((A.ell_ambig < 0.0f) ||
+                        ((A.ell_ambig > 0.0f) && (fabsf(v2) < A.ell_ambig * m2 || fabsf(v3) < A.ell_ambig * m3 ||
+                                                  2.0f * b2max > A.ell_gmax * root * root))) {
+                        auto get = [&](int m) { const LayerV v = shift_layer(q, m); return RefLyr{v.a, v.b, v.rho, v.d}; };
+                        v2 = delta_rayleigh_ref_gen(get, mm, root, Ts, 2);
+                        v3 = delta_rayleigh_ref_gen(get, mm, root, Ts, 3);
+                    }
+                    ell = 0.5f * v3 / v2;                        // surfa.f:363
+                }
+            }
+        }
+        if (bad) root = c0;                                      // (the partials pass runs on it; the combination writes NaN)
+    }
+    A.cs[idx] = root;
+    if (A.ratio) A.ratio[idx] = ell;
+    A.fail[idx] = bad;
+}
+
+// shaped as surfdisp_kern_transpose_kernel: 64 units x 64 layers per workgroup through an LDS tile.  A unit without phase
+// partials (factor 0 at T: unsolved) gets a row of zeros, a solved unit whose shifted pass failed a row of NaN.
+__global__ __launch_bounds__(256) void surfdisp_group_combine_kernel(GroupCombineArgs A)
+{
+    __shared__ float tile[64][65];
+    const int B = A.B, P = A.P, Lmax = A.Lmax;
+    float *__restrict__ out = (blockIdx.z == 0) ? A.ub : ((blockIdx.z == 1) ? A.ua : A.ur);
+    if (!out) return;                                        // (block-uniform)
+    const size_t arr = (size_t)Lmax * P * B;
+    const float *__restrict__ sm = A.kscr_m + (size_t)blockIdx.z * arr;
+    const float *__restrict__ sp = A.kscr_p + (size_t)blockIdx.z * arr;
+    const bool zero_only = (blockIdx.z == 1) && (A.kind != 2);   // Love has no dU/dVp
+    const int nbb = (B + 63) / 64;
+    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
+    const size_t PB = (size_t)P * B;
+    const int bl = threadIdx.x % 64;
+    int mode = 0;                                            // 0 zeros, 1 NaN, 2 the combination
+    float scm = 0.0f, scp = 0.0f, f1 = 0.0f, f2 = 0.0f;
+    int hsm = -1, hsp = -1;
+    if (b0 + bl < B && !zero_only) {
+        const size_t o = (size_t)k * B + b0 + bl;
+        if (A.ksc0[o] != 0.0f) {
+            scm = A.ksc_m[o]; scp = A.ksc_p[o];
+            hsm = A.khs_m[o]; hsp = A.khs_p[o];
+            const float c = A.c[o], u = A.u[o];
+            const bool ok = !A.fail[o] && !A.fail[PB + o] && scm != 0.0f && scp != 0.0f && c > 0.0f && u > 0.0f;
+            mode = ok ? 2 : 1;
+            if (ok) {
+                const float r = u / c;
+                f1 = 0.5f * r * (2.0f - r);                      // (U/c)(2 - U/c) x the mean
+                f2 = r * r * A.inv_dlnT;                         // (U/c)^2 / d ln T
+            } else if (A.n_failed && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) {
+                atomicAdd(A.n_failed, 1);
+            }
+        }
+    }
+    for (int il = threadIdx.x / 64; il < 64; il += 4) {
+        const int i = i0 + il;
+        float v = 0.0f;
+        if (mode == 1) {
+            v = __builtin_nanf("");
+        } else if (mode == 2) {
+            const size_t q = (size_t)i * PB + (size_t)k * B + b0 + bl;
+            const float km = (i <= hsm) ? sm[q] * scm : 0.0f;
+            const float kp = (i <= hsp) ? sp[q] * scp : 0.0f;
+            v = f1 * (km + kp) - f2 * (kp - km);
+        }
+        tile[il][bl] = v;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
+        const int bq = t / 64, il = t % 64;
+        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
+    }
+}
+
 }  // namespace sd
 
 // ======================================================================================= launch
@@ -2909,6 +3133,22 @@ hipError_t launch_kern_transpose(hipStream_t s, const KernTransposeArgs &a)
 {
     const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 3u);
     hipLaunchKernelGGL(surfdisp_kern_transpose_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shift(hipStream_t s, const ShiftArgs &a)
+{
+    const size_t total = (size_t)2 * a.B * a.P;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (a.kind == 2) hipLaunchKernelGGL((surfdisp_shift_kernel<2>), grid, dim3(256), 0, s, a);
+    else             hipLaunchKernelGGL((surfdisp_shift_kernel<1>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_group_combine(hipStream_t s, const GroupCombineArgs &a)
+{
+    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 3u);
+    hipLaunchKernelGGL(surfdisp_group_combine_kernel, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -213,6 +213,47 @@ class BatchPlan:
         _lib.check(rc)
         return self.c, self.u, self.status, dcdb, dcda, dcdr
 
+    def run_group_kernels(self, model, periods, kind=2, nlay=None, dlnT_frac=0.01, want_vp=True, want_rho=True):
+        """``run_kernels`` plus the analytic partials of the GROUP velocity (``surfdisp_forward_group_kernels_device``):
+        returns (c, u, status, dcdb, dcda, dcdr, dudb, duda, dudr, n_failed).  c .. dcdr equal ``run_kernels``' bit for bit;
+        dudb / duda / dudr float32 [B, P, L] = d U(period) / d (Vs | Vp | rho) of input layer i (``None`` where not
+        requested; Love has no duda), from the phase partials at T (1 -+ dlnT_frac).  Rows of unsolved periods are zeros,
+        rows of units whose shifted root failed are NaN; ``n_failed`` (int, synchronises the stream) counts the latter."""
+        torch = self.torch
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        rayleigh = (int(kind) & 3) == _lib.KIND_RAYLEIGH
+        dcdb, dudb = mk(), mk()
+        dcda, duda = (mk(), mk()) if (want_vp and rayleigh) else (None, None)
+        dcdr, dudr = (mk(), mk()) if want_rho else (None, None)
+        if getattr(self, "gworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
+            self.gws_bytes = int(_lib.lib().surfdisp_group_kernels_workspace_bytes(self.B, self.L, self.P))
+            self.gworkspace = torch.empty(self.gws_bytes, dtype=torch.uint8, device=self.device)
+            self.nfail = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._last_ws = self.gworkspace
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().surfdisp_forward_group_kernels_device(
+                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                float(dlnT_frac), ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                ptr(dudb), ptr(duda), ptr(dudr), ptr(self.nfail), ptr(self.gworkspace), self.gws_bytes)
+        _lib.check(rc)
+        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(self.nfail.item())
+
+    def shifted_roots(self):
+        """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
+        own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""
+        off = int(_lib.lib().surfdisp_group_kernels_shift_offset(self.B, self.L, self.P))
+        n = 2 * self.P * self.B * 4
+        return self.gworkspace[off:off + n].view(self.torch.float32).view(2, self.P, self.B).transpose(1, 2).clone()
+
 
 class EventRing:
     """n x 4 HIP events owned by the caller, recorded by ``BatchPlan.run(..., events=ring.slot(i))``

@@ -9,6 +9,10 @@ Differences from the reference, on purpose:
 * ``wtype='L'``: the reference reads ``cr0`` even for Love (``senskernel.py:188-192``, SURVEY.md
   section 4 defect 7) so its Love kernels are ``None``; here Love uses the Love phase velocities.
 * group-velocity kernels (``ytype='grv'``) come for free from the same batch.
+* analytic group-velocity kernels (``analytic_kernels(group=True)``, ``SensKernel``) follow the toolkit's construction
+  (GRV_SENS_KERNEL.f:99-108: phase partials at T x 0.99 and T x 1.01, their mean and central difference), but with the
+  derived sign for all three columns: the toolkit's ``dudrho`` (GRV_SENS_KERNEL.f:107) adds the frequency term where
+  ``dudb`` / ``duda`` (lines 106, 108) subtract it, and central differences of U itself side with the subtraction.
 """
 from __future__ import annotations
 
@@ -127,7 +131,24 @@ def sens_kernel_pert_batch(model, periods, wtype="R", nlay=None, lo=0.999, hi=1.
     return out
 
 
-def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True):
+def group_from_phase_partials(c, u, k_minus, k_plus, dlnT):
+    """The combination rule of the group-velocity kernels in float64 (the host statement of what the HIP combine kernel
+    computes): differentiating U = d omega / dk at fixed omega (Rodi et al. 1975),
+
+        dU/dm = (U/c) (2 - U/c) dc/dm - (U/c)^2 d(dc/dm)/d ln T,
+
+    with dc/dm the mean of the phase partials ``k_minus`` / ``k_plus`` at T (1 - d) and T (1 + d) and the derivative their
+    central difference over ``dlnT`` = ln((1 + d) / (1 - d)).  c, u broadcast against the partials (e.g. [P, 1] against
+    [P, L])."""
+    c = np.asarray(c, np.float64)
+    u = np.asarray(u, np.float64)
+    km = np.asarray(k_minus, np.float64)
+    kp = np.asarray(k_plus, np.float64)
+    r = u / c
+    return r * (2.0 - r) * 0.5 * (km + kp) - r * r * (kp - km) / float(dlnT)
+
+
+def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
     the partial derivatives REIGEN / LEIGEN form from their energy integrals and never return
     (surfa.f:1130-1135, 1204-1207; 561-565, 584-585), with the chain factors of the attenuation
@@ -136,16 +157,26 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     model: torch float32 [M, 5, L] (vp, vs, rho, h, 1/Qs) on a HIP device; periods float32 [P].
     Returns dict(dcdb, dcda, dcdr: float32 [M, P, L] = d c / d (Vs | Vp | rho) per layer (dcda only for
     Rayleigh); c0, u0 [M, P]; status [M]; phv = dcdb * Vs / 100 / h, the reference's ``SensKernelPert``
-    units ((v(1.001 Vs) - v(0.999 Vs)) / 0.2 / H, senskernel.py:150))."""
+    units ((v(1.001 Vs) - v(0.999 Vs)) / 0.2 / H, senskernel.py:150)).
+    ``group=True`` (``surfdisp_forward_group_kernels_device``): also dudb, duda, dudr [M, P, L] = d U / d (Vs | Vp | rho)
+    from the phase partials at T (1 -+ dlnT_frac) (see ``group_from_phase_partials``; NaN rows where a shifted root
+    failed), grv = dudb * Vs / 100 / h in phv's units, and n_failed."""
     import torch
     kind = {"R": 2, "L": 1}[wtype]
     M, _, L = model.shape
     plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
-    c, u, st, kb, ka, kr = plan.run_kernels(model, periods, kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
+    if group:
+        c, u, st, kb, ka, kr, ub, ua, ur, nf = plan.run_group_kernels(model, periods, kind=kind, nlay=nlay, dlnT_frac=dlnT_frac,
+                                                                      want_vp=want_vp, want_rho=want_rho)
+    else:
+        c, u, st, kb, ka, kr = plan.run_kernels(model, periods, kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
     h = model[:, 3, :][:, None, :]
     vs = model[:, 1, :][:, None, :]
-    phv = torch.where(h > 0, kb * vs / 100.0 / torch.where(h > 0, h, torch.ones_like(h)), torch.zeros_like(kb))
-    return dict(dcdb=kb, dcda=ka, dcdr=kr, c0=c, u0=u, status=st, phv=phv)
+    per_km = lambda k: torch.where(h > 0, k * vs / 100.0 / torch.where(h > 0, h, torch.ones_like(h)), torch.zeros_like(k))
+    out = dict(dcdb=kb, dcda=ka, dcdr=kr, c0=c, u0=u, status=st, phv=per_km(kb))
+    if group:
+        out.update(dudb=ub, duda=ua, dudr=ur, grv=per_km(ub), n_failed=nf)
+    return out
 
 
 class SensKernelPert:
@@ -161,7 +192,9 @@ class SensKernelPert:
     and converts them, dc/dx * x / 100 / H - the same quantity without the fp32 differencing noise
     (for a layer whose Vp/Rho/Qs follow from Vs through ``Grp``, the reference's Vs perturbation also moves
     them; the analytic route applies that chain rule).  Love kernels use Love velocities (the reference
-    reads ``cr0`` for both wave types and returns ``None`` for Love, SURVEY.md section 4 defect 7)."""
+    reads ``cr0`` for both wave types and returns ``None`` for Love, SURVEY.md section 4 defect 7).
+    ``kernel_grv`` holds the same for the group velocity: ``fd`` from the U of the same perturbed batch, ``analytic`` from
+    ``surfdisp_forward_group_kernels_device`` with the same chain rule; ``plot(per, ytype='phv' | 'grv', xtype)``."""
 
     def __init__(self, model, wtype="R", Tmin=20, Tmax=100, Tstep=10, dz=2, method="fd", device=0):
         import pandas as pd
@@ -180,11 +213,13 @@ class SensKernelPert:
         col = lambda k: df[k].to_numpy(float) if k in df else None
         Vp, Rho, Qs = col("Vp"), col("Rho"), col("Qs")
         self.H, self.Vs = H, Vs
-        self.kernel = {}
+        self.kernel, self.kernel_grv = {}, {}
         if method == "fd":
-            self.kernel["Vs"] = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, "Vs", device)["phv"]
-            if Vp is not None:
-                self.kernel["Vp"] = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, "Vp", device)["phv"]
+            for x in ("Vs", "Vp"):
+                if x == "Vp" and Vp is None:
+                    continue
+                out = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, x, device)
+                self.kernel[x], self.kernel_grv[x] = out["phv"], out["grv"]
         elif method == "analytic":
             import torch
             dVp, dRho, dQs = (None, None, None) if grp is None else _derive(Vs, grp)
@@ -195,10 +230,7 @@ class SensKernelPert:
             m = np.stack([vp[keep], Vs[keep], rho[keep], H[keep], 1.0 / qs[keep]])[None].astype(np.float32)
             dev = torch.device(f"cuda:{device}")
             per = torch.as_tensor(np.asarray(list(self.periods), np.float32), device=dev)
-            out = analytic_kernels(torch.from_numpy(m).to(dev), per, wtype=wtype)
-            kb = out["dcdb"][0].double().cpu().numpy()
-            ka = out["dcda"][0].double().cpu().numpy() if out["dcda"] is not None else np.zeros_like(kb)
-            kr = out["dcdr"][0].double().cpu().numpy()
+            out = analytic_kernels(torch.from_numpy(m).to(dev), per, wtype=wtype, group=True)
             Hk, vsk, vpk = H[keep], Vs[keep], vp[keep]
             dvp = np.zeros_like(vsk); drho = np.zeros_like(vsk)      # d(Vp, Rho)/dVs through the Grp rules
             if grp is not None:
@@ -208,12 +240,119 @@ class SensKernelPert:
                 if Rho is None:
                     drho = np.select([g == "sediment", g == "crust", g == "mantle"],
                                      [0.3601 * 1.23, 0.3601 * 1.8, 1.0 / 4.5], 0.0)
-            full = np.zeros((len(list(self.periods)), H.size))
-            full[:, keep] = (kb + ka * dvp[None, :] + kr * drho[None, :]) * vsk[None, :] / 100.0 / Hk[None, :]
-            self.kernel["Vs"] = full
-            if Vp is not None:
-                fullp = np.zeros_like(full)
-                fullp[:, keep] = ka * vpk[None, :] / 100.0 / Hk[None, :]
-                self.kernel["Vp"] = fullp
+            for dst, (b, a, r) in ((self.kernel, ("dcdb", "dcda", "dcdr")), (self.kernel_grv, ("dudb", "duda", "dudr"))):
+                kb = out[b][0].double().cpu().numpy()
+                ka = out[a][0].double().cpu().numpy() if out[a] is not None else np.zeros_like(kb)
+                kr = out[r][0].double().cpu().numpy()
+                full = np.zeros((len(list(self.periods)), H.size))
+                full[:, keep] = (kb + ka * dvp[None, :] + kr * drho[None, :]) * vsk[None, :] / 100.0 / Hk[None, :]
+                dst["Vs"] = full
+                if Vp is not None:
+                    fullp = np.zeros_like(full)
+                    fullp[:, keep] = ka * vpk[None, :] / 100.0 / Hk[None, :]
+                    dst["Vp"] = fullp
         else:
             raise ValueError("method must be 'fd' or 'analytic'")
+
+    def plot(self, per=None, ytype="phv", xtype="Vs"):
+        """The reference's ``SensKernelPert.plot`` (senskernel.py:193-206), with the ``grv`` branch it leaves commented out:
+        one curve per period against the layers' mid depths."""
+        import matplotlib.pyplot as plt
+        if ytype == "phv":
+            kernel = self.kernel
+        elif ytype == "grv":
+            kernel = self.kernel_grv
+        else:
+            raise ValueError(ytype)
+        fig, ax = plt.subplots(1, 1, figsize=[6, 8])
+        zdeps = np.cumsum(self.H) - self.H / 2
+        for iper, p in enumerate(self.periods):
+            if per is None or p == per:
+                ax.plot(kernel[xtype][iper, :], zdeps, label=f"{p}s")
+        ax.invert_yaxis()
+        ax.legend()
+        return fig
+
+
+class SensKernel:
+    """Drop-in for the reference's ``SensKernel`` (``senskernel.py:8-86``), which runs the senskernel-1.0 toolkit
+    (SURF_PERTURB, PHV_SENS_KERNEL, GRV_SENS_KERNEL) on a temporary copy of the model.  Here the kernels come from one
+    batched call of ``surfdisp_forward_group_kernels_device`` (analytic phase partials at T and at T x (1 -+ 0.01)).
+
+    ``model``: CSV path or DataFrame with columns H, Vp, Vs, Rho, Qs (the toolkit's model file, one row per layer, the last
+    row the half space; layers with H <= 1e-3 are dropped as ``SensKernelPert`` does).  ``model=None`` -> ValueError: the
+    reference's default PREM file belongs to the reference's tree.  Fundamental mode only: ``endmode != 0`` -> ValueError.
+
+    After construction ``kernel_phv`` / ``kernel_grv`` are float [1, nCol, P, nz] on ``zdeps = arange(0, sum(H), dz)`` in the
+    toolkit's units, (dc/c)/(dx/x) resp. (dU/U)/(dx/x) per km, columns (Vs, Vp, Rho) for 'R' and (Vs, Rho) for 'L'.  Each
+    depth sample carries the per-km value of the LAYER that contains it (layer partial x value / velocity / thickness): the
+    toolkit splits the model into dz sublayers and samples inside layers, so its curves vary within a thick layer where these
+    are flat - their layer means agree.  Differences from the toolkit: its ``dudrho`` has the wrong sign on the frequency
+    term (see the module docstring); NaN where a shifted root failed."""
+
+    def __init__(self, model=None, wtype="R", Tmin=20, Tmax=100, Tstep=10, endmode=0, dz=2, device=0):
+        import pandas as pd
+        import torch
+        if model is None:
+            raise ValueError("SensKernel needs a model: the reference's default PREM file is not part of this package")
+        if isinstance(model, str):
+            self.model = pd.read_csv(model)
+        elif isinstance(model, pd.DataFrame):
+            self.model = model.copy()
+        else:
+            raise ValueError(f"Wrong model input: {model}")
+        if endmode != 0:
+            raise ValueError("SensKernel: fundamental mode only (endmode=0); overtones are not supported")
+        if wtype == "R":
+            self.xtype = ["Vs", "Vp", "Rho"]
+        elif wtype == "L":
+            self.xtype = ["Vs", "Rho"]
+        else:
+            raise ValueError("Wrong surface wave type!")
+        self.wtype = wtype
+        self.zdeps = np.arange(0, self.model["H"].sum(), dz)
+        self.periods = range(Tmin, Tmax + Tstep // 2, Tstep)
+        col = lambda k: self.model[k].to_numpy(float)
+        H, Vp, Vs, Rho, Qs = col("H"), col("Vp"), col("Vs"), col("Rho"), col("Qs")
+        keep = H > 1e-3
+        H, Vp, Vs, Rho, Qs = H[keep], Vp[keep], Vs[keep], Rho[keep], Qs[keep]
+        m = np.stack([Vp, Vs, Rho, H, 1.0 / Qs])[None].astype(np.float32)
+        dev = torch.device(f"cuda:{device}")
+        per = torch.as_tensor(np.asarray(list(self.periods), np.float32), device=dev)
+        out = analytic_kernels(torch.from_numpy(m).to(dev), per, wtype=wtype, group=True)
+        c = out["c0"][0].double().cpu().numpy()[:, None]
+        u = out["u0"][0].double().cpu().numpy()[:, None]
+        vals = {"Vs": Vs, "Vp": Vp, "Rho": Rho}
+        keys = {"Vs": ("dcdb", "dudb"), "Vp": ("dcda", "duda"), "Rho": ("dcdr", "dudr")}
+        # layer of each depth sample: top <= z < bottom
+        lay = np.minimum(np.searchsorted(np.cumsum(H), self.zdeps, side="right"), H.size - 1)
+        nCol = len(self.xtype)
+        self.kernel_phv = np.full((1, nCol, len(self.periods), self.zdeps.size), np.nan)
+        self.kernel_grv = np.full_like(self.kernel_phv, np.nan)
+        self.layer_phv, self.layer_grv = {}, {}
+        for ic, x in enumerate(self.xtype):
+            for dst, lay_dst, key, v in ((self.kernel_phv, self.layer_phv, keys[x][0], c),
+                                         (self.kernel_grv, self.layer_grv, keys[x][1], u)):
+                k = out[key][0].double().cpu().numpy()
+                per_km = k * vals[x][None, :] / v / H[None, :]
+                per_km[v[:, 0] <= 0, :] = np.nan                     # unsolved periods
+                lay_dst[x] = per_km                                  # [P, L] per layer
+                dst[0, ic] = per_km[:, lay]
+
+    def plot(self, mode=0, per=None, ytype="phv", xtype="Vs"):
+        """The reference's ``SensKernel.plot`` (senskernel.py:72-85): one curve per period against depth."""
+        import matplotlib.pyplot as plt
+        if ytype == "phv":
+            kernel = self.kernel_phv
+        elif ytype == "grv":
+            kernel = self.kernel_grv
+        else:
+            raise ValueError(ytype)
+        ix = self.xtype.index(xtype)
+        fig, ax = plt.subplots(1, 1, figsize=[6, 8])
+        for iper, p in enumerate(self.periods):
+            if per is None or p == per:
+                ax.plot(kernel[mode, ix, iper, :], self.zdeps, label=f"{p}s")
+        ax.invert_yaxis()
+        ax.legend()
+        return fig
