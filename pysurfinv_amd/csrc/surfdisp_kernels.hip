@@ -2172,6 +2172,83 @@ SD_HD __forceinline__ RProp make_prop(const RCoef &q)
     }
     return P;
 }
+// Closed-form powers of P.  Every polynomial in A has the block form of P above, so
+//   P^m = [[F(N1), G(N1) M1], [G(N2) M2, F(N2)]],   F(N) = f0 I + f1 N,  G(N) = g0 I + g1 N:
+// N1 and N2 share their trace t and determinant d, and every polynomial in N reduces modulo N^2 = t N - d I.  P^m is
+// carried as its four scalars and multiplied as (F, G)(F', G') = (F F' + N G G', F G' + G F'), each product reduced with
+// the same rule: no division, and valid when the two eigenvalues of N coincide.
+struct RPow { double f0, f1, g0, g1; };
+struct RBase { M2x2 m1, m2, n1, n2; double t, d; RPow p; };   // one layer: the blocks of A, N1, N2, and P's scalars
+SD_HD __forceinline__ RBase make_base(const RCoef &q)
+{
+#pragma clang fp contract(off)
+    // k1..k4, M1, M2, t, d and P's scalars exactly as make_prop forms them
+    const double wh = (double)(0.5f * q.ddz), w1 = (double)(1.0f * q.ddz);
+    const double t6 = (double)((1.0f / 6.0f) * q.ddz), t3 = (double)((1.0f / 3.0f) * q.ddz);
+    const double k1 = (t6 + t3) + (t3 + t6);
+    const double k2 = (t3 * wh + t3 * wh) + t6 * w1;
+    const double k3 = t3 * wh * wh + t6 * w1 * wh;
+    const double k4 = t6 * w1 * wh * wh;
+    RBase r;
+    r.m1 = M2x2{(double)q.a31, (double)q.a34, (double)q.a21, (double)q.a24};
+    r.m2 = M2x2{(double)q.a13, (double)q.a12, (double)q.a43, (double)q.a42};
+    r.n1 = mm(r.m1, r.m2);
+    r.n2 = mm(r.m2, r.m1);
+    r.t = r.n1.a + r.n1.d;
+    r.d = fma(r.n1.a, r.n1.d, -(r.n1.b * r.n1.c));
+    r.p = RPow{fma(-k4, r.d, 1.0), fma(k4, r.t, k2), k1, k3};
+    return r;
+}
+// x y for two polynomials reduced modulo N^2 = t N - d I: (x0 y0 - d x1 y1) + (x0 y1 + x1 y0 + t x1 y1) N
+SD_HD __forceinline__ RPow pow_mul(const RPow &x, const RPow &y, double t, double d)
+{
+#pragma clang fp contract(off)
+    const double ff = x.f1 * y.f1, gg = x.g1 * y.g1, fg = fma(x.f1, y.g1, x.g1 * y.f1);
+    // F F' and G G' (reduced), then F F' + N G G' with N (g0 + g1 N) = -d g1 + (g0 + t g1) N
+    const double a0 = fma(x.f0, y.f0, -d * ff), a1 = fma(x.f0, y.f1, fma(x.f1, y.f0, t * ff));
+    const double b0 = fma(x.g0, y.g0, -d * gg), b1 = fma(x.g0, y.g1, fma(x.g1, y.g0, t * gg));
+    RPow r;
+    r.f0 = fma(-d, b1, a0);
+    r.f1 = fma(t, b1, a1 + b0);
+    r.g0 = fma(x.f0, y.g0, fma(x.g0, y.f0, -d * fg));
+    r.g1 = fma(x.f0, y.g1, fma(x.f1, y.g0, fma(x.g0, y.f1, fma(x.g1, y.f0, t * fg))));
+    return r;
+}
+SD_HD __forceinline__ RPow pow_sq(const RPow &x, double t, double d)
+{
+#pragma clang fp contract(off)
+    const double ff = x.f1 * x.f1, gg = x.g1 * x.g1, fg = x.f1 * x.g1;
+    const double a0 = fma(x.f0, x.f0, -d * ff), a1 = fma(2.0 * x.f0, x.f1, t * ff);
+    const double b0 = fma(x.g0, x.g0, -d * gg), b1 = fma(2.0 * x.g0, x.g1, t * gg);
+    RPow r;
+    r.f0 = fma(-d, b1, a0);
+    r.f1 = fma(t, b1, a1 + b0);
+    r.g0 = 2.0 * fma(x.f0, x.g0, -d * fg);
+    r.g1 = 2.0 * fma(x.f0, x.g1, fma(x.f1, x.g0, t * fg));
+    return r;
+}
+// P^(4 nreg), nreg >= 1: two squarings to P^4 (one sublayer), then binary powering (nreg = 5: P^16 P^4)
+SD_HD __forceinline__ RPow pow_sublayers(const RBase &L, int nreg)
+{
+    RPow q = pow_sq(pow_sq(L.p, L.t, L.d), L.t, L.d);
+    RPow r = (nreg & 1) ? q : RPow{1.0, 0.0, 0.0, 0.0};   // (a product with the identity is exact)
+    for (int e = nreg >> 1; e > 0; e >>= 1) {
+        q = pow_sq(q, L.t, L.d);
+        if (e & 1) r = pow_mul(r, q, L.t, L.d);
+    }
+    return r;
+}
+// the 16 entries of P^m from its scalars
+SD_HD __forceinline__ RProp pow_expand(const RBase &L, const RPow &x)
+{
+#pragma clang fp contract(off)
+    RProp P;
+    P.p11 = M2x2{fma(x.f1, L.n1.a, x.f0), x.f1 * L.n1.b, x.f1 * L.n1.c, fma(x.f1, L.n1.d, x.f0)};
+    P.p22 = M2x2{fma(x.f1, L.n2.a, x.f0), x.f1 * L.n2.b, x.f1 * L.n2.c, fma(x.f1, L.n2.d, x.f0)};
+    P.p12 = mm(M2x2{fma(x.g1, L.n1.a, x.g0), x.g1 * L.n1.b, x.g1 * L.n1.c, fma(x.g1, L.n1.d, x.g0)}, L.m1);
+    P.p21 = mm(M2x2{fma(x.g1, L.n2.a, x.g0), x.g1 * L.n2.b, x.g1 * L.n2.c, fma(x.g1, L.n2.d, x.g0)}, L.m2);
+    return P;
+}
 SD_HD __forceinline__ RProp prop_sq(const RProp &P)
 {
     RProp Q;
@@ -2195,11 +2272,11 @@ SD_HD __forceinline__ void prop_apply(const RProp &P, double v[4])
 }
 
 // integrate both solutions from the half space to the surface.  INTEG = false: only the surface
-// values are wanted, so each sublayer is one application of P^4.  INTEG = true: step by step, and
+// values are wanted, so a layer is one application of P^(4 nreg).  INTEG = true: step by step, and
 // accumulate the Boole energy integrals of the combined solution (xnorm*y + z)/bb
 // (surfa.f:1087-1129).  The two sweeps agree to fp64 rounding (~1e-15 relative), far inside what the
 // ~1e6 cancellation of the combination needs.
-// MODE 0: surface values only, one application of P^4 per sublayer (fast path);
+// MODE 0: surface values only, one application of the closed-form P^(4 nreg) per layer (fast path's fit);
 // MODE 1: surface values only, four applications of P per sublayer - bit-identical to what MODE 2
 //         computes, which the robust path needs (see group_rayleigh);
 // MODE 2: energy integrals.  two_vec = false: z[] is the combined solution itself (fast path);
@@ -2240,15 +2317,14 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
         q.a34 = 1.0f / xmu;
         q.a42 = -q.a13;
         q.a43 = q.a21 + 4.0f * wvnosq * xmu * (xlamb + xmu) * q.a12;
-        const RProp P = make_prop(q);
         if (MODE == 0) {
-            const RProp P4 = prop_sq(prop_sq(P));
-            for (int s = 0; s < nreg; ++s) {
-                if (do_y) prop_apply(P4, y);
-                prop_apply(P4, z);
-            }
+            const RBase L = make_base(q);
+            const RProp Pm = pow_expand(L, pow_sublayers(L, nreg));   // all nreg sublayers at once
+            if (do_y) prop_apply(Pm, y);
+            prop_apply(Pm, z);
             continue;
         }
+        const RProp P = make_prop(q);
         if (MODE == 1) {
             for (int s = 0; s < nreg; ++s) {
 #pragma unroll
@@ -2341,6 +2417,12 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
     }
 }
 
+#ifdef SD_COUNT_RESTARTS
+// development build (make variant EXTRA=-DSD_COUNT_RESTARTS, scripts/restart_count.py): lanes and wavefronts whose fast fit
+// restarts, read with surfdisp_dev_restart_count
+__device__ unsigned long long sd_restart_count[2];
+#endif
+
 template <bool KERN = false>
 SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int b, int n,
                                 float T, float c, float ratio, double *dbg = nullptr,
@@ -2424,7 +2506,8 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     double y[4], z[4];
     double xnorm = 0.0, bbn = 1.0;
     // Surface fit (surfa.f:1056-1069) + one refinement (restart solution 2 from the combined start
-    // vector, surfa.f:990-998).  STEP = 0: P^4 per sublayer; STEP = 1: step by step.
+    // vector, surfa.f:990-998).  STEP = 0: closed-form P^(4 nreg) per layer, and the restart by linearity instead of a
+    // second sweep; STEP = 1: step by step, restart re-integrated (bit-consistent with the robust path's MODE 2 sweep).
     auto fit = [&](auto step_tag) -> double {
         constexpr int STEP = decltype(step_tag)::value;
         for (int i = 0; i < 4; ++i) { y[i] = y0[i]; z[i] = z0[i]; }
@@ -2440,10 +2523,23 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         bbn = bb;
         const float ampur = (float)((xnorm * yt0 + z[0]) / bb);
         const float xtest = fabsf(ampur / ratio - 1.0f);
+#if defined(SD_COUNT_RESTARTS) && defined(__HIP_DEVICE_COMPILE__)
+        if (STEP == 0) {                                              // development count: restarting lanes, wavefronts
+            const unsigned long long m = __ballot(xtest >= 0.00001f);
+            if (m && (__lane_id() == __ffsll(__ballot(1)) - 1)) atomicAdd(&sd_restart_count[1], 1ull);
+            if (xtest >= 0.00001f) atomicAdd(&sd_restart_count[0], 1ull);
+        }
+#endif
         if (xtest >= 0.00001f) {
-            for (int i = 0; i < 4; ++i) { z0[i] = z0[i] + xnorm * y0[i]; z[i] = z0[i]; }
-            rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                 y, z, false, 0.0, 1.0, acc);
+            for (int i = 0; i < 4; ++i) z0[i] = z0[i] + xnorm * y0[i];
+            if (STEP == 0) {
+                // the RK4 map is linear: re-integrating z0 + xnorm y0 gives z + xnorm y at the surface
+                for (int i = 0; i < 4; ++i) z[i] = z[i] + xnorm * y[i];
+            } else {
+                for (int i = 0; i < 4; ++i) z[i] = z0[i];
+                rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, false, 0.0, 1.0, acc);
+            }
             aa = z[0] - ratio * z[1];
             bb = ratio * yt1 - yt0;
             if (fabs(bb) < 1.e-10) bb = copysign(1.e-10, bb);
@@ -3195,3 +3291,17 @@ hipError_t launch_group(hipStream_t s, int kind, const GroupArgs &a_in)
 
 }  // namespace sd
 
+
+#ifdef SD_COUNT_RESTARTS
+// development build only: read (and with reset != 0 clear) the restart counts {lanes, wavefronts}
+extern "C" int surfdisp_dev_restart_count(unsigned long long *out2, int reset)
+{
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(out2, HIP_SYMBOL(sd::sd_restart_count), 2 * sizeof(unsigned long long));
+    if (e == hipSuccess && reset) {
+        const unsigned long long z[2] = {0, 0};
+        e = hipMemcpyToSymbol(HIP_SYMBOL(sd::sd_restart_count), z, sizeof(z));
+    }
+    return (int)e;
+}
+#endif
