@@ -311,8 +311,25 @@ __device__ __forceinline__ float rcp_nr(float x)
     return fmaf(r, fmaf(-x, r, 1.0f), r);
 }
 __device__ __forceinline__ float sqrt_hw(float x) { return __builtin_amdgcn_sqrtf(x); }
+// v_rsq_f32 and v_exp_f32.  The host versions only let a CPU test compile layer_coef (tests/hostcheck/lcoefcheck.hip).
+SD_HD __forceinline__ float rsq_hw(float x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_rsqf(x);
+#else
+    return 1.0f / sqrtf(x);
+#endif
+}
+SD_HD __forceinline__ float exp2_hw(float x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_exp2f(x);
+#else
+    return exp2f(x);
+#endif
+}
 // sinh(x), cosh(x): 0.5 e^x and 0.5 e^-x straight from v_exp_f32 (the 0.5 folded into the exponent)
-__device__ __forceinline__ void sinhcosh_sp(float x, float *sh, float *ch)
+SD_HD __forceinline__ void sinhcosh_sp(float x, float *sh, float *ch)
 {
     // no low-order correction of x log2(e): e^x and e^-x then carry relative errors +-|x| 9e-8, which for |x| > 1 is a
     // common scale factor of sinh and cosh (the secular function's root does not move) - root search 6 % faster
@@ -326,11 +343,14 @@ __device__ __forceinline__ void sinhcosh_sp(float x, float *sh, float *ch)
     // against the exact kernel 5.4e-6 -> 1.2e-5, one sediment fixture entry 5.5e-5; made safe (kink test, unscaled
     // values for NEVILL, overflow cue from the product of the factors) the gain was gone (profiles/r02e/ab_experiments.txt).
     const float t = x * 1.44269502e+00f;
-    const float p = __builtin_amdgcn_exp2f(t - 1.0f), q = __builtin_amdgcn_exp2f(-t - 1.0f);
+    const float p = exp2_hw(t - 1.0f), q = exp2_hw(-t - 1.0f);
     *sh = p - q;
     *ch = p + q;
 }
-__device__ __forceinline__ void sincos_cw(float x, float *sn, float *cs)
+// The quadrant n picks sin or cos of the reduced argument (one compare, two selects) and flips their signs by an XOR of the
+// sign bit: sin for n = 2, 3 (mod 4), cos for n = 1, 2.  Odd in x to the bit for every x != 0 (rint, the reduction and ps
+// are odd, pc even, and n -> -n swaps the signs as sin and cos do) - layer_coef relies on it.
+SD_HD __forceinline__ void sincos_cw(float x, float *sn, float *cs)
 {
     const float TWO_OVER_PI = 6.36619747e-01f;
     const float P1 = 1.57079601e+00f, P2 = 3.13916473e-07f, P3 = 5.39030253e-15f;   // pi/2 split (Cody-Waite)
@@ -346,8 +366,8 @@ __device__ __forceinline__ void sincos_cw(float x, float *sn, float *cs)
                     r2 * r2, fmaf(-0.5f, r2, 1.0f));
     const float s0 = (n & 1) ? pc : ps;
     const float c0 = (n & 1) ? ps : pc;
-    *sn = (n & 2) ? -s0 : s0;
-    *cs = ((n + 1) & 2) ? -c0 : c0;
+    *sn = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, s0) ^ ((uint32_t)(n & 2) << 30));
+    *cs = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, c0) ^ ((uint32_t)((n + 1) & 2) << 30));
 }
 
 // The working stack's derived per-layer values (W_IR, W_IA2, W_IB2), one expression each, shared by the root search's
@@ -366,15 +386,21 @@ __device__ __forceinline__ float wk_ilove(const float rho, const float b) { retu
 //      ph = x where oscillatory, else 0                         sinr = sinh(x) / r, cs = cosh x, surfa.f:263-279)
 // |arg| is clamped away from zero: c == v to the last bit then runs through the oscillatory formulas with r = 1e-15, which
 // give the degenerate values (rsin = 0, sinr = k d, cs = 1) to 1e-15 - no separate branch.
+// r = copysign(|r|, -arg), but each branch takes the sign from what it knows rather than from a bit-insert before the branch:
+// evanescent, r < 0 and the negations ride on the products as source modifiers; oscillatory, r > 0 except at arg = +0 (and
+// a NaN with a clear sign bit), and rsin, sinr and cs are even in r (sincos_cw is odd), so they are evaluated at k d |r| and
+// only r, x and ph - which the default root search does not use - pay for the sign.  Bit for bit the values of the form
+// with r signed before the branch wherever k d |r| != 0 (tests/test_layer_coef_bits.py); k d |r| = 0 needs a layer of zero
+// thickness, which the prep kernel rejects.
 struct LCoef { float r, rsin, sinr, cs, x, ph; };
-__device__ __forceinline__ LCoef layer_coef(const float arg, const float wd)
+SD_HD __forceinline__ LCoef layer_coef(const float arg, const float wd)
 {
-    const float xs = fmaxf(fabsf(arg), 1.0e-30f), y = __builtin_amdgcn_rsqf(xs);
-    const float r = copysignf(xs * y, -arg), ir = copysignf(y, -arg);   // r = x rsq(x) to ~1.5 ulp; < 0: evanescent
+    const float xs = fmaxf(fabsf(arg), 1.0e-30f), y = rsq_hw(xs);
+    const float ra = xs * y;                                    // |r| = x rsq(x) to ~1.5 ulp
     LCoef o;
-    o.r = r;
-    o.x = wd * r;
     if (arg > 0.0f) {
+        o.r = -ra;
+        o.x = wd * o.r;
         float sh, ch; sinhcosh_sp(o.x, &sh, &ch);
         // sinh of a small argument: the difference of the two exponentials carries their absolute error (~6e-8), i.e. a
         // relative error 6e-8 / |x| that sinr = sinh(x) / r passes on - 1 % one float below a thin layer's velocity, a jump
@@ -383,11 +409,13 @@ __device__ __forceinline__ LCoef layer_coef(const float arg, const float wd)
         const float x2 = o.x * o.x;
         const float shs = fmaf(o.x * x2, fmaf(x2, 8.33333333e-3f, 1.66666667e-1f), o.x);
         if (fabsf(o.x) < 0.25f) sh = shs;
-        o.rsin = -r * sh; o.sinr = sh * ir; o.cs = ch;
+        o.rsin = ra * sh; o.sinr = sh * -y; o.cs = ch;
         o.ph = 0.0f;
     } else {
-        float sn, cs; sincos_cw(o.x, &sn, &cs);
-        o.rsin = r * sn; o.sinr = sn * ir; o.cs = cs;
+        o.r = copysignf(ra, -arg);
+        o.x = wd * o.r;
+        float sn, cs; sincos_cw(wd * ra, &sn, &cs);
+        o.rsin = ra * sn; o.sinr = sn * y; o.cs = cs;
         o.ph = o.x;
     }
     return o;
@@ -458,9 +486,13 @@ __device__ __forceinline__ RState ray_start(const RTrial &t, const int start, co
 #ifndef SD_RCERT
 #define SD_RCERT 1              // 1: the Rayleigh FAST instantiations (opt-in, SURFDISP_FASTSCAN) are the count-guided scan; 0: the r01
 #endif                          // heuristic scan; 2: the first attempt (interface-only count; profiles/r04a/rayleigh_count.txt)
-template <bool FIRST, bool CERT = false>
+// mid(0) and mid(1): called once the step has read all of the layer's values and again after the P coefficients - where the
+// single-register-set loop of delta_rayleigh issues the next layer's loads into the registers the step has freed (not
+// called by a liquid top layer)
+struct NoMid { __device__ void operator()(int) const {} };
+template <bool FIRST, bool CERT = false, class Mid = NoMid>
 __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr &y, const int start, float &phi, int *kc = nullptr,
-                                         bool *kunc = nullptr)
+                                         bool *kunc = nullptr, const Mid &mid = Mid())
 {
     float b1 = s.b1, h2 = s.h2, h3 = s.h3, h4 = s.h4, h5 = s.h5;
     const float wvno = t.wvno, csq = t.csq, icsq = t.icsq;
@@ -485,10 +517,13 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
         s.b1 = n1; s.h2 = n2; s.h3 = 0.0f; s.h4 = 0.0f; s.h5 = n5;
         return;
     }
+    mid(0);
     const float argb = fmaf(-csq, ib2, 1.0f);
     const float g = 2.0f * (sv * sv) * icsq;
     const float g1 = g - 1.0f;
-    const LCoef P = layer_coef(arga, wd), Q = layer_coef(argb, wd);   // surfa.f:263-279
+    const LCoef P = layer_coef(arga, wd);                              // surfa.f:263-279
+    mid(1);
+    const LCoef Q = layer_coef(argb, wd);
     const float rsinp = P.rsin, sinpr = P.sinr, cosp = P.cs;
     const float rsinq = Q.rsin, sinqr = Q.sinr, cosq = Q.cs, qm = Q.x;
     phi += P.ph;
@@ -646,11 +681,18 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
         // set in flight: their wavefronts share SIMDs with the group-velocity kernel's (168 VGPRs), and three of them
         // fit beside one of those only while 3 x VGPRs + 168 <= 512 (101 this way; measured at 120: the three-batch
         // headline drops 7 %, profiles/r02e/ab_experiments.txt)
+        // Layer m+1's values are loaded field by field once layer m's are no longer needed: d and 1/a^2 as soon as the step
+        // has read the layer, 1/b^2 after the P coefficients, b and rho(m)/rho(m+1) after the update.  Each load is in flight
+        // for a whole layer and lands in the registers of the field it replaces (loaded all at once at the top of the loop,
+        // four values had to be copied at every layer).
         while (m + 1 <= last) {
-            const RLyr Bq = load(m + 1);
-            if (CERT && count) ray_step<false, true>(s, t, A, start, phi, kc, kunc); else ray_step<false>(s, t, A, start, phi);
-            A = Bq;
-            m += 1;
+            const int n = m + 1;
+            auto mid = [&](int stage) {
+                if (stage == 0) { A.d = W_D(n); A.ia2 = W_IA2(n); } else { A.ib2 = W_IB2(n); }
+            };
+            if (CERT && count) ray_step<false, true>(s, t, A, start, phi, kc, kunc, mid); else ray_step<false>(s, t, A, start, phi, nullptr, nullptr, mid);
+            A.sv = W_B(n); A.rat = W_IR(n);
+            m = n;
         }
     }
     if (m < last) {
