@@ -39,6 +39,7 @@ struct EnvKnobs {
     int balance = -1;             // SURFDISP_BALANCE (developer knob): wavefront priority by progress, -1 = automatic
     int lockstep = -1;            // SURFDISP_LOCKSTEP (developer knob): -1 = automatic (on), 0 / 1, 2 = also for (stack, period) units
     int certscan = 1;             // SURFDISP_CERTSCAN (developer knob): 0 = Love root searches walk every grid point (no certified skipping)
+    int leanscan = 1;             // SURFDISP_LEANSCAN (developer knob): 0 = pure scan passes take the general pass body too
     int host_slots = 3;           // SURFDISP_HOST_SLOTS (developer knob): chunks in flight of a large host-buffer call (2 or 3)
     long host_chunk_layers = 327680;   // SURFDISP_HOST_CHUNK (developer knob): layers' worth of stacks per chunk
     int host_pipeline = 1;        // SURFDISP_HOST_PIPELINE (developer knob): 0 = large host-buffer calls as one chunk
@@ -70,6 +71,7 @@ struct EnvKnobs {
         if (const char *e = getenv("SURFDISP_LOCKSTEP")) lockstep = atoi(e);
         if (const char *e = getenv("SURFDISP_HOST_PIPELINE")) host_pipeline = atoi(e);
         if (const char *e = getenv("SURFDISP_CERTSCAN")) certscan = atoi(e);
+        if (const char *e = getenv("SURFDISP_LEANSCAN")) leanscan = atoi(e);
         if (const char *e = getenv("SURFDISP_HOST_SLOTS")) host_slots = atoi(e);
         if (const char *e = getenv("SURFDISP_HOST_CHUNK")) { host_chunk_layers = atol(e); if (host_chunk_layers < 1024) host_chunk_layers = 1024; }
     }
@@ -417,6 +419,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     ph.hist = (ell_k || ell_fix) ? w.hist : nullptr;
     ph.lockstep = kn.lockstep >= 0 ? kn.lockstep : 1;
     ph.ambig = kn.ambig; ph.phimulti = kn.phimulti; ph.amb_count = w.amb_count; ph.ell_ambig = ell_fix ? kn.ell_ambig : 0.0f; ph.ell_gmax = kn.ell_gmax;
+    ph.scan_general = kn.leanscan ? 0 : 1;
     SD_HIP(sd::launch_phase(s, kind, G, indep, ph));
     // the exact fallback re-solves what the production kernel listed (normally nothing: idle blocks exit at once)
     ph.overlap = 0; ph.fast = 0;

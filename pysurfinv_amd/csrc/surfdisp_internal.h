@@ -60,6 +60,7 @@ struct PhaseArgs {
     int *amb_count;       // nullptr, or [2]: number of scan trials / of ellipticities evaluated again (statistics)
     float ell_ambig;      // in-kernel ellipticity passes: a closure below this fraction of its terms marks the pair for the ellipticity kernel
     float ell_gmax;       // ... and so does g = 2 b^2 / c^2 of the stack's fastest layer beyond this
+    int scan_general;     // 1: pure scan passes also run the general pass body (SURFDISP_LEANSCAN=0, for A/B and the tests)
 #ifdef SD_WAVECLOCK
     unsigned long long *wclk;   // developer build: [waves][2] s_memrealtime at wavefront start / end
 #endif

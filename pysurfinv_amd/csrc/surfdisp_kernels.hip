@@ -964,6 +964,11 @@ __device__ __forceinline__ int drop_layers(const float *wq, const int LS, const 
     return mm < 2 ? 2 : mm;
 }
 
+// the other lane of a two-lane team (lane ^ 1): one DPP move (quad_perm [1,0,3,2]) instead of an LDS permute and its wait.
+// Every lane of the wavefront must be active.
+__device__ __forceinline__ int pair_swap(int x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xF, 0xF, true); }
+__device__ __forceinline__ float pair_swap(float x) { return __int_as_float(pair_swap(__float_as_int(x))); }
+
 // ================================================================================== K1: phase
 // ST_WREF / ST_WEND (lock step, see PhaseArgs::lockstep): a team that has its bracket / its root waits for the other teams
 // of its wavefront, so that the refine pass and the end-of-period block run ONCE per period for all of them
@@ -1250,6 +1255,17 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
 
     int wprio = -1;
     const bool LOCK = !EXACT && (INDEP ? A.lockstep >= 2 : A.lockstep != 0);
+    // Pure scan passes (every team of the wavefront scans, waits for the refine pass or is done: nine passes in ten) take
+    // a lean body after the evaluation - the crossing and guard tests, one permute per value instead of fifteen, and only
+    // the bracket / carry bookkeeping of the scan branch below, with the same values and decisions.  Default scan of two-lane
+    // teams only (the headline's pipelined launch: root search 1.39 -> 1.36 ms, profiles/r08a); teams of 4 .. 32 lanes
+    // gained nothing measurable from it and the deep-stack c5 leg lost 1 % to the larger kernel, 64 lanes lost a wavefront per
+    // SIMD (Love: six more VGPRs).
+#if defined(SD_AMBIG) || defined(SD_DEBUG_TRIALS)
+    constexpr bool LEAN = false;
+#else
+    constexpr bool LEAN = !FAST && !EXACT && !INDEP && (G == 2);
+#endif
     // NEVILL's prologue, surfa.f:12-16, from the scan's bracket (del1 is the scan's value, whatever layer dropping it was computed
     // with - as in the reference)
     auto nevill_start = [&]() {
@@ -1281,6 +1297,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 else __builtin_amdgcn_s_setprio(0);
             }
         }
+        const bool lean = LEAN && !OVERLAP && A.scan_general == 0 && __all(st == ST_SCAN || st == ST_WREF || st == ST_DONE);
         // ---------------------------------------------------------------- choose the trial point
         float cj = 1.0f;
         int mmj = 2, start = 1;
@@ -1413,6 +1430,83 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
 #ifdef SD_WAVECLOCK
         wcyc_eval += __builtin_readcyclecounter() - we0;
 #endif
+        if (lean) {
+            // ------------------------------------------------------------ lean scan pass (see LEAN)
+            // What the general body below does for ST_SCAN, ST_WREF and ST_DONE teams, and nothing else.  Per team, the lane q
+            // whose trial is kept: the first one with a crossing or the guard (bracket: q and the trial before it), else the
+            // last one (the carry).  Teams of two read the other lane with DPP; q and the trial before it are then both in
+            // hand.  (Other team sizes, if enabled above: they permute from lane - 1 and from q.)
+            const bool scan = (st == ST_SCAN);
+            auto negnan = [](float x) { return signbit(x) && !(x != x); };   // (as below)
+            float oc = cj, od = val; int omm = mmj;            // G == 2: the other lane of the team
+            float sc = p0c, sv_ = p0d; int smm = p0mm;         // the previous lane's trial
+            if (G == 2) {
+                oc = pair_swap(cj); od = pair_swap(val); omm = pair_swap(mmj);
+                sc = oc; sv_ = od; smm = omm;
+            } else if (G > 2) {
+                const int lm1 = (lane + 63) & 63;
+                sc = __shfl(cj, lm1); sv_ = __shfl(val, lm1); smm = __shfl(mmj, lm1);
+            }
+            const float pc = (j == 0) ? p0c : sc, pd = (j == 0) ? p0d : sv_;
+            const int pmm = (j == 0) ? p0mm : smm;
+            const bool has_prev = !(first && j == 0);
+            const bool cross = has_prev && (negnan(val) != negnan(pd));
+            bool guard = false;
+            if (scan && has_prev && !cross)                    // calcul.f:165-166
+                guard = (cj < 0.8f * b1top) || !(cj < W_B(mmj - 1) + 0.3f);
+            const unsigned long long em = __ballot(scan && (cross || guard)) & tmask;
+            const int fl = em ? (__ffsll((long long)em) - 1) : -1;
+            const int q = (fl < 0) ? tbase + G - 1 : fl;
+            const bool q_cross = ((__ballot(cross) >> q) & 1ull) != 0ull;
+            float q_c, q_d, q_pc, q_pd;
+            int q_mm, q_pmm;
+            if (G == 1) {
+                q_c = cj; q_d = val; q_mm = mmj; q_pc = pc; q_pd = pd; q_pmm = pmm;
+            } else if (G == 2) {
+                const bool mine = (q == lane), q_lo = (q == tbase);
+                q_c = mine ? cj : oc; q_d = mine ? val : od; q_mm = mine ? mmj : omm;
+                q_pc = q_lo ? p0c : ((j == 0) ? cj : oc);     // before the team's second lane: its first
+                q_pd = q_lo ? p0d : ((j == 0) ? val : od);
+                q_pmm = q_lo ? p0mm : ((j == 0) ? mmj : omm);
+            } else {
+                q_c = __shfl(cj, q); q_d = __shfl(val, q); q_mm = __shfl(mmj, q);
+                q_pc = __shfl(pc, q); q_pd = __shfl(pd, q); q_pmm = __shfl(pmm, q);
+            }
+            if (scan && ((__ballot(scan && !fin(val)) & tmask) != 0ull)) defer = true;   // -> exact fallback kernel
+            bool failed = false;
+            if (scan) {
+                ++passes;
+                if (fl >= 0 && q_cross) {                      // bracket found -> refine (see the general body)
+                    p0c = q_pc; p0d = q_pd; cb = q_c; db = q_d; mm_frozen = q_mm; p0mm = q_pmm;
+                    p0ok = (q_pmm == q_mm);
+                    passes = 0;
+                    st = LOCK ? ST_WREF : ST_REFINE;
+#ifndef SD_NO_PHASEMULTI
+                    if (!LOCK && bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
+#endif
+                } else if (fl >= 0) {
+                    failed = true;                             // label 250
+                } else {
+                    p0c = q_c; p0d = q_d; p0mm = q_mm; first = false;
+                    if (passes > 100000) failed = true;
+                }
+            }
+            if (defer) {
+                if (j == 0) A.fb_list[atomicAdd(A.fb_count, 1)] = (int)tg;
+                defer = false; st = ST_DONE; failed = false;
+            }
+            if (failed) {
+                status = (k == 0) ? SURFDISP_NOROOT : SURFDISP_PARTIAL;
+                st = ST_DONE;
+            }
+            if (LOCK && !__any(st == ST_SCAN) && st == ST_WREF) {   // (no team ends its period in a scan pass)
+                st = ST_REFINE;
+#ifndef SD_NO_PHASEMULTI
+                if (bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
+#endif
+            }
+            continue;
+        }
         // ---------------------------------------------------------------- team-level decisions
         const int lm1 = (lane + 63) & 63;
         const float sc = __shfl(cj, lm1), sv_ = __shfl(val, lm1);
@@ -1518,9 +1612,9 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         const int l_Kp = CERT ? __shfl(kpk, lastl) : 0;
         const int e_pKp = CERT ? __shfl(pKp, src) : 0;
         // the values of the team's first two lanes: the two ellipticity recursions, and NEVILL's del3 (every lane of the team
-        // evaluated the same c3) - only where some team of the wavefront needs them
+        // evaluated the same c3) - only where some team of the wavefront needs them (not in a scan or refine pass of a c+U call)
         float v0 = 0.0f, v1 = 0.0f;
-        if (__any(want_ratio || st == ST_NEVILL || st == ST_NEVILL0)) { v0 = __shfl(val, tbase); v1 = __shfl(val, (G > 1) ? tbase + 1 : tbase); }
+        if (__any(st == ST_ELLIP || st == ST_NEVILL || st == ST_NEVILL0 || (OVERLAP && ell_pend && st == ST_SCAN))) { v0 = __shfl(val, tbase); v1 = __shfl(val, (G > 1) ? tbase + 1 : tbase); }
         // what only a REFINE pass reads (wavefront-uniform test: in lock step most passes have no refining team):
         // the right neighbour of the crossing lane, the lane before the last one, and - the fourth point of the second
         // three-point estimate - two lanes below / above the crossing lane and two before the last one
