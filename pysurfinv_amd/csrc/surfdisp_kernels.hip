@@ -2407,6 +2407,37 @@ SD_HD __forceinline__ void prop_apply(const RProp &P, double v[4])
     v[3] = fma(P.p21.c, ur, fma(P.p21.d, tz, fma(P.p22.c, uz, P.p22.d * tr)));
 }
 
+// Sublayers of the fast path's energy-integral sweep.  The reference splits every layer into ndiv = min(5, 99/(n-1))
+// sublayers of 4 RK4 steps whatever the layer's wavelength (surfa.f:781-822); the fast path (combined solution, one
+// 4-vector) integrates a layer's depth H in n' <= nreg equal sublayers, the fewest with lambda h <= SD_GROUP_LAMH,
+// h = H / (4 n') the RK4 step and lambda = k max(|1 - c^2/a^2|, |1 - c^2/b^2|)^(1/2) the layer's largest |eigenvalue|.
+// Error per step (fp32 knots: integrands rounded to 6e-8 relative):
+//   RK4, local:  (lambda h)^5 / 120                     0.05: 2.6e-9   (<= 20 steps per layer: <= 5e-8)
+//   Boole, one sublayer of an e^(2 lambda z) integrand:  (8/945) (2 lambda h)^6 / 4 = 0.135 (lambda h)^6   0.05: 2.1e-9
+// both below the fp32 rounding of a single knot's integrand.  (lambda H)^2 = H^2 max(|k^2 - w^2/a^2|, |k^2 - w^2/b^2|)
+// from the step's own coefficients (a21 = -w^2 rho, a12 = 1/(rho a^2), a34 = 1/(rho b^2)): no square root, no division.
+// A layer that needs all nreg sublayers keeps the reference's step bit for bit.  SD_GROUP_LAMH <= 0: the reference's
+// split everywhere.  The fast path's fit (MODE 0) steps the same split as its sweep (own = true in both, group_rayleigh);
+// the robust path (MODE 1 and the two-vector sweep) keeps the reference's split.
+#ifndef SD_GROUP_LAMH
+#define SD_GROUP_LAMH 0.05f
+#endif
+#ifndef SD_GROUP_OWN_CANCEL
+#define SD_GROUP_OWN_CANCEL 1.0e5    // largest fit cancellation at which the fast path keeps its own split (group_rayleigh)
+#endif
+SD_HD __forceinline__ int fast_sublayers(const RCoef &q, float wvnosq, float dsub, int nreg)
+{
+    if (!(SD_GROUP_LAMH > 0.0f)) return nreg;
+    const float lam2 = fmaxf(fabsf(fmaf(q.a21, q.a12, wvnosq)), fabsf(fmaf(q.a21, q.a34, wvnosq)));
+    const float H = dsub * (float)nreg;
+    const float x = lam2 * H * H;                                     // (lambda H)^2
+    constexpr float t = 16.0f * SD_GROUP_LAMH * SD_GROUP_LAMH;        // (4 lambda h)^2 at the bound, n' = 1
+    int m = 1;
+#pragma unroll
+    for (int i = 1; i < 5; ++i) m += (x > t * (float)(i * i)) ? 1 : 0;
+    return m < nreg ? m : nreg;
+}
+
 // integrate both solutions from the half space to the surface.  INTEG = false: only the surface
 // values are wanted, so a layer is one application of P^(4 nreg).  INTEG = true: step by step, and
 // accumulate the Boole energy integrals of the combined solution (xnorm*y + z)/bb
@@ -2422,9 +2453,10 @@ template <int MODE, bool KERN = false>
 SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t fs, int B, int b,
                                                int n, float lnT, int ndiv, bool water, float div,
                                                const Drop dr, float wvno, float wvnosq, float omegsq,
-                                               double y[4], double z[4], bool do_y,
+                                               double y[4], double z[4], bool do_y, bool own,
                                                double xnorm, double bbn, RInt &acc,
-                                               const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float cw = 0.0f, K3 *hold = nullptr)
+                                               const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float cw = 0.0f, K3 *hold = nullptr,
+                                               bool *shorter = nullptr)
 {
 #pragma clang fp contract(off)   // both sweeps must see identical coefficients
     LayerRaw nraw = layer_load(mdl, fs, (size_t)dr.hs_layer * B + b);
@@ -2439,13 +2471,12 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
             if (MODE == 2 && KERN && jl > 0) ko.put(jl, 0.0f, 0.0f, 0.0f);   // (the top layer's entry: group_rayleigh)
             continue;
         }
-        const float dsub = (ndiv > 1 && !(jl == 0 && water)) ? v.d / div : v.d;
+        float dsub = (ndiv > 1 && !(jl == 0 && water)) ? v.d / div : v.d;
         const float xmu = v.rho * v.b * v.b;                         // surfa.f:831-832
         const float xlamb = v.rho * (v.a * v.a - 2.0f * v.b * v.b);
         KC kc{};
         if (MODE == 2 && KERN) kc = kern_coef(raw, v, lnT, jl == n - 1, cw, ko.raw != 0);
         RCoef q;
-        q.ddz = -dsub / (4.0f * 1.0f);
         q.a12 = 1.0f / (xlamb + 2.0f * xmu);
         q.a13 = wvno * xlamb * q.a12;
         q.a21 = -omegsq * v.rho;
@@ -2453,9 +2484,21 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
         q.a34 = 1.0f / xmu;
         q.a42 = -q.a13;
         q.a43 = q.a21 + 4.0f * wvnosq * xmu * (xlamb + xmu) * q.a12;
+        int nstep = nreg;                                            // sublayers this sweep steps through the layer
+        if (MODE != 1 && own) {                                      // fast path (its fit and its sweep): its own split
+            nstep = fast_sublayers(q, wvnosq, dsub, nreg);
+            if (nstep < nreg) {
+                dsub = (dsub * (float)nreg) / (float)nstep;
+                if (shorter) *shorter = true;                        // (the fit: some layer left the reference's split)
+            }
+        }
+#ifdef SD_SPLIT_PROBE
+        if (MODE == 2 && !do_y) SD_SPLIT_PROBE(nreg, nstep);         // host test builds only (tests/hostcheck/splitcheck.hip)
+#endif
+        q.ddz = -dsub / (4.0f * 1.0f);
         if (MODE == 0) {
             const RBase L = make_base(q);
-            const RProp Pm = pow_expand(L, pow_sublayers(L, nreg));   // all nreg sublayers at once
+            const RProp Pm = pow_expand(L, pow_sublayers(L, nstep));  // all the layer's sublayers at once
             if (do_y) prop_apply(Pm, y);
             prop_apply(Pm, z);
             continue;
@@ -2510,7 +2553,7 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
 #endif
             }
         };
-        for (int s = 0; s < nreg; ++s) {
+        for (int s = 0; s < nstep; ++s) {
             // bottom knot: the top knot of the sublayer below when it belongs to the same layer
             if (s == 0) knot(4);
             else { f_mr[4] = f_mr[0]; f_mz[4] = f_mz[0]; f_rz[4] = f_rz[0]; f_zr[4] = f_zr[0];
@@ -2644,11 +2687,12 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     // Surface fit (surfa.f:1056-1069) + one refinement (restart solution 2 from the combined start
     // vector, surfa.f:990-998).  STEP = 0: closed-form P^(4 nreg) per layer, and the restart by linearity instead of a
     // second sweep; STEP = 1: step by step, restart re-integrated (bit-consistent with the robust path's MODE 2 sweep).
-    auto fit = [&](auto step_tag) -> double {
+    bool shorter = false;                                             // (the fast fit left the reference's split somewhere)
+    auto fit = [&](auto step_tag, bool own) -> double {
         constexpr int STEP = decltype(step_tag)::value;
         for (int i = 0; i < 4; ++i) { y[i] = y0[i]; z[i] = z0[i]; }
         rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                             y, z, true, 0.0, 1.0, acc);
+                             y, z, true, own, 0.0, 1.0, acc, KOut{nullptr, 1, 0, 0, 0}, 0.0f, nullptr, &shorter);
         const double yt0 = y[0], yt1 = y[1];
         double aa = z[0] - ratio * z[1];
         double bb = ratio * yt1 - yt0;
@@ -2674,7 +2718,7 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
             } else {
                 for (int i = 0; i < 4; ++i) z[i] = z0[i];
                 rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                     y, z, false, 0.0, 1.0, acc);
+                                     y, z, false, false, 0.0, 1.0, acc);
             }
             aa = z[0] - ratio * z[1];
             bb = ratio * yt1 - yt0;
@@ -2689,7 +2733,19 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         return fmax(fmax(fabs(yt0), fabs(yt1)), fmax(fabs(z[0]), fabs(z[1]))) / fabs(bbn);
     };
     const double z0_orig[4] = {z0[0], z0[1], z0[2], z0[3]};
-    const double cancel = fit(std::integral_constant<int, 0>{});
+    // The fast path's fit and sweep step its own split (fast_sublayers) together: the combined start vector is fitted
+    // with the propagator that then integrates it.  Its split differs from the reference's by the RK4 error of the
+    // growth factors, and the fit's cancellation amplifies that difference (measured on high-contrast stacks: U within
+    // 7e-7 of the reference's split up to cancel 1e6, 2e-4 between 1e6 and 1e7): above SD_GROUP_OWN_CANCEL the fit is
+    // redone in the reference's split, which the sweep then steps too (unless no layer left it: the same fit).
+    bool own = SD_GROUP_LAMH > 0.0f;
+    double cancel;
+    for (;;) {
+        cancel = fit(std::integral_constant<int, 0>{}, own);
+        if (!own || !shorter || !(cancel > SD_GROUP_OWN_CANCEL) || cancel > 1.0e7) break;
+        own = false;
+        for (int i = 0; i < 4; ++i) z0[i] = z0_orig[i];
+    }
     if (dbg) { for (int i = 0; i < 4; ++i) { dbg[i] = y[i]; dbg[4 + i] = z[i]; } dbg[12] = dr.hs_layer; dbg[13] = dr.nreg_hs; dbg[14] = ndiv; dbg[8] = xnorm; dbg[9] = bbn; }
     // half-space analytic terms use the combined vector at the top of the half space
     float aur, auz;
@@ -2702,7 +2758,7 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         for (int i = 0; i < 4; ++i) { z[i] = (xnorm * y0[i] + z0[i]) / bbn; y[i] = 0.0; }
         aur = (float)z[0]; auz = (float)z[1];
         rayleigh_sweep<2, KERN>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                y, z, false, xnorm, bbn, acc, ko, cw, &hold);
+                                y, z, false, own, xnorm, bbn, acc, ko, cw, &hold);
     } else {
         // Robust path (thick structure / short period: the solutions grow by up to ~1e27 and the
         // rounding noise excited on the way up is far larger than the answer).  The reference stays
@@ -2711,12 +2767,12 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         // step, then step y and z again with bit-identical arithmetic (make_prop / prop_apply are
         // built with contraction off and explicit fma) and combine at every knot.
         for (int i = 0; i < 4; ++i) z0[i] = z0_orig[i];
-        (void)fit(std::integral_constant<int, 1>{});
+        (void)fit(std::integral_constant<int, 1>{}, false);
         for (int i = 0; i < 4; ++i) { y[i] = y0[i]; z[i] = z0[i]; }
         aur = (float)((xnorm * y0[0] + z0[0]) / bbn);
         auz = (float)((xnorm * y0[1] + z0[1]) / bbn);
         rayleigh_sweep<2, KERN>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                y, z, true, xnorm, bbn, acc, ko, cw, &hold);
+                                y, z, true, false, xnorm, bbn, acc, ko, cw, &hold);
     }
     if (wet && !any_solid) { aur = ratio; auz = 1.0f; }              // label 77777, surfa.f:1140-1144
     {   // label 7002, surfa.f:1145-1186
