@@ -294,6 +294,28 @@ int surfdisp_mcmc_accept_tree_device(void *stream, int C, int N, int P, int dept
                                      long row_stride, long step_stride, unsigned long long seed, unsigned long long counter,
                                      long chain0);
 
+/* Joint data - Rayleigh and Love, phase and group velocity (pysurfinv_amd.obsdata; added within ABI 4): the accept entries
+ * above with the misfit of several observed curves.  pred[4] = {cR, uR, cL, uL} (fp32 as the solver returns them, stack s's
+ * row at pred[k] + s * pred_stride[k]; NULL where absent; a wave type has data iff its phase array is given), nper[2] the
+ * periods of the Rayleigh / Love solve, status[2] their [stacks] status arrays (NULL: no check).  cols [Ptot][2] (device):
+ * per observation column the source array (0..3) and the period index in that solve (Ptot <= 800); weights [Ptot]; obs / uncer / mask
+ * [Ptot], or [C][Ptot] with obs_per_chain.  chi2 = sum over the columns in ascending order of w ((obs - pred) / uncer)^2 over
+ * the masked-in entries, N = their count, misfit = sqrt(chi2 / N), then the clamp and L of the plain entries.  (88888, 88888, 0)
+ * when a wave type with data has status != 0 or a phase velocity < 0.01 at any period of its solve, or when a group
+ * velocity a column reads is not >= 0.01 (NaN included), or a column names a missing array or a period beyond nper.  With
+ * one Rayleigh-phase column set of weight 1 (cols = (0, k)) every row equals surfdisp_mcmc_accept(_tree)_device's bit for bit. */
+int surfdisp_mcmc_accept_joint_device(void *stream, int C, int N, const float *const pred[4], const long pred_stride[4],
+                                      const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
+                                      const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                                      const double *p1, double *p0, double *chi0, double *row, long row_stride,
+                                      unsigned long long seed, unsigned long long counter, int first, long chain0);
+int surfdisp_mcmc_accept_tree_joint_device(void *stream, int C, int N, int depth, int nsteps, const float *const pred[4],
+                                           const long pred_stride[4], const int nper[2], const int *const status[2], int Ptot,
+                                           const int *cols, const double *weights, const double *obs, const double *uncer,
+                                           const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
+                                           double *row, long row_stride, long step_stride, unsigned long long seed,
+                                           unsigned long long counter, long chain0);
+
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular
  *          function that leaves the fp32 range (the reference's overflow points depend on how it forms its matrix

@@ -32,6 +32,7 @@ EXPORTS = (
     "surfdisp_events_elapsed_ms", "surfdisp_stream_wait_event", "surfdisp_params_to_model_device",
     "surfdisp_params_to_model_thermal_device", "surfdisp_thermal_scratch_bytes",
     "surfdisp_mcmc_propose_device", "surfdisp_mcmc_accept_device", "surfdisp_prior_device", "surfdisp_mcmc_propose_masked_device", "surfdisp_mcmc_propose_tree_device", "surfdisp_mcmc_accept_tree_device",
+    "surfdisp_mcmc_accept_joint_device", "surfdisp_mcmc_accept_tree_joint_device",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes","surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
@@ -135,6 +136,16 @@ def lib() -> ctypes.CDLL:
     L.surfdisp_mcmc_accept_tree_device.restype = ctypes.c_int
     L.surfdisp_mcmc_accept_tree_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
                                                    ctypes.c_int, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long, u64, u64, ctypes.c_long]
+    if hasattr(L, "surfdisp_mcmc_accept_joint_device"):        # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        vpp, lp, ipp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)
+        L.surfdisp_mcmc_accept_joint_device.restype = ctypes.c_int
+        L.surfdisp_mcmc_accept_joint_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vpp, lp, ipp, vpp, ctypes.c_int, vp, vp, vp, vp,
+                                                        vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_long, u64, u64, ctypes.c_int,
+                                                        ctypes.c_long]
+        L.surfdisp_mcmc_accept_tree_joint_device.restype = ctypes.c_int
+        L.surfdisp_mcmc_accept_tree_joint_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vpp, lp, ipp,
+                                                             vpp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp,
+                                                             ctypes.c_long, ctypes.c_long, u64, u64, ctypes.c_long]
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -671,6 +671,61 @@ int surfdisp_mcmc_accept_tree_device(void *stream, int C, int N, int P, int dept
     return SURFDISP_SUCCESS;
 }
 
+// Joint data (Rayleigh / Love, phase / group velocity): the accept entries above with the misfit summed over a column table.
+static int mcmc_accept_joint(const char *name, void *stream, int C, int N, const float *const pred[4], const long pred_stride[4],
+                             const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
+                             const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                             const double *p1, double *p0, double *chi0, double *row, long row_stride, long step_stride,
+                             unsigned long long seed, unsigned long long counter, int first, long chain0, int depth, int nsteps)
+{
+    bool ok = C >= 1 && N >= 1 && Ptot >= 1 && Ptot <= sd::SD_MCMC_JOINT_MAX_COLS && pred && pred_stride && nper && status && cols && weights && obs && uncer && mask &&
+              p1 && p0 && chi0 && chain0 >= 0 && depth >= 1 && depth <= sd::SD_MCMC_MAX_DEPTH && nsteps >= 1 && nsteps <= depth;
+    sd::McmcJointArgs j{};
+    for (int w = 0; ok && w < 2; ++w) {
+        j.nper[w] = nper[w];
+        j.status[w] = status[w];
+        if (!pred[2 * w] && pred[2 * w + 1]) ok = false;                  // a group array without the phase array of its solve
+        for (int k = 2 * w; ok && k < 2 * w + 2; ++k) {
+            j.pred[k] = pred[k];
+            j.pstride[k] = pred_stride[k];
+            if (pred[k] && (nper[w] < 1 || nper[w] > SURFDISP_NPER_MAX || pred_stride[k] < nper[w])) ok = false;
+        }
+    }
+    if (ok && !pred[0] && !pred[2]) ok = false;
+    if (!ok) {
+        set_err("%s: bad argument (1 <= nsteps <= depth <= 4, 1 <= Ptot <= 800, every given prediction array with 1 <= nper <= stride)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    j.cols = cols;
+    j.weights = weights;
+    j.a = sd::McmcAcceptArgs{C, N, Ptot, nullptr, nullptr, obs, uncer, mask, obs_per_chain ? 1 : 0, p1, p0, chi0, row, row_stride,
+                             seed, counter, first ? 1 : 0, chain0, depth, nsteps, step_stride};
+    SD_HIP(sd::launch_mcmc_accept_joint(static_cast<hipStream_t>(stream), j));
+    return SURFDISP_SUCCESS;
+}
+
+int surfdisp_mcmc_accept_joint_device(void *stream, int C, int N, const float *const pred[4], const long pred_stride[4],
+                                      const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
+                                      const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                                      const double *p1, double *p0, double *chi0, double *row, long row_stride,
+                                      unsigned long long seed, unsigned long long counter, int first, long chain0)
+{
+    return mcmc_accept_joint("surfdisp_mcmc_accept_joint_device", stream, C, N, pred, pred_stride, nper, status, Ptot, cols, weights,
+                             obs, uncer, mask, obs_per_chain, p1, p0, chi0, row, row_stride, 0, seed, counter, first, chain0, 1, 1);
+}
+
+int surfdisp_mcmc_accept_tree_joint_device(void *stream, int C, int N, int depth, int nsteps, const float *const pred[4],
+                                           const long pred_stride[4], const int nper[2], const int *const status[2], int Ptot,
+                                           const int *cols, const double *weights, const double *obs, const double *uncer,
+                                           const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
+                                           double *row, long row_stride, long step_stride, unsigned long long seed,
+                                           unsigned long long counter, long chain0)
+{
+    return mcmc_accept_joint("surfdisp_mcmc_accept_tree_joint_device", stream, C, N, pred, pred_stride, nper, status, Ptot, cols,
+                             weights, obs, uncer, mask, obs_per_chain, q, p0, chi0, row, row_stride, step_stride, seed, counter, 0,
+                             chain0, depth, nsteps);
+}
+
 // Measurement variant that does NOT synchronise: the caller owns four events per call
 // (surfdisp_events_create) which are recorded on the launch stream before prep, between the
 // kernels and after finish; durations are read later with surfdisp_events_elapsed_ms, after the

@@ -164,6 +164,7 @@ struct LayersArgs {
     double *scratch;       // [C][64][2] (vs, qs) of the thermal layer's grid points, or nullptr
 };
 constexpr int SD_MCMC_MAX_DEPTH = 4, SD_MCMC_MAX_NODES = (1 << SD_MCMC_MAX_DEPTH) - 1;
+constexpr int SD_MCMC_JOINT_MAX_COLS = 800;   // observation columns of the joint accept kernel: four curves of <= 200 periods
 struct McmcProposeArgs {
     int C, N;
     const double *p;        // [C][N] current parameters
@@ -195,8 +196,20 @@ struct McmcAcceptArgs {
     int depth, nsteps;      // speculative tree: walk nsteps <= depth steps (depth <= 1: the plain single test)
     long step_stride;       // doubles between the mcTrack rows of consecutive steps of one chain
 };
+// joint data (Rayleigh / Love, phase / group): the accept kernel's arguments plus the solves' predictions and the column table.
+// In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
+struct McmcJointArgs {
+    McmcAcceptArgs a;
+    const float *pred[4];   // cR, uR, cL, uL: [stacks][pstride[s]] or nullptr; a wave type has data iff its c array is given
+    long pstride[4];        // floats between the stacks' rows of each array
+    int nper[2];            // periods of the Rayleigh / Love solve
+    const int *status[2];   // [stacks] or nullptr
+    const int *cols;        // [Ptot][2]: source array (0..3), period index in that solve
+    const double *weights;  // [Ptot]
+};
 hipError_t launch_mcmc_propose(hipStream_t s, const McmcProposeArgs &a);
 hipError_t launch_mcmc_accept(hipStream_t s, const McmcAcceptArgs &a);
+hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a);
 hipError_t launch_layers(hipStream_t s, const LayersArgs &a, int L);
 hipError_t launch_prior(hipStream_t s, const LayersArgs &a, int L, const int *flags, double vs_max, int only_tag, int mark_tag, unsigned char *tags);
 hipError_t launch_thermal(hipStream_t s, const LayersArgs &a);

@@ -163,6 +163,111 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArg
     A.chi0[c] = chi0;
 }
 
+// Joint misfit of stack q (pysurfinv_amd/obsdata.py): chi2 = sum over the columns, in ascending order, of w ((obs - pred) / uncer)^2
+// over the masked-in entries, N = their count.  Failed: a wave type with data whose status is not 0 or whose phase velocity is
+// below 0.01 at any period of its solve, or a group velocity that a column reads that is not >= 0.01 (NaN included).  col[j]:
+// the block's copy of the column table in LDS, source << 16 | period index, or -1 for a column that names a missing array or a
+// period beyond its solve (it fails the model: no read out of bounds).  With one Rayleigh-phase data set of weight 1 this gives
+// misfit_of's bits (the same operations on the masked-in entries, an exact +0 for the others).  The loops are unrolled so that
+// one thread has several columns' loads in flight: at 100 chains the kernel is bound by the latency of those loads.
+__device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const int *col, const double *wt, size_t q, size_t ob,
+                                                double &mis, double &chi, double &L)
+{
+    const McmcAcceptArgs &A = J.a;
+    bool failed = false;
+    for (int w = 0; w < 2; ++w) {
+        const float *cw = J.pred[2 * w];
+        if (!cw) continue;
+        if (J.status[w] && J.status[w][q] != 0) failed = true;
+        cw += q * J.pstride[2 * w];
+        float m = cw[0];                                               // (fminf skips NaN, as the test v < 0.01 does)
+#pragma unroll 8
+        for (int k = 1; k < J.nper[w]; ++k) m = fminf(m, cw[k]);
+        if ((double)m < 0.01) failed = true;                           // models.py:29-33, per wave type
+    }
+    const float *base[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) base[k] = J.pred[k] ? J.pred[k] + q * J.pstride[k] : nullptr;
+    chi = 0.0;
+    int cnt = 0;
+    // every load of a column is unconditional (a masked-out entry adds an exact 0), so the unrolled loop keeps them in flight
+#pragma unroll 8
+    for (int j = 0; j < A.P; ++j) {
+        const int e = col[j];
+        const bool in = A.mask[ob + j] != 0;
+        const double o = A.c_obs[ob + j], sg = A.uncer[ob + j];
+        if (e < 0) { failed = true; continue; }
+        const int s = e >> 16;
+        const float *b = s == 0 ? base[0] : s == 1 ? base[1] : s == 2 ? base[2] : base[3];
+        const double v = (double)b[e & 0xffff];
+        if ((s & 1) && !(v >= 0.01)) failed = true;                    // a group velocity the data use
+        const double r = in ? (o - v) / sg : 0.0;
+        chi += (wt[j] * r) * r;
+        cnt += in ? 1 : 0;
+    }
+    mis = sqrt(chi / (double)cnt);
+    if (!(chi < 50.0)) chi = sqrt(chi * 50.0);
+    L = exp(-0.5 * chi);
+    if (failed) { mis = 88888.0; chi = 88888.0; L = 0.0; }
+}
+
+// surfdisp_mcmc_accept_kernel with the joint misfit: the same accept rule, random stream, tree walk and mcTrack rows.
+__global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJointArgs J)
+{
+    const McmcAcceptArgs &A = J.a;
+    __shared__ int col[SD_MCMC_JOINT_MAX_COLS];
+    __shared__ double wt[SD_MCMC_JOINT_MAX_COLS];
+    for (int j = threadIdx.x; j < A.P; j += blockDim.x) {
+        const int s = J.cols[2 * j], i = J.cols[2 * j + 1];
+        const bool ok = s >= 0 && s <= 3 && J.pred[s] && i >= 0 && i < J.nper[s >> 1];
+        col[j] = ok ? (s << 16) | i : -1;
+        wt[j] = J.weights[j];
+    }
+    __syncthreads();
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= A.C) return;
+    const int N = A.N;
+    const int M = A.depth > 1 ? (1 << A.depth) - 1 : 1;
+    const int nsteps = A.depth > 1 ? A.nsteps : 1;
+    const size_t ob = A.obs_per_chain ? (size_t)c * A.P : 0;
+    const unsigned long long gc = (unsigned long long)(A.chain0 + c);
+    double *p0 = A.p0 + (size_t)c * N;
+    double chi0 = A.chi0[c];
+    int node = 0;
+    for (int s = 0; s < nsteps; ++s) {
+        const size_t q = (size_t)c * M + node;
+        double mis, chi, L;
+        joint_misfit_of(J, col, wt, q, ob, mis, chi, L);
+        bool acc;
+        if (A.first) acc = true;
+        else if (chi < chi0) acc = true;                               // point.py:34-37
+        else {
+            const U4 r = philox4x32_10(U4{(uint32_t)A.counter, (uint32_t)(A.counter >> 32) ^ 0x00aaaa00u ^ ((uint32_t)s << 28),
+                                          (uint32_t)gc, (uint32_t)(gc >> 32)}, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
+            const double u = u53(r.x, r.y);
+            acc = u > 1.0 - exp(-(chi - chi0) / 2.0);
+        }
+        const double *p1 = A.p1 + q * N;
+        if (A.row) {
+            double *row = A.row + (size_t)c * A.row_stride + (size_t)s * A.step_stride;
+            row[0] = mis; row[1] = L; row[2] = acc ? 1.0 : 0.0;
+            for (int n = 0; n < N; ++n) row[3 + n] = p1[n];
+        }
+        if (acc) {
+            for (int n = 0; n < N; ++n) p0[n] = p1[n];
+            chi0 = chi;
+        }
+        node = acc ? 2 * node + 1 : 2 * node + 2;
+    }
+    A.chi0[c] = chi0;
+}
+
+hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a)
+{
+    hipLaunchKernelGGL(surfdisp_mcmc_accept_joint_kernel, dim3((unsigned)((a.a.C + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_mcmc_propose(hipStream_t s, const McmcProposeArgs &a)
 {
     const long total = (long)a.C * a.N;

@@ -5,6 +5,8 @@ The reference advances one chain per process, one forward solve per step.  Here 
 many grid points) advance in lock step: every step is ONE batched forward solve of C stacks through
 ``libsurfdisp_hip`` (root-search kernel only - the misfit uses Rayleigh phase velocity,
 ``point.py:11,18``), with proposals, misfit and the accept rule evaluated by torch ops on the device.
+With ``data=`` (``pysurfinv_amd.obsdata``) the misfit is the joint one of Rayleigh and / or Love, phase and / or group
+velocity curves: one solve per wave type with data, the group-velocity kernel only where U data exist.
 
 Semantics kept from the reference:
 * proposal: every random-walk scalar moves by a bounded Gaussian step (``brownian.py:20-27``), the
@@ -24,6 +26,7 @@ exact stream for one chain (trace parity, ``tests/test_mcmc.py``).
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -85,6 +88,7 @@ class ChainGroups:
             lo, hi = self.bounds[g], self.bounds[g + 1]
             ch = copy.copy(mc)                                  # shares spec, proposer (bounds, steps, seed), periods, to_model
             ch._plan, ch._fz, ch.event_ring, ch._ev_i, ch.n_forward, ch._groups, ch._plans = None, None, None, 0, 0, {}, {}
+            ch._jplans, ch._side = {}, None                     # (joint data: the group's own Rayleigh and Love plans)
             if mc.c_obs.ndim == 2:
                 if mc.c_obs.shape[0] != self.C:
                     raise ValueError(f"{self.C} chains against {mc.c_obs.shape[0]} rows of observations")
@@ -110,6 +114,7 @@ class ChainGroups:
                 ch.c_obs, ch.uncer, ch.mask = mc.c_obs, mc.uncer, mc.mask
             ch.local_rows = None if mc.local_rows is None else mc.local_rows[lo:hi]
             ch.independent, ch.fast_scan, ch.isgood = mc.independent, mc.fast_scan, mc.isgood
+            ch.joint, ch.periods = mc.joint, mc.periods
             ch._chain0 = mc._chain0 + lo
             if ch._fz is not None and (ch._fz["c_obs"].data_ptr() != ch.c_obs.contiguous().data_ptr()):
                 ch._fz = None                                   # (the fused buffers hold contiguous copies of the observations)
@@ -151,13 +156,16 @@ class MetropolisBatch:
     isgood(params) -> bool[C] tensor (None: always good, ``MCinv.isgood`` default, models.py:220-224)
     c_obs, uncer: [P] or [C, P]; entries with uncer <= 0 or NaN c_obs are masked out (the
     reference uses a masked array, point.py:23-26).
+    data: instead of (periods, c_obs, uncer), a list of ``obsdata.DispersionData`` - Rayleigh and / or Love, phase and / or
+    group velocity, each [P_d] or [C, P_d] - fitted jointly (the misfit, period lists and failure rule of
+    ``pysurfinv_amd.obsdata``): one solve per wave type and lock step, both from the one ``to_model`` output.
     """
 
     AUTO_INDEP_CHAINS = 3072        # 64-lane teams of fewer chains leave the chip's 196 608 lanes partly empty
 
-    def __init__(self, spec: ParamSpec, to_model, periods, c_obs, uncer, device="cuda:0",
+    def __init__(self, spec: ParamSpec, to_model, periods=None, c_obs=None, uncer=None, device="cuda:0",
                  isgood=None, proposer=None, seed=None, forward=None, independent=False, fast_scan=False,
-                 local_rows=None):
+                 local_rows=None, data=None):
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -165,14 +173,20 @@ class MetropolisBatch:
         self.to_model = to_model
         self.isgood = isgood
         self.proposer = proposer if proposer is not None else TorchProposer(spec, self.device, seed)
-        self.periods = torch.as_tensor(np.asarray(periods, np.float32), device=self.device)
-        co = torch.as_tensor(np.asarray(c_obs, np.float64), device=self.device)
-        un = torch.as_tensor(np.asarray(uncer, np.float64), device=self.device)
-        self.mask = torch.isfinite(co) & torch.isfinite(un) & (un > 0)
-        self.c_obs = torch.where(self.mask, co, torch.zeros_like(co))
-        self.uncer = torch.where(self.mask, un, torch.ones_like(un))
+        self.joint = None
+        self._fz = None
+        if data is not None:
+            if periods is not None or c_obs is not None or uncer is not None:
+                raise ValueError("MetropolisBatch: pass either data= or (periods, c_obs, uncer), not both")
+            self.data = data
+        else:
+            if periods is None or c_obs is None or uncer is None:
+                raise ValueError("MetropolisBatch: needs (periods, c_obs, uncer) or data=")
+            self.periods = torch.as_tensor(np.asarray(periods, np.float32), device=self.device)
+            self._set_obs(c_obs, uncer)
         self._plan = None
-        self._forward = forward                                 # test hook: callable(model, nlay) -> (c, status)
+        # test hook: callable(model, nlay) -> (c, status); with data=: -> dict(cR, uR, cL, uL, statusR, statusL)
+        self._forward = forward
         # independent=True: period-parallel root search (SURFDISP_INDEPENDENT) - lower latency for few
         # chains; only for smooth parameterisations (no low-velocity roughness), see include/surfdisp.h.
         # independent="auto": that decomposition whenever the lock step is too small to fill the chip with whole-stack
@@ -200,6 +214,30 @@ class MetropolisBatch:
         self._pipelined = False                                 # a chain group: another group's solve is in flight beside this one
         self._chain0 = 0                                        # index of this object's chain 0 in the whole sampler (chain groups)
         self._groups = {}
+        self._side = None                                       # joint data, one chain group: the Love solve's stream
+
+    def _set_obs(self, c_obs, uncer):
+        torch = self.torch
+        co = torch.as_tensor(np.asarray(c_obs, np.float64), device=self.device)
+        un = torch.as_tensor(np.asarray(uncer, np.float64), device=self.device)
+        self.mask = torch.isfinite(co) & torch.isfinite(un) & (un > 0)
+        self.c_obs = torch.where(self.mask, co, torch.zeros_like(co))
+        self.uncer = torch.where(self.mask, un, torch.ones_like(un))
+
+    @property
+    def data(self):
+        """The ``DispersionData`` sets of a joint sampler (None: the (periods, c_obs, uncer) form).  Assigning a new list
+        replaces the observations (``c_obs`` / ``uncer`` / ``mask`` are then their concatenated columns, [Ptot] or [C, Ptot]);
+        the fused path's buffers are keyed on the data object, so the next lock step uses the new data."""
+        return None if self.joint is None else self.joint.datasets
+
+    @data.setter
+    def data(self, data):
+        from .obsdata import JointData
+        self.joint = JointData(data, device=self.device)
+        self.periods = None
+        self._set_obs(self.joint.obs_raw, self.joint.uncer_raw)
+        self._fz = None
 
     # ------------------------------------------------------------------ forward + misfit
     def forward_c(self, params, rows=None):
@@ -215,8 +253,17 @@ class MetropolisBatch:
         if self._forward is not None:
             self.n_forward += model.shape[0]
             return self._forward(model, nlay)
+        if self.joint is not None:
+            return self._solve_joint(model, nlay)
         c, st = self._solve_model(model, nlay)
         return c.to(torch.float64), st
+
+    def forward_joint(self, params, rows=None):
+        """Joint data: dict(cR, uR, cL, uL, statusR, statusL) of the stacks of ``params`` (None for a wave type without
+        data; a wave type without U data is solved phase-only, its u is not meaningful)."""
+        if self.joint is None:
+            raise ValueError("forward_joint needs a sampler built with data=")
+        return self.forward_c(params, rows)
 
     def misfit(self, params, rows=None, return_c=False):
         """(misfit, chiSqr, L) per row of ``params`` - point.py:15-31.  With per-chain observations (``c_obs``
@@ -224,8 +271,11 @@ class MetropolisBatch:
         index tensor) is given - the speculative sampler evaluates several proposals per chain, the grid driver
         one average model per point."""
         torch = self.torch
-        cP, st = self.forward_c(params, rows)
-        failed = (st != 0) | (cP < 0.01).any(dim=1)            # models.py:29-33
+        if self.joint is not None:                              # cP: the predictions of the observation columns
+            cP, failed = self.joint.predictions(self.forward_joint(params, rows))
+        else:
+            cP, st = self.forward_c(params, rows)
+            failed = (st != 0) | (cP < 0.01).any(dim=1)        # models.py:29-33
         c_obs, uncer, mask = self.c_obs, self.uncer, self.mask
         if c_obs.ndim == 2:
             if rows is not None:
@@ -233,7 +283,7 @@ class MetropolisBatch:
             elif c_obs.shape[0] != cP.shape[0]:
                 raise ValueError(f"{cP.shape[0]} models against {c_obs.shape[0]} rows of observations: pass rows=")
         r = torch.where(mask, (c_obs - cP) / uncer, torch.zeros_like(cP))
-        chi = (r * r).sum(dim=1)
+        chi = (r * r).sum(dim=1) if self.joint is None else (self.joint.weights * r * r).sum(dim=1)
         N = mask.sum(dim=-1).to(torch.float64)
         mis = torch.sqrt(chi / N)
         chi = torch.where(chi < 50, chi, torch.sqrt(chi * 50.0))
@@ -256,9 +306,9 @@ class MetropolisBatch:
     def _fused_buffers(self, C):
         torch = self.torch
         st = getattr(self, "_fz", None)
-        if st is None or st["C"] != C:
+        if st is None or st["C"] != C or st.get("data") is not self.joint:
             N = self.spec.n
-            st = dict(C=C, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
+            st = dict(C=C, data=self.joint, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
                       chi=torch.zeros(C, dtype=torch.float64, device=self.device),
                       mask8=self.mask.to(torch.uint8).contiguous(), c_obs=self.c_obs.contiguous(), uncer=self.uncer.contiguous())
             self._fz = st
@@ -270,7 +320,7 @@ class MetropolisBatch:
             model, nlay = self.to_model(params, self.local_rows if rows is None else self.local_rows[rows])
         else:
             model, nlay = self.to_model(params)
-        return self._solve_model(model, nlay)
+        return self._solve_joint(model, nlay) if self.joint is not None else self._solve_model(model, nlay)
 
     def _solve_model(self, model, nlay):
         self.n_forward += model.shape[0]
@@ -293,6 +343,80 @@ class MetropolisBatch:
                                   nlay=nlay, independent=indep, fast_scan=self.fast_scan, events=ev,
                                   pipelined=self._pipelined)
         return c, st
+
+    def _solve_joint(self, model, nlay):
+        """Joint data: one solve per wave type with data, both on the same stacks -> dict(cR, uR, cL, uL, statusR, statusL)
+        of the solver's own fp32 output tensors (None for a wave type without data).  Kind flags: ``JointData.kind`` (phase
+        only unless the wave type has U data), ``independent`` / ``fast_scan`` as for the Rayleigh-only sampler.  Two solves:
+        SURFDISP_PIPELINED for both; as one chain group the Love solve runs on a second stream forked from, and joined back
+        into, the current one (as ``forward.JointPlan``; no host synchronisation), inside a chain group after the Rayleigh
+        solve on the group's stream.  ``n_forward`` counts stacks (models), not solves."""
+        from .forward import BatchPlan
+        torch = self.torch
+        jd = self.joint
+        self.n_forward += model.shape[0]
+        C, _, L = model.shape
+        model = model.contiguous()
+        plans = self.__dict__.setdefault("_jplans", {})
+        ev = None
+        if self.event_ring is not None:
+            ev = self.event_ring.slot(self._ev_i)
+            self._ev_i += 1
+        indep = (C < self.AUTO_INDEP_CHAINS) if self.independent == "auto" else bool(self.independent)
+        keys = [(C, L, w, jd.solve_periods[w].size) for w in jd.waves]
+        if any(k not in plans for k in keys):
+            if len(plans) + len(keys) > 8:                     # (speculative lock steps alternate between two stack counts)
+                plans.clear()
+            for k in keys:
+                if k not in plans:
+                    plans[k] = BatchPlan(C, L, k[3], device=self.device)
+        two = len(jd.waves) == 2
+        fork = two and not self._pipelined
+        cur = torch.cuda.current_stream(self.device)
+        if fork:                                               # (after the plans' allocation: their zero fills run on cur)
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.device)
+            self._side.wait_stream(cur)
+        out = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None)
+        for i, (w, key) in enumerate(zip(jd.waves, keys)):
+            with (torch.cuda.stream(self._side) if (fork and i == 1) else contextlib.nullcontext()):
+                c, u, st = plans[key].run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, independent=indep,
+                                          fast_scan=self.fast_scan, events=ev if i == 0 else None,
+                                          pipelined=self._pipelined or two)
+            out["c" + w], out["u" + w], out["status" + w] = c, u, st
+        if fork:
+            cur.wait_stream(self._side)
+        return out
+
+    def _accept_joint(self, stream, pred, st, p1, p, rowp, row_stride, counter, first=False, depth=1, nsteps=1, step_stride=0):
+        """The joint accept kernel (``surfdisp_mcmc_accept_joint_device`` / ``_tree_joint_device``) on the solves of ``pred``."""
+        import ctypes
+        jd = self.joint
+        C, N = p.shape
+        if st["c_obs"].shape[-1] != jd.Ptot or (st["c_obs"].ndim == 2 and st["c_obs"].shape[0] != C):
+            raise ValueError(f"joint accept: observations of shape {tuple(st['c_obs'].shape)} against {C} chains x {jd.Ptot} columns")
+        L = _lib.lib()
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        arrs = [pred["cR"], pred["uR"] if jd.with_group.get("R") else None,
+                pred["cL"], pred["uL"] if jd.with_group.get("L") else None]
+        for a in arrs:
+            if a is not None and (a.dtype != self.torch.float32 or a.stride(1) != 1):
+                raise ValueError("joint accept: predictions must be float32 rows of the solver's outputs")
+        predp = (ctypes.c_void_p * 4)(*[a.data_ptr() if a is not None else None for a in arrs])
+        strides = (ctypes.c_long * 4)(*[a.stride(0) if a is not None else 0 for a in arrs])
+        nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
+        stat = (ctypes.c_void_p * 2)(*[pred["status" + w].data_ptr() if pred["status" + w] is not None else None
+                                       for w in ("R", "L")])
+        table = (predp, strides, nper, stat, jd.Ptot, ptr(jd.cols), ptr(jd.weights), ptr(st["c_obs"]), ptr(st["uncer"]),
+                 ptr(st["mask8"]), 1 if st["c_obs"].ndim == 2 else 0)
+        pr = self.proposer
+        if depth <= 1:
+            _lib.check(L.surfdisp_mcmc_accept_joint_device(stream, C, N, *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp,
+                                                           int(row_stride), pr.seed_int, counter, 1 if first else 0, self._chain0))
+        else:
+            _lib.check(L.surfdisp_mcmc_accept_tree_joint_device(stream, C, N, int(depth), int(nsteps), *table, ptr(p1), ptr(p),
+                                                                ptr(st["chi"]), rowp, int(row_stride), int(step_stride),
+                                                                pr.seed_int, counter, self._chain0))
 
     def fused_step(self, p, row=None, row_stride=0, first=False, counter=None, row_offset=0):
         """One Metropolis step of every chain, in place on the state ``p`` [C, N] (float64, contiguous): proposal
@@ -321,6 +445,9 @@ class MetropolisBatch:
                                                           pr.seed_int, counter, 0, ptr(p1), self._chain0))
                 if self.isgood is not None:
                     self._redraw_with_rules(p, p1, counter, stream)
+            if self.joint is not None:
+                self._accept_joint(stream, self._solve_raw(p1), st, p1, p, rowp, row_stride, counter, first=first)
+                return p
             c, status = self._solve_raw(p1)
             _lib.check(L.surfdisp_mcmc_accept_device(stream, C, N, int(self.periods.numel()), ptr(c), ptr(status),
                                                      ptr(st["c_obs"]), ptr(st["uncer"]), ptr(st["mask8"]),
@@ -407,6 +534,10 @@ class MetropolisBatch:
         with torch.cuda.device(self.device):
             _lib.check(L.surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), ptr(p), ptr(pr.vmin), ptr(pr.vmax), ptr(pr.step),
                                                            pr.seed_int, counter, ptr(st["q"]), self._chain0))
+            if self.joint is not None:
+                self._accept_joint(stream, self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"]), st, st["q"], p, rowp,
+                                   row_stride, counter, depth=depth, nsteps=nsteps, step_stride=step_stride)
+                return p
             c, status = self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"])
             _lib.check(L.surfdisp_mcmc_accept_tree_device(stream, C, N, int(self.periods.numel()), int(depth), int(nsteps),
                                                           ptr(c), ptr(status), ptr(st["c_obs"]), ptr(st["uncer"]), ptr(st["mask8"]),
@@ -688,6 +819,8 @@ class MetropolisBatch:
         for all practical purposes.  Random numbers come from torch's default device generator
         (graph-safe Philox)."""
         torch = self.torch
+        if self.joint is not None:
+            raise ValueError("run_graphed: joint data (data=) are not supported; use run()")
         if self.isgood is not None or not self.fused_available():
             # (the captured step is torch glue with torch's graph-safe generator - the fused kernels take their Philox counter by
             # value, which a graph would freeze -, and that glue has no redraw loop: no predicate here, PriorRules or callback)

@@ -6,6 +6,13 @@ GPU (``MetropolisBatch``) instead of one process per chain.
     p.misfit()                                   # (misfit, chiSqr, L) of the initial model, point.py:15-31
     p.MCinvMP(outdir, pid, runN=50000, chainL=1000, seed=42)        # -> {outdir}/{pid}.npz
 
+Joint data (Rayleigh / Love, phase / group velocity; ``pysurfinv_amd.obsdata``):
+
+    p = Point(setting, data={"RayPhase": (T, c, sigma), "RayGroup": (T_U, U, sigma_U), "LoveGroup": (...)})
+
+The ``.npz``'s ``obs`` then keeps the reference's ``T`` / ``c`` / ``uncer`` (the Rayleigh-phase set, empty without one) and
+adds ``data``: every data set as a dict of plain arrays (``DispersionData.to_dict``), which ``PostPoint`` reads back.
+
 The ``.npz`` has the reference's keys (``mcTrack`` rows ``[misfit, L, accepted, *params]`` in
 ``MCinv._brownians()`` order, ``setting``, ``obs``, ``invMeta``; ``point.py:82-85,120-123``), so
 ``PostPoint`` / ``Model3D.loadInvDir`` read it unchanged.  Differences, on purpose: ``nprocess`` is
@@ -27,7 +34,7 @@ from .mcmc import MetropolisBatch
 
 class Point:
     def __init__(self, setting=None, localInfo={}, modelTypeCustom=None, layerClassCustom={},
-                 periods=[], vels=[], uncers=[], device="cuda:0"):
+                 periods=[], vels=[], uncers=[], device="cuda:0", data=None):
         if modelTypeCustom is not None or layerClassCustom:
             raise NotImplementedError("custom model / layer classes are Python callbacks of the reference; "
                                       "Model1DBatch supports the built-in layer types")
@@ -37,10 +44,21 @@ class Point:
         self.device = device
         self.initMod = Model1DBatch(setting, device=device)
         self.obs = {"T": periods, "c": vels, "uncer": uncers}      # Rayleigh wave, phase velocity only
+        self.data = None
+        if data is not None:                                       # joint data: obs["data"] holds every set
+            from .obsdata import as_datasets
+            if len(periods) or len(vels) or len(uncers):
+                raise ValueError("Point: pass either data= or periods / vels / uncers, not both")
+            self.data = as_datasets(data)
+            rc = [d for d in self.data if (d.wave, d.quantity) == ("R", "c")]
+            self.obs = {"T": rc[0].periods if rc else [], "c": rc[0].values if rc else [], "uncer": rc[0].uncer if rc else [],
+                        "data": [d.to_dict() for d in self.data]}
         self.pid = "test"
         self._mc = None
 
     def _sampler(self, seed=None, **kw):
+        if self.data is not None:
+            return MetropolisBatch(self.initMod.spec, self.initMod.to_model, device=self.device, seed=seed, data=self.data, **kw)
         return MetropolisBatch(self.initMod.spec, self.initMod.to_model, self.obs["T"], self.obs["c"],
                                self.obs["uncer"], device=self.device, seed=seed, **kw)
 
@@ -115,8 +133,12 @@ class PostPoint(Point):
             tmp = np.load(npzMC, allow_pickle=True)
             self.MC, setting, obs = np.array(tmp["mcTrack"], float), tmp["setting"][()], tmp["obs"][()]
             self.invMeta = tmp["invMeta"][()]
-            Point.__init__(self, setting, modelTypeCustom=modelTypeCustom, layerClassCustom=layerClassCustom,
-                           periods=obs["T"], vels=obs["c"], uncers=obs["uncer"], device=device if device is not None else "cpu")
+            if obs.get("data") is not None:                       # a joint inversion's file: its data sets
+                Point.__init__(self, setting, modelTypeCustom=modelTypeCustom, layerClassCustom=layerClassCustom,
+                               device=device if device is not None else "cpu", data=obs["data"])
+            else:
+                Point.__init__(self, setting, modelTypeCustom=modelTypeCustom, layerClassCustom=layerClassCustom,
+                               periods=obs["T"], vels=obs["c"], uncers=obs["uncer"], device=device if device is not None else "cpu")
             self.pid = self.invMeta.get("pid", self.pid) if isinstance(self.invMeta, dict) else self.pid
             self.N = self.MC.shape[0]
             self.misfits, self.Ls, self.accepts = self.MC[:, 0], self.MC[:, 1], self.MC[:, 2]
