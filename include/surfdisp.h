@@ -33,7 +33,8 @@ extern "C" {
 #endif
 
 #define SURFDISP_ABI_VERSION 4      /* 4 (r04): + SURFDISP_KERN_REFCOORD, surfdisp_workspace_counters, surfdisp_prior_device, surfdisp_mcmc_propose_masked_device; every ABI-3 symbol kept;
-                                       additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes */
+                                       additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes,
+                                       surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -221,6 +222,33 @@ int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const i
                                           float *c, float *u, int *status,
                                           float *dcdb, float *dcda, float *dcdr,
                                           float *dudb, float *duda, float *dudr, int *n_shift_failed,
+                                          void *workspace, size_t workspace_bytes);
+
+/* ---- (5d) ... and the analytic partials of the Rayleigh ELLIPTICITY chi (the H/V ratio of (3b), COMMON /o/ ratio,
+ *          calcul.f:195), added within ABI 4.  With D(e) = h^T A_{n-1} ... A_1 e the layer recursion of DLTAR4 (surfa.f:193-363)
+ *          from the start vector e to the half-space row, F = D(e1) is the secular function and chi = D(e3) / (2 D(e2)); the
+ *          two ellipticity passes skip a liquid top layer and run on the working stack the root search left (its frozen mmax,
+ *          the layers refreshed at earlier periods).  At the root c*(m):
+ *              dchi/dm_i = dchi/dm_i|_c + (dchi/dc) dc/dm_i,   dc/dm_i = -(dF/dm_i) / (dF/dc),
+ *          each term a contraction of one adjoint row with the forward state of e1, e2 or e3 (dF/dc includes the liquid
+ *          layer's term).  fp64, layer coefficients from sin(x)/x and sinh(x)/x (continuous across c = Vp or Vs).  After the
+ *          launches of (5b) - c, u, status, dcdb, dcda, dcdr bit-identical to surfdisp_forward_kernels_device on the same
+ *          inputs, `ratio` [B][P] as surfdisp_forward_batch_device2 writes it - one more kernel and a transposition:
+ *          dedb / deda / dedr [B][P][Lmax] = d chi(period) / d (Vs | Vp | rho) of input layer i, caller's coordinates (the
+ *          chain factors of (5b), at the period that last refreshed each layer).
+ *          Rows: zeros for water layers, layers below the effective half space, unsolved periods and bad stacks; every entry
+ *          NaN for a solved unit whose result is not finite (D(e2) ~ 0: a node of the vertical motion at the surface; dF/dc ~
+ *          0) or that the exact fallback solver took (no recorded working stack) - *n_nonfinite (device int, may be NULL)
+ *          counts those units.  deda, dedr, dcda, dcdr may be NULL.  SURFDISP_ERR_INVALID, before anything is launched:
+ *          Love `kind`, SURFDISP_PHASE_ONLY, SURFDISP_KERN_REFCOORD, SURFDISP_STRICT, NULL ratio / dedb / dcdb, and a
+ *          workspace smaller than surfdisp_ellip_kernels_workspace_bytes (that of (5b) plus the layer-major scratches of the
+ *          adjoint rows - 5 doubles per layer and unit - and of the shares: there is no direct route). */
+size_t surfdisp_ellip_kernels_workspace_bytes(int B, int Lmax, int P);
+int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind,
+                                          float *c, float *u, float *ratio, int *status,
+                                          float *dcdb, float *dcda, float *dcdr,
+                                          float *dedb, float *deda, float *dedr, int *n_nonfinite,
                                           void *workspace, size_t workspace_bytes);
 
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:

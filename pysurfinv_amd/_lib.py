@@ -34,7 +34,8 @@ EXPORTS = (
     "surfdisp_mcmc_propose_device", "surfdisp_mcmc_accept_device", "surfdisp_prior_device", "surfdisp_mcmc_propose_masked_device", "surfdisp_mcmc_propose_tree_device", "surfdisp_mcmc_accept_tree_device",
     "surfdisp_mcmc_accept_joint_device", "surfdisp_mcmc_accept_tree_joint_device",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
-    "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes","surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
+    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes","surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -111,6 +112,11 @@ def lib() -> ctypes.CDLL:
     L.surfdisp_forward_group_kernels_device.restype = ctypes.c_int
     L.surfdisp_forward_group_kernels_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
                                                         ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    L.surfdisp_ellip_kernels_workspace_bytes.restype = ctypes.c_size_t
+    L.surfdisp_ellip_kernels_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.surfdisp_forward_ellip_kernels_device.restype = ctypes.c_int
+    L.surfdisp_forward_ellip_kernels_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
     L.surfdisp_group_kernels_shift_offset.restype = ctypes.c_size_t     # test read-out (not in include/surfdisp.h)
     L.surfdisp_group_kernels_shift_offset.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.surfdisp_thermal_scratch_bytes.restype = ctypes.c_size_t

@@ -303,6 +303,37 @@ static GCarve gcarve(void *base, int B, int Lmax, int P)
     return g;
 }
 
+// workspace of surfdisp_forward_ellip_kernels_device: that of the kernels entry, then per layer and unit the refreshing period
+// (int), the adjoint row (5 doubles) and the two shares (3 + 3 floats), and per unit gamma and the deepest layer
+struct ECarve {
+    int *kpk;
+    double *wscr;
+    float *xscr, *fscr, *gam;
+    int *khs;
+    size_t total;
+};
+static ECarve ecarve(void *base, int B, int Lmax, int P)
+{
+    char *p = static_cast<char *>(base);
+    const size_t PB = (size_t)P * B, LPB = (size_t)Lmax * PB;
+    size_t off = align_up(surfdisp_kernels_workspace_bytes(B, Lmax, P));
+    ECarve e;
+    e.kpk = reinterpret_cast<int *>(p + off);      off += align_up(LPB * sizeof(int));
+    e.wscr = reinterpret_cast<double *>(p + off);  off += align_up(5 * LPB * sizeof(double));
+    e.xscr = reinterpret_cast<float *>(p + off);   off += align_up(3 * LPB * sizeof(float));
+    e.fscr = reinterpret_cast<float *>(p + off);   off += align_up(3 * LPB * sizeof(float));
+    e.gam = reinterpret_cast<float *>(p + off);    off += align_up(PB * sizeof(float));
+    e.khs = reinterpret_cast<int *>(p + off);      off += align_up(PB * sizeof(int));
+    e.total = off;
+    return e;
+}
+
+size_t surfdisp_ellip_kernels_workspace_bytes(int B, int Lmax, int P)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    return ecarve(nullptr, B, Lmax, P).total;
+}
+
 size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P)
 {
     if (B < 1 || Lmax < 2 || P < 1) return 0;
@@ -347,7 +378,8 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
                                const float *model, int P, const float *per, int kind,
                                float *c, float *u, int *status,
                                void *workspace, size_t workspace_bytes, hipEvent_t *ev,
-                               float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr)
+                               float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr,
+                               bool force_hist = false)
 {
     int rc = check_args(B, Lmax, P, kind, model, per, c, u);
     if (rc) return rc;
@@ -416,7 +448,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // (two-lane teams compute their ellipticities themselves but record the history too: the pairs whose closure cancels
     // are redone by the ellipticity kernel)
     const bool ell_fix = ell_in && !strict && kn.ell_kernel != 0 && kn.ell_ambig != 0.0f;
-    ph.hist = (ell_k || ell_fix) ? w.hist : nullptr;
+    ph.hist = (ell_k || ell_fix || force_hist) ? w.hist : nullptr;   // (force_hist: the ellipticity kernels replay it too)
     ph.lockstep = kn.lockstep >= 0 ? kn.lockstep : 1;
     ph.ambig = kn.ambig; ph.phimulti = kn.phimulti; ph.amb_count = w.amb_count; ph.ell_ambig = ell_fix ? kn.ell_ambig : 0.0f; ph.ell_gmax = kn.ell_gmax;
     ph.scan_general = kn.leanscan ? 0 : 1;
@@ -550,6 +582,44 @@ int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const i
     sd::GroupCombineArgs ca{B, P, Lmax, wave, kscr, g.kscr_p, g.ksc, g.ksc + PB, g.khs, g.khs + PB, kscale0, g.fail,
                             w.ct, w.ut, inv_dlnT, dudb, duda, dudr, n_shift_failed};
     SD_HIP(sd::launch_group_combine(s, ca));
+    return SURFDISP_SUCCESS;
+}
+
+// The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit; `ratio` as
+// surfdisp_forward_batch_device2), then the analytic partials of the Rayleigh ellipticity (K5 in surfdisp_kernels.hip).
+int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind,
+                                          float *c, float *u, float *ratio, int *status,
+                                          float *dcdb, float *dcda, float *dcdr,
+                                          float *dedb, float *deda, float *dedr, int *n_nonfinite,
+                                          void *workspace, size_t workspace_bytes)
+{
+    if (!ratio || !dedb || !dcdb) { set_err("surfdisp_forward_ellip_kernels_device: ratio, dedb or dcdb is NULL"); return SURFDISP_ERR_INVALID; }
+    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD | SURFDISP_STRICT)) {
+        set_err("surfdisp_forward_ellip_kernels_device: no PHASE_ONLY, no KERN_REFCOORD, no STRICT");
+        return SURFDISP_ERR_INVALID;
+    }
+    if ((kind & ~SD_KIND_FLAGS) != SURFDISP_KIND_RAYLEIGH) {
+        set_err("surfdisp_forward_ellip_kernels_device: Rayleigh only (Love waves have no ellipticity)");
+        return SURFDISP_ERR_INVALID;
+    }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < surfdisp_ellip_kernels_workspace_bytes(B, Lmax, P)) {
+        set_err("workspace too small (surfdisp_ellip_kernels_workspace_bytes)");
+        return SURFDISP_ERR_INVALID;
+    }
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, ratio, true);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Carve w = carve(workspace, B, Lmax, P);
+    const ECarve e = ecarve(workspace, B, Lmax, P);
+    if (n_nonfinite) SD_HIP(hipMemsetAsync(n_nonfinite, 0, sizeof(int), s));
+    sd::EllipKernArgs ea{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.hist, w.nsolved, e.kpk, e.wscr, e.xscr, e.fscr, e.gam, e.khs,
+                         n_nonfinite};
+    sd::EllipTransposeArgs ta{B, P, Lmax, e.xscr, e.fscr, e.gam, e.khs, dedb, deda, dedr};
+    SD_HIP(sd::launch_ellip_kern(s, ea, ta));
     return SURFDISP_SUCCESS;
 }
 

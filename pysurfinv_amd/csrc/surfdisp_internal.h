@@ -50,8 +50,8 @@ struct PhaseArgs {
     const float *msrc;
     long ms_b, ms_f, ms_i;
     // nullptr, or [P][B]: per solved period the state the ellipticity kernel replays the working stack from - (number of
-    // layers the period's rebuild refreshed) | (frozen effective half space << 16); -1: this period's ellipticity was
-    // computed in the kernel itself (exact fallback)
+    // layers the period's rebuild refreshed) | (frozen effective half space << 16); sign bit set: this period's ellipticity
+    // was computed in the kernel itself (exact fallback; the two fields are still recorded for the ellipticity kernels)
     int *hist;
     int lockstep;         // the teams of a wavefront refine and end their periods together (see the root search's main loop)
     float ambig;          // a scan trial with |value| below this fraction of its terms' magnitude is evaluated again with the
@@ -142,6 +142,30 @@ struct EllipArgs {
     const float *ovf;     // [3][B] prep statistics (entry 2: 4 ln(2 bmax^2))
 };
 hipError_t launch_ellip(hipStream_t s, const EllipArgs &a);
+
+// ellipticity kernels (surfdisp_forward_ellip_kernels_device): dchi/d(Vs, Vp, rho) of the Rayleigh ellipticity, see K5
+struct EllipKernArgs {
+    int B, Lmax, P;
+    const float *mdl;     // SoA staged fields
+    const int *nl;
+    const float *per;
+    const float *c;       // [P][B] roots
+    const int *hist;      // [P][B], see PhaseArgs
+    const int *nsolved;   // [B]
+    int *kpk;             // [Lmax][P][B] scratch: per layer the period whose rebuild it comes from | 0x10000 (half-space form)
+    double *wscr;         // [5][Lmax][P][B] scratch: the adjoint rows
+    float *xscr, *fscr;   // [3][Lmax][P][B] scratch: per layer dchi/d(Vs, Vp, rho) at fixed c, and dF/d(Vs, Vp, rho)
+    float *gam;           // [P][B] out: -(dchi/dc) / (dF/dc)
+    int *khs;             // [P][B] out: deepest layer with partials; -1 none (zeros), -2 non-finite (NaN rows)
+    int *n_nonfinite;     // nullptr, or [1]: units with NaN rows
+};
+struct EllipTransposeArgs {
+    int B, P, Lmax;
+    const float *xscr, *fscr, *gam;
+    const int *khs;
+    float *eb, *ea, *er;  // the caller's [B][P][Lmax] rows (ea, er may be nullptr)
+};
+hipError_t launch_ellip_kern(hipStream_t s, const EllipKernArgs &a, const EllipTransposeArgs &t);
 
 struct FinishArgs {
     int B, P;

@@ -1945,7 +1945,9 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             if (j == 0) {
                 A.c[(size_t)k * B + b] = croot;                // period-major: coalesced across teams
                 if (want_ratio && !ell_pend) A.ratio[(size_t)k * B + b] = r12;
-                if (A.hist) A.hist[(size_t)k * B + b] = EXACT ? -1 : (nflat_cur | (mm_frozen << 16) | (ell_flag ? 0x40000000 : 0));
+                // (exact kernel: negative - its ellipticity is final - with the same two fields, for the ellipticity kernels' replay)
+                if (A.hist) A.hist[(size_t)k * B + b] = EXACT ? (int)(0x80000000u | (unsigned)nflat_cur | ((unsigned)mm_frozen << 16))
+                                                              : (nflat_cur | (mm_frozen << 16) | (ell_flag ? 0x40000000 : 0));
             }
             ell_flag = false;
             nsolved = ++k;
@@ -3478,6 +3480,369 @@ hipError_t launch_group(hipStream_t s, int kind, const GroupArgs &a_in)
     else if (kind == 2)     hipLaunchKernelGGL((surfdisp_group_kernel<2, false>), dim3(grid), dim3(256), 0, s, a);
     else if (kern)          hipLaunchKernelGGL((surfdisp_group_kernel<1, true>), dim3(grid), dim3(256), 0, s, a);
     else                    hipLaunchKernelGGL((surfdisp_group_kernel<1, false>), dim3(grid), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+
+// ====================================================================== K5: ellipticity kernels
+// surfdisp_forward_ellip_kernels_device, behind the forward + partials launches (whose outputs it leaves as they are).
+// The ellipticity is chi = D(e3) / (2 D(e2)) with D(e) = h^T A_{last-1} ... A_0 e the reference's layer recursion (DLTAR4,
+// surfa.f:193-363) on the working stack the root search left (replayed from the hist words as surfdisp_ellip_kernel does; a
+// liquid top layer is skipped by the two ellipticity passes), and the root obeys F = D(e1) = 0.  At the root
+//     dchi/dm_i = (dD3_i - 2 chi dD2_i) / (2 D2) + gamma dF_i,   gamma = -(dchi/dc) / (dF/dc),
+// where dD(e)_i = u_i (dA_i/dm_i) v_{i-1}(e) contracts the adjoint row u_i = h^T A_{last-1} ... A_{i+1} with the forward state
+// v_{i-1}(e) = A_{i-1} ... A_0 e (the half space: dh/dm v_{last-1}), and d/dc sums such terms over every layer - the liquid
+// top layer's included for F.  fp64 throughout; the layer matrix is written with C(z) = cos sqrt(z), S(z) = sin sqrt(z) /
+// sqrt(z) of z = d^2 (omega^2 / a^2 - k^2) (entire functions: cosh / sinh for z < 0, a series near 0), so it is smooth
+// across c = a or b, and its derivatives come from one dual-number evaluation per direction (a, b, rho, c).
+// One lane per (stack, period) unit, three sweeps: K5a the layer history (which period last refreshed each layer), K5b the
+// adjoint rows upward into a layer-major scratch [5][Lmax][P*B] (fp64), K5c downward: forward states of e1, e2, e3, the
+// contractions, the chain factors of calcul.f:122-126 / flat1.f:44-62 at the refreshing period - the two per-layer shares
+// (dchi/dm at fixed c, dF/dm) go to layer-major fp32 scratches, gamma and the deepest layer to per-unit words.
+// K5d surfdisp_ellip_transpose_kernel: share + gamma x F-share -> the caller's rows (zeros below the half space; NaN rows).
+struct Dd { double v, d; };
+__device__ __forceinline__ Dd operator+(Dd x, Dd y) { return Dd{x.v + y.v, x.d + y.d}; }
+__device__ __forceinline__ Dd operator-(Dd x, Dd y) { return Dd{x.v - y.v, x.d - y.d}; }
+__device__ __forceinline__ Dd operator-(Dd x) { return Dd{-x.v, -x.d}; }
+__device__ __forceinline__ Dd operator*(Dd x, Dd y) { return Dd{x.v * y.v, x.v * y.d + x.d * y.v}; }
+__device__ __forceinline__ Dd operator/(Dd x, Dd y) { const double q = x.v / y.v; return Dd{q, (x.d - q * y.d) / y.v}; }
+__device__ __forceinline__ Dd operator*(double s, Dd x) { return Dd{s * x.v, s * x.d}; }
+__device__ __forceinline__ Dd operator+(double s, Dd x) { return Dd{s + x.v, x.d}; }
+__device__ __forceinline__ Dd operator-(double s, Dd x) { return Dd{s - x.v, -x.d}; }
+__device__ __forceinline__ Dd operator-(Dd x, double s) { return Dd{x.v - s, x.d}; }
+__device__ __forceinline__ Dd operator/(double s, Dd x) { const double q = s / x.v; return Dd{q, -q * x.d / x.v}; }
+__device__ __forceinline__ double dval(double x) { return x; }
+__device__ __forceinline__ double dval(Dd x) { return x.v; }
+__device__ __forceinline__ double dder(double) { return 0.0; }
+__device__ __forceinline__ double dder(Dd x) { return x.d; }
+__device__ __forceinline__ double dsqrt(double x) { return sqrt(x); }
+__device__ __forceinline__ Dd dsqrt(Dd x) { const double r = sqrt(x.v); return Dd{r, 0.5 * x.d / r}; }
+// C(z), S(z) and their z-derivatives (C' = -S/2, S' = (C - S) / (2 z); series for |z| < 1, where that quotient cancels)
+struct CSv { double C, S, dC, dS; };
+// sin and cos of q >= 0 (q = sqrt(z) stays far below 2^20 wherever the recursion is finite): Cody-Waite reduction by pi/2 in
+// three parts and Taylor polynomials on [-pi/4, pi/4] (the library's fp64 sin / cos keep a private array for huge arguments)
+__device__ __forceinline__ void ell_sincos(double q, double *sn, double *cn)
+{
+    const double n = rint(q * 0.63661977236758134308);
+    const double r = ((q - n * 1.57079632673412561417e+00) - n * 6.07710050630396597660e-11) - n * 2.02226624879595063154e-21;
+    const double r2 = r * r;
+    double ps = 1.0, pc = 1.0;                              // Horner, inside out: 1 - r^2 / ((2m) (2m+1)) (...), 1 - r^2 / ((2m-1) 2m) (...)
+#pragma unroll
+    for (int m = 10; m >= 1; --m) {
+        ps = 1.0 - r2 * ps / ((2.0 * m) * (2.0 * m + 1.0));
+        pc = 1.0 - r2 * pc / ((2.0 * m - 1.0) * (2.0 * m));
+    }
+    const double sr = r * ps, cr = pc;
+    const int j = (int)((long long)n & 3);
+    *sn = (j == 0) ? sr : ((j == 1) ? cr : ((j == 2) ? -sr : -cr));
+    *cn = (j == 0) ? cr : ((j == 1) ? -sr : ((j == 2) ? -cr : sr));
+}
+__device__ __forceinline__ CSv cs_of(double z)
+{
+    CSv r;
+    if (fabs(z) < 1.0) {
+        double t = 1.0, C = 0.0, S = 0.0, dS = 0.0;             // t = (-z)^n
+        double fc = 1.0, fs = 1.0;                              // 1 / (2n)!, 1 / (2n+1)!
+#pragma unroll
+        for (int m = 0; m < 11; ++m) {
+            C += t * fc; S += t * fs;
+            if (m < 10) dS -= (double)(m + 1) * t * fs / ((2.0 * m + 2.0) * (2.0 * m + 3.0));   // (n+1) (-z)^n (-1) / (2n+3)!
+            t *= -z;
+            fc /= (2.0 * m + 1.0) * (2.0 * m + 2.0);
+            fs /= (2.0 * m + 2.0) * (2.0 * m + 3.0);
+        }
+        r.C = C; r.S = S; r.dS = dS;
+    } else if (z > 0.0) {
+        const double q = sqrt(z);
+        double sn, cn; ell_sincos(q, &sn, &cn);
+        r.C = cn; r.S = sn / q; r.dS = (r.C - r.S) / (2.0 * z);
+    } else {
+        const double q = sqrt(-z), e = exp(q), ie = 1.0 / e;
+        r.C = 0.5 * (e + ie); r.S = 0.5 * (e - ie) / q; r.dS = (r.C - r.S) / (2.0 * z);
+    }
+    r.dC = -0.5 * r.S;
+    return r;
+}
+__device__ __forceinline__ double cs_lift(double v, double, double) { return v; }
+__device__ __forceinline__ Dd cs_lift(double v, double dv, Dd z) { return Dd{v, dv * z.d}; }
+template <class T> struct EMat { T a11, a12, a13, a14, a15, a21, a22, a23, a24, a31, a32, a33, a41, a42, a51; };
+struct EV5 { double x[5]; };
+// z of the P and S phases of a layer (values only: what cs_of is evaluated at)
+__device__ __forceinline__ void ell_z(double a, double b, double d, double c, double k, double *za, double *zb)
+{
+    const double kd2 = (k * d) * (k * d), csq = c * c;
+    *za = -(1.0 - csq / (a * a)) * kd2;
+    *zb = (b > 0.0) ? -(1.0 - csq / (b * b)) * kd2 : 0.0;
+}
+// the layer matrix of DLTAR4 (surfa.f:253-357; liquid: 216-251) in the C / S form
+template <class T>
+__device__ __forceinline__ EMat<T> ell_mat(T a, T b, T rho, T d, T c, T k, const CSv &ca, const CSv &cb, bool liquid)
+{
+    const T csq = c * c, kd = k * d;
+    const T arga = 1.0 - csq / (a * a);
+    const T za = -(arga * kd * kd);
+    const T Sa = cs_lift(ca.S, ca.dS, za);
+    const T cosp = cs_lift(ca.C, ca.dC, za), sinpr = kd * Sa, rsinp = -(arga * kd * Sa);
+    const T rhoc = rho * csq;
+    // (one straight path, the liquid case selected per entry: two return paths put the matrix in private memory)
+    const T argb = 1.0 - csq / (b * b);
+    const T zb = -(argb * kd * kd);
+    const T Sb = cs_lift(cb.S, cb.dS, zb);
+    const T cosq = cs_lift(cb.C, cb.dC, zb), sinqr = kd * Sb, rsinq = -(argb * kd * Sb);
+    const T g = 2.0 * (b * b) / csq, g1 = g - 1.0;
+    const T rr = rsinp * rsinq, ss = sinpr * sinqr, cc = cosp * cosq;
+    const T rs1 = rsinp * cosq, rs2 = sinqr * cosp, rs3 = sinpr * cosq, rs4 = rsinq * cosp;
+    const T gm = 2.0 * g - 1.0, gs = g * g, g1s = g1 * g1, ccm = 1.0 - cc, gg1 = g * g1;
+    const T rhocs = rhoc * rhoc;
+    const T suu = gs * rr + g1s * ss;
+    const T z = csq - csq;
+    EMat<T> m;
+    m.a11 = liquid ? cosp : (2.0 * gs - gm) * cc - suu - 2.0 * gg1;
+    m.a12 = liquid ? z : -(rs1 + rs2) / rhoc;
+    m.a13 = liquid ? z : -2.0 * (gm * ccm + g1 * ss + g * rr) / rhoc;
+    m.a14 = liquid ? z : (rs3 + rs4) / rhoc;
+    m.a15 = liquid ? z : (2.0 * ccm + rr + ss) / rhocs;
+    m.a21 = liquid ? rhoc * sinpr : rhoc * (g1s * rs3 + gs * rs4);
+    m.a22 = liquid ? z : cc;
+    m.a23 = liquid ? z : 2.0 * (g * rs4 + g1 * rs3);
+    m.a24 = liquid ? z : sinpr * rsinq;
+    m.a31 = liquid ? z : rhoc * (gg1 * gm * ccm + g1s * g1 * ss + gs * g * rr);
+    m.a32 = liquid ? z : g1 * rs2 + g * rs1;
+    m.a33 = liquid ? z : 1.0 + 2.0 * (2.0 * gg1 * ccm + suu);
+    m.a41 = liquid ? z : -(rhoc * (g1s * rs2 + gs * rs1));
+    m.a42 = liquid ? z : rsinp * sinqr;
+    m.a51 = liquid ? z : rhocs * (2.0 * gs * g1s * ccm + gs * gs * rr + g1s * g1s * ss);
+    return m;
+}
+// the half-space row h (label 52 of DLTAR4, surfa.f:346-363), the factor 2 of h13 folded in
+template <class T>
+__device__ __forceinline__ void ell_hrow(T a, T b, T rho, T c, T h[5])
+{
+    const T csq = c * c;
+    const T arga = 1.0 - csq / (a * a), argb = 1.0 - csq / (b * b);
+    const T ra = (dval(arga) > 0.0) ? -dsqrt(arga) : dsqrt(0.0 - arga);
+    const T rb = (dval(argb) > 0.0) ? -dsqrt(argb) : dsqrt(0.0 - argb);
+    const T g = 2.0 * (b * b) / csq, g1 = g - 1.0;
+    const T sss = b * b, ppp = a * a, rhp = rho * a;
+    const T gra = g * ra, rba = rb - 1.0 / ra;
+    const T h12r = rhp * a;
+    h[0] = -2.0 * rb * sss / ppp + csq * (g1 * g1) / ppp / gra;
+    h[1] = -1.0 / g / h12r;
+    h[2] = 2.0 * (-rb / h12r + g1 / h12r / gra);
+    h[3] = rb / h12r / gra;
+    h[4] = rba / rhp / rhp / csq / g;
+}
+template <bool DER, class T>
+__device__ __forceinline__ EV5 ell_act(const EMat<T> &A, const EV5 &b)
+{
+    auto e = [](const T &x) { return DER ? dder(x) : dval(x); };
+    const double a11 = e(A.a11), a12 = e(A.a12), a13 = e(A.a13), a14 = e(A.a14), a15 = e(A.a15), a21 = e(A.a21), a22 = e(A.a22),
+                 a23 = e(A.a23), a24 = e(A.a24), a31 = e(A.a31), a32 = e(A.a32), a33 = e(A.a33), a41 = e(A.a41), a42 = e(A.a42),
+                 a51 = e(A.a51);
+    const double b1 = b.x[0], b2 = b.x[1], b3 = b.x[2], b4 = b.x[3], b5 = b.x[4];
+    EV5 r;
+    r.x[0] = a11 * b1 + a12 * b2 + a13 * b3 + a14 * b4 + a15 * b5;
+    r.x[1] = a21 * b1 + a22 * b2 + a23 * b3 + a24 * b4 - a14 * b5;
+    r.x[2] = a31 * b1 + a32 * b2 + a33 * b3 - 0.5 * a23 * b4 + 0.5 * a13 * b5;
+    r.x[3] = a41 * b1 + a42 * b2 - 2.0 * a32 * b3 + a22 * b4 - a12 * b5;
+    r.x[4] = a51 * b1 - a41 * b2 + 2.0 * a31 * b3 - a21 * b4 + a11 * b5;
+    return r;
+}
+// the row u A (the adjoint step)
+__device__ __forceinline__ EV5 ell_act_row(const EMat<double> &A, const EV5 &u)
+{
+    const double u1 = u.x[0], u2 = u.x[1], u3 = u.x[2], u4 = u.x[3], u5 = u.x[4];
+    EV5 r;
+    r.x[0] = A.a11 * u1 + A.a21 * u2 + A.a31 * u3 + A.a41 * u4 + A.a51 * u5;
+    r.x[1] = A.a12 * u1 + A.a22 * u2 + A.a32 * u3 + A.a42 * u4 - A.a41 * u5;
+    r.x[2] = A.a13 * u1 + A.a23 * u2 + A.a33 * u3 - 2.0 * A.a32 * u4 + 2.0 * A.a31 * u5;
+    r.x[3] = A.a14 * u1 + A.a24 * u2 - 0.5 * A.a23 * u3 + A.a22 * u4 - A.a21 * u5;
+    r.x[4] = A.a15 * u1 - A.a14 * u2 + 0.5 * A.a13 * u3 - A.a12 * u4 + A.a11 * u5;
+    return r;
+}
+__device__ __forceinline__ double ell_dot(const EV5 &u, const EV5 &v)
+{
+    return u.x[0] * v.x[0] + u.x[1] * v.x[1] + u.x[2] * v.x[2] + u.x[3] * v.x[3] + u.x[4] * v.x[4];
+}
+__device__ __forceinline__ bool finite64(double x) { return fabs(x) <= 1.7976931348623157e308; }
+
+// one working-stack layer of unit (b, k): its values, as the rebuild of period kk formed them, and their chain factors
+struct ELayer { double a, b, rho, d; Chain ch; bool liquid; };
+__device__ __forceinline__ ELayer ell_layer(const EllipKernArgs &A, int b, int i, int kpk)
+{
+    const size_t fs = (size_t)A.Lmax * A.B;
+    const LayerRaw raw = layer_load(A.mdl, fs, (size_t)i * A.B + b);
+    const float lnT = logf(1.0f / A.per[kpk & 0xffff]);
+    const bool hs = (kpk & 0x10000) != 0;
+    const LayerV v = layer_derive(raw, lnT, hs);
+    ELayer e;
+    e.a = v.a; e.b = v.b; e.rho = v.rho; e.d = v.d;
+    e.ch = chain_of(raw, lnT, hs, false);
+    e.liquid = !(fabsf(v.b) > 1.e-8f);                      // DLTAR4's test, surfa.f:216
+    return e;
+}
+
+__global__ __launch_bounds__(256) void surfdisp_ellip_kern_kernel(EllipKernArgs A)
+{
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int B = A.B, P = A.P;
+    if (idx >= (size_t)B * P) return;
+    const int b = (int)(idx % B), k = (int)(idx / B);       // a wavefront = 64 stacks, one period: coalesced scratch
+    const size_t PB = (size_t)P * B;
+    const int n = A.nl[b];
+    int top = -1;                                           // deepest layer with partials; -2: NaN row
+    float gam = 0.0f;
+    const int hk = (n >= 2 && k < A.nsolved[b] && A.c[idx] > 0.0f) ? A.hist[idx] : 0x7fffffff;
+    if (hk == 0x7fffffff) {
+        // unsolved period or bad stack: zeros
+    } else if (((hk >> 16) & 0x3fff) < 2 || ((hk >> 16) & 0x3fff) > n) {
+        top = -2;                                           // (no recursion to differentiate)
+    } else {
+        const int last = ((hk >> 16) & 0x3fff) - 1;         // the half space of the recursion (frozen mmax - 1)
+        // K5a: which period's rebuild the working stack's layer i comes from (surfdisp_ellip_kernel's replay)
+        {
+            int kk = k, nflat = hk & 0xffff;
+            for (int i = 0; i <= last; ++i) {
+                while (nflat <= i && kk > 0) {
+                    --kk;
+                    nflat = A.hist[(size_t)kk * B + b] & 0xffff;      // (periods the exact kernel solved: sign bit set)
+                }
+                A.kpk[(size_t)i * PB + idx] = kk | ((i == nflat - 1) ? 0x10000 : 0);
+            }
+        }
+        const double c = A.c[idx], T = A.per[k];
+        const double kw = 6.283185307179586 / (c * T);       // wavenumber
+        // K5b: adjoint rows, upward.  u_{last-1} = h; u_{i-1} = u_i A_i
+        EV5 u;
+        ELayer hl = ell_layer(A, b, last, A.kpk[(size_t)last * PB + idx]);
+        {
+            double h[5];
+            ell_hrow<double>(hl.a, hl.b, hl.rho, c, h);
+            for (int q = 0; q < 5; ++q) u.x[q] = h[q];
+        }
+        for (int i = last - 1; i >= 0; --i) {
+            for (int q = 0; q < 5; ++q) A.wscr[((size_t)q * A.Lmax + i) * PB + idx] = u.x[q];
+            const ELayer L = ell_layer(A, b, i, A.kpk[(size_t)i * PB + idx]);
+            double za, zb; ell_z(L.a, L.b, L.d, c, kw, &za, &zb);
+            const CSv ca = cs_of(za), cb = cs_of(zb);
+            const EMat<double> M = ell_mat<double>(L.a, L.b, L.rho, L.d, c, kw, ca, cb, L.liquid && i == 0);
+            u = ell_act_row(M, u);
+        }
+        // u is now u_{-1} = h A_{last-1} ... A_0: D(e) = u_{-1} e, or - liquid top layer, skipped by the ellipticity passes -
+        // u_0 e
+        const bool wtop = (last >= 1) && ell_layer(A, b, 0, A.kpk[idx]).liquid;
+        double D2, D3;
+        if (wtop) {
+            D2 = A.wscr[((size_t)1 * A.Lmax + 0) * PB + idx];
+            D3 = A.wscr[((size_t)2 * A.Lmax + 0) * PB + idx];
+        } else {
+            D2 = u.x[1]; D3 = u.x[2];
+        }
+        const double chi = 0.5 * D3 / D2;
+        const double i2D2 = 0.5 / D2;
+        // K5c: forward states of e1, e2, e3, downward, and the contractions
+        EV5 v1{{1.0, 0.0, 0.0, 0.0, 0.0}}, v2{{0.0, 1.0, 0.0, 0.0, 0.0}}, v3{{0.0, 0.0, 1.0, 0.0, 0.0}};
+        double Fc = 0.0, Xc = 0.0;                          // dF/dc, d(D3 - 2 chi D2)/dc at fixed chi
+        bool ok = finite64(chi) && finite64(i2D2);
+        const size_t arr = (size_t)A.Lmax * PB;
+        for (int i = 0; i <= last; ++i) {
+            const bool is_hs = (i == last);
+            const ELayer L = is_hs ? hl : ell_layer(A, b, i, A.kpk[(size_t)i * PB + idx]);
+            const bool liq = L.liquid && i == 0 && !is_hs;
+            double sF[4] = {0.0, 0.0, 0.0, 0.0}, sX[4] = {0.0, 0.0, 0.0, 0.0};   // directions a, b, rho, c
+            if (is_hs) {
+#pragma unroll
+                for (int dir = 0; dir < 4; ++dir) {
+                    const Dd a{L.a, dir == 0 ? 1.0 : 0.0}, bb{L.b, dir == 1 ? 1.0 : 0.0}, r{L.rho, dir == 2 ? 1.0 : 0.0},
+                             cc{c, dir == 3 ? 1.0 : 0.0};
+                    Dd h[5];
+                    ell_hrow<Dd>(a, bb, r, cc, h);
+                    EV5 dh;
+                    for (int q = 0; q < 5; ++q) dh.x[q] = h[q].d;
+                    sF[dir] = ell_dot(dh, v1);
+                    sX[dir] = ell_dot(dh, v3) - 2.0 * chi * ell_dot(dh, v2);
+                }
+            } else {
+                EV5 ui;
+                for (int q = 0; q < 5; ++q) ui.x[q] = A.wscr[((size_t)q * A.Lmax + i) * PB + idx];
+                double za, zb; ell_z(L.a, L.b, L.d, c, kw, &za, &zb);
+                const CSv ca = cs_of(za), cb = cs_of(zb);
+                EMat<double> M{};
+#pragma unroll
+                for (int dir = 0; dir < 4; ++dir) {
+                    if (liq && dir < 3) continue;
+                    const Dd a{L.a, dir == 0 ? 1.0 : 0.0}, bb{L.b, dir == 1 ? 1.0 : 0.0}, r{L.rho, dir == 2 ? 1.0 : 0.0},
+                             cc{c, dir == 3 ? 1.0 : 0.0}, kk{kw, dir == 3 ? -kw / c : 0.0}, d{L.d, 0.0};
+                    const EMat<Dd> Md = ell_mat<Dd>(a, bb, r, d, cc, kk, ca, cb, liq);
+                    sF[dir] = ell_dot(ui, ell_act<true>(Md, v1));
+                    if (!liq) sX[dir] = ell_dot(ui, ell_act<true>(Md, v3)) - 2.0 * chi * ell_dot(ui, ell_act<true>(Md, v2));
+                    if (dir == 3) {
+#define SD_EV(f) M.f = Md.f.v
+                        SD_EV(a11); SD_EV(a12); SD_EV(a13); SD_EV(a14); SD_EV(a15); SD_EV(a21); SD_EV(a22); SD_EV(a23);
+                        SD_EV(a24); SD_EV(a31); SD_EV(a32); SD_EV(a33); SD_EV(a41); SD_EV(a42); SD_EV(a51);
+#undef SD_EV
+                    }
+                }
+                v1 = ell_act<false>(M, v1);
+                if (!liq) { v2 = ell_act<false>(M, v2); v3 = ell_act<false>(M, v3); }
+            }
+            Fc += sF[3];
+            Xc += sX[3];
+            // flattened (a, b, rho) -> the caller's (Vs, Vp, rho) of input layer i; a liquid layer gets none
+            const Chain ch = L.ch;
+            const double xb = liq ? 0.0 : i2D2 * (sX[1] * ch.dbdb + sX[0] * ch.dadb), xa = liq ? 0.0 : i2D2 * sX[0] * ch.dada,
+                         xr = liq ? 0.0 : i2D2 * sX[2] * ch.rfac;
+            const double fb = liq ? 0.0 : sF[1] * ch.dbdb + sF[0] * ch.dadb, fa = liq ? 0.0 : sF[0] * ch.dada,
+                         fr = liq ? 0.0 : sF[2] * ch.rfac;
+            ok = ok && finite64(xb) && finite64(xa) && finite64(xr) && finite64(fb) && finite64(fa) && finite64(fr);
+            const size_t o = (size_t)i * PB + idx;
+            A.xscr[o] = (float)xb; A.xscr[arr + o] = (float)xa; A.xscr[2 * arr + o] = (float)xr;
+            A.fscr[o] = (float)fb; A.fscr[arr + o] = (float)fa; A.fscr[2 * arr + o] = (float)fr;
+        }
+        // F-shares are stored unscaled; the unit's gamma = -(dchi/dc) / (dF/dc) carries 1 / (dF/dc)
+        const double g = -(i2D2 * Xc) / Fc;
+        ok = ok && finite64(g) && Fc != 0.0 && fabs(g) <= 3.0e38;
+        top = ok ? last : -2;
+        gam = ok ? (float)g : 0.0f;
+    }
+    A.gam[idx] = gam;
+    A.khs[idx] = top;
+    if (top == -2 && A.n_nonfinite) atomicAdd(A.n_nonfinite, 1);
+}
+
+// K5d: share + gamma x F-share -> the caller's [B][P][Lmax] rows through an LDS tile (as surfdisp_kern_transpose_kernel);
+// zeros below the unit's half space and for units without partials, NaN for every entry of a non-finite unit
+__global__ __launch_bounds__(256) void surfdisp_ellip_transpose_kernel(EllipTransposeArgs A)
+{
+    __shared__ float tile[64][65];
+    const int B = A.B, P = A.P, Lmax = A.Lmax;
+    float *__restrict__ out = (blockIdx.z == 0) ? A.eb : ((blockIdx.z == 1) ? A.ea : A.er);
+    if (!out) return;                                        // (block-uniform)
+    const size_t PB = (size_t)P * B;
+    const float *__restrict__ xs = A.xscr + (size_t)blockIdx.z * Lmax * PB;
+    const float *__restrict__ fsr = A.fscr + (size_t)blockIdx.z * Lmax * PB;
+    const int nbb = (B + 63) / 64;
+    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
+    const int bl = threadIdx.x % 64;
+    float g = 0.0f; int hs = -1;
+    if (b0 + bl < B) { g = A.gam[(size_t)k * B + b0 + bl]; hs = A.khs[(size_t)k * B + b0 + bl]; }
+    for (int il = threadIdx.x / 64; il < 64; il += 4) {
+        const size_t o = (size_t)(i0 + il) * PB + (size_t)k * B + b0 + bl;
+        tile[il][bl] = (hs == -2) ? __int_as_float(0x7fc00000) : ((i0 + il <= hs) ? fmaf(g, fsr[o], xs[o]) : 0.0f);
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
+        const int bq = t / 64, il = t % 64;
+        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
+    }
+}
+
+hipError_t launch_ellip_kern(hipStream_t s, const EllipKernArgs &a, const EllipTransposeArgs &t)
+{
+    const size_t total = (size_t)a.B * a.P;
+    hipLaunchKernelGGL(surfdisp_ellip_kern_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)(t.P * ((t.B + 63) / 64)), (unsigned)((t.Lmax + 63) / 64), 3u);
+    hipLaunchKernelGGL(surfdisp_ellip_transpose_kernel, grid, dim3(256), 0, s, t);
     return hipGetLastError();
 }
 

@@ -247,6 +247,43 @@ class BatchPlan:
         _lib.check(rc)
         return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(self.nfail.item())
 
+    def run_ellip_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True):
+        """``run_kernels`` plus the Rayleigh ellipticity and its analytic partials (``surfdisp_forward_ellip_kernels_device``):
+        returns (c, u, status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, n_nonfinite).  c .. dcdr equal ``run_kernels``' bit
+        for bit, ratio [B, P] is ``run(want_ratio=True)``'s; dedb / deda / dedr float32 [B, P, L] = d chi(period) / d (Vs | Vp |
+        rho) of input layer i (``None`` where not requested).  Rows of unsolved periods, water layers and layers below the half
+        space are zeros, rows of units whose result is not finite are NaN; ``n_nonfinite`` (int, synchronises the stream)
+        counts the latter.  Rayleigh only."""
+        torch = self.torch
+        if (int(kind) & 3) != _lib.KIND_RAYLEIGH:
+            raise ValueError("run_ellip_kernels: Rayleigh only (kind=2); Love waves have no ellipticity")
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        dcdb, dedb = mk(), mk()
+        dcda, deda = (mk(), mk()) if want_vp else (None, None)
+        dcdr, dedr = (mk(), mk()) if want_rho else (None, None)
+        ratio = torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
+        if getattr(self, "eworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
+            self.ews_bytes = int(_lib.lib().surfdisp_ellip_kernels_workspace_bytes(self.B, self.L, self.P))
+            self.eworkspace = torch.empty(self.ews_bytes, dtype=torch.uint8, device=self.device)
+            self.nnonfin = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._last_ws = self.eworkspace
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().surfdisp_forward_ellip_kernels_device(
+                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                ptr(self.c), ptr(self.u), ptr(ratio), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                ptr(dedb), ptr(deda), ptr(dedr), ptr(self.nnonfin), ptr(self.eworkspace), self.ews_bytes)
+        _lib.check(rc)
+        return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(self.nnonfin.item()))
+
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
         own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""

@@ -9,6 +9,8 @@ Differences from the reference, on purpose:
 * ``wtype='L'``: the reference reads ``cr0`` even for Love (``senskernel.py:188-192``, SURVEY.md
   section 4 defect 7) so its Love kernels are ``None``; here Love uses the Love phase velocities.
 * group-velocity kernels (``ytype='grv'``) come for free from the same batch.
+* analytic Rayleigh ellipticity (H/V) kernels (``analytic_kernels(ellipticity=True)``, ``ytype='ell'``) differentiate the
+  reference's own recursion (DLTAR4) at the root: dchi/dm = dchi/dm|_c + (dchi/dc) dc/dm, with dc/dm from the same recursion.
 * analytic group-velocity kernels (``analytic_kernels(group=True)``, ``SensKernel``) follow the toolkit's construction
   (GRV_SENS_KERNEL.f:99-108: phase partials at T x 0.99 and T x 1.01, their mean and central difference), but with the
   derived sign for all three columns: the toolkit's ``dudrho`` (GRV_SENS_KERNEL.f:107) adds the frequency term where
@@ -65,16 +67,29 @@ def perturbed_batch(H, Vs, Vp=None, Rho=None, Qs=None, Grp=None, xtype="Vs", lo=
 
 
 def sens_kernel_pert(H, Vs, Vp=None, Rho=None, Qs=None, Grp=None, periods=range(20, 101, 10),
-                     wtype="R", xtype="Vs", device=0):
-    """dict(phv=[P, L], grv=[P, L], c0=[P], u0=[P]); NaN columns where a perturbed solve failed."""
+                     wtype="R", xtype="Vs", device=0, ellipticity=False):
+    """dict(phv=[P, L], grv=[P, L], c0=[P], u0=[P]); NaN columns where a perturbed solve failed.
+    ``ellipticity=True`` (Rayleigh): the batch is solved on the device with the ellipticity (``BatchPlan.run(want_ratio=True)``)
+    and ell=[P, L] holds the same differences of chi."""
     kind = {"R": 2, "L": 1}[wtype]
+    if ellipticity and kind != 2:
+        raise ValueError("ellipticity kernels are Rayleigh only (wtype='R')")
     model, kept = perturbed_batch(H, Vs, Vp, Rho, Qs, Grp, xtype)
     per = np.asarray(list(periods), np.float32)
-    c, u, st = _forward.forward_batch(model, per, kind=kind, device=device)
+    curves = []
+    if ellipticity:
+        import torch
+        dev = torch.device(f"cuda:{device}")
+        plan = _forward.BatchPlan(model.shape[0], model.shape[2], per.size, device=dev)
+        c, u, st, ratio = plan.run(torch.from_numpy(model).to(dev), torch.from_numpy(per).to(dev), kind=kind, want_ratio=True)
+        c, u, st, ratio = (t.cpu().numpy() for t in (c, u, st, ratio))
+        curves = [("ell", ratio)]
+    else:
+        c, u, st = _forward.forward_batch(model, per, kind=kind, device=device)
     Lk = kept.size
     Hk = np.asarray(H, float)[kept]
     out = {}
-    for name, v in (("phv", c), ("grv", u)):
+    for name, v in [("phv", c), ("grv", u)] + curves:
         vL, vH = v[1:1 + Lk].astype(np.float64), v[1 + Lk:1 + 2 * Lk].astype(np.float64)
         k = (vH - vL) / 0.2 / Hk[:, None]                      # senskernel.py:150
         bad = (st[1:1 + Lk] != 0) | (st[1 + Lk:] != 0)
@@ -148,7 +163,8 @@ def group_from_phase_partials(c, u, k_minus, k_plus, dlnT):
     return r * (2.0 - r) * 0.5 * (km + kp) - r * r * (kp - km) / float(dlnT)
 
 
-def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01):
+def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01,
+                     ellipticity=False):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
     the partial derivatives REIGEN / LEIGEN form from their energy integrals and never return
     (surfa.f:1130-1135, 1204-1207; 561-565, 584-585), with the chain factors of the attenuation
@@ -160,12 +176,22 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     units ((v(1.001 Vs) - v(0.999 Vs)) / 0.2 / H, senskernel.py:150)).
     ``group=True`` (``surfdisp_forward_group_kernels_device``): also dudb, duda, dudr [M, P, L] = d U / d (Vs | Vp | rho)
     from the phase partials at T (1 -+ dlnT_frac) (see ``group_from_phase_partials``; NaN rows where a shifted root
-    failed), grv = dudb * Vs / 100 / h in phv's units, and n_failed."""
+    failed), grv = dudb * Vs / 100 / h in phv's units, and n_failed.
+    ``ellipticity=True`` (``surfdisp_forward_ellip_kernels_device``, Rayleigh only): also ratio [M, P] (the ellipticity chi),
+    dedb, deda, dedr [M, P, L] = d chi / d (Vs | Vp | rho), ell = dedb * Vs / 100 / h in phv's units, and n_nonfinite (units
+    whose rows are NaN).  It is one entry of its own: combined with ``group=True`` it is refused (call twice)."""
     import torch
     kind = {"R": 2, "L": 1}[wtype]
+    if ellipticity and kind != 2:
+        raise ValueError("analytic_kernels: ellipticity kernels are Rayleigh only (wtype='R')")
+    if ellipticity and group:
+        raise ValueError("analytic_kernels: ellipticity=True and group=True are separate entries; call once for each")
     M, _, L = model.shape
     plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
-    if group:
+    if ellipticity:
+        c, u, st, ratio, kb, ka, kr, eb, ea, er, nnf = plan.run_ellip_kernels(model, periods, kind=kind, nlay=nlay,
+                                                                             want_vp=want_vp, want_rho=want_rho)
+    elif group:
         c, u, st, kb, ka, kr, ub, ua, ur, nf = plan.run_group_kernels(model, periods, kind=kind, nlay=nlay, dlnT_frac=dlnT_frac,
                                                                       want_vp=want_vp, want_rho=want_rho)
     else:
@@ -176,6 +202,8 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     out = dict(dcdb=kb, dcda=ka, dcdr=kr, c0=c, u0=u, status=st, phv=per_km(kb))
     if group:
         out.update(dudb=ub, duda=ua, dudr=ur, grv=per_km(ub), n_failed=nf)
+    if ellipticity:
+        out.update(ratio=ratio, dedb=eb, deda=ea, dedr=er, ell=per_km(eb), n_nonfinite=nnf)
     return out
 
 
@@ -194,9 +222,11 @@ class SensKernelPert:
     them; the analytic route applies that chain rule).  Love kernels use Love velocities (the reference
     reads ``cr0`` for both wave types and returns ``None`` for Love, SURVEY.md section 4 defect 7).
     ``kernel_grv`` holds the same for the group velocity: ``fd`` from the U of the same perturbed batch, ``analytic`` from
-    ``surfdisp_forward_group_kernels_device`` with the same chain rule; ``plot(per, ytype='phv' | 'grv', xtype)``."""
+    ``surfdisp_forward_group_kernels_device`` with the same chain rule; ``plot(per, ytype='phv' | 'grv' | 'ell', xtype)``.
+    ``ellipticity=True`` (Rayleigh) also fills ``kernel_ell`` for the ellipticity chi: ``fd`` from the ratio of the same
+    perturbed batch (solved with the ellipticity), ``analytic`` from ``surfdisp_forward_ellip_kernels_device``."""
 
-    def __init__(self, model, wtype="R", Tmin=20, Tmax=100, Tstep=10, dz=2, method="fd", device=0):
+    def __init__(self, model, wtype="R", Tmin=20, Tmax=100, Tstep=10, dz=2, method="fd", device=0, ellipticity=False):
         import pandas as pd
         if isinstance(model, str):
             df = pd.read_csv(model)
@@ -213,12 +243,17 @@ class SensKernelPert:
         col = lambda k: df[k].to_numpy(float) if k in df else None
         Vp, Rho, Qs = col("Vp"), col("Rho"), col("Qs")
         self.H, self.Vs = H, Vs
-        self.kernel, self.kernel_grv = {}, {}
+        self.kernel, self.kernel_grv, self.kernel_ell = {}, {}, {}
+        ell = bool(ellipticity) and wtype == "R"
         if method == "fd":
             for x in ("Vs", "Vp"):
                 if x == "Vp" and Vp is None:
                     continue
-                out = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, x, device)
+                if ell:
+                    out = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, x, device, ellipticity=True)
+                    self.kernel_ell[x] = out["ell"]
+                else:
+                    out = sens_kernel_pert(H, Vs, Vp, Rho, Qs, grp, self.periods, wtype, x, device)
                 self.kernel[x], self.kernel_grv[x] = out["phv"], out["grv"]
         elif method == "analytic":
             import torch
@@ -240,7 +275,11 @@ class SensKernelPert:
                 if Rho is None:
                     drho = np.select([g == "sediment", g == "crust", g == "mantle"],
                                      [0.3601 * 1.23, 0.3601 * 1.8, 1.0 / 4.5], 0.0)
-            for dst, (b, a, r) in ((self.kernel, ("dcdb", "dcda", "dcdr")), (self.kernel_grv, ("dudb", "duda", "dudr"))):
+            dsts = [(self.kernel, ("dcdb", "dcda", "dcdr"), out), (self.kernel_grv, ("dudb", "duda", "dudr"), out)]
+            if ell:
+                oe = analytic_kernels(torch.from_numpy(m).to(dev), per, wtype=wtype, ellipticity=True)
+                dsts.append((self.kernel_ell, ("dedb", "deda", "dedr"), oe))
+            for dst, (b, a, r), out in dsts:
                 kb = out[b][0].double().cpu().numpy()
                 ka = out[a][0].double().cpu().numpy() if out[a] is not None else np.zeros_like(kb)
                 kr = out[r][0].double().cpu().numpy()
@@ -262,8 +301,10 @@ class SensKernelPert:
             kernel = self.kernel
         elif ytype == "grv":
             kernel = self.kernel_grv
+        elif ytype == "ell" and self.kernel_ell:
+            kernel = self.kernel_ell
         else:
-            raise ValueError(ytype)
+            raise ValueError(ytype if ytype != "ell" else "ytype='ell' needs ellipticity=True (Rayleigh)")
         fig, ax = plt.subplots(1, 1, figsize=[6, 8])
         zdeps = np.cumsum(self.H) - self.H / 2
         for iper, p in enumerate(self.periods):
@@ -288,9 +329,11 @@ class SensKernel:
     depth sample carries the per-km value of the LAYER that contains it (layer partial x value / velocity / thickness): the
     toolkit splits the model into dz sublayers and samples inside layers, so its curves vary within a thick layer where these
     are flat - their layer means agree.  Differences from the toolkit: its ``dudrho`` has the wrong sign on the frequency
-    term (see the module docstring); NaN where a shifted root failed."""
+    term (see the module docstring); NaN where a shifted root failed.
+    ``ellipticity=True`` (Rayleigh) also fills ``kernel_ell`` [1, nCol, P, nz] = (dchi/chi)/(dx/x) per km for the ellipticity
+    chi (H/V), in ``kernel_phv``'s convention, from ``surfdisp_forward_ellip_kernels_device``; ``plot(ytype='ell')``."""
 
-    def __init__(self, model=None, wtype="R", Tmin=20, Tmax=100, Tstep=10, endmode=0, dz=2, device=0):
+    def __init__(self, model=None, wtype="R", Tmin=20, Tmax=100, Tstep=10, endmode=0, dz=2, device=0, ellipticity=False):
         import pandas as pd
         import torch
         if model is None:
@@ -338,6 +381,18 @@ class SensKernel:
                 per_km[v[:, 0] <= 0, :] = np.nan                     # unsolved periods
                 lay_dst[x] = per_km                                  # [P, L] per layer
                 dst[0, ic] = per_km[:, lay]
+        self.kernel_ell, self.layer_ell = None, {}
+        if ellipticity and wtype == "R":
+            oe = analytic_kernels(torch.from_numpy(m).to(dev), per, wtype=wtype, ellipticity=True)
+            chi = oe["ratio"][0].double().cpu().numpy()[:, None]
+            self.kernel_ell = np.full_like(self.kernel_phv, np.nan)
+            for ic, x in enumerate(self.xtype):
+                k = oe[{"Vs": "dedb", "Vp": "deda", "Rho": "dedr"}[x]][0].double().cpu().numpy()
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    per_km = k * vals[x][None, :] / chi / H[None, :]
+                per_km[chi[:, 0] == 0, :] = np.nan                   # unsolved periods
+                self.layer_ell[x] = per_km
+                self.kernel_ell[0, ic] = per_km[:, lay]
 
     def plot(self, mode=0, per=None, ytype="phv", xtype="Vs"):
         """The reference's ``SensKernel.plot`` (senskernel.py:72-85): one curve per period against depth."""
@@ -346,8 +401,10 @@ class SensKernel:
             kernel = self.kernel_phv
         elif ytype == "grv":
             kernel = self.kernel_grv
+        elif ytype == "ell" and self.kernel_ell is not None:
+            kernel = self.kernel_ell
         else:
-            raise ValueError(ytype)
+            raise ValueError(ytype if ytype != "ell" else "ytype='ell' needs ellipticity=True (Rayleigh)")
         ix = self.xtype.index(xtype)
         fig, ax = plt.subplots(1, 1, figsize=[6, 8])
         for iper, p in enumerate(self.periods):
