@@ -34,7 +34,8 @@ extern "C" {
 
 #define SURFDISP_ABI_VERSION 4      /* 4 (r04): + SURFDISP_KERN_REFCOORD, surfdisp_workspace_counters, surfdisp_prior_device, surfdisp_mcmc_propose_masked_device; every ABI-3 symbol kept;
                                        additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes,
-                                       surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes */
+                                       surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes,
+                                       surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -172,6 +173,11 @@ int surfdisp_forward_batch_device_events(void *stream, int B, int Lmax, const in
                                          const float *model, int P, const float *per, int kind,
                                          float *c, float *u, int *status,
                                          void *workspace, size_t workspace_bytes, void *const *events4);
+/*          ... and of (3b), added within ABI 4: the same four events around the solve that also returns the ellipticity. */
+int surfdisp_forward_batch_device2_events(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind,
+                                          float *c, float *u, float *ratio, int *status,
+                                          void *workspace, size_t workspace_bytes, void *const *events4);
 int surfdisp_events_create(int n, void **events);
 int surfdisp_events_destroy(int n, void **events);
 int surfdisp_events_elapsed_ms(void *start, void *stop, float *ms);
@@ -343,6 +349,24 @@ int surfdisp_mcmc_accept_tree_joint_device(void *stream, int C, int N, int depth
                                            const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
                                            double *row, long row_stride, long step_stride, unsigned long long seed,
                                            unsigned long long counter, long chain0);
+/* ... and the Rayleigh ELLIPTICITY as a fifth curve (added within ABI 4): the two entries above with pred[5] / pred_stride[5],
+ * pred[4] = the [stacks][nper[0]] ratio array of the Rayleigh solve (surfdisp_forward_batch_device2; NULL where absent, and only
+ * together with pred[0]).  Column sources 0..3 as above, 4 = chi as the solver returns it (signed), 5 = |chi| of the same array (a
+ * measured H/V curve carries no sign).  On top of the rule above, (88888, 88888, 0) when an ellipticity value a column reads is
+ * not finite (NaN or inf: D(e2) ~ 0, see (5d)); no lower bound - chi near 0 and negative chi are legitimate predictions.  A column
+ * with source 4 or 5 whose pred[4] is NULL, or whose period index is beyond nper[0], fails the model and reads nothing.  Without
+ * such a column every row equals the four-array entries' bit for bit (those are this kernel compiled without the fifth source). */
+int surfdisp_mcmc_accept_joint5_device(void *stream, int C, int N, const float *const pred[5], const long pred_stride[5],
+                                       const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
+                                       const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                                       const double *p1, double *p0, double *chi0, double *row, long row_stride,
+                                       unsigned long long seed, unsigned long long counter, int first, long chain0);
+int surfdisp_mcmc_accept_tree_joint5_device(void *stream, int C, int N, int depth, int nsteps, const float *const pred[5],
+                                            const long pred_stride[5], const int nper[2], const int *const status[2], int Ptot,
+                                            const int *cols, const double *weights, const double *obs, const double *uncer,
+                                            const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
+                                            double *row, long row_stride, long step_stride, unsigned long long seed,
+                                            unsigned long long counter, long chain0);
 
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular

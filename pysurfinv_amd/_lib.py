@@ -33,6 +33,7 @@ EXPORTS = (
     "surfdisp_params_to_model_thermal_device", "surfdisp_thermal_scratch_bytes",
     "surfdisp_mcmc_propose_device", "surfdisp_mcmc_accept_device", "surfdisp_prior_device", "surfdisp_mcmc_propose_masked_device", "surfdisp_mcmc_propose_tree_device", "surfdisp_mcmc_accept_tree_device",
     "surfdisp_mcmc_accept_joint_device", "surfdisp_mcmc_accept_tree_joint_device",
+    "surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_forward_batch_device2_events",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
     "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes","surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
@@ -94,6 +95,11 @@ def lib() -> ctypes.CDLL:
     L.surfdisp_forward_batch_device_events.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp,
                                                        ctypes.c_int, vp, ctypes.c_int, vp, vp, vp,
                                                        vp, ctypes.c_size_t, ctypes.POINTER(vp)]
+    if hasattr(L, "surfdisp_forward_batch_device2_events"):   # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        L.surfdisp_forward_batch_device2_events.restype = ctypes.c_int
+        L.surfdisp_forward_batch_device2_events.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp,
+                                                            ctypes.c_int, vp, ctypes.c_int, vp, vp, vp, vp,
+                                                            vp, ctypes.c_size_t, ctypes.POINTER(vp)]
     L.surfdisp_events_create.restype = ctypes.c_int
     L.surfdisp_events_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
     L.surfdisp_events_destroy.restype = ctypes.c_int
@@ -152,6 +158,11 @@ def lib() -> ctypes.CDLL:
         L.surfdisp_mcmc_accept_tree_joint_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vpp, lp, ipp,
                                                              vpp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp,
                                                              ctypes.c_long, ctypes.c_long, u64, u64, ctypes.c_long]
+    if hasattr(L, "surfdisp_mcmc_accept_joint5_device"):       # (the same signatures with five prediction arrays)
+        for five, four in (("surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_joint_device"),
+                           ("surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_mcmc_accept_tree_joint_device")):
+            getattr(L, five).restype = ctypes.c_int
+            getattr(L, five).argtypes = getattr(L, four).argtypes
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -742,7 +742,8 @@ int surfdisp_mcmc_accept_tree_device(void *stream, int C, int N, int P, int dept
 }
 
 // Joint data (Rayleigh / Love, phase / group velocity): the accept entries above with the misfit summed over a column table.
-static int mcmc_accept_joint(const char *name, void *stream, int C, int N, const float *const pred[4], const long pred_stride[4],
+// ellip: the five-array entries (pred[4] = the Rayleigh solve's ellipticity, NULL allowed; column sources 4 and 5).
+static int mcmc_accept_joint(const char *name, bool ellip, void *stream, int C, int N, const float *const *pred, const long *pred_stride,
                              const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
                              const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
                              const double *p1, double *p0, double *chi0, double *row, long row_stride, long step_stride,
@@ -762,6 +763,11 @@ static int mcmc_accept_joint(const char *name, void *stream, int C, int N, const
         }
     }
     if (ok && !pred[0] && !pred[2]) ok = false;
+    if (ok && ellip && pred[4]) {                                           // chi [stacks][nper[0]] of the Rayleigh solve
+        j.pred[4] = pred[4];
+        j.pstride[4] = pred_stride[4];
+        if (!pred[0] || pred_stride[4] < nper[0]) ok = false;
+    }
     if (!ok) {
         set_err("%s: bad argument (1 <= nsteps <= depth <= 4, 1 <= Ptot <= 800, every given prediction array with 1 <= nper <= stride)", name);
         return SURFDISP_ERR_INVALID;
@@ -770,7 +776,7 @@ static int mcmc_accept_joint(const char *name, void *stream, int C, int N, const
     j.weights = weights;
     j.a = sd::McmcAcceptArgs{C, N, Ptot, nullptr, nullptr, obs, uncer, mask, obs_per_chain ? 1 : 0, p1, p0, chi0, row, row_stride,
                              seed, counter, first ? 1 : 0, chain0, depth, nsteps, step_stride};
-    SD_HIP(sd::launch_mcmc_accept_joint(static_cast<hipStream_t>(stream), j));
+    SD_HIP(sd::launch_mcmc_accept_joint(static_cast<hipStream_t>(stream), j, ellip));
     return SURFDISP_SUCCESS;
 }
 
@@ -780,7 +786,7 @@ int surfdisp_mcmc_accept_joint_device(void *stream, int C, int N, const float *c
                                       const double *p1, double *p0, double *chi0, double *row, long row_stride,
                                       unsigned long long seed, unsigned long long counter, int first, long chain0)
 {
-    return mcmc_accept_joint("surfdisp_mcmc_accept_joint_device", stream, C, N, pred, pred_stride, nper, status, Ptot, cols, weights,
+    return mcmc_accept_joint("surfdisp_mcmc_accept_joint_device", false, stream, C, N, pred, pred_stride, nper, status, Ptot, cols, weights,
                              obs, uncer, mask, obs_per_chain, p1, p0, chi0, row, row_stride, 0, seed, counter, first, chain0, 1, 1);
 }
 
@@ -791,7 +797,30 @@ int surfdisp_mcmc_accept_tree_joint_device(void *stream, int C, int N, int depth
                                            double *row, long row_stride, long step_stride, unsigned long long seed,
                                            unsigned long long counter, long chain0)
 {
-    return mcmc_accept_joint("surfdisp_mcmc_accept_tree_joint_device", stream, C, N, pred, pred_stride, nper, status, Ptot, cols,
+    return mcmc_accept_joint("surfdisp_mcmc_accept_tree_joint_device", false, stream, C, N, pred, pred_stride, nper, status, Ptot, cols,
+                             weights, obs, uncer, mask, obs_per_chain, q, p0, chi0, row, row_stride, step_stride, seed, counter, 0,
+                             chain0, depth, nsteps);
+}
+
+// ... and with a fifth prediction array, the ellipticity of the Rayleigh solve (column sources 4: chi, 5: |chi|).
+int surfdisp_mcmc_accept_joint5_device(void *stream, int C, int N, const float *const pred[5], const long pred_stride[5],
+                                       const int nper[2], const int *const status[2], int Ptot, const int *cols, const double *weights,
+                                       const double *obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                                       const double *p1, double *p0, double *chi0, double *row, long row_stride,
+                                       unsigned long long seed, unsigned long long counter, int first, long chain0)
+{
+    return mcmc_accept_joint("surfdisp_mcmc_accept_joint5_device", true, stream, C, N, pred, pred_stride, nper, status, Ptot, cols, weights,
+                             obs, uncer, mask, obs_per_chain, p1, p0, chi0, row, row_stride, 0, seed, counter, first, chain0, 1, 1);
+}
+
+int surfdisp_mcmc_accept_tree_joint5_device(void *stream, int C, int N, int depth, int nsteps, const float *const pred[5],
+                                            const long pred_stride[5], const int nper[2], const int *const status[2], int Ptot,
+                                            const int *cols, const double *weights, const double *obs, const double *uncer,
+                                            const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
+                                            double *row, long row_stride, long step_stride, unsigned long long seed,
+                                            unsigned long long counter, long chain0)
+{
+    return mcmc_accept_joint("surfdisp_mcmc_accept_tree_joint5_device", true, stream, C, N, pred, pred_stride, nper, status, Ptot, cols,
                              weights, obs, uncer, mask, obs_per_chain, q, p0, chi0, row, row_stride, step_stride, seed, counter, 0,
                              chain0, depth, nsteps);
 }
@@ -810,6 +839,19 @@ int surfdisp_forward_batch_device_events(void *stream, int B, int Lmax, const in
     for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(events4[i]);
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
                                workspace, workspace_bytes, ev);
+}
+
+// ... of surfdisp_forward_batch_device2: the same events around the solve that also returns the ellipticity
+int surfdisp_forward_batch_device2_events(void *stream, int B, int Lmax, const int *nlay,
+                                          const float *model, int P, const float *per, int kind,
+                                          float *c, float *u, float *ratio, int *status,
+                                          void *workspace, size_t workspace_bytes, void *const *events4)
+{
+    if (!events4) { set_err("events4 is NULL"); return SURFDISP_ERR_INVALID; }
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(events4[i]);
+    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                               workspace, workspace_bytes, ev, nullptr, nullptr, nullptr, ratio);
 }
 
 int surfdisp_events_create(int n, void **events)

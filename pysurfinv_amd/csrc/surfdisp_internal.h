@@ -220,20 +220,20 @@ struct McmcAcceptArgs {
     int depth, nsteps;      // speculative tree: walk nsteps <= depth steps (depth <= 1: the plain single test)
     long step_stride;       // doubles between the mcTrack rows of consecutive steps of one chain
 };
-// joint data (Rayleigh / Love, phase / group): the accept kernel's arguments plus the solves' predictions and the column table.
-// In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
+// joint data (Rayleigh / Love, phase / group, Rayleigh ellipticity): the accept kernel's arguments plus the solves' predictions and
+// the column table.  In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
 struct McmcJointArgs {
     McmcAcceptArgs a;
-    const float *pred[4];   // cR, uR, cL, uL: [stacks][pstride[s]] or nullptr; a wave type has data iff its c array is given
-    long pstride[4];        // floats between the stacks' rows of each array
+    const float *pred[5];   // cR, uR, cL, uL, chi of the Rayleigh solve: [stacks][pstride[s]] or nullptr; a wave type has data iff its c array is given
+    long pstride[5];        // floats between the stacks' rows of each array
     int nper[2];            // periods of the Rayleigh / Love solve
     const int *status[2];   // [stacks] or nullptr
-    const int *cols;        // [Ptot][2]: source array (0..3), period index in that solve
+    const int *cols;        // [Ptot][2]: source (0..3 the arrays; 4 chi, 5 |chi|: pred[4], the joint5 entries only), period index in that solve
     const double *weights;  // [Ptot]
 };
 hipError_t launch_mcmc_propose(hipStream_t s, const McmcProposeArgs &a);
 hipError_t launch_mcmc_accept(hipStream_t s, const McmcAcceptArgs &a);
-hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a);
+hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a, bool ellip);   // ellip: the kernel that knows the sources 4 and 5
 hipError_t launch_layers(hipStream_t s, const LayersArgs &a, int L);
 hipError_t launch_prior(hipStream_t s, const LayersArgs &a, int L, const int *flags, double vs_max, int only_tag, int mark_tag, unsigned char *tags);
 hipError_t launch_thermal(hipStream_t s, const LayersArgs &a);

@@ -170,6 +170,12 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArg
 // period beyond its solve (it fails the model: no read out of bounds).  With one Rayleigh-phase data set of weight 1 this gives
 // misfit_of's bits (the same operations on the masked-in entries, an exact +0 for the others).  The loops are unrolled so that
 // one thread has several columns' loads in flight: at 100 chains the kernel is bound by the latency of those loads.
+// E (surfdisp_mcmc_accept_joint5_device): a fifth prediction array, the Rayleigh ellipticity chi of the Rayleigh solve (pred[4],
+// [stacks][nper[0]]), read by the sources 4 (chi as it is) and 5 (|chi|); a value a column reads that is not finite fails the
+// model - no lower bound, chi <= 0 is a legitimate prediction.  The sources 0..3 go through the same operations in the same
+// order with and without E (the kernels of the four-array entries are the E = false instantiation), and the source select stays
+// a chain of compares on scalars: no indexed private array, no scratch.
+template <bool E>
 __device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const int *col, const double *wt, size_t q, size_t ob,
                                                 double &mis, double &chi, double &L)
 {
@@ -188,6 +194,7 @@ __device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const in
     const float *base[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) base[k] = J.pred[k] ? J.pred[k] + q * J.pstride[k] : nullptr;
+    const float *base4 = (E && J.pred[4]) ? J.pred[4] + q * J.pstride[4] : nullptr;
     chi = 0.0;
     int cnt = 0;
     // every load of a column is unconditional (a masked-out entry adds an exact 0), so the unrolled loop keeps them in flight
@@ -198,9 +205,12 @@ __device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const in
         const double o = A.c_obs[ob + j], sg = A.uncer[ob + j];
         if (e < 0) { failed = true; continue; }
         const int s = e >> 16;
-        const float *b = s == 0 ? base[0] : s == 1 ? base[1] : s == 2 ? base[2] : base[3];
-        const double v = (double)b[e & 0xffff];
-        if ((s & 1) && !(v >= 0.01)) failed = true;                    // a group velocity the data use
+        const float *b = s == 0 ? base[0] : s == 1 ? base[1] : s == 2 ? base[2] : (!E || s == 3) ? base[3] : base4;
+        double v = (double)b[e & 0xffff];
+        if (E && s >= 4) {
+            if (!(fabs(v) <= 1.7976931348623157e308)) failed = true;   // an ellipticity the data use: NaN or inf
+            if (s == 5) v = fabs(v);                                   // a measured H/V curve: |chi|
+        } else if ((s & 1) && !(v >= 0.01)) failed = true;             // a group velocity the data use
         const double r = in ? (o - v) / sg : 0.0;
         chi += (wt[j] * r) * r;
         cnt += in ? 1 : 0;
@@ -212,6 +222,7 @@ __device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const in
 }
 
 // surfdisp_mcmc_accept_kernel with the joint misfit: the same accept rule, random stream, tree walk and mcTrack rows.
+template <bool E>
 __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJointArgs J)
 {
     const McmcAcceptArgs &A = J.a;
@@ -219,7 +230,9 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJoi
     __shared__ double wt[SD_MCMC_JOINT_MAX_COLS];
     for (int j = threadIdx.x; j < A.P; j += blockDim.x) {
         const int s = J.cols[2 * j], i = J.cols[2 * j + 1];
-        const bool ok = s >= 0 && s <= 3 && J.pred[s] && i >= 0 && i < J.nper[s >> 1];
+        // (sources 4 and 5 both read pred[4], at a period of the Rayleigh solve)
+        const bool ell = E && (s == 4 || s == 5);
+        const bool ok = (ell ? J.pred[4] != nullptr : (s >= 0 && s <= 3 && J.pred[s])) && i >= 0 && i < J.nper[ell ? 0 : s >> 1];
         col[j] = ok ? (s << 16) | i : -1;
         wt[j] = J.weights[j];
     }
@@ -237,7 +250,7 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJoi
     for (int s = 0; s < nsteps; ++s) {
         const size_t q = (size_t)c * M + node;
         double mis, chi, L;
-        joint_misfit_of(J, col, wt, q, ob, mis, chi, L);
+        joint_misfit_of<E>(J, col, wt, q, ob, mis, chi, L);
         bool acc;
         if (A.first) acc = true;
         else if (chi < chi0) acc = true;                               // point.py:34-37
@@ -262,9 +275,11 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJoi
     A.chi0[c] = chi0;
 }
 
-hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a)
+hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a, bool ellip)
 {
-    hipLaunchKernelGGL(surfdisp_mcmc_accept_joint_kernel, dim3((unsigned)((a.a.C + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((a.a.C + 255) / 256));
+    if (ellip) hipLaunchKernelGGL(surfdisp_mcmc_accept_joint_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(surfdisp_mcmc_accept_joint_kernel<false>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

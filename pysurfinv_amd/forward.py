@@ -139,14 +139,15 @@ class BatchPlan:
                 rc = _lib.lib().surfdisp_forward_batch_device_timed(*args, ms)
                 _lib.check(rc)
                 return self.c, self.u, self.status, tuple(float(x) for x in ms)
-            if want_ratio and events is not None:
-                raise ValueError("BatchPlan.run: want_ratio and events cannot be combined (no events variant of surfdisp_forward_batch_device2)")
             if want_ratio:
                 # ABI 3: also the Rayleigh ellipticity (the reference's COMMON /o/ ratio, calcul.f:195) -> self.ratio [B, P]
                 if getattr(self, "ratio", None) is None:
                     self.ratio = torch.zeros(self.B, self.P, dtype=torch.float32, device=self.device)
                 a2 = args[:10] + [ctypes.c_void_p(self.ratio.data_ptr())] + args[10:]
-                rc = _lib.lib().surfdisp_forward_batch_device2(*a2)
+                if events is not None:
+                    rc = _lib.lib().surfdisp_forward_batch_device2_events(*a2, events)
+                else:
+                    rc = _lib.lib().surfdisp_forward_batch_device2(*a2)
             elif events is not None:
                 rc = _lib.lib().surfdisp_forward_batch_device_events(*args, events)
             else:

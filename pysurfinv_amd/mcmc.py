@@ -259,8 +259,9 @@ class MetropolisBatch:
         return c.to(torch.float64), st
 
     def forward_joint(self, params, rows=None):
-        """Joint data: dict(cR, uR, cL, uL, statusR, statusL) of the stacks of ``params`` (None for a wave type without
-        data; a wave type without U data is solved phase-only, its u is not meaningful)."""
+        """Joint data: dict(cR, uR, cL, uL, statusR, statusL, eR) of the stacks of ``params`` (None for a wave type without
+        data; a wave type without U data is solved phase-only, its u is not meaningful).  eR: the ellipticity of the Rayleigh
+        solve (``BatchPlan.run(want_ratio=True)``) when there is an ellipticity data set, None otherwise."""
         if self.joint is None:
             raise ValueError("forward_joint needs a sampler built with data=")
         return self.forward_c(params, rows)
@@ -345,8 +346,9 @@ class MetropolisBatch:
         return c, st
 
     def _solve_joint(self, model, nlay):
-        """Joint data: one solve per wave type with data, both on the same stacks -> dict(cR, uR, cL, uL, statusR, statusL)
-        of the solver's own fp32 output tensors (None for a wave type without data).  Kind flags: ``JointData.kind`` (phase
+        """Joint data: one solve per wave type with data, both on the same stacks -> dict(cR, uR, cL, uL, statusR, statusL, eR)
+        of the solver's own fp32 output tensors (None for a wave type without data; eR, the Rayleigh solve's ellipticity, only
+        with an ellipticity data set: that solve then runs with ``want_ratio``).  Kind flags: ``JointData.kind`` (phase
         only unless the wave type has U data), ``independent`` / ``fast_scan`` as for the Rayleigh-only sampler.  Two solves:
         SURFDISP_PIPELINED for both; as one chain group the Love solve runs on a second stream forked from, and joined back
         into, the current one (as ``forward.JointPlan``; no host synchronisation), inside a chain group after the Rayleigh
@@ -377,19 +379,22 @@ class MetropolisBatch:
             if self._side is None:
                 self._side = torch.cuda.Stream(device=self.device)
             self._side.wait_stream(cur)
-        out = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None)
+        out = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
         for i, (w, key) in enumerate(zip(jd.waves, keys)):
             with (torch.cuda.stream(self._side) if (fork and i == 1) else contextlib.nullcontext()):
-                c, u, st = plans[key].run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, independent=indep,
-                                          fast_scan=self.fast_scan, events=ev if i == 0 else None,
-                                          pipelined=self._pipelined or two)
-            out["c" + w], out["u" + w], out["status" + w] = c, u, st
+                res = plans[key].run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, independent=indep,
+                                     fast_scan=self.fast_scan, events=ev if i == 0 else None,
+                                     pipelined=self._pipelined or two, want_ratio=jd.with_ratio and w == "R")
+            out["c" + w], out["u" + w], out["status" + w] = res[:3]
+            if len(res) > 3:
+                out["eR"] = res[3]
         if fork:
             cur.wait_stream(self._side)
         return out
 
     def _accept_joint(self, stream, pred, st, p1, p, rowp, row_stride, counter, first=False, depth=1, nsteps=1, step_stride=0):
-        """The joint accept kernel (``surfdisp_mcmc_accept_joint_device`` / ``_tree_joint_device``) on the solves of ``pred``."""
+        """The joint accept kernel (``surfdisp_mcmc_accept_joint_device`` / ``_tree_joint_device``; with an ellipticity data
+        set their five-array forms ``..._joint5_device``) on the solves of ``pred``."""
         import ctypes
         jd = self.joint
         C, N = p.shape
@@ -399,24 +404,29 @@ class MetropolisBatch:
         ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
         arrs = [pred["cR"], pred["uR"] if jd.with_group.get("R") else None,
                 pred["cL"], pred["uL"] if jd.with_group.get("L") else None]
+        if jd.with_ratio:
+            if pred.get("eR") is None:
+                raise ValueError("joint accept: an ellipticity data set, but the Rayleigh solve returned no ratio")
+            arrs.append(pred["eR"])
         for a in arrs:
             if a is not None and (a.dtype != self.torch.float32 or a.stride(1) != 1):
                 raise ValueError("joint accept: predictions must be float32 rows of the solver's outputs")
-        predp = (ctypes.c_void_p * 4)(*[a.data_ptr() if a is not None else None for a in arrs])
-        strides = (ctypes.c_long * 4)(*[a.stride(0) if a is not None else 0 for a in arrs])
+        predp = (ctypes.c_void_p * len(arrs))(*[a.data_ptr() if a is not None else None for a in arrs])
+        strides = (ctypes.c_long * len(arrs))(*[a.stride(0) if a is not None else 0 for a in arrs])
         nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
         stat = (ctypes.c_void_p * 2)(*[pred["status" + w].data_ptr() if pred["status" + w] is not None else None
                                        for w in ("R", "L")])
         table = (predp, strides, nper, stat, jd.Ptot, ptr(jd.cols), ptr(jd.weights), ptr(st["c_obs"]), ptr(st["uncer"]),
                  ptr(st["mask8"]), 1 if st["c_obs"].ndim == 2 else 0)
         pr = self.proposer
+        plain, tree = ((L.surfdisp_mcmc_accept_joint5_device, L.surfdisp_mcmc_accept_tree_joint5_device) if jd.with_ratio else
+                       (L.surfdisp_mcmc_accept_joint_device, L.surfdisp_mcmc_accept_tree_joint_device))
         if depth <= 1:
-            _lib.check(L.surfdisp_mcmc_accept_joint_device(stream, C, N, *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp,
+            _lib.check(plain(stream, C, N, *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp,
                                                            int(row_stride), pr.seed_int, counter, 1 if first else 0, self._chain0))
         else:
-            _lib.check(L.surfdisp_mcmc_accept_tree_joint_device(stream, C, N, int(depth), int(nsteps), *table, ptr(p1), ptr(p),
-                                                                ptr(st["chi"]), rowp, int(row_stride), int(step_stride),
-                                                                pr.seed_int, counter, self._chain0))
+            _lib.check(tree(stream, C, N, int(depth), int(nsteps), *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp, int(row_stride),
+                            int(step_stride), pr.seed_int, counter, self._chain0))
 
     def fused_step(self, p, row=None, row_stride=0, first=False, counter=None, row_offset=0):
         """One Metropolis step of every chain, in place on the state ``p`` [C, N] (float64, contiguous): proposal

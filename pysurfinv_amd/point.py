@@ -6,12 +6,15 @@ GPU (``MetropolisBatch``) instead of one process per chain.
     p.misfit()                                   # (misfit, chiSqr, L) of the initial model, point.py:15-31
     p.MCinvMP(outdir, pid, runN=50000, chainL=1000, seed=42)        # -> {outdir}/{pid}.npz
 
-Joint data (Rayleigh / Love, phase / group velocity; ``pysurfinv_amd.obsdata``):
+Joint data (Rayleigh / Love, phase / group velocity, Rayleigh ellipticity; ``pysurfinv_amd.obsdata``):
 
     p = Point(setting, data={"RayPhase": (T, c, sigma), "RayGroup": (T_U, U, sigma_U), "LoveGroup": (...)})
+    p = Point(setting, data={"RayPhase": (T, c, sigma), "RayHV": (T_E, hv, sigma_E)})     # a measured H/V curve: |chi|
+                                                                                          # ("RayEllip": the signed chi)
 
 The ``.npz``'s ``obs`` then keeps the reference's ``T`` / ``c`` / ``uncer`` (the Rayleigh-phase set, empty without one) and
-adds ``data``: every data set as a dict of plain arrays (``DispersionData.to_dict``), which ``PostPoint`` reads back.
+adds ``data``: every data set as a dict of plain arrays (``DispersionData.to_dict``, an ellipticity set's ``absolute`` flag
+included), which ``PostPoint`` reads back.
 
 The ``.npz`` has the reference's keys (``mcTrack`` rows ``[misfit, L, accepted, *params]`` in
 ``MCinv._brownians()`` order, ``setting``, ``obs``, ``invMeta``; ``point.py:82-85,120-123``), so

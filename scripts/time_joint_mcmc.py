@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""GPU box: what U data and a Love solve add to a Metropolis lock step (MetropolisBatch(data=...), pysurfinv_amd.obsdata).
+"""GPU box: what U data, a Love solve and the Rayleigh ellipticity add to a Metropolis lock step (MetropolisBatch(data=...),
+pysurfinv_amd.obsdata).
 
-For the data sets {Rc}, {Rc, RU} and {Rc, RU, Lc, LU} (all on the 19 periods of MCMC_PERIODS, per-chain synthetic
-observations of the 96-layer continental model) and, as the baseline, the (periods, c_obs, uncer) sampler: ms per lock
+For the data sets {Rc}, {Rc, RU}, {Rc, RU, Lc, LU}, {Rc, RE} and {Rc, RU, Lc, LU, RE} (all on the 19 periods of MCMC_PERIODS,
+per-chain synthetic observations of the 96-layer continental model; RE: the signed ellipticity of the Rayleigh solve, which
+then also runs the ellipticity passes) and, as the baseline, the (periods, c_obs, uncer) sampler: ms per lock
 step of MetropolisBatch.run on its default path, and the joint accept kernel's time (HIP events around repeated launches
 on the last lock step's predictions, all chains in one launch, alone on the chip) as a share of the lock step.
 
@@ -31,7 +33,8 @@ from pysurfinv_amd.obsdata import DispersionData
 
 
 def observations(mb, n_points, dev, seed=100):
-    """Rc, RU, Lc, LU [n_points, P] of 'true' models (prior draws shrunk towards the start model), 1 % / 2 % errors."""
+    """Rc, RU, RE, Lc, LU [n_points, P] of 'true' models (prior draws shrunk towards the start model), 1 % / 2 % errors
+    (RE: 2 % of |chi|)."""
     per = torch.as_tensor(np.asarray(settings.MCMC_PERIODS, np.float32), device=dev)
     v0 = torch.as_tensor(mb.spec.v0, dtype=torch.float64, device=dev)[None, :]
     truth = torch.cat([v0, v0 + 0.3 * (TorchProposer(mb.spec, dev, seed=seed).reset(n_points) - v0)])
@@ -39,11 +42,11 @@ def observations(mb, n_points, dev, seed=100):
     out = {}
     for w, kind in (("R", _lib.KIND_RAYLEIGH), ("L", _lib.KIND_LOVE)):
         plan = BatchPlan(model.shape[0], model.shape[2], per.numel(), device=dev)
-        c, u, st = (t.clone() for t in plan.run(model.contiguous(), per, kind=kind, nlay=nlay))
-        bad = (st != 0)[:, None] | (c < 0.01) | ~(u >= 0.01)
-        for q, a in (("c", c), ("U", u)):
+        c, u, st, e = (t.clone() for t in plan.run(model.contiguous(), per, kind=kind, nlay=nlay, want_ratio=True))
+        bad = (st != 0)[:, None] | (c < 0.01) | ~(u >= 0.01) | ~torch.isfinite(e)
+        for q, a in (("c", c), ("U", u)) + ((("E", e),) if w == "R" else ()):
             a = torch.where(bad.any(dim=1, keepdim=True), a[:1].expand_as(a), a)[1:].double().cpu().numpy()
-            out[w + q] = (a, (0.01 if q == "c" else 0.02) * a)
+            out[w + q] = (a, (0.01 if q == "c" else 0.02) * np.abs(a))
     return out
 
 
@@ -94,7 +97,8 @@ def lock_step_ms(mc, C, steps, depth, trials=3):
 
 
 CONFIGS = (("(periods, c_obs, uncer) sampler", None), ("data={Rc}", ("Rc",)), ("data={Rc, RU}", ("Rc", "RU")),
-           ("data={Rc, RU, Lc, LU}", ("Rc", "RU", "Lc", "LU")))
+           ("data={Rc, RU, Lc, LU}", ("Rc", "RU", "Lc", "LU")), ("data={Rc, RE}", ("Rc", "RE")),
+           ("data={Rc, RU, Lc, LU, RE}", ("Rc", "RU", "Lc", "LU", "RE")))
 
 
 def one(C, which, steps):
