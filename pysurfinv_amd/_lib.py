@@ -140,29 +140,24 @@ def lib() -> ctypes.CDLL:
         L.surfdisp_prior_device.restype = ctypes.c_int
         L.surfdisp_prior_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int,
                                             ctypes.c_int, vp]
-    L.surfdisp_mcmc_accept_device.restype = ctypes.c_int
-    L.surfdisp_mcmc_accept_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int,
-                                              vp, vp, vp, vp, ctypes.c_long, u64, u64, ctypes.c_int, ctypes.c_long]
     L.surfdisp_mcmc_propose_tree_device.restype = ctypes.c_int
     L.surfdisp_mcmc_propose_tree_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, u64, u64, vp, ctypes.c_long]
-    L.surfdisp_mcmc_accept_tree_device.restype = ctypes.c_int
-    L.surfdisp_mcmc_accept_tree_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp,
-                                                   ctypes.c_int, vp, vp, vp, vp, ctypes.c_long, ctypes.c_long, u64, u64, ctypes.c_long]
-    if hasattr(L, "surfdisp_mcmc_accept_joint_device"):        # (absent from an older build loaded through SURFDISP_LIB_PATH)
-        vpp, lp, ipp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)
-        L.surfdisp_mcmc_accept_joint_device.restype = ctypes.c_int
-        L.surfdisp_mcmc_accept_joint_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vpp, lp, ipp, vpp, ctypes.c_int, vp, vp, vp, vp,
-                                                        vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_long, u64, u64, ctypes.c_int,
-                                                        ctypes.c_long]
-        L.surfdisp_mcmc_accept_tree_joint_device.restype = ctypes.c_int
-        L.surfdisp_mcmc_accept_tree_joint_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vpp, lp, ipp,
-                                                             vpp, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp,
-                                                             ctypes.c_long, ctypes.c_long, u64, u64, ctypes.c_long]
-    if hasattr(L, "surfdisp_mcmc_accept_joint5_device"):       # (the same signatures with five prediction arrays)
-        for five, four in (("surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_joint_device"),
-                           ("surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_mcmc_accept_tree_joint_device")):
-            getattr(L, five).restype = ctypes.c_int
-            getattr(L, five).argtypes = getattr(L, four).argtypes
+    # the accept entries: (stream, C, N, [P,] [depth, nsteps,] predictions, c_obs, uncer, mask, obs_per_chain, p1, p0, chi0, row,
+    # row_stride, [step_stride,] seed, counter, [first,] chain0) - P and the predictions differ between the Rayleigh-phase entries
+    # and the joint ones, the tree entries take depth, nsteps and step_stride in place of first
+    vpp, lp, ipp = ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int)
+    pred_c, pred_joint = [vp, vp], [vpp, lp, ipp, vpp, ctypes.c_int, vp, vp]
+    for name, tree, head, pred in (("surfdisp_mcmc_accept_device", False, [ctypes.c_int], pred_c),
+                                   ("surfdisp_mcmc_accept_tree_device", True, [ctypes.c_int], pred_c),
+                                   ("surfdisp_mcmc_accept_joint_device", False, [], pred_joint),
+                                   ("surfdisp_mcmc_accept_tree_joint_device", True, [], pred_joint),
+                                   ("surfdisp_mcmc_accept_joint5_device", False, [], pred_joint),
+                                   ("surfdisp_mcmc_accept_tree_joint5_device", True, [], pred_joint)):
+        if pred is pred_c or hasattr(L, name):                 # (the joint entries: absent from an older build loaded through SURFDISP_LIB_PATH)
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = ([vp, ctypes.c_int, ctypes.c_int] + head + ([ctypes.c_int, ctypes.c_int] if tree else []) + pred
+                                         + [vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_long] + ([ctypes.c_long] if tree else [])
+                                         + [u64, u64] + ([] if tree else [ctypes.c_int]) + [ctypes.c_long])
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -664,13 +664,25 @@ int surfdisp_params_to_model_thermal_device(void *stream, int C, int N, int L, c
 }
 
 // Metropolis glue on the device (surfdisp_mcmc.hip): proposal and misfit / accept / state update of one lock step.
+// The three proposal entries: one proposal per chain (depth 1), the speculative tree (depth > 1), or the masked redraw (tags).
+static int mcmc_propose(const char *name, void *stream, int C, int N, const double *p, const double *vmin, const double *vmax,
+                        const double *step, unsigned long long seed, unsigned long long counter, int reset, double *out, long chain0,
+                        int depth, bool masked, const unsigned char *tags, int attempt, int tag)
+{
+    if (C < 1 || N < 1 || !p || !vmin || !vmax || !step || !out || chain0 < 0 || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH ||
+        (masked && (!tags || attempt < 0 || attempt > 1023 || reset < 0 || reset > 2 || tag < 1 || tag > 255))) {
+        set_err("%s: bad argument%s", name, depth != 1 ? " (1 <= depth <= 4)" : ""); return SURFDISP_ERR_INVALID;
+    }
+    sd::McmcProposeArgs a{C, N, p, vmin, vmax, step, seed, counter, reset, out, chain0, depth, tags, attempt, tag};
+    SD_HIP(sd::launch_mcmc_propose(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 int surfdisp_mcmc_propose_device(void *stream, int C, int N, const double *p, const double *vmin, const double *vmax,
                                  const double *step, unsigned long long seed, unsigned long long counter, int reset, double *out, long chain0)
 {
-    if (C < 1 || N < 1 || !p || !vmin || !vmax || !step || !out || chain0 < 0) { set_err("surfdisp_mcmc_propose_device: bad argument"); return SURFDISP_ERR_INVALID; }
-    sd::McmcProposeArgs a{C, N, p, vmin, vmax, step, seed, counter, reset ? 1 : 0, out, chain0, 1, nullptr, 0, 0};
-    SD_HIP(sd::launch_mcmc_propose(static_cast<hipStream_t>(stream), a));
-    return SURFDISP_SUCCESS;
+    return mcmc_propose("surfdisp_mcmc_propose_device", stream, C, N, p, vmin, vmax, step, seed, counter, reset ? 1 : 0, out, chain0, 1,
+                        false, nullptr, 0, 0);
 }
 
 // masked redraw of the chains the prior kernel tagged (tags[c] == tag; see surfdisp_prior_device); mode 0: bounded Gaussian step,
@@ -679,13 +691,15 @@ int surfdisp_mcmc_propose_masked_device(void *stream, int C, int N, const double
                                         const double *step, unsigned long long seed, unsigned long long counter, int attempt, int mode,
                                         const unsigned char *tags, int tag, double *out, long chain0)
 {
-    if (C < 1 || N < 1 || !p || !vmin || !vmax || !step || !out || !tags || chain0 < 0 || attempt < 0 || attempt > 1023 || mode < 0 || mode > 2 ||
-        tag < 1 || tag > 255) {
-        set_err("surfdisp_mcmc_propose_masked_device: bad argument"); return SURFDISP_ERR_INVALID;
-    }
-    sd::McmcProposeArgs a{C, N, p, vmin, vmax, step, seed, counter, mode, out, chain0, 1, tags, attempt, tag};
-    SD_HIP(sd::launch_mcmc_propose(static_cast<hipStream_t>(stream), a));
-    return SURFDISP_SUCCESS;
+    return mcmc_propose("surfdisp_mcmc_propose_masked_device", stream, C, N, p, vmin, vmax, step, seed, counter, mode, out, chain0, 1,
+                        true, tags, attempt, tag);
+}
+
+int surfdisp_mcmc_propose_tree_device(void *stream, int C, int N, int depth, const double *p, const double *vmin, const double *vmax,
+                                      const double *step, unsigned long long seed, unsigned long long counter, double *out, long chain0)
+{
+    return mcmc_propose("surfdisp_mcmc_propose_tree_device", stream, C, N, p, vmin, vmax, step, seed, counter, 0, out, chain0, depth,
+                        false, nullptr, 0, 0);
 }
 
 // The generic prior predicates on the device (csrc/surfdisp_layers.hip, surfdisp_prior_kernel): tags[c] = mark_tag where chain c's
@@ -702,14 +716,20 @@ int surfdisp_prior_device(void *stream, int C, int N, int L, const double *param
     return SURFDISP_SUCCESS;
 }
 
-int surfdisp_mcmc_propose_tree_device(void *stream, int C, int N, int depth, const double *p, const double *vmin, const double *vmax,
-                                      const double *step, unsigned long long seed, unsigned long long counter, double *out, long chain0)
+// The two accept entries of the Rayleigh phase-velocity misfit.  need_chain0: surfdisp_mcmc_accept_tree_device rejects a negative
+// chain0, surfdisp_mcmc_accept_device never did.
+static int mcmc_accept(const char *name, bool need_chain0, void *stream, int C, int N, int P, const float *c, const int *status,
+                       const double *c_obs, const double *uncer, const unsigned char *mask, int obs_per_chain,
+                       const double *p1, double *p0, double *chi0, double *row, long row_stride, long step_stride,
+                       unsigned long long seed, unsigned long long counter, int first, long chain0, int depth, int nsteps)
 {
-    if (C < 1 || N < 1 || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH || !p || !vmin || !vmax || !step || !out || chain0 < 0) {
-        set_err("surfdisp_mcmc_propose_tree_device: bad argument (1 <= depth <= 4)"); return SURFDISP_ERR_INVALID;
+    if (C < 1 || N < 1 || P < 1 || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH || nsteps < 1 || nsteps > depth ||
+        !c || !c_obs || !uncer || !mask || !p1 || !p0 || !chi0 || (need_chain0 && chain0 < 0)) {
+        set_err("%s: bad argument%s", name, need_chain0 ? " (1 <= nsteps <= depth <= 4)" : ""); return SURFDISP_ERR_INVALID;
     }
-    sd::McmcProposeArgs a{C, N, p, vmin, vmax, step, seed, counter, 0, out, chain0, depth, nullptr, 0, 0};
-    SD_HIP(sd::launch_mcmc_propose(static_cast<hipStream_t>(stream), a));
+    sd::McmcAcceptArgs a{C, N, P, c, status, c_obs, uncer, mask, obs_per_chain ? 1 : 0, p1, p0, chi0, row, row_stride, seed, counter,
+                         first ? 1 : 0, chain0, depth, nsteps, step_stride};
+    SD_HIP(sd::launch_mcmc_accept(static_cast<hipStream_t>(stream), a));
     return SURFDISP_SUCCESS;
 }
 
@@ -718,12 +738,8 @@ int surfdisp_mcmc_accept_device(void *stream, int C, int N, int P, const float *
                                 const double *p1, double *p0, double *chi0, double *row, long row_stride,
                                 unsigned long long seed, unsigned long long counter, int first, long chain0)
 {
-    if (C < 1 || N < 1 || P < 1 || !c || !c_obs || !uncer || !mask || !p1 || !p0 || !chi0) {
-        set_err("surfdisp_mcmc_accept_device: bad argument"); return SURFDISP_ERR_INVALID;
-    }
-    sd::McmcAcceptArgs a{C, N, P, c, status, c_obs, uncer, mask, obs_per_chain ? 1 : 0, p1, p0, chi0, row, row_stride, seed, counter, first ? 1 : 0, chain0, 1, 1, 0};
-    SD_HIP(sd::launch_mcmc_accept(static_cast<hipStream_t>(stream), a));
-    return SURFDISP_SUCCESS;
+    return mcmc_accept("surfdisp_mcmc_accept_device", false, stream, C, N, P, c, status, c_obs, uncer, mask, obs_per_chain, p1, p0, chi0,
+                       row, row_stride, 0, seed, counter, first, chain0, 1, 1);
 }
 
 int surfdisp_mcmc_accept_tree_device(void *stream, int C, int N, int P, int depth, int nsteps, const float *c, const int *status,
@@ -731,14 +747,8 @@ int surfdisp_mcmc_accept_tree_device(void *stream, int C, int N, int P, int dept
                                      const double *q, double *p0, double *chi0, double *row, long row_stride, long step_stride,
                                      unsigned long long seed, unsigned long long counter, long chain0)
 {
-    if (C < 1 || N < 1 || P < 1 || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH || nsteps < 1 || nsteps > depth ||
-        !c || !c_obs || !uncer || !mask || !q || !p0 || !chi0 || chain0 < 0) {
-        set_err("surfdisp_mcmc_accept_tree_device: bad argument (1 <= nsteps <= depth <= 4)"); return SURFDISP_ERR_INVALID;
-    }
-    sd::McmcAcceptArgs a{C, N, P, c, status, c_obs, uncer, mask, obs_per_chain ? 1 : 0, q, p0, chi0, row, row_stride, seed, counter, 0,
-                         chain0, depth, nsteps, step_stride};
-    SD_HIP(sd::launch_mcmc_accept(static_cast<hipStream_t>(stream), a));
-    return SURFDISP_SUCCESS;
+    return mcmc_accept("surfdisp_mcmc_accept_tree_device", true, stream, C, N, P, c, status, c_obs, uncer, mask, obs_per_chain, q, p0, chi0,
+                       row, row_stride, step_stride, seed, counter, 0, chain0, depth, nsteps);
 }
 
 // Joint data (Rayleigh / Love, phase / group velocity): the accept entries above with the misfit summed over a column table.

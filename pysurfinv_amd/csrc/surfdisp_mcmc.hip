@@ -119,18 +119,18 @@ __device__ __forceinline__ void misfit_of(const McmcAcceptArgs &A, const float *
     if (failed) { mis = 88888.0; chi = 88888.0; L = 0.0; }             // point.py:20-21
 }
 
-// One thread per chain: misfit of the proposal against the chain's observations, accept rule, state update, mcTrack row.
+// One chain's Metropolis test(s): misfit of the proposal against the chain's observations, accept rule, state update, mcTrack row.
 // depth d > 1: the chain walks the tree of surfdisp_mcmc_propose_kernel for nsteps <= d steps - at node k the usual test of
 // proposal k against the current state, then child 2k+1 (accepted) or 2k+2 - one mcTrack row per step, step_stride doubles
 // apart.  Every proposal was drawn from the state the chain is in when it is tested, so the chain is the plain sampler's.
-__global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArgs A)
+// misfit(q, ob, mis, chi, L): the misfit of stack q of the batched solve against the observations at offset ob.
+template <class Misfit>
+__device__ __forceinline__ void accept_walk(const McmcAcceptArgs &A, int c, Misfit misfit)
 {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= A.C) return;
-    const int P = A.P, N = A.N;
+    const int N = A.N;
     const int M = A.depth > 1 ? (1 << A.depth) - 1 : 1;
     const int nsteps = A.depth > 1 ? A.nsteps : 1;
-    const size_t ob = A.obs_per_chain ? (size_t)c * P : 0;
+    const size_t ob = A.obs_per_chain ? (size_t)c * A.P : 0;
     const unsigned long long gc = (unsigned long long)(A.chain0 + c);
     double *p0 = A.p0 + (size_t)c * N;
     double chi0 = A.chi0[c];
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArg
     for (int s = 0; s < nsteps; ++s) {
         const size_t q = (size_t)c * M + node;                         // this step's proposal: stack q of the batched solve
         double mis, chi, L;
-        misfit_of(A, A.c + q * P, A.status && A.status[q] != 0, ob, mis, chi, L);
+        misfit(q, ob, mis, chi, L);
         bool acc;
         if (A.first) acc = true;                                       // a chain's first row: the start model itself
         else if (chi < chi0) acc = true;                               // point.py:34-37
@@ -161,6 +161,16 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArg
         node = acc ? 2 * node + 1 : 2 * node + 2;
     }
     A.chi0[c] = chi0;
+}
+
+// One thread per chain: accept_walk with the Rayleigh phase-velocity misfit.
+__global__ __launch_bounds__(256) void surfdisp_mcmc_accept_kernel(McmcAcceptArgs A)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= A.C) return;
+    accept_walk(A, c, [&](size_t q, size_t ob, double &mis, double &chi, double &L) {
+        misfit_of(A, A.c + q * A.P, A.status && A.status[q] != 0, ob, mis, chi, L);
+    });
 }
 
 // Joint misfit of stack q (pysurfinv_amd/obsdata.py): chi2 = sum over the columns, in ascending order, of w ((obs - pred) / uncer)^2
@@ -221,7 +231,7 @@ __device__ __forceinline__ void joint_misfit_of(const McmcJointArgs &J, const in
     if (failed) { mis = 88888.0; chi = 88888.0; L = 0.0; }
 }
 
-// surfdisp_mcmc_accept_kernel with the joint misfit: the same accept rule, random stream, tree walk and mcTrack rows.
+// surfdisp_mcmc_accept_kernel with the joint misfit (accept_walk: the same accept rule, random stream, tree walk and mcTrack rows).
 template <bool E>
 __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJointArgs J)
 {
@@ -239,40 +249,9 @@ __global__ __launch_bounds__(256) void surfdisp_mcmc_accept_joint_kernel(McmcJoi
     __syncthreads();
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= A.C) return;
-    const int N = A.N;
-    const int M = A.depth > 1 ? (1 << A.depth) - 1 : 1;
-    const int nsteps = A.depth > 1 ? A.nsteps : 1;
-    const size_t ob = A.obs_per_chain ? (size_t)c * A.P : 0;
-    const unsigned long long gc = (unsigned long long)(A.chain0 + c);
-    double *p0 = A.p0 + (size_t)c * N;
-    double chi0 = A.chi0[c];
-    int node = 0;
-    for (int s = 0; s < nsteps; ++s) {
-        const size_t q = (size_t)c * M + node;
-        double mis, chi, L;
+    accept_walk(A, c, [&](size_t q, size_t ob, double &mis, double &chi, double &L) {
         joint_misfit_of<E>(J, col, wt, q, ob, mis, chi, L);
-        bool acc;
-        if (A.first) acc = true;
-        else if (chi < chi0) acc = true;                               // point.py:34-37
-        else {
-            const U4 r = philox4x32_10(U4{(uint32_t)A.counter, (uint32_t)(A.counter >> 32) ^ 0x00aaaa00u ^ ((uint32_t)s << 28),
-                                          (uint32_t)gc, (uint32_t)(gc >> 32)}, (uint32_t)A.seed, (uint32_t)(A.seed >> 32));
-            const double u = u53(r.x, r.y);
-            acc = u > 1.0 - exp(-(chi - chi0) / 2.0);
-        }
-        const double *p1 = A.p1 + q * N;
-        if (A.row) {
-            double *row = A.row + (size_t)c * A.row_stride + (size_t)s * A.step_stride;
-            row[0] = mis; row[1] = L; row[2] = acc ? 1.0 : 0.0;
-            for (int n = 0; n < N; ++n) row[3 + n] = p1[n];
-        }
-        if (acc) {
-            for (int n = 0; n < N; ++n) p0[n] = p1[n];
-            chi0 = chi;
-        }
-        node = acc ? 2 * node + 1 : 2 * node + 2;
-    }
-    A.chi0[c] = chi0;
+    });
 }
 
 hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a, bool ellip)

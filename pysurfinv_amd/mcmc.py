@@ -27,6 +27,7 @@ exact stream for one chain (trace parity, ``tests/test_mcmc.py``).
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import os
 
 import numpy as np
@@ -35,6 +36,29 @@ from . import _lib
 from .brownian import ParamSpec, TorchProposer
 
 FAIL = 88888.0                                                  # point.py:21
+
+# the accept entries of libsurfdisp_hip: (data kind, tree walk) -> symbol (include/surfdisp.h)
+_ACCEPT_ENTRIES = {
+    ("c", False): "surfdisp_mcmc_accept_device", ("c", True): "surfdisp_mcmc_accept_tree_device",
+    ("joint", False): "surfdisp_mcmc_accept_joint_device", ("joint", True): "surfdisp_mcmc_accept_tree_joint_device",
+    ("joint5", False): "surfdisp_mcmc_accept_joint5_device", ("joint5", True): "surfdisp_mcmc_accept_tree_joint5_device",
+}
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _accept_rule(torch, chi0, chi1, u):
+    """bool[C]: ``chi1 < chi0`` or ``u > 1 - exp(-(chi1 - chi0) / 2)`` (point.py:34-37).  Pure tensor code: no host
+    synchronisation, so it can be captured in a HIP graph."""
+    better = chi1 < chi0
+    return better | (~better & (u > 1.0 - torch.exp(-(chi1 - chi0) / 2.0)))
+
+
+def _put_row(track, i, mis, L, acc, p):
+    """mcTrack row ``i`` of every chain: [misfit, L, accepted, *params] of the proposed model (models.py:254-256)."""
+    track[:, i, 0] = mis; track[:, i, 1] = L; track[:, i, 2] = acc; track[:, i, 3:] = p
 
 
 class PriorRules:
@@ -85,23 +109,15 @@ class ChainGroups:
         self.streams = [torch.cuda.Stream(device=mc.device) for _ in range(self.G)]
         self.children = []
         for g in range(self.G):
-            lo, hi = self.bounds[g], self.bounds[g + 1]
             ch = copy.copy(mc)                                  # shares spec, proposer (bounds, steps, seed), periods, to_model
-            ch._plan, ch._fz, ch.event_ring, ch._ev_i, ch.n_forward, ch._groups, ch._plans = None, None, None, 0, 0, {}, {}
-            ch._jplans, ch._side = {}, None                     # (joint data: the group's own Rayleigh and Love plans)
-            if mc.c_obs.ndim == 2:
-                if mc.c_obs.shape[0] != self.C:
-                    raise ValueError(f"{self.C} chains against {mc.c_obs.shape[0]} rows of observations")
-                ch.c_obs, ch.uncer, ch.mask = mc.c_obs[lo:hi], mc.uncer[lo:hi], mc.mask[lo:hi]
-            if mc.local_rows is not None:
-                ch.local_rows = mc.local_rows[lo:hi]
-            ch._chain0 = mc._chain0 + lo
+            ch._fresh_state()                                   # (its own plans, fused buffers, counters, Love stream)
             ch._pipelined = True                                # the library sizes its teams for both groups' stacks
             self.children.append(ch)
+        self._refresh()
 
     def _refresh(self):
-        """The children's slices of the parent's observations / local rows and its run-time switches, taken afresh at every
-        fork: a parent whose observations or ``local_rows`` were replaced, or whose ``independent`` / ``fast_scan`` changed after
+        """The children's slices of the parent's observations / local rows and its run-time switches, taken at construction and
+        afresh at every fork: a parent whose observations or ``local_rows`` were replaced, or whose ``independent`` / ``fast_scan`` changed after
         a first grouped run, must not advance on the first run's copies."""
         mc = self.mc
         for g, ch in enumerate(self.children):
@@ -162,6 +178,7 @@ class MetropolisBatch:
     """
 
     AUTO_INDEP_CHAINS = 3072        # 64-lane teams of fewer chains leave the chip's 196 608 lanes partly empty
+    PLAN_CACHE = 8                  # plans kept: the speculative lock step alternates between two stack counts, two wave types each
 
     def __init__(self, spec: ParamSpec, to_model, periods=None, c_obs=None, uncer=None, device="cuda:0",
                  isgood=None, proposer=None, seed=None, forward=None, independent=False, fast_scan=False,
@@ -174,7 +191,7 @@ class MetropolisBatch:
         self.isgood = isgood
         self.proposer = proposer if proposer is not None else TorchProposer(spec, self.device, seed)
         self.joint = None
-        self._fz = None
+        self._fresh_state()
         if data is not None:
             if periods is not None or c_obs is not None or uncer is not None:
                 raise ValueError("MetropolisBatch: pass either data= or (periods, c_obs, uncer), not both")
@@ -184,7 +201,6 @@ class MetropolisBatch:
                 raise ValueError("MetropolisBatch: needs (periods, c_obs, uncer) or data=")
             self.periods = torch.as_tensor(np.asarray(periods, np.float32), device=self.device)
             self._set_obs(c_obs, uncer)
-        self._plan = None
         # test hook: callable(model, nlay) -> (c, status); with data=: -> dict(cR, uR, cL, uL, statusR, statusL)
         self._forward = forward
         # independent=True: period-parallel root search (SURFDISP_INDEPENDENT) - lower latency for few
@@ -202,19 +218,24 @@ class MetropolisBatch:
         # fast_scan=True: opt into the heuristic coarse-to-fine scan (SURFDISP_FASTSCAN); the default walks every
         # grid point of the reference's scan, so root selection and failures are the reference's on every input
         self.fast_scan = bool(fast_scan)
-        self.n_forward = 0
         # local_rows [C]: row of the model's per-point local-information table (Model1DBatch.set_local_info) each chain
         # belongs to; to_model is then called as to_model(params, rows)
         self.local_rows = None if local_rows is None else torch.as_tensor(np.asarray(local_rows), dtype=torch.int64,
                                                                           device=self.device)
-        # measurement hook (bench.py): a forward.EventRing whose next slot brackets the solver's kernels of each call
-        self.event_ring = None
-        self._ev_i = 0
         self._counter = 0                                       # calls of the fused kernels so far: the Philox counter of the next one
         self._pipelined = False                                 # a chain group: another group's solve is in flight beside this one
         self._chain0 = 0                                        # index of this object's chain 0 in the whole sampler (chain groups)
+
+    def _fresh_state(self):
+        """What a sampler owns and a chain group's child (a shallow copy of its parent) must not share with it."""
+        self._plans = {}                                        # (C, L, P, wave) -> forward.BatchPlan
+        self._fz = None                                         # the fused path's buffers (_fused_buffers)
         self._groups = {}
         self._side = None                                       # joint data, one chain group: the Love solve's stream
+        self.n_forward = 0
+        # measurement hook (bench.py): a forward.EventRing whose next slot brackets the solver's kernels of each call
+        self.event_ring = None
+        self._ev_i = 0
 
     def _set_obs(self, c_obs, uncer):
         torch = self.torch
@@ -243,20 +264,22 @@ class MetropolisBatch:
     def forward_c(self, params, rows=None):
         """Rayleigh phase velocities c[C, P] and status[C] for the stacks of ``params`` (``rows``: the chain each row
         of ``params`` belongs to, when it is not simply row i = chain i)."""
-        torch = self.torch
-        if self.local_rows is not None:
-            if rows is None and params.shape[0] != self.local_rows.shape[0]:
-                raise ValueError(f"{params.shape[0]} models against {self.local_rows.shape[0]} chains with local information: pass rows=")
-            model, nlay = self.to_model(params, self.local_rows if rows is None else self.local_rows[rows])
-        else:
-            model, nlay = self.to_model(params)
+        model, nlay = self._stacks(params, rows)
         if self._forward is not None:
             self.n_forward += model.shape[0]
             return self._forward(model, nlay)
         if self.joint is not None:
             return self._solve_joint(model, nlay)
         c, st = self._solve_model(model, nlay)
-        return c.to(torch.float64), st
+        return c.to(self.torch.float64), st
+
+    def _stacks(self, params, rows=None):
+        """(model[C, 5, L], nlay) of ``to_model`` for the rows of ``params``, each with the local information of its chain."""
+        if self.local_rows is None:
+            return self.to_model(params)
+        if rows is None and params.shape[0] != self.local_rows.shape[0]:
+            raise ValueError(f"{params.shape[0]} models against {self.local_rows.shape[0]} chains with local information: pass rows=")
+        return self.to_model(params, self.local_rows if rows is None else self.local_rows[rows])
 
     def forward_joint(self, params, rows=None):
         """Joint data: dict(cR, uR, cL, uL, statusR, statusL, eR) of the stacks of ``params`` (None for a wave type without
@@ -306,7 +329,7 @@ class MetropolisBatch:
 
     def _fused_buffers(self, C):
         torch = self.torch
-        st = getattr(self, "_fz", None)
+        st = self._fz
         if st is None or st["C"] != C or st.get("data") is not self.joint:
             N = self.spec.n
             st = dict(C=C, data=self.joint, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
@@ -316,33 +339,45 @@ class MetropolisBatch:
         return st
 
     def _solve_raw(self, params, rows=None):
-        """fp32 c[C, P] and status[C] of the solver's own output tensors (no copies) for the stacks of ``params``."""
-        if self.local_rows is not None:
-            model, nlay = self.to_model(params, self.local_rows if rows is None else self.local_rows[rows])
-        else:
-            model, nlay = self.to_model(params)
+        """The solver's own fp32 output tensors (no copies) for the stacks of ``params``: (c[C, P], status[C]), or with joint
+        data the dict of ``_solve_joint``."""
+        model, nlay = self._stacks(params, rows)
         return self._solve_joint(model, nlay) if self.joint is not None else self._solve_model(model, nlay)
+
+    def _plans_for(self, C, L, waves):
+        """The ``BatchPlan`` of C stacks x L layers for each (wave, periods) of ``waves``.  The cache is emptied when it would
+        grow beyond ``PLAN_CACHE`` plans - after the new ones are counted, so the plans of one lock step always stay together."""
+        keys = [(C, L, P, w) for w, P in waves]
+        try:
+            return [self._plans[k] for k in keys]
+        except KeyError:
+            from .forward import BatchPlan
+            new = [k for k in keys if k not in self._plans]
+            if len(self._plans) + len(new) > self.PLAN_CACHE:
+                self._plans.clear()
+                new = keys
+            for k in new:
+                self._plans[k] = BatchPlan(C, L, k[2], device=self.device)
+            return [self._plans[k] for k in keys]
+
+    def _next_events(self):
+        """The next slot of ``event_ring`` (None without a ring)."""
+        if self.event_ring is None:
+            return None
+        self._ev_i += 1
+        return self.event_ring.slot(self._ev_i - 1)
+
+    def _indep(self, C):
+        """Whether a solve of C stacks takes the period-parallel root search (``independent``)."""
+        return (C < self.AUTO_INDEP_CHAINS) if self.independent == "auto" else bool(self.independent)
 
     def _solve_model(self, model, nlay):
         self.n_forward += model.shape[0]
-        from .forward import BatchPlan
         C, _, L = model.shape
-        if self._plan is None or (self._plan.B, self._plan.L) != (C, L):
-            # (the speculative lock step alternates between C and C * (2^d - 1) stacks: keep a plan per size)
-            plans = self.__dict__.setdefault("_plans", {})
-            if (C, L) not in plans:
-                if len(plans) >= 4:
-                    plans.clear()
-                plans[(C, L)] = BatchPlan(C, L, self.periods.numel(), device=self.device)
-            self._plan = plans[(C, L)]
-        ev = None
-        if self.event_ring is not None:
-            ev = self.event_ring.slot(self._ev_i)
-            self._ev_i += 1
-        indep = (C < self.AUTO_INDEP_CHAINS) if self.independent == "auto" else bool(self.independent)
-        c, _, st = self._plan.run(model.contiguous(), self.periods, kind=_lib.KIND_RAYLEIGH | _lib.PHASE_ONLY,
-                                  nlay=nlay, independent=indep, fast_scan=self.fast_scan, events=ev,
-                                  pipelined=self._pipelined)
+        plan, = self._plans_for(C, L, [("R", self.periods.numel())])
+        c, _, st = plan.run(model.contiguous(), self.periods, kind=_lib.KIND_RAYLEIGH | _lib.PHASE_ONLY,
+                            nlay=nlay, independent=self._indep(C), fast_scan=self.fast_scan, events=self._next_events(),
+                            pipelined=self._pipelined)
         return c, st
 
     def _solve_joint(self, model, nlay):
@@ -353,25 +388,13 @@ class MetropolisBatch:
         SURFDISP_PIPELINED for both; as one chain group the Love solve runs on a second stream forked from, and joined back
         into, the current one (as ``forward.JointPlan``; no host synchronisation), inside a chain group after the Rayleigh
         solve on the group's stream.  ``n_forward`` counts stacks (models), not solves."""
-        from .forward import BatchPlan
         torch = self.torch
         jd = self.joint
         self.n_forward += model.shape[0]
         C, _, L = model.shape
         model = model.contiguous()
-        plans = self.__dict__.setdefault("_jplans", {})
-        ev = None
-        if self.event_ring is not None:
-            ev = self.event_ring.slot(self._ev_i)
-            self._ev_i += 1
-        indep = (C < self.AUTO_INDEP_CHAINS) if self.independent == "auto" else bool(self.independent)
-        keys = [(C, L, w, jd.solve_periods[w].size) for w in jd.waves]
-        if any(k not in plans for k in keys):
-            if len(plans) + len(keys) > 8:                     # (speculative lock steps alternate between two stack counts)
-                plans.clear()
-            for k in keys:
-                if k not in plans:
-                    plans[k] = BatchPlan(C, L, k[3], device=self.device)
+        ev, indep = self._next_events(), self._indep(C)
+        plans = self._plans_for(C, L, [(w, jd.solve_periods[w].size) for w in jd.waves])
         two = len(jd.waves) == 2
         fork = two and not self._pipelined
         cur = torch.cuda.current_stream(self.device)
@@ -380,11 +403,11 @@ class MetropolisBatch:
                 self._side = torch.cuda.Stream(device=self.device)
             self._side.wait_stream(cur)
         out = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
-        for i, (w, key) in enumerate(zip(jd.waves, keys)):
+        for i, (w, plan) in enumerate(zip(jd.waves, plans)):
             with (torch.cuda.stream(self._side) if (fork and i == 1) else contextlib.nullcontext()):
-                res = plans[key].run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, independent=indep,
-                                     fast_scan=self.fast_scan, events=ev if i == 0 else None,
-                                     pipelined=self._pipelined or two, want_ratio=jd.with_ratio and w == "R")
+                res = plan.run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, independent=indep,
+                               fast_scan=self.fast_scan, events=ev if i == 0 else None,
+                               pipelined=self._pipelined or two, want_ratio=jd.with_ratio and w == "R")
             out["c" + w], out["u" + w], out["status" + w] = res[:3]
             if len(res) > 3:
                 out["eR"] = res[3]
@@ -392,16 +415,11 @@ class MetropolisBatch:
             cur.wait_stream(self._side)
         return out
 
-    def _accept_joint(self, stream, pred, st, p1, p, rowp, row_stride, counter, first=False, depth=1, nsteps=1, step_stride=0):
-        """The joint accept kernel (``surfdisp_mcmc_accept_joint_device`` / ``_tree_joint_device``; with an ellipticity data
-        set their five-array forms ``..._joint5_device``) on the solves of ``pred``."""
-        import ctypes
+    def _joint_table(self, pred, st, C):
+        """The arguments of the joint accept entries that describe the solves of ``pred`` and the observation columns."""
         jd = self.joint
-        C, N = p.shape
         if st["c_obs"].shape[-1] != jd.Ptot or (st["c_obs"].ndim == 2 and st["c_obs"].shape[0] != C):
             raise ValueError(f"joint accept: observations of shape {tuple(st['c_obs'].shape)} against {C} chains x {jd.Ptot} columns")
-        L = _lib.lib()
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
         arrs = [pred["cR"], pred["uR"] if jd.with_group.get("R") else None,
                 pred["cL"], pred["uL"] if jd.with_group.get("L") else None]
         if jd.with_ratio:
@@ -416,17 +434,37 @@ class MetropolisBatch:
         nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
         stat = (ctypes.c_void_p * 2)(*[pred["status" + w].data_ptr() if pred["status" + w] is not None else None
                                        for w in ("R", "L")])
-        table = (predp, strides, nper, stat, jd.Ptot, ptr(jd.cols), ptr(jd.weights), ptr(st["c_obs"]), ptr(st["uncer"]),
-                 ptr(st["mask8"]), 1 if st["c_obs"].ndim == 2 else 0)
-        pr = self.proposer
-        plain, tree = ((L.surfdisp_mcmc_accept_joint5_device, L.surfdisp_mcmc_accept_tree_joint5_device) if jd.with_ratio else
-                       (L.surfdisp_mcmc_accept_joint_device, L.surfdisp_mcmc_accept_tree_joint_device))
-        if depth <= 1:
-            _lib.check(plain(stream, C, N, *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp,
-                                                           int(row_stride), pr.seed_int, counter, 1 if first else 0, self._chain0))
+        return (predp, strides, nper, stat, jd.Ptot, _ptr(jd.cols), _ptr(jd.weights))
+
+    def _accept(self, stream, pred, st, p1, p, rowp, row_stride, counter, tree, first=False, depth=1, nsteps=1, step_stride=0):
+        """The accept kernel on the solve ``pred`` (``_solve_raw``) of the proposals ``p1``: misfit, accept rule, state ``p`` and
+        chi-square update, mcTrack rows.  ``tree``: the tree entries (``nsteps`` steps through the tree ``p1`` of ``depth``, rows
+        ``step_stride`` doubles apart; with joint data a tree of depth 1 goes through the plain entry); joint data: the joint
+        entries, with an ellipticity set their five-array forms."""
+        C, N = p.shape
+        if self.joint is not None:
+            tree = tree and depth > 1
+        if self.joint is None:
+            c, status = pred
+            kind, head, table = "c", (int(self.periods.numel()),), (_ptr(c), _ptr(status))
         else:
-            _lib.check(tree(stream, C, N, int(depth), int(nsteps), *table, ptr(p1), ptr(p), ptr(st["chi"]), rowp, int(row_stride),
-                            int(step_stride), pr.seed_int, counter, self._chain0))
+            kind, head, table = "joint5" if self.joint.with_ratio else "joint", (), self._joint_table(pred, st, C)
+        entry = getattr(_lib.lib(), _ACCEPT_ENTRIES[kind, tree])
+        _lib.check(entry(stream, C, N, *head, *((int(depth), int(nsteps)) if tree else ()), *table,
+                         _ptr(st["c_obs"]), _ptr(st["uncer"]), _ptr(st["mask8"]), 1 if st["c_obs"].ndim == 2 else 0,
+                         _ptr(p1), _ptr(p), _ptr(st["chi"]), rowp, int(row_stride), *((int(step_stride),) if tree else ()),
+                         self.proposer.seed_int, counter, *(() if tree else (1 if first else 0,)), self._chain0))
+
+    def _fused_call(self, C, row, row_offset, counter):
+        """What one launch sequence of the fused path starts from: the buffers, the current stream, this step's Philox
+        counter (default: one more than the last call's) and the address of chain 0's mcTrack row."""
+        st = self._fused_buffers(C)
+        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+        if counter is None:
+            self._counter += 1
+            counter = self._counter
+        rowp = ctypes.c_void_p(row.data_ptr() + 8 * int(row_offset) if row is not None else 0)
+        return st, stream, counter, rowp
 
     def fused_step(self, p, row=None, row_stride=0, first=False, counter=None, row_offset=0):
         """One Metropolis step of every chain, in place on the state ``p`` [C, N] (float64, contiguous): proposal
@@ -434,36 +472,19 @@ class MetropolisBatch:
         misfit / accept / update.  ``row``: a float64 tensor whose element ``row_offset`` is where chain 0's mcTrack row
         goes, chain c's ``row_stride`` doubles further.  ``counter``: the Philox counter of this step (default: one more
         than the last call's).  Everything stream-ordered on the current stream."""
-        import ctypes
-        torch = self.torch
         C, N = p.shape
-        st = self._fused_buffers(C)
-        L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        st, stream, counter, rowp = self._fused_call(C, row, row_offset, counter)
         pr = self.proposer
-        if counter is None:
-            self._counter += 1
-            counter = self._counter
-        rowp = ctypes.c_void_p(row.data_ptr() + 8 * int(row_offset)) if row is not None else ctypes.c_void_p(0)
-        with torch.cuda.device(self.device):
+        with self.torch.cuda.device(self.device):
             if first:
                 p1 = p
             else:
                 p1 = st["p1"]
-                _lib.check(L.surfdisp_mcmc_propose_device(stream, C, N, ptr(p), ptr(pr.vmin), ptr(pr.vmax), ptr(pr.step),
-                                                          pr.seed_int, counter, 0, ptr(p1), self._chain0))
+                _lib.check(_lib.lib().surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
+                                                                   pr.seed_int, counter, 0, _ptr(p1), self._chain0))
                 if self.isgood is not None:
                     self._redraw_with_rules(p, p1, counter, stream)
-            if self.joint is not None:
-                self._accept_joint(stream, self._solve_raw(p1), st, p1, p, rowp, row_stride, counter, first=first)
-                return p
-            c, status = self._solve_raw(p1)
-            _lib.check(L.surfdisp_mcmc_accept_device(stream, C, N, int(self.periods.numel()), ptr(c), ptr(status),
-                                                     ptr(st["c_obs"]), ptr(st["uncer"]), ptr(st["mask8"]),
-                                                     1 if st["c_obs"].ndim == 2 else 0, ptr(p1), ptr(p), ptr(st["chi"]),
-                                                     rowp, int(row_stride), pr.seed_int, counter, 1 if first else 0,
-                                                     self._chain0))
+            self._accept(stream, self._solve_raw(p1), st, p1, p, rowp, row_stride, counter, False, first=first)
         return p
 
     def _redraw_with_rules(self, p, p1, counter, stream):
@@ -471,7 +492,6 @@ class MetropolisBatch:
         without a host synchronisation: the prior kernel marks the chains whose proposal ``p1`` breaks a rule, the masked
         proposal kernel draws those again - ``rounds`` Gaussian rounds, ``reset_rounds`` uniform ones, then the chain's own
         state.  One tag per chain, rising from round to round (cleared once per step)."""
-        import ctypes
         torch = self.torch
         rules = self.isgood
         C, N = p1.shape
@@ -483,7 +503,6 @@ class MetropolisBatch:
             st["tags"] = torch.zeros(C, dtype=torch.uint8, device=self.device)
         tags = st["tags"]
         L = _lib.lib()
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
         pr = self.proposer
         vmax = -1.0 if rules.vs_max is None else rules.vs_max
         pfull = lambda q: q if mb.n_aux == 0 else mb._full(q).contiguous()
@@ -492,12 +511,12 @@ class MetropolisBatch:
         for r in range(total):
             q = pfull(p1)
             # round r: chains redrawn in round r - 1 carry tag r (all chains in round 0); the ones that break a rule get r + 1 ...
-            _lib.check(L.surfdisp_prior_device(stream, C, q.shape[1], int(Lout), ptr(q), ptr(idesc), ptr(fdesc), ptr(flags),
-                                               ctypes.c_double(vmax), r if r > 0 else -1, r + 1, ptr(tags)))
+            _lib.check(L.surfdisp_prior_device(stream, C, q.shape[1], int(Lout), _ptr(q), _ptr(idesc), _ptr(fdesc), _ptr(flags),
+                                               ctypes.c_double(vmax), r if r > 0 else -1, r + 1, _ptr(tags)))
             # ... and draw again: Gaussian rounds, then uniform prior draws, last the chain's own state
             mode = 0 if r < rules.rounds else (1 if r < rules.rounds + rules.reset_rounds else 2)
-            _lib.check(L.surfdisp_mcmc_propose_masked_device(stream, C, N, ptr(p), ptr(pr.vmin), ptr(pr.vmax), ptr(pr.step),
-                                                             pr.seed_int, counter, r, mode, ptr(tags), r + 1, ptr(p1), self._chain0))
+            _lib.check(L.surfdisp_mcmc_propose_masked_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
+                                                             pr.seed_int, counter, r, mode, _ptr(tags), r + 1, _ptr(p1), self._chain0))
 
     SPEC_MAX_STACKS = 2048          # stacks per speculative lock step: a 64-lane team = one wavefront each, the chip holds 4 096
 
@@ -508,7 +527,7 @@ class MetropolisBatch:
         (100 chains x 96 layers: 0.96 ms per step plain, 0.345 with d = 3, 0.31 with d = 4 at 4.1 forward solves per step;
         scripts/time_speculative.py): 4 up to 136 chains, 3 up to 292, 2 up to 682, 1 from 683 chains on, and 1 where the (stack, period) decomposition fills the chip
         instead (``independent``: 0.24 ms per step plain, 0.29 with d = 3)."""
-        if self.independent is True or (self.independent == "auto" and C < self.AUTO_INDEP_CHAINS):
+        if self._indep(C):
             return 1
         if self.isgood is not None:
             return 1                                               # (prior rules: the redraw rounds belong to the plain lock step)
@@ -524,35 +543,20 @@ class MetropolisBatch:
         through one forward solve; ``surfdisp_mcmc_accept_tree_device`` walks the tree with the usual test).  Every
         proposal is drawn from and tested against the state the chain is in at that step: the chain is distributed exactly
         as with ``fused_step``.  mcTrack rows of the steps ``step_stride`` doubles apart, the first at ``row_offset``."""
-        import ctypes
         torch = self.torch
         C, N = p.shape
         M = (1 << int(depth)) - 1
-        st = self._fused_buffers(C)
+        st, stream, counter, rowp = self._fused_call(C, row, row_offset, counter)
         if st.get("M") != M:
             st["M"] = M
             st["q"] = torch.empty((C, M, N), dtype=torch.float64, device=self.device)
             st["qrows"] = torch.arange(C, device=self.device).repeat_interleave(M) if self.local_rows is not None else None
-        L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
         pr = self.proposer
-        if counter is None:
-            self._counter += 1
-            counter = self._counter
-        rowp = ctypes.c_void_p(row.data_ptr() + 8 * int(row_offset)) if row is not None else ctypes.c_void_p(0)
         with torch.cuda.device(self.device):
-            _lib.check(L.surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), ptr(p), ptr(pr.vmin), ptr(pr.vmax), ptr(pr.step),
-                                                           pr.seed_int, counter, ptr(st["q"]), self._chain0))
-            if self.joint is not None:
-                self._accept_joint(stream, self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"]), st, st["q"], p, rowp,
-                                   row_stride, counter, depth=depth, nsteps=nsteps, step_stride=step_stride)
-                return p
-            c, status = self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"])
-            _lib.check(L.surfdisp_mcmc_accept_tree_device(stream, C, N, int(self.periods.numel()), int(depth), int(nsteps),
-                                                          ptr(c), ptr(status), ptr(st["c_obs"]), ptr(st["uncer"]), ptr(st["mask8"]),
-                                                          1 if st["c_obs"].ndim == 2 else 0, ptr(st["q"]), ptr(p), ptr(st["chi"]),
-                                                          rowp, int(row_stride), int(step_stride), pr.seed_int, counter, self._chain0))
+            _lib.check(_lib.lib().surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax),
+                                                                    _ptr(pr.step), pr.seed_int, counter, _ptr(st["q"]), self._chain0))
+            self._accept(stream, self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"]), st, st["q"], p, rowp, row_stride, counter,
+                         True, depth=depth, nsteps=nsteps, step_stride=step_stride)
         return p
 
     # ------------------------------------------------------------------ chain groups
@@ -688,38 +692,19 @@ class MetropolisBatch:
                 cg.join()
             self._counter = base + chainL
             return track
-        p0 = self.reset(C) if not (init_first and C == 1) else None
-        if init_first:
-            v0 = torch.as_tensor(self.spec.v0, dtype=torch.float64, device=self.device)[None, :]
-            if not bool(self._good(v0)[0]):
-                v0 = self.perturb(v0)                              # point.py:50-51
-            p0 = v0 if p0 is None else torch.cat([v0, p0[1:]], dim=0)
-        if _init_mask is not None:                                # several points: chain 0 of each
-            v0 = torch.as_tensor(self.spec.v0, dtype=torch.float64, device=self.device)[None, :]
-            if not bool(self._good(v0)[0]):
-                v0 = self.perturb(v0)
-            p0 = torch.where(_init_mask[:, None], v0.expand_as(p0), p0)
-        mis0, chi0, L0 = self.misfit(p0)
-        track[:, 0, 0] = mis0; track[:, 0, 1] = L0; track[:, 0, 2] = 1.0; track[:, 0, 3:] = p0
+        p0 = self._start(C, init_first, _init_mask)
+        chi0 = self._first_row(track, p0)
         for i in range(1, chainL):
             p1 = self.perturb(p0)
             if priori:                                             # point.py:66-69
-                track[:, i, 0] = 0.0; track[:, i, 1] = 1.0; track[:, i, 2] = 1.0; track[:, i, 3:] = p1
+                _put_row(track, i, 0.0, 1.0, 1.0, p1)
                 p0 = p1
                 continue
             mis1, chi1, L1 = self.misfit(p1)
-            better = chi1 < chi0
             # the reference draws random() only when chi1 >= chi0 (point.py:35-37)
-            u = torch.zeros_like(chi1)
-            need = ~better
-            if bool(need.any()):
-                if C == 1:
-                    u = self.proposer.uniform(1)
-                else:
-                    u = self.proposer.uniform(C)
-            acc = better | (need & (u > 1.0 - torch.exp(-(chi1 - chi0) / 2.0)))
-            track[:, i, 0] = mis1; track[:, i, 1] = L1; track[:, i, 2] = acc.to(torch.float64)
-            track[:, i, 3:] = p1
+            u = self.proposer.uniform(C) if bool((~(chi1 < chi0)).any()) else torch.zeros_like(chi1)
+            acc = _accept_rule(torch, chi0, chi1, u)
+            _put_row(track, i, mis1, L1, acc, p1)
             p0 = torch.where(acc[:, None], p1, p0)
             chi0 = torch.where(acc, chi1, chi0)
         return track
@@ -737,14 +722,19 @@ class MetropolisBatch:
                 p0 = v0 if p0 is None else torch.cat([v0, p0[1:]], dim=0)
         return p0
 
+    def _first_row(self, track, p):
+        """mcTrack row 0: the start models ``p`` themselves, accepted (point.py:58).  Returns their chi-squares."""
+        mis, chi, L = self.misfit(p)
+        _put_row(track, 0, mis, L, 1.0, p)
+        return chi
+
     def _run_speculative(self, n_chains, chainL, init_first, _init_mask, d):
         torch = self.torch
         C, N = int(n_chains), self.spec.n
         M = (1 << d) - 1                                           # proposals per chain per lock step
         track = torch.zeros((C, chainL, 3 + N), dtype=torch.float64, device=self.device)
         p = self._start(C, init_first, _init_mask)
-        mis, chi, L = self.misfit(p)
-        track[:, 0, 0] = mis; track[:, 0, 1] = L; track[:, 0, 2] = 1.0; track[:, 0, 3:] = p
+        chi = self._first_row(track, p)
         ar = torch.arange(C, device=self.device)
         i = 1
         while i < chainL:
@@ -766,11 +756,8 @@ class MetropolisBatch:
             node = torch.zeros(C, dtype=torch.int64, device=self.device)
             for _ in range(min(d, chainL - i)):
                 chi1, q = chiQ[ar, node], Q[ar, node]
-                better = chi1 < chi
-                u = self.proposer.uniform(C)
-                acc = better | (~better & (u > 1.0 - torch.exp(-(chi1 - chi) / 2.0)))
-                track[:, i, 0] = misQ[ar, node]; track[:, i, 1] = LQ[ar, node]
-                track[:, i, 2] = acc.to(torch.float64); track[:, i, 3:] = q
+                acc = _accept_rule(torch, chi, chi1, self.proposer.uniform(C))
+                _put_row(track, i, misQ[ar, node], LQ[ar, node], acc, q)
                 p = torch.where(acc[:, None], q, p)
                 chi = torch.where(acc, chi1, chi)
                 node = torch.where(acc, 2 * node + 1, 2 * node + 2)
@@ -840,8 +827,7 @@ class MetropolisBatch:
         pr = self.proposer
         track = torch.zeros((C, chainL, 3 + N), dtype=torch.float64, device=dev)
         p = self._start(C, init_first, None)
-        mis, chi, L = self.misfit(p)
-        track[:, 0, 0] = mis; track[:, 0, 1] = L; track[:, 0, 2] = 1.0; track[:, 0, 3:] = p
+        chi = self._first_row(track, p)
         step = torch.ones(1, dtype=torch.int64, device=dev)          # row the next step writes
         p = p.clone(); chi = chi.clone()
 
@@ -854,9 +840,7 @@ class MetropolisBatch:
             uni = pr.vmin + (pr.vmax - pr.vmin) * torch.rand((C, N), dtype=torch.float64, device=dev)
             new = torch.where(ok.any(dim=1), chosen, uni)
             mis1, chi1, L1 = self.misfit(new)
-            better = chi1 < chi
-            u = torch.rand(C, dtype=torch.float64, device=dev)
-            acc = better | (~better & (u > 1.0 - torch.exp(-(chi1 - chi) / 2.0)))
+            acc = _accept_rule(torch, chi, chi1, torch.rand(C, dtype=torch.float64, device=dev))
             row = torch.cat([mis1[:, None], L1[:, None], acc.to(torch.float64)[:, None], new], dim=1)
             track.index_copy_(1, step, row[:, None, :])
             p.copy_(torch.where(acc[:, None], new, p))

@@ -52,7 +52,7 @@ def observations(mb, n_points, dev, seed=100):
 
 def accept_ms(mc, C, depth, reps=50):
     """ms of one accept launch over all C chains on the predictions of C * (2^depth - 1) start models (the joint kernel,
-    or for a (periods, c_obs, uncer) sampler the existing one; state, chi-squares and rows on copies)."""
+    or for a (periods, c_obs, uncer) sampler the Rayleigh-phase one; state, chi-squares and rows on copies)."""
     st = mc._fused_buffers(C)
     M = (1 << depth) - 1 if depth > 1 else 1
     q = torch.as_tensor(mc.spec.v0, dtype=torch.float64, device=mc.device)[None, :].repeat(C * M, 1).contiguous()
@@ -61,16 +61,8 @@ def accept_ms(mc, C, depth, reps=50):
     row = torch.zeros((C, max(depth, 1), 3 + mc.spec.n), dtype=torch.float64, device=mc.device)
     stream = ctypes.c_void_p(torch.cuda.current_stream(mc.device).cuda_stream)
     rowp = ctypes.c_void_p(row.data_ptr())
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    if mc.joint is not None:
-        go = lambda: mc._accept_joint(stream, pred, st, q, p, rowp, row.stride(0), 1, depth=depth, nsteps=max(depth, 1),
-                                      step_stride=3 + mc.spec.n)
-    else:
-        c, status = pred
-        go = lambda: _lib.check(_lib.lib().surfdisp_mcmc_accept_tree_device(
-            stream, C, mc.spec.n, int(mc.periods.numel()), max(depth, 1), max(depth, 1), ptr(c), ptr(status), ptr(st["c_obs"]),
-            ptr(st["uncer"]), ptr(st["mask8"]), 1 if st["c_obs"].ndim == 2 else 0, ptr(q), ptr(p), ptr(st["chi"]), rowp,
-            row.stride(0), 3 + mc.spec.n, mc.proposer.seed_int, 1, 0))
+    go = lambda: mc._accept(stream, pred, st, q, p, rowp, row.stride(0), 1, True, depth=max(depth, 1), nsteps=max(depth, 1),
+                            step_stride=3 + mc.spec.n)
     go(); torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
