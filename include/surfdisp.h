@@ -35,7 +35,8 @@ extern "C" {
 #define SURFDISP_ABI_VERSION 4      /* 4 (r04): + SURFDISP_KERN_REFCOORD, surfdisp_workspace_counters, surfdisp_prior_device, surfdisp_mcmc_propose_masked_device; every ABI-3 symbol kept;
                                        additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes,
                                        surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes,
-                                       surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events */
+                                       surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events,
+                                       surfdisp_lsq_step_device */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -367,6 +368,50 @@ int surfdisp_mcmc_accept_tree_joint5_device(void *stream, int C, int N, int dept
                                             const unsigned char *mask, int obs_per_chain, const double *q, double *p0, double *chi0,
                                             double *row, long row_stride, long step_stride, unsigned long long seed,
                                             unsigned long long counter, long chain0);
+
+/* ---- (6d) one damped, smoothed least-squares step of the layers' Vs on the device, added within ABI 4: the consumer of the
+ *          partial arrays of (5b)-(5d) (csrc/surfdisp_lsq.hip; the classical Gauss-Newton / Levenberg-Marquardt iteration of the
+ *          surf96 family, one step per call; pysurfinv_amd.linearized iterates it with the forward solves).  Per stack s the
+ *          unknowns x are the Vs of its FREE layers: layer i < nlay[s] with free_mask[i] != 0 (free_mask [Lmax], or [B][Lmax] with
+ *          free_per_stack; NULL: every layer), n of them, x0 = row 1 of `model`.  nfree_max: an upper bound of n over the batch
+ *          (1..128, <= Lmax) - it sizes the kernel's LDS; a stack with more free layers is not solved (flag 3).
+ *   rows:  the column table of surfdisp_mcmc_accept_joint5_device - cols [N][2] (source 0 cR, 1 uR, 2 cL, 3 uL, 4 chi, 5 |chi|; period
+ *          index in that source's solve), weights [N], obs / uncer / mask [N] or [B][N] with obs_per_stack, pred[5] / pred_stride[5] /
+ *          nper[2] the solves' predictions (N <= 800).  part[15] = {source 0..4} x {d/dVs, d/dVp, d/drho}: the [B][nper][Lmax] fp32
+ *          arrays exactly as (5b)-(5d) write them (part[3] = dudb of the Rayleigh solve, part[12] = dedb, ...; NULL: that column is
+ *          absent; Love has no d/dVp).  The effective Jacobian row over the free layers i:
+ *              G[r,i] = K_b[r,i] + p_i K_a[r,i] + q_i K_rho[r,i],      residual  res_r = obs_r - pred_r,
+ *          p = vp_slope, q = rho_slope: dVp/dVs and drho/dVs of layer i ([Lmax], or [B][Lmax] with slope_per_stack; NULL or an entry
+ *          of 0: held fixed, the column is not read).  Source 5 compares |chi| and multiplies its row by sign(chi).
+ *          A row is DROPPED from this step when it is masked out, when its observation is not finite or its uncertainty not
+ *          finite or <= 0, when its prediction is an unsolved period (c or U not >= 0.01; chi not finite, or c < 0.01 at chi's
+ *          period), when it names a missing array or a period beyond its solve, or when any G[r,i] is not finite (the NaN rows
+ *          of (5c) / (5d)).
+ *   solve: in fp64 from the fp32 inputs, by Cholesky factorisation,
+ *              (G^T W G + alpha D^T Q D + lam_s I) delta = G^T W res - alpha D^T Q D x0,     W = diag(w_r / uncer_r^2),
+ *          D the first difference between CONSECUTIVE FREE layers, Q its weights: Q [Lmax-1] (or [B][Lmax-1] with q_per_stack;
+ *          NULL: 1) weighs the interface between the layers k and k+1, and two consecutive free layers a < b take the smallest
+ *          of Q[a..b-1] (0 cuts the smoothing across a discontinuity); alpha >= 0 a scalar; lam [B] (device) the damping.
+ *   out:   delta [B][Lmax] fp64 (0 at layers that are not free); stats [B][3] fp64 = data misfit sum W res^2 and roughness
+ *          x0^T D^T Q D x0 at x0, and the objective the linear model predicts at x0 + delta, sum W (res - G delta)^2 + alpha
+ *          roughness(x0 + delta); info [B][3] int = rows used, rows dropped, flag: 0 solved; 1 no usable row; 2 a pivot <= 0 or
+ *          not finite (or a step that is not finite); 3 more than nfree_max free layers.  For a flag other than 0 delta is all
+ *          zeros, never NaN, and the predicted objective is the one at x0.
+ *          One workgroup per stack, the packed triangle of the augmented normal equations in LDS (66 KB at n = 128): the first
+ *          call that needs more dynamic LDS than any before it raises the kernel's limit, so make it outside a graph capture.
+ *          No workspace.  SURFDISP_ERR_INVALID, before anything is launched: B < 1, Lmax outside 1..200, N outside 1..800,
+ *          nfree_max outside 1..min(128, Lmax), alpha < 0 or not finite, a NULL required pointer (model, part, pred, pred_stride,
+ *          nper, cols, weights, obs, uncer, mask, lam, delta, stats, info), no phase array at all, a group or chi array without
+ *          the phase array of its solve, a prediction array with nper outside 1..200 or a stride below nper, a partial array of
+ *          a source without predictions. */
+int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                             const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                             const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                             int N, const int *cols, const double *weights,
+                             const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                             const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                             double alpha, const double *Q, int q_per_stack, const double *lam,
+                             double *delta, double *stats, int *info);
 
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular

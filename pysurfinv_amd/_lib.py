@@ -36,7 +36,7 @@ EXPORTS = (
     "surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_forward_batch_device2_events",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
-    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes","surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -158,6 +158,12 @@ def lib() -> ctypes.CDLL:
             getattr(L, name).argtypes = ([vp, ctypes.c_int, ctypes.c_int] + head + ([ctypes.c_int, ctypes.c_int] if tree else []) + pred
                                          + [vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_long] + ([ctypes.c_long] if tree else [])
                                          + [u64, u64] + ([] if tree else [ctypes.c_int]) + [ctypes.c_long])
+    # (stream, B, Lmax, nlay, model, free_mask, free_per_stack, nfree_max, part[15], pred[5], pred_stride[5], nper[2], N, cols, weights,
+    #  obs, uncer, mask, obs_per_stack, vp_slope, rho_slope, slope_per_stack, alpha, Q, q_per_stack, lam, delta, stats, info)
+    L.surfdisp_lsq_step_device.restype = ctypes.c_int
+    L.surfdisp_lsq_step_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vpp, vpp, lp, ipp,
+                                           ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int,
+                                           ctypes.c_double, vp, ctypes.c_int, vp, vp, vp, vp]
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

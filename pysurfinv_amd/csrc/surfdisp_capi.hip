@@ -835,6 +835,57 @@ int surfdisp_mcmc_accept_tree_joint5_device(void *stream, int C, int N, int dept
                              chain0, depth, nsteps);
 }
 
+// One damped least-squares step of the free layers' Vs of every stack (csrc/surfdisp_lsq.hip): the prediction arrays and the
+// column table of the joint accept entries, plus the partial arrays of the kernel entries.
+int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                             const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                             const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                             int N, const int *cols, const double *weights,
+                             const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                             const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                             double alpha, const double *Q, int q_per_stack, const double *lam,
+                             double *delta, double *stats, int *info)
+{
+    bool ok = B >= 1 && Lmax >= 1 && Lmax <= SURFDISP_NLAY_MAX && N >= 1 && N <= sd::SD_MCMC_JOINT_MAX_COLS &&
+              nfree_max >= 1 && nfree_max <= sd::SD_LSQ_MAX_FREE && nfree_max <= Lmax &&
+              model && part && pred && pred_stride && nper && cols && weights && obs && uncer && mask && lam && delta && stats && info &&
+              alpha >= 0.0 && alpha <= 1.7976931348623157e308;
+    sd::LsqArgs a{};
+    for (int w = 0; ok && w < 2; ++w) {
+        a.nper[w] = nper[w];
+        if (!pred[2 * w] && pred[2 * w + 1]) ok = false;                  // a group array without the phase array of its solve
+        for (int k = 2 * w; ok && k < 2 * w + 2; ++k) {
+            a.pred[k] = pred[k];
+            a.pstride[k] = pred_stride[k];
+            if (pred[k] && (nper[w] < 1 || nper[w] > SURFDISP_NPER_MAX || pred_stride[k] < nper[w])) ok = false;
+        }
+    }
+    if (ok && !pred[0] && !pred[2]) ok = false;
+    if (ok && pred[4]) {                                                    // chi [B][nper[0]] of the Rayleigh solve
+        a.pred[4] = pred[4];
+        a.pstride[4] = pred_stride[4];
+        if (!pred[0] || pred_stride[4] < nper[0]) ok = false;
+    }
+    for (int k = 0; ok && k < 5; ++k) {                                     // a source's partials need its predictions
+        bool any = false;
+        for (int q = 0; q < 3; ++q) { a.part[3 * k + q] = part[3 * k + q]; any = any || part[3 * k + q]; }
+        if (any && !pred[k]) ok = false;
+    }
+    if (!ok) {
+        set_err("surfdisp_lsq_step_device: bad argument (B >= 1, 1 <= Lmax <= 200, 1 <= N <= 800, 1 <= nfree_max <= min(128, Lmax), alpha >= 0, "
+                "required pointers, every given prediction array with 1 <= nper <= stride, partials only of sources with predictions)");
+        return SURFDISP_ERR_INVALID;
+    }
+    a.B = B; a.Lmax = Lmax; a.N = N; a.nmax = nfree_max;
+    a.nlay = nlay; a.model = model; a.free_mask = free_mask; a.free_per_stack = free_per_stack ? 1 : 0;
+    a.cols = cols; a.weights = weights; a.obs = obs; a.uncer = uncer; a.mask = mask; a.obs_per_stack = obs_per_stack ? 1 : 0;
+    a.vp_slope = vp_slope; a.rho_slope = rho_slope; a.slope_per_stack = slope_per_stack ? 1 : 0;
+    a.alpha = alpha; a.Q = Q; a.q_per_stack = q_per_stack ? 1 : 0; a.lam = lam;
+    a.delta = delta; a.stats = stats; a.info = info;
+    SD_HIP(sd::launch_lsq_step(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Measurement variant that does NOT synchronise: the caller owns four events per call
 // (surfdisp_events_create) which are recorded on the launch stream before prep, between the
 // kernels and after finish; durations are read later with surfdisp_events_elapsed_ms, after the

@@ -231,6 +231,36 @@ struct McmcJointArgs {
     const int *cols;        // [Ptot][2]: source (0..3 the arrays; 4 chi, 5 |chi|: pred[4], the joint5 entries only), period index in that solve
     const double *weights;  // [Ptot]
 };
+// damped least-squares step of the free layers' Vs (csrc/surfdisp_lsq.hip; include/surfdisp.h section (6d))
+constexpr int SD_LSQ_MAX_FREE = 128;    // unknowns per stack: the packed triangle of 129 x 129 doubles is 66 KB of LDS
+constexpr int SD_LSQ_TILE_ROWS = 16;    // data rows staged in LDS at a time
+struct LsqArgs {
+    int B, Lmax, N, nmax;   // stacks, layers per row, data rows, upper bound of the free layers of any stack (sizes the LDS)
+    const int *nlay;        // [B] or nullptr
+    const float *model;     // [B][5][Lmax]: row 1 (Vs) is the linearisation point
+    const unsigned char *free_mask;   // [Lmax] or [B][Lmax] (free_per_stack), nullptr: every layer below nlay
+    int free_per_stack;
+    const float *part[15];  // [source 0..4: cR, uR, cL, uL, chi][d/dVs, d/dVp, d/drho]: [B][nper of the source's solve][Lmax] or nullptr
+    const float *pred[5];   // the same solves' predictions (McmcJointArgs)
+    long pstride[5];
+    int nper[2];
+    const int *cols;        // [N][2] (McmcJointArgs)
+    const double *weights;  // [N]
+    const double *obs, *uncer;        // [N], or [B][N] when obs_per_stack
+    const unsigned char *mask;        // same shape
+    int obs_per_stack;
+    const double *vp_slope, *rho_slope;   // dVp/dVs, drho/dVs: [Lmax] or [B][Lmax] (slope_per_stack), nullptr: 0
+    int slope_per_stack;
+    double alpha;
+    const double *Q;        // interface weights [Lmax-1] or [B][Lmax-1] (q_per_stack), nullptr: 1
+    int q_per_stack;
+    const double *lam;      // [B]
+    double *delta;          // [B][Lmax]
+    double *stats;          // [B][3]: data misfit, roughness, predicted objective
+    int *info;              // [B][3]: rows used, rows dropped, flag
+};
+size_t lsq_lds_bytes(int nmax);
+hipError_t launch_lsq_step(hipStream_t s, const LsqArgs &a);
 hipError_t launch_mcmc_propose(hipStream_t s, const McmcProposeArgs &a);
 hipError_t launch_mcmc_accept(hipStream_t s, const McmcAcceptArgs &a);
 hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a, bool ellip);   // ellip: the kernel that knows the sources 4 and 5

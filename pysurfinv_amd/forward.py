@@ -214,12 +214,13 @@ class BatchPlan:
         _lib.check(rc)
         return self.c, self.u, self.status, dcdb, dcda, dcdr
 
-    def run_group_kernels(self, model, periods, kind=2, nlay=None, dlnT_frac=0.01, want_vp=True, want_rho=True):
+    def run_group_kernels(self, model, periods, kind=2, nlay=None, dlnT_frac=0.01, want_vp=True, want_rho=True, count=True):
         """``run_kernels`` plus the analytic partials of the GROUP velocity (``surfdisp_forward_group_kernels_device``):
         returns (c, u, status, dcdb, dcda, dcdr, dudb, duda, dudr, n_failed).  c .. dcdr equal ``run_kernels``' bit for bit;
         dudb / duda / dudr float32 [B, P, L] = d U(period) / d (Vs | Vp | rho) of input layer i (``None`` where not
         requested; Love has no duda), from the phase partials at T (1 -+ dlnT_frac).  Rows of unsolved periods are zeros,
-        rows of units whose shifted root failed are NaN; ``n_failed`` (int, synchronises the stream) counts the latter."""
+        rows of units whose shifted root failed are NaN; ``n_failed`` (int, synchronises the stream) counts the latter
+        (``count=False``: the device tensor itself, no synchronisation)."""
         torch = self.torch
         for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
             if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
@@ -246,15 +247,15 @@ class BatchPlan:
                 float(dlnT_frac), ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
                 ptr(dudb), ptr(duda), ptr(dudr), ptr(self.nfail), ptr(self.gworkspace), self.gws_bytes)
         _lib.check(rc)
-        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(self.nfail.item())
+        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(self.nfail.item()) if count else self.nfail
 
-    def run_ellip_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True):
+    def run_ellip_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, count=True):
         """``run_kernels`` plus the Rayleigh ellipticity and its analytic partials (``surfdisp_forward_ellip_kernels_device``):
         returns (c, u, status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, n_nonfinite).  c .. dcdr equal ``run_kernels``' bit
         for bit, ratio [B, P] is ``run(want_ratio=True)``'s; dedb / deda / dedr float32 [B, P, L] = d chi(period) / d (Vs | Vp |
         rho) of input layer i (``None`` where not requested).  Rows of unsolved periods, water layers and layers below the half
         space are zeros, rows of units whose result is not finite are NaN; ``n_nonfinite`` (int, synchronises the stream)
-        counts the latter.  Rayleigh only."""
+        counts the latter (``count=False``: the device tensor itself, no synchronisation).  Rayleigh only."""
         torch = self.torch
         if (int(kind) & 3) != _lib.KIND_RAYLEIGH:
             raise ValueError("run_ellip_kernels: Rayleigh only (kind=2); Love waves have no ellipticity")
@@ -283,7 +284,7 @@ class BatchPlan:
                 ptr(self.c), ptr(self.u), ptr(ratio), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
                 ptr(dedb), ptr(deda), ptr(dedr), ptr(self.nnonfin), ptr(self.eworkspace), self.ews_bytes)
         _lib.check(rc)
-        return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(self.nnonfin.item()))
+        return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(self.nnonfin.item()) if count else self.nnonfin)
 
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's

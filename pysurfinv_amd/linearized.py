@@ -1,0 +1,403 @@
+"""Linearised inversion of the layers' shear velocities: the classical companion of the Metropolis sampler.
+
+An iterated, damped, smoothed least-squares fit (Gauss-Newton with Levenberg-Marquardt damping, as in the surf96 family) of
+the Vs of the FREE layers of every stack of a batch, fed by the analytic sensitivity kernels of the library (dc/dm, dU/dm,
+dchi/dm for Rayleigh, dc/dm, dU/dm for Love) and solved on the device, one workgroup per stack
+(``surfdisp_lsq_step_device``, csrc/surfdisp_lsq.hip).  Fundamental mode, fixed thicknesses.
+
+One step, per stack, with x the Vs of the n free layers and x0 the current model:
+
+    G[r, i] = K_b[r, i] + p_i K_a[r, i] + q_i K_rho[r, i]          (p, q: dVp/dVs, drho/dVs of layer i; 0 = held fixed)
+    res_r   = obs_r - pred_r,    W = diag(w_r / uncer_r^2)
+    (G^T W G + alpha D^T Q D + lam I) delta = G^T W res - alpha D^T Q D x0
+
+D is the first difference between consecutive free layers, Q its weights (``consecutive_weights``), lam the damping of the
+stack.  ``lsq_step_reference`` states the step in numpy float64; the kernel is tested against it.
+
+* ``LsqPlan``: the kernels + step of one batch as device tensors.
+* ``LinearizedBatch``: the iteration - kernels and step at x, ONE forward solve of the trials, accept where the objective
+  (chi-square of ``obsdata`` + alpha roughness) fell, lam down on accept, up on reject - without a host synchronisation.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .obsdata import JointData
+
+MAX_FREE = 128          # unknowns per stack the step kernel takes (SD_LSQ_MAX_FREE)
+FAIL = 88888.0          # the misfit of a failed solve (point.py:20-21)
+
+# d(Vp, rho) / dVs of the layer groups of senskernel.GROUP_RULES (sensModel._convert)
+GROUP_SLOPES = {"water": (0.0, 0.0), "sediment": (1.23, 0.3601 * 1.23), "crust": (1.8, 0.3601 * 1.8), "mantle": (1.76, 1.0 / 4.5)}
+
+
+def group_slopes(grp):
+    """(vp_slope, rho_slope) [L] of a list of layer group names: the slopes of ``senskernel.GROUP_RULES``."""
+    try:
+        s = np.array([GROUP_SLOPES[g] for g in grp], np.float64)
+    except KeyError as e:
+        raise ValueError(f"group_slopes: unknown layer group {e.args[0]!r} (expected {sorted(GROUP_SLOPES)})")
+    return s[:, 0].copy(), s[:, 1].copy()
+
+
+def consecutive_weights(free, Q=None):
+    """Weights of the first differences between CONSECUTIVE FREE layers: ``free`` bool [L], ``Q`` [L-1] the weight of the
+    interface between the layers k and k+1 (None: 1).  Two consecutive free layers a < b take min(Q[a:b]) - an interface of
+    weight 0 anywhere between them cuts the smoothing.  Returns (layers [n], weights [n-1])."""
+    idx = np.nonzero(np.asarray(free, bool))[0]
+    Q = np.ones(max(len(free) - 1, 0)) if Q is None else np.asarray(Q, np.float64)
+    w = np.array([Q[a:b].min() for a, b in zip(idx[:-1], idx[1:])], np.float64)
+    return idx, w
+
+
+def normal_equations(G, r, w_over_sigma2, x0, alpha, Q, lam):
+    """(A, g) of the step, numpy float64: A = G^T W G + alpha D^T Q D + lam I, g = G^T W r - alpha D^T Q D x0.  G [N, n], r and
+    w_over_sigma2 [N], x0 [n], Q [n-1] (weights of the differences of consecutive unknowns)."""
+    G = np.asarray(G, np.float64).reshape(-1, np.size(x0))
+    r = np.asarray(r, np.float64).ravel()
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    x0 = np.asarray(x0, np.float64).ravel()
+    n = x0.size
+    D = np.zeros((max(n - 1, 0), n))
+    for k in range(n - 1):
+        D[k, k], D[k, k + 1] = -1.0, 1.0
+    Qd = np.diag(np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]) if n > 1 else np.zeros((0, 0))
+    S = D.T @ Qd @ D
+    A = G.T @ (w[:, None] * G) + float(alpha) * S + float(lam) * np.eye(n)
+    g = G.T @ (w * r) - float(alpha) * (S @ x0)
+    return A, g
+
+
+def lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam):
+    """One damped least-squares step of one stack in numpy float64 - the statement ``surfdisp_lsq_step_device`` is tested
+    against.  G [N, n]: the effective Jacobian rows of the USED data rows, r [N] their residuals obs - pred, w_over_sigma2 [N],
+    x0 [n] the free layers' Vs, Q [n-1] the weights of the differences of consecutive free layers, alpha, lam scalars.
+    Returns dict(delta [n], misfit = sum W r^2, roughness = x0^T D^T Q D x0, predicted = sum W (r - G delta)^2 + alpha
+    roughness(x0 + delta), flag): flag 1 without rows, 2 when the Cholesky factorisation fails - then delta = 0 and
+    predicted = misfit + alpha roughness."""
+    x0 = np.asarray(x0, np.float64).ravel()
+    n = x0.size
+    G = np.asarray(G, np.float64).reshape(-1, n)
+    r = np.asarray(r, np.float64).ravel()
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    Qv = np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]
+    rough = lambda x: float((Qv * np.diff(x) ** 2).sum())
+    misfit = float((w * r * r).sum())
+    out = dict(delta=np.zeros(n), misfit=misfit, roughness=rough(x0), predicted=misfit + float(alpha) * rough(x0), flag=0)
+    if G.shape[0] == 0:
+        out["flag"] = 1
+        return out
+    A, g = normal_equations(G, r, w, x0, alpha, Qv, lam)
+    try:
+        if not np.isfinite(A).all():
+            raise np.linalg.LinAlgError
+        Lc = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        out["flag"] = 2
+        return out
+    delta = np.linalg.solve(Lc.T, np.linalg.solve(Lc, g))
+    t = r - G @ delta
+    out["delta"] = delta
+    out["predicted"] = float((w * t * t).sum()) + float(alpha) * rough(x0 + delta)
+    return out
+
+
+def _per_layer(name, v, M, L, cols=None):
+    """A scalar, [cols] or [M, cols] argument as float64 (cols = L unless given); ValueError otherwise."""
+    cols = L if cols is None else cols
+    a = np.asarray(v, np.float64)
+    if a.ndim == 0:
+        return np.full(cols, float(a))
+    if a.shape not in ((cols,), (M, cols)):
+        raise ValueError(f"{name}: shape {a.shape}, expected a scalar, ({cols},) or ({M}, {cols})")
+    return np.ascontiguousarray(a)
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+class LsqPlan:
+    """The sensitivity kernels and the least-squares step of B stacks of L layers against ``datasets`` (``obsdata``
+    ``DispersionData`` sets, or their dict form), on ``device``.  Owns the ``BatchPlan`` of each wave type with data, the
+    ``JointData`` table and the output buffers.  ``mask``: bool [Ptot] or [B, Ptot], rows to leave out on top of the data's own
+    unusable entries (columns in data-set order)."""
+
+    def __init__(self, B, L, datasets, device="cuda:0", mask=None):
+        import torch
+        self.torch = torch
+        self.B, self.L = int(B), int(L)
+        self.joint = jd = JointData(datasets, device="cpu")
+        if jd.C is not None and jd.C != self.B:
+            raise ValueError(f"per-stack data of {jd.C} rows against {self.B} stacks")
+        obs, unc = np.asarray(jd.obs_raw, np.float64), np.asarray(jd.uncer_raw, np.float64)
+        ok = np.isfinite(obs) & np.isfinite(unc) & (unc > 0)              # the rule of DispersionData
+        if mask is not None:
+            m = np.asarray(mask, bool)
+            if m.shape not in ((jd.Ptot,), (self.B, jd.Ptot)):
+                raise ValueError(f"mask: shape {m.shape}, expected ({jd.Ptot},) or ({self.B}, {jd.Ptot})")
+            if m.ndim == 2 and obs.ndim == 1:
+                obs, unc, ok = (np.broadcast_to(a, (self.B, jd.Ptot)) for a in (obs, unc, ok))
+            ok = ok & m
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.SurfdispError("LsqPlan needs a HIP device (no CPU fallback)")
+        from .forward import BatchPlan
+        jd.to(self.device)
+        dev = self.device
+        self.mask = torch.as_tensor(np.ascontiguousarray(ok), device=dev)
+        self.obs = torch.as_tensor(np.where(ok, obs, 0.0), device=dev).contiguous()
+        self.uncer = torch.as_tensor(np.where(ok, unc, 1.0), device=dev).contiguous()
+        self.mask8 = self.mask.to(torch.uint8).contiguous()
+        self.plans = {w: BatchPlan(self.B, self.L, jd.solve_periods[w].size, device=dev) for w in jd.waves}
+        self.delta = torch.zeros(self.B, self.L, dtype=torch.float64, device=dev)
+        self.stats = torch.zeros(self.B, 3, dtype=torch.float64, device=dev)
+        self.info = torch.zeros(self.B, 3, dtype=torch.int32, device=dev)
+        self._sets = {w: {d.quantity for d in jd.datasets if d.wave == w} for w in jd.waves}
+
+    def kernels(self, model, nlay=None, want_vp=True, want_rho=True):
+        """The kernel entries the data need, once per wave type: U data -> ``run_group_kernels``, an "E" set ->
+        ``run_ellip_kernels``, both -> both calls (``senskernel.analytic_kernels``), otherwise ``run_kernels``.  Returns (pred,
+        part): the forward dict of ``JointData.predictions`` (the plans' own output tensors) and the 15 partial arrays
+        [source 0..4][Vs, Vp, rho] (None where absent).  No host synchronisation."""
+        jd = self.joint
+        pred = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
+        part = [None] * 15
+        for w in jd.waves:
+            plan, per = self.plans[w], jd.periods_t[w]
+            kind = _lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE
+            o = 0 if w == "R" else 6
+            q = self._sets[w]
+            done = False
+            if "U" in q:
+                c, u, st, kb, ka, kr, ub, ua, ur, _ = plan.run_group_kernels(model, per, kind=kind, nlay=nlay, want_vp=want_vp,
+                                                                             want_rho=want_rho, count=False)
+                part[o:o + 6] = [kb, ka, kr, ub, ua, ur]
+                pred["u" + w] = u
+                done = True
+            if "E" in q:
+                c, u, st, ratio, kb, ka, kr, eb, ea, er, _ = plan.run_ellip_kernels(model, per, kind=kind, nlay=nlay,
+                                                                                  want_vp=want_vp, want_rho=want_rho, count=False)
+                part[0:3] = [kb, ka, kr]
+                part[12:15] = [eb, ea, er]
+                pred["eR"] = ratio
+                done = True
+            if not done:
+                c, u, st, kb, ka, kr = plan.run_kernels(model, per, kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
+                part[o:o + 3] = [kb, ka, kr]
+            pred["c" + w], pred["status" + w] = c, st
+        return pred, part
+
+    def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None):
+        """Kernels at ``model`` (float32 [B, 5, L]) and one least-squares step.  Device tensors: ``lam`` float64 [B]; ``nlay``
+        int32 [B]; ``free`` uint8 [L] or [B, L] (None: every layer); ``vp_slope`` / ``rho_slope`` float64 [L] or [B, L] (None:
+        held fixed, the Vp / rho partials are not computed); ``Q`` float64 [L-1] or [B, L-1] (None: 1).  ``nfree_max``: an
+        upper bound of the free layers of any stack (default L; at most 128).  Returns dict(delta [B, L] float64, misfit,
+        roughness, predicted [B] float64, used, dropped, flag [B] int32, pred, part) - views of the plan's buffers, rewritten by
+        the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max."""
+        torch = self.torch
+        B, L = self.B, self.L
+        nmax = L if nfree_max is None else int(nfree_max)
+        if not 1 <= nmax <= min(MAX_FREE, L):
+            raise ValueError(f"nfree_max = {nmax}: the step kernel takes 1..{min(MAX_FREE, L)} free layers per stack (give nfree_max "
+                             "when L > 128)")
+
+        def chk(name, t, dtype, cols):
+            if t is None:
+                return 0
+            if t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) not in ((cols,), (B, cols)):
+                raise ValueError(f"{name}: expected contiguous {dtype} ({cols},) or ({B}, {cols}) on {self.device}, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+            return 1 if t.ndim == 2 else 0
+
+        free_ps = chk("free", free, torch.uint8, L)
+        sl_ps = chk("vp_slope", vp_slope, torch.float64, L)
+        if rho_slope is not None and vp_slope is not None and rho_slope.ndim != vp_slope.ndim:
+            raise ValueError("vp_slope and rho_slope: both [L] or both [B, L]")
+        sl_ps = max(sl_ps, chk("rho_slope", rho_slope, torch.float64, L))
+        q_ps = chk("Q", Q, torch.float64, L - 1) if L > 1 else 0
+        if lam.dtype != torch.float64 or tuple(lam.shape) != (B,) or lam.device != self.device or not lam.is_contiguous():
+            raise ValueError(f"lam: expected contiguous float64 ({B},) on {self.device}")
+        pred, part = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None)
+        jd = self.joint
+        arrs = [pred["cR"], pred["uR"], pred["cL"], pred["uL"], pred["eR"]]
+        predp = (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in arrs])
+        strides = (ctypes.c_long * 5)(*[a.stride(0) if a is not None else 0 for a in arrs])
+        partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
+        nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().surfdisp_lsq_step_device(
+                stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, partp, predp, strides, nper,
+                jd.Ptot, _ptr(jd.cols), _ptr(jd.weights), _ptr(self.obs), _ptr(self.uncer), _ptr(self.mask8),
+                1 if self.obs.ndim == 2 else 0, _ptr(vp_slope), _ptr(rho_slope), sl_ps, float(alpha), _ptr(Q), q_ps, _ptr(lam),
+                _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
+        return dict(delta=self.delta, misfit=self.stats[:, 0], roughness=self.stats[:, 1], predicted=self.stats[:, 2],
+                    used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=pred, part=part)
+
+    def forward(self, model, nlay=None):
+        """ONE forward solve per wave type of ``model`` (``BatchPlan.run``, with the ratio when an "E" set is present; kind
+        flags of ``JointData.kind``) -> the forward dict of ``JointData.predictions``."""
+        jd = self.joint
+        out = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
+        for w in jd.waves:
+            res = self.plans[w].run(model, jd.periods_t[w], kind=jd.kind(w), nlay=nlay, want_ratio=jd.with_ratio and w == "R")
+            out["c" + w], out["u" + w], out["status" + w] = res[:3]
+            if len(res) > 3:
+                out["eR"] = res[3]
+        return out
+
+    def chi_square(self, model, nlay=None):
+        """(chi2, rms, failed) [B] of ``model`` by the definition of ``obsdata``: chi2 = sum_d w_d sum ((obs - pred) / uncer)^2
+        over the usable entries, rms = sqrt(chi2 / N) with N their count (88888 for a failed solve - status, c < 0.01, a group
+        velocity or ellipticity the data read: the rule of the module ``obsdata``)."""
+        torch = self.torch
+        cP, failed = self.joint.predictions(self.forward(model, nlay))
+        r = torch.where(self.mask, (self.obs - cP) / self.uncer, torch.zeros_like(cP))
+        chi = (self.joint.weights * r * r).sum(dim=1)
+        N = self.mask.sum(dim=-1).to(torch.float64)
+        rms = torch.where(failed, torch.full_like(chi, FAIL), torch.sqrt(chi / N))
+        return chi, rms, failed
+
+
+class LinearizedBatch:
+    """Damped least-squares inversion of the Vs of M stacks at once.
+
+    ``model0`` float32 [M, 5, L] (vp, vs, rho, h, 1/Qs; numpy or torch): the starting models.  ``datasets``: as
+    ``MetropolisBatch(data=...)``.  ``free`` bool [L] or [M, L]: the layers whose Vs is an unknown (default: every layer with
+    Vs > 0 above the half space, plus the half space); at most 128 per stack.  ``vp_slope`` / ``rho_slope``: dVp/dVs and
+    drho/dVs, a scalar, [L] or [M, L] (default 0: Vp and rho stay fixed; ``group_slopes`` gives the slopes of
+    ``senskernel.GROUP_RULES``).  ``alpha``: weight of the roughness; ``Q`` [L-1] or [M, L-1]: weights of the layer
+    interfaces (0 cuts the smoothing across a discontinuity; ``consecutive_weights``).  ``lam0``, ``nu``, ``lam_min``: the
+    Levenberg-Marquardt damping and its factor.  ``vs_bounds`` = (lo, hi), scalars or arrays that broadcast to [M, L]: the
+    trial Vs of the free layers is clamped into them.  ``nlay`` int [M]: layers of each stack.  ``mask``: see ``LsqPlan``.
+
+    ``run(n_iter)``, per iteration and with no host synchronisation (everything is ``torch.where`` on device tensors):
+    kernels and step at x; trial = clamp(x + delta), Vp and rho moved along their slopes by the Vs change; ONE forward solve of
+    the trials; objective = chi-square + alpha roughness of the trial, by the misfit rule of ``obsdata`` (a failed solve is a
+    rejected trial: its objective is inf); per stack, where the objective fell: accept, lam <- max(lam / nu, lam_min), else keep
+    x and lam <- lam nu.  A rejected stack's kernels are computed again in the next iteration although x did not move (they
+    are not cached per stack): the batch stays one launch, and a rejected step is the rare case."""
+
+    def __init__(self, model0, datasets, free=None, vp_slope=0.0, rho_slope=0.0, alpha=1.0, Q=None, lam0=1.0, nu=4.0,
+                 lam_min=1e-9, vs_bounds=None, nlay=None, mask=None, device="cuda:0"):
+        m0 = model0.detach().cpu().numpy() if hasattr(model0, "detach") else np.asarray(model0)
+        if m0.ndim != 3 or m0.shape[1] != 5:
+            raise ValueError("model0 must be [M, 5, L]")
+        m0 = np.ascontiguousarray(m0, np.float32)
+        M, _, L = m0.shape
+        self.M, self.L = M, L
+        nl = np.full(M, L, np.int64) if nlay is None else np.asarray(nlay, np.int64).ravel()
+        if nl.size != M or (nl < 2).any() or (nl > L).any():
+            raise ValueError(f"nlay: {M} entries in 2..{L} expected")
+        inside = np.arange(L)[None, :] < nl[:, None]
+        if free is None:
+            fr = (m0[:, 1, :] > 0) | (np.arange(L)[None, :] == nl[:, None] - 1)
+        else:
+            fr = np.asarray(free, bool)
+            if fr.shape not in ((L,), (M, L)):
+                raise ValueError(f"free: shape {fr.shape}, expected ({L},) or ({M}, {L})")
+            fr = np.broadcast_to(fr, (M, L))
+        fr = fr & inside
+        nfree = fr.sum(axis=1)
+        if nfree.max() > MAX_FREE:
+            raise ValueError(f"{int(nfree.max())} free layers in a stack: the step kernel takes at most {MAX_FREE}")
+        if nfree.max() < 1:
+            raise ValueError("no free layer")
+        self.nfree_max = int(nfree.max())
+        ps = _per_layer("vp_slope", vp_slope, M, L)
+        qs = _per_layer("rho_slope", rho_slope, M, L)
+        Qa = None if Q is None else _per_layer("Q", Q, M, L, cols=L - 1)
+        if not (np.isfinite(alpha) and alpha >= 0):
+            raise ValueError("alpha must be finite and >= 0")
+        if not (lam0 > 0 and nu > 1 and lam_min >= 0):
+            raise ValueError("lam0 > 0, nu > 1, lam_min >= 0 expected")
+        self.alpha, self.nu, self.lam_min = float(alpha), float(nu), float(lam_min)
+        # the differences of consecutive free layers, padded to nfree_max - 1 per stack (weight 0 on the padding)
+        K = max(self.nfree_max - 1, 1)
+        ia, ib, qw = np.zeros((M, K), np.int64), np.zeros((M, K), np.int64), np.zeros((M, K))
+        for m in range(M):
+            idx, w = consecutive_weights(fr[m], None if Qa is None else (Qa if Qa.ndim == 1 else Qa[m]))
+            ia[m, :w.size], ib[m, :w.size], qw[m, :w.size] = idx[:-1], idx[1:], w
+        if vs_bounds is not None:
+            lo, hi = (np.broadcast_to(np.asarray(b, np.float64), (M, L)) for b in vs_bounds)
+        self.plan = plan = LsqPlan(M, L, datasets, device=device, mask=mask)      # (data errors: ValueError; no HIP device: SurfdispError)
+        import torch
+        self.torch = torch
+        dev = self.device = plan.device
+        t = lambda a, dt=None: torch.as_tensor(np.ascontiguousarray(a), device=dev) if dt is None else \
+            torch.as_tensor(np.ascontiguousarray(a), device=dev).to(dt).contiguous()
+        self.model = t(m0)
+        self.nlay = None if nlay is None else t(nl, torch.int32)
+        self.free = t(fr)
+        self.free8 = t(fr.astype(np.uint8))
+        self.has_vp, self.has_rho = bool((ps != 0).any()), bool((qs != 0).any())
+        self.vp_slope, self.rho_slope = t(ps), t(qs)
+        self.Q = None if Qa is None else t(Qa)
+        self._ia, self._ib, self._qw = t(ia), t(ib), t(qw)
+        self.bounds = None if vs_bounds is None else (t(lo), t(hi))
+        self.lam = torch.full((M,), float(lam0), dtype=torch.float64, device=dev)
+        chi, rms, failed = plan.chi_square(self.model, self.nlay)
+        self.objective = torch.where(failed, torch.full_like(chi, float("inf")), chi + self.alpha * self.roughness(self.model))
+        self.rms = rms
+
+    def roughness(self, model):
+        """x^T D^T Q D x [M] float64 of the free layers' Vs of ``model`` [M, 5, L]."""
+        vs = model[:, 1, :].to(self.torch.float64)
+        d = vs.gather(1, self._ib) - vs.gather(1, self._ia)
+        return (self._qw * d * d).sum(dim=1)
+
+    def trial(self, model, delta):
+        """model with Vs + delta on the free layers (clamped into ``vs_bounds``), Vp and rho moved along their slopes by the Vs
+        change that float32 holds."""
+        torch = self.torch
+        vs = model[:, 1, :].to(torch.float64)
+        nv = vs + delta
+        if self.bounds is not None:
+            nv = torch.minimum(torch.maximum(nv, self.bounds[0]), self.bounds[1])
+        nv32 = torch.where(self.free, nv.to(torch.float32), model[:, 1, :])
+        out = model.clone()
+        out[:, 1, :] = nv32
+        dv = nv32.to(torch.float64) - vs
+        if self.has_vp:
+            out[:, 0, :] = (model[:, 0, :].to(torch.float64) + self.vp_slope * dv).to(torch.float32)
+        if self.has_rho:
+            out[:, 2, :] = (model[:, 2, :].to(torch.float64) + self.rho_slope * dv).to(torch.float32)
+        return out
+
+    def run(self, n_iter, keep_models=False):
+        """``n_iter`` iterations from the current state (a second call goes on).  Returns dict(model [M, 5, L] the final models;
+        per iteration, [n_iter, M]: objective and rms (the data rms misfit sqrt(chi2 / N) of ``obsdata``; 88888 for a model
+        whose solve fails) of the state AFTER the iteration, lam after its update, accepted (bool), flag, used, dropped (of the
+        step), predicted (the step's linear prediction of the objective); models [n_iter, M, 5, L] with ``keep_models``)."""
+        torch = self.torch
+        plan = self.plan
+        keys = ("objective", "rms", "lam", "accepted", "flag", "used", "dropped", "predicted")
+        hist = {k: [] for k in keys}
+        models = []
+        inf = torch.full((self.M,), float("inf"), dtype=torch.float64, device=self.device)
+        for _ in range(int(n_iter)):
+            st = plan.step(self.model, self.lam, nlay=self.nlay, free=self.free8, nfree_max=self.nfree_max,
+                           vp_slope=self.vp_slope if self.has_vp else None, rho_slope=self.rho_slope if self.has_rho else None,
+                           alpha=self.alpha, Q=self.Q)
+            flag, used, dropped, predicted = (st[k].clone() for k in ("flag", "used", "dropped", "predicted"))
+            tr = self.trial(self.model, st["delta"])
+            chi, rms, failed = plan.chi_square(tr, self.nlay)
+            obj = torch.where(failed, inf, chi + self.alpha * self.roughness(tr))
+            acc = obj < self.objective
+            self.model = torch.where(acc[:, None, None], tr, self.model)
+            self.objective = torch.where(acc, obj, self.objective)
+            self.rms = torch.where(acc, rms, self.rms)
+            self.lam = torch.where(acc, torch.clamp(self.lam / self.nu, min=self.lam_min), self.lam * self.nu)
+            for k, v in zip(keys, (self.objective, self.rms, self.lam, acc, flag, used, dropped, predicted)):
+                hist[k].append(v)
+            if keep_models:
+                models.append(self.model)
+        out = {k: torch.stack(v) for k, v in hist.items()} if n_iter > 0 else {}
+        out["model"] = self.model
+        if keep_models:
+            out["models"] = torch.stack(models)
+        return out
