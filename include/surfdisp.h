@@ -36,7 +36,7 @@ extern "C" {
                                        additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes,
                                        surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes,
                                        surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events,
-                                       surfdisp_lsq_step_device */
+                                       surfdisp_lsq_step_device, surfdisp_lsq_resolution_device */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -412,6 +412,37 @@ int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, con
                              const double *vp_slope, const double *rho_slope, int slope_per_stack,
                              double alpha, const double *Q, int q_per_stack, const double *lam,
                              double *delta, double *stats, int *info);
+
+/* ---- (6e) posterior covariance and resolution of the problem of (6d) at the same point, added within ABI 4 (csrc/surfdisp_lsq.hip):
+ *          what a linearised inversion is reported with.  Unknowns (unknown j = the j-th free layer in increasing layer index),
+ *          rows, weights, dropped rows, Q, alpha, lam and nfree_max are those of (6d), and the arguments up to and including `lam`
+ *          are the argument list of surfdisp_lsq_step_device: pred decides which rows are used and the sign of a source-5 row,
+ *          obs is read for the finite test only.  Per stack, with n free layers:
+ *              H = G^T W G,   A = H + alpha D^T Q D + lam_s I,   C = A^-1 (posterior covariance of the damped, smoothed problem),
+ *              R = C H (model resolution matrix: row i is the averaging kernel of unknown i),   Cd = C H C = R C (covariance
+ *              of the estimate from the data errors alone),   dof = trace(R).
+ *   out:   cov, res [B][nfree_max][nfree_max] fp64, row-major, in unknown order: C and R, rows and columns >= n zeros; either
+ *          may be NULL and is then not written; cov is exactly symmetric.  sigma_post, sigma_data, rdiag [B][Lmax] fp64 (required):
+ *          sqrt(C_jj), sqrt(Cd_jj) and R_jj at free layer i = layer of unknown j, 0 at layers that are not free.  stats [B][2]
+ *          fp64 = dof and log det A (twice the sum of the logs of the Cholesky pivots: the normalisation of the Gaussian
+ *          approximation exp(-(x - x^)^T A (x - x^) / 2)).  info [B][3] int = rows used, rows dropped, flag, as (6d): 0 solved;
+ *          1 no usable row; 2 a pivot <= 0 or not finite (or an inverse that is not finite); 3 more than nfree_max free layers.
+ *          For a flag other than 0 every output of that stack is zeros, never NaN; the other stacks are not affected.
+ *          In fp64: A is factorised, its factor inverted and C = L^-T L^-1 formed in one packed triangle of LDS (66 KB at
+ *          n = 128; the dynamic-LDS limit is raised as in (6d): first call outside a graph capture); R = I - C (alpha D^T Q D +
+ *          lam I), the same matrix since H = A - alpha D^T Q D - lam I, at O(n^2): its entries carry an absolute error of a few
+ *          ulp of 1.  No workspace.  SURFDISP_ERR_INVALID, before anything is launched: the conditions of (6d), the required
+ *          pointers being model, part, pred, pred_stride, nper, cols, weights, obs, uncer, mask, lam, sigma_post, sigma_data,
+ *          rdiag, stats, info. */
+int surfdisp_lsq_resolution_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                   const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                   const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                   int N, const int *cols, const double *weights,
+                                   const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                   const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                   double alpha, const double *Q, int q_per_stack, const double *lam,
+                                   double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
+                                   double *stats, int *info);
 
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular

@@ -36,7 +36,7 @@ EXPORTS = (
     "surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_forward_batch_device2_events",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
-    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -164,6 +164,10 @@ def lib() -> ctypes.CDLL:
     L.surfdisp_lsq_step_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vpp, vpp, lp, ipp,
                                            ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, vp, ctypes.c_int,
                                            ctypes.c_double, vp, ctypes.c_int, vp, vp, vp, vp]
+    # the same up to lam, then (cov, res, sigma_post, sigma_data, rdiag, stats, info)
+    if hasattr(L, "surfdisp_lsq_resolution_device"):          # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        L.surfdisp_lsq_resolution_device.restype = ctypes.c_int
+        L.surfdisp_lsq_resolution_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + [vp] * 7
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -835,22 +835,20 @@ int surfdisp_mcmc_accept_tree_joint5_device(void *stream, int C, int N, int dept
                              chain0, depth, nsteps);
 }
 
-// One damped least-squares step of the free layers' Vs of every stack (csrc/surfdisp_lsq.hip): the prediction arrays and the
-// column table of the joint accept entries, plus the partial arrays of the kernel entries.
-int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
-                             const unsigned char *free_mask, int free_per_stack, int nfree_max,
-                             const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
-                             int N, const int *cols, const double *weights,
-                             const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
-                             const double *vp_slope, const double *rho_slope, int slope_per_stack,
-                             double alpha, const double *Q, int q_per_stack, const double *lam,
-                             double *delta, double *stats, int *info)
+// The arguments the two least-squares entries share (sections (6d), (6e)): checked and copied into `a`; `outputs`: the entry's
+// required output pointers are all given.  false (and the error text set) for a bad argument.
+static bool lsq_args(const char *name, sd::LsqArgs &a, int B, int Lmax, const int *nlay, const float *model,
+                     const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                     const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                     int N, const int *cols, const double *weights,
+                     const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                     const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                     double alpha, const double *Q, int q_per_stack, const double *lam, bool outputs)
 {
     bool ok = B >= 1 && Lmax >= 1 && Lmax <= SURFDISP_NLAY_MAX && N >= 1 && N <= sd::SD_MCMC_JOINT_MAX_COLS &&
               nfree_max >= 1 && nfree_max <= sd::SD_LSQ_MAX_FREE && nfree_max <= Lmax &&
-              model && part && pred && pred_stride && nper && cols && weights && obs && uncer && mask && lam && delta && stats && info &&
+              model && part && pred && pred_stride && nper && cols && weights && obs && uncer && mask && lam && outputs &&
               alpha >= 0.0 && alpha <= 1.7976931348623157e308;
-    sd::LsqArgs a{};
     for (int w = 0; ok && w < 2; ++w) {
         a.nper[w] = nper[w];
         if (!pred[2 * w] && pred[2 * w + 1]) ok = false;                  // a group array without the phase array of its solve
@@ -872,17 +870,57 @@ int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, con
         if (any && !pred[k]) ok = false;
     }
     if (!ok) {
-        set_err("surfdisp_lsq_step_device: bad argument (B >= 1, 1 <= Lmax <= 200, 1 <= N <= 800, 1 <= nfree_max <= min(128, Lmax), alpha >= 0, "
-                "required pointers, every given prediction array with 1 <= nper <= stride, partials only of sources with predictions)");
-        return SURFDISP_ERR_INVALID;
+        set_err("%s: bad argument (B >= 1, 1 <= Lmax <= 200, 1 <= N <= 800, 1 <= nfree_max <= min(128, Lmax), alpha >= 0, "
+                "required pointers, every given prediction array with 1 <= nper <= stride, partials only of sources with predictions)", name);
+        return false;
     }
     a.B = B; a.Lmax = Lmax; a.N = N; a.nmax = nfree_max;
     a.nlay = nlay; a.model = model; a.free_mask = free_mask; a.free_per_stack = free_per_stack ? 1 : 0;
     a.cols = cols; a.weights = weights; a.obs = obs; a.uncer = uncer; a.mask = mask; a.obs_per_stack = obs_per_stack ? 1 : 0;
     a.vp_slope = vp_slope; a.rho_slope = rho_slope; a.slope_per_stack = slope_per_stack ? 1 : 0;
     a.alpha = alpha; a.Q = Q; a.q_per_stack = q_per_stack ? 1 : 0; a.lam = lam;
+    return true;
+}
+
+// One damped least-squares step of the free layers' Vs of every stack (csrc/surfdisp_lsq.hip): the prediction arrays and the
+// column table of the joint accept entries, plus the partial arrays of the kernel entries.
+int surfdisp_lsq_step_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                             const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                             const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                             int N, const int *cols, const double *weights,
+                             const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                             const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                             double alpha, const double *Q, int q_per_stack, const double *lam,
+                             double *delta, double *stats, int *info)
+{
+    sd::LsqArgs a{};
+    if (!lsq_args("surfdisp_lsq_step_device", a, B, Lmax, nlay, model, free_mask, free_per_stack, nfree_max, part, pred, pred_stride,
+                  nper, N, cols, weights, obs, uncer, mask, obs_per_stack, vp_slope, rho_slope, slope_per_stack, alpha, Q, q_per_stack,
+                  lam, delta && stats && info))
+        return SURFDISP_ERR_INVALID;
     a.delta = delta; a.stats = stats; a.info = info;
     SD_HIP(sd::launch_lsq_step(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
+// Posterior covariance and resolution of the same problem at the same point (section (6e)): the step's arguments up to lam.
+int surfdisp_lsq_resolution_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                   const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                   const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                   int N, const int *cols, const double *weights,
+                                   const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                   const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                   double alpha, const double *Q, int q_per_stack, const double *lam,
+                                   double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
+                                   double *stats, int *info)
+{
+    sd::LsqArgs a{};
+    if (!lsq_args("surfdisp_lsq_resolution_device", a, B, Lmax, nlay, model, free_mask, free_per_stack, nfree_max, part, pred,
+                  pred_stride, nper, N, cols, weights, obs, uncer, mask, obs_per_stack, vp_slope, rho_slope, slope_per_stack, alpha, Q,
+                  q_per_stack, lam, sigma_post && sigma_data && rdiag && stats && info))
+        return SURFDISP_ERR_INVALID;
+    a.cov = cov; a.res = res; a.sigma_post = sigma_post; a.sigma_data = sigma_data; a.rdiag = rdiag; a.stats = stats; a.info = info;
+    SD_HIP(sd::launch_lsq_resolution(static_cast<hipStream_t>(stream), a));
     return SURFDISP_SUCCESS;
 }
 

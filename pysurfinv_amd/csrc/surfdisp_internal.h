@@ -258,9 +258,14 @@ struct LsqArgs {
     double *delta;          // [B][Lmax]
     double *stats;          // [B][3]: data misfit, roughness, predicted objective
     int *info;              // [B][3]: rows used, rows dropped, flag
+    // the resolution kernel only (section (6e)); there stats is [B][2]: dof, log det A, and delta is not used
+    double *cov, *res;      // [B][nmax][nmax] or nullptr
+    double *sigma_post, *sigma_data, *rdiag;   // [B][Lmax]
 };
 size_t lsq_lds_bytes(int nmax);
+size_t lsq_resolution_lds_bytes(int nmax);
 hipError_t launch_lsq_step(hipStream_t s, const LsqArgs &a);
+hipError_t launch_lsq_resolution(hipStream_t s, const LsqArgs &a);
 hipError_t launch_mcmc_propose(hipStream_t s, const McmcProposeArgs &a);
 hipError_t launch_mcmc_accept(hipStream_t s, const McmcAcceptArgs &a);
 hipError_t launch_mcmc_accept_joint(hipStream_t s, const McmcJointArgs &a, bool ellip);   // ellip: the kernel that knows the sources 4 and 5

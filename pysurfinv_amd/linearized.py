@@ -14,7 +14,11 @@ One step, per stack, with x the Vs of the n free layers and x0 the current model
 D is the first difference between consecutive free layers, Q its weights (``consecutive_weights``), lam the damping of the
 stack.  ``lsq_step_reference`` states the step in numpy float64; the kernel is tested against it.
 
-* ``LsqPlan``: the kernels + step of one batch as device tensors.
+What the result is reported with (``surfdisp_lsq_resolution_device``, the same file): with H = G^T W G and A the matrix above, the
+posterior covariance C = A^-1, the resolution matrix R = C H, the layers' standard errors sqrt(C_jj) and their data share
+sqrt((C H C)_jj), dof = trace R and log det A.  ``lsq_resolution_reference`` states them in numpy float64.
+
+* ``LsqPlan``: the kernels + step (``step``) or covariance and resolution (``resolution``) of one batch as device tensors.
 * ``LinearizedBatch``: the iteration - kernels and step at x, ONE forward solve of the trials, accept where the objective
   (chi-square of ``obsdata`` + alpha roughness) fell, lam down on accept, up on reject - without a host synchronisation.
 """
@@ -27,7 +31,7 @@ import numpy as np
 from . import _lib
 from .obsdata import JointData
 
-MAX_FREE = 128          # unknowns per stack the step kernel takes (SD_LSQ_MAX_FREE)
+MAX_FREE = 128          # unknowns per stack the step and resolution kernels take (SD_LSQ_MAX_FREE)
 FAIL = 88888.0          # the misfit of a failed solve (point.py:20-21)
 
 # d(Vp, rho) / dVs of the layer groups of senskernel.GROUP_RULES (sensModel._convert)
@@ -102,6 +106,47 @@ def lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam):
     t = r - G @ delta
     out["delta"] = delta
     out["predicted"] = float((w * t * t).sum()) + float(alpha) * rough(x0 + delta)
+    return out
+
+
+def lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam):
+    """Posterior covariance and resolution of one stack's damped, smoothed problem in numpy float64 - the statement
+    ``surfdisp_lsq_resolution_device`` is tested against.  G [N, n] and w_over_sigma2 [N] as ``lsq_step_reference``; ``x0_or_n``:
+    the unknowns' vector or just their number n (the matrices do not depend on x0); Q [n-1], alpha, lam.  With H = G^T W G and
+    A = H + alpha D^T Q D + lam I (``normal_equations``):
+
+        cov = A^-1,   res = cov H,   sigma_post = sqrt(diag cov),   sigma_data = sqrt(diag(res cov)),   rdiag = diag res,
+        dof = trace res
+
+    Returns dict(cov, res [n, n], sigma_post, sigma_data, rdiag [n], dof, logdet = log det A, flag): flag 1 without rows, 2
+    when the Cholesky factorisation fails or A is not finite - then every array is zeros, dof and logdet 0."""
+    n = int(x0_or_n) if np.ndim(x0_or_n) == 0 else np.size(x0_or_n)
+    G = np.asarray(G, np.float64).reshape(-1, n)
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    z = np.zeros(n)
+    out = dict(cov=np.zeros((n, n)), res=np.zeros((n, n)), sigma_post=z.copy(), sigma_data=z.copy(), rdiag=z.copy(), dof=0.0,
+               logdet=0.0, flag=0)
+    if G.shape[0] == 0:
+        out["flag"] = 1
+        return out
+    A, _ = normal_equations(G, np.zeros(G.shape[0]), w, z, alpha, np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)], lam)
+    H = G.T @ (w[:, None] * G)
+    try:
+        if not np.isfinite(A).all():
+            raise np.linalg.LinAlgError
+        Lc = np.linalg.cholesky(A)
+        T = np.linalg.solve(Lc, np.eye(n))
+        cov = T.T @ T
+        cov = 0.5 * (cov + cov.T)
+        res = cov @ H
+        cd = np.einsum("ij,ji->i", res, cov)
+        if not (np.isfinite(cov).all() and np.isfinite(res).all() and np.isfinite(cd).all()):
+            raise np.linalg.LinAlgError
+    except np.linalg.LinAlgError:
+        out["flag"] = 2
+        return out
+    out.update(cov=cov, res=res, sigma_post=np.sqrt(np.diag(cov)), sigma_data=np.sqrt(np.maximum(cd, 0.0)), rdiag=np.diag(res).copy(),
+               dof=float(np.trace(res)), logdet=float(2.0 * np.log(np.diag(Lc)).sum()))
     return out
 
 
@@ -191,13 +236,9 @@ class LsqPlan:
             pred["c" + w], pred["status" + w] = c, st
         return pred, part
 
-    def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None):
-        """Kernels at ``model`` (float32 [B, 5, L]) and one least-squares step.  Device tensors: ``lam`` float64 [B]; ``nlay``
-        int32 [B]; ``free`` uint8 [L] or [B, L] (None: every layer); ``vp_slope`` / ``rho_slope`` float64 [L] or [B, L] (None:
-        held fixed, the Vp / rho partials are not computed); ``Q`` float64 [L-1] or [B, L-1] (None: 1).  ``nfree_max``: an
-        upper bound of the free layers of any stack (default L; at most 128).  Returns dict(delta [B, L] float64, misfit,
-        roughness, predicted [B] float64, used, dropped, flag [B] int32, pred, part) - views of the plan's buffers, rewritten by
-        the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max."""
+    def _step_args(self, model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q):
+        """The argument checks of ``step`` / ``resolution``, one call of ``kernels``, and the entries' shared argument list (up to
+        and including lam).  Returns (args, pred, part); args keeps its ctypes arrays alive."""
         torch = self.torch
         B, L = self.B, self.L
         nmax = L if nfree_max is None else int(nfree_max)
@@ -229,14 +270,57 @@ class LsqPlan:
         partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
         nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_lsq_step_device(
-                stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, partp, predp, strides, nper,
+        head = (stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, partp, predp, strides, nper,
                 jd.Ptot, _ptr(jd.cols), _ptr(jd.weights), _ptr(self.obs), _ptr(self.uncer), _ptr(self.mask8),
-                1 if self.obs.ndim == 2 else 0, _ptr(vp_slope), _ptr(rho_slope), sl_ps, float(alpha), _ptr(Q), q_ps, _ptr(lam),
-                _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
+                1 if self.obs.ndim == 2 else 0, _ptr(vp_slope), _ptr(rho_slope), sl_ps, float(alpha), _ptr(Q), q_ps, _ptr(lam))
+        return head, pred, part
+
+    def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None):
+        """Kernels at ``model`` (float32 [B, 5, L]) and one least-squares step.  Device tensors: ``lam`` float64 [B]; ``nlay``
+        int32 [B]; ``free`` uint8 [L] or [B, L] (None: every layer); ``vp_slope`` / ``rho_slope`` float64 [L] or [B, L] (None:
+        held fixed, the Vp / rho partials are not computed); ``Q`` float64 [L-1] or [B, L-1] (None: 1).  ``nfree_max``: an
+        upper bound of the free layers of any stack (default L; at most 128).  Returns dict(delta [B, L] float64, misfit,
+        roughness, predicted [B] float64, used, dropped, flag [B] int32, pred, part) - views of the plan's buffers, rewritten by
+        the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max."""
+        head, pred, part = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q)
+        with self.torch.cuda.device(self.device):
+            _lib.check(_lib.lib().surfdisp_lsq_step_device(*head, _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
         return dict(delta=self.delta, misfit=self.stats[:, 0], roughness=self.stats[:, 1], predicted=self.stats[:, 2],
                     used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=pred, part=part)
+
+    def resolution(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None,
+                   want_cov=True, want_res=True):
+        """Kernels at ``model`` and the posterior covariance and resolution of the step's problem there
+        (``surfdisp_lsq_resolution_device``; arguments as ``step``): with H = G^T W G and A = H + alpha D^T Q D + lam I, cov = A^-1,
+        res = cov H.  One ``kernels`` call, one launch, no host synchronisation.  Returns dict(cov, res [B, nmax, nmax] float64 in
+        unknown order (zeros beyond a stack's unknowns; None when not wanted), sigma_post = sqrt(diag cov), sigma_data =
+        sqrt(diag(cov H cov)), rdiag = diag res [B, L] float64 (0 at layers that are not free), dof = trace res, logdet = log det A
+        [B] float64, used, dropped, flag [B] int32 (flags as ``step``; every output of a stack with a flag is zeros), free_index
+        [B, nmax] int64 (layer of unknown j, -1 as padding), nfree [B] int64, pred, part) - the plan's buffers, allocated at
+        the first call and rewritten by the next."""
+        torch = self.torch
+        head, pred, part = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q)
+        B, L, nmax, dev = self.B, self.L, head[7], self.device
+        if getattr(self, "_res", None) is None:
+            z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
+            self._res = dict(sigma_post=z(B, L), sigma_data=z(B, L), rdiag=z(B, L), stats=z(B, 2), info=z(B, 3, dtype=torch.int32))
+        buf = self._res
+        for name, want in (("cov", want_cov), ("res", want_res)):
+            if want and (buf.get(name) is None or buf[name].shape[1] != nmax):
+                buf[name] = torch.zeros(B, nmax, nmax, dtype=torch.float64, device=dev)
+        cov, res = (buf[k] if w else None for k, w in (("cov", want_cov), ("res", want_res)))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().surfdisp_lsq_resolution_device(*head, _ptr(cov), _ptr(res), _ptr(buf["sigma_post"]),
+                                                                _ptr(buf["sigma_data"]), _ptr(buf["rdiag"]), _ptr(buf["stats"]),
+                                                                _ptr(buf["info"])))
+        lay = torch.arange(L, device=dev)
+        fr = torch.ones(B, L, dtype=torch.bool, device=dev) if free is None else (free != 0).expand(B, L)
+        if nlay is not None:
+            fr = fr & (lay[None, :] < nlay[:, None])
+        order = torch.where(fr, lay[None, :], L).sort(dim=1).values[:, :nmax]
+        return dict(cov=cov, res=res, sigma_post=buf["sigma_post"], sigma_data=buf["sigma_data"], rdiag=buf["rdiag"],
+                    dof=buf["stats"][:, 0], logdet=buf["stats"][:, 1], used=buf["info"][:, 0], dropped=buf["info"][:, 1],
+                    flag=buf["info"][:, 2], free_index=torch.where(order < L, order, -1), nfree=fr.sum(dim=1), pred=pred, part=part)
 
     def forward(self, model, nlay=None):
         """ONE forward solve per wave type of ``model`` (``BatchPlan.run``, with the ratio when an "E" set is present; kind
@@ -401,3 +485,23 @@ class LinearizedBatch:
         if keep_models:
             out["models"] = torch.stack(models)
         return out
+
+    def resolution(self, lam=None, want_cov=True, want_res=True):
+        """Posterior covariance and resolution of the linearised problem at the CURRENT model (``LsqPlan.resolution``): the
+        Gaussian approximation of the posterior the iteration ends on.  ``lam``: the damping - None: the batch's current
+        ``lam``; a scalar or [M]; 0.0 leaves the smoothing as the only regularisation (a singular A is flag 2).  Does not advance
+        the iteration: ``model``, ``lam`` and ``objective`` stay as they are.  No host synchronisation."""
+        torch = self.torch
+        if lam is None:
+            lam_t = self.lam
+        else:
+            lam_t = torch.as_tensor(lam, dtype=torch.float64, device=self.device)
+            if lam_t.ndim == 0:
+                lam_t = lam_t.expand(self.M)
+            if tuple(lam_t.shape) != (self.M,):
+                raise ValueError(f"lam: a scalar or ({self.M},) expected, got {tuple(lam_t.shape)}")
+            lam_t = lam_t.contiguous()
+        return self.plan.resolution(self.model, lam_t, nlay=self.nlay, free=self.free8, nfree_max=self.nfree_max,
+                                    vp_slope=self.vp_slope if self.has_vp else None,
+                                    rho_slope=self.rho_slope if self.has_rho else None, alpha=self.alpha, Q=self.Q,
+                                    want_cov=want_cov, want_res=want_res)

@@ -1,0 +1,263 @@
+"""surfdisp_lsq_resolution_device (posterior covariance and resolution of the damped least-squares problem) and the Python
+methods built on it, on the GPU, against pysurfinv_amd.linearized.lsq_resolution_reference on the random inputs of
+tests/test_lsq_gpu.py.
+
+Bars.  The backward-error bar of tests/test_lsq_gpu.py carried to a matrix right-hand side, with A and H formed in numpy
+float64 from the same fp32 inputs:  max|A cov - I| <= 1e-11 (||A||inf max|cov| + 1),  max|A res - H| <= 1e-11 (||A||inf max|res|
++ max|H|).  A float64 numpy statement of the kernel's route (Cholesky, L^-1, L^-T L^-1, I - C (alpha S + lam I)) leaves at
+most 2e-5 of the first bar and 2e-4 of the second on these cases; a float32 factorisation leaves 1e-7 to 7e-5 for the first
+residual, above its bar.  Diagonals (rdiag, sigma_post^2, sigma_data^2) against the reference: relative 1e-9 plus 1e-12 of the
+largest; dof to 1e-9 n; log det A to 1e-10 (|log det A| + n).  The conditioning of A on these cases is below 1e4, so cond(A) eps
+~ 1e-12 stands three digits below the relative bar.  Counts, flags, zeros and the symmetry of cov are exact."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from pysurfinv_amd import _lib, linearized, synth
+from test_lsq_gpu import (ALPHA, CASES, LAM0, LAM_MIN, NU, SETS3, _case, _datasets, _forward_all, _rows_of,
+                          _true_and_start)
+
+pytestmark = pytest.mark.gpu
+
+NAMES = ("cov", "res", "sigma_post", "sigma_data", "rdiag", "stats", "info")
+
+
+def _launch(c, nfree_max=None, lam_scale=1.0, no_cov=False, no_res=False, **null):
+    """surfdisp_lsq_resolution_device on the arrays of ``c``; ``null``: inputs passed as NULL; ``no_cov`` / ``no_res``: that
+    output passed as NULL.  Every output buffer is pre-filled with 7.  Returns (rc, dict of numpy outputs)."""
+    import torch
+    dev = torch.device("cuda:0")
+    t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    B, Lmax, N = c["B"], c["Lmax"], c["N"]
+    nmax = Lmax if nfree_max is None else nfree_max
+    keep = {k: t(None if null.get(k) else c[k]) for k in ("nlay", "model", "free", "cols", "weights", "obs", "uncer", "mask",
+                                                          "vp_slope", "rho_slope", "Q")}
+    keep["lam"] = None if null.get("lam") else t(c["lam"] * lam_scale)
+    part, pred = [t(a) for a in c["part"]], [t(a) for a in c["pred"]]
+    f7 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float64, device=dev)
+    nm = min(nmax, 128)                                                     # (a refused launch writes nothing)
+    out = dict(cov=f7(B, nm, nm), res=f7(B, nm, nm), sigma_post=f7(B, Lmax), sigma_data=f7(B, Lmax), rdiag=f7(B, Lmax),
+               stats=f7(B, 2), info=torch.full((B, 3), 7, dtype=torch.int32, device=dev))
+    p = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)
+    po = lambda k: p(None if null.get(k) or (k == "cov" and no_cov) or (k == "res" and no_res) else out[k])
+    partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
+    predp = (ctypes.c_void_p * 5)(*[a.data_ptr() for a in pred])
+    strides = (ctypes.c_long * 5)(*[c["P"]] * 5)
+    nper = (ctypes.c_int * 2)(c["P"], c["P"])
+    rc = _lib.lib().surfdisp_lsq_resolution_device(
+        None, B, Lmax, p(keep["nlay"]), p(keep["model"]), p(keep["free"]), int(c["free"].ndim == 2), nmax, partp, predp, strides,
+        nper, N, p(keep["cols"]), p(keep["weights"]), p(keep["obs"]), p(keep["uncer"]), p(keep["mask"]), int(c["obs"].ndim == 2),
+        p(keep["vp_slope"]), p(keep["rho_slope"]), 1, float(c["alpha"]), p(keep["Q"]), int(c["Q"].ndim == 2), p(keep["lam"]),
+        *[po(k) for k in NAMES])
+    torch.cuda.synchronize()
+    return rc, {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _check_stack(tag, idx, Qw, G, w, alpha, lam, o, b, N):
+    """The outputs ``o`` of stack b against the reference: counts, flag, zeros, the two residuals, the diagonals."""
+    n = idx.size
+    ref = linearized.lsq_resolution_reference(G, w, n, alpha, Qw, lam)
+    used, dropped, flag = (int(v) for v in o["info"][b])
+    assert (used, dropped) == (len(w), N - len(w)), (tag, used, dropped, len(w))
+    assert flag == ref["flag"], (tag, flag, ref["flag"])
+    cov, res = o["cov"][b], o["res"][b]
+    per_layer = [o[k][b] for k in ("sigma_post", "sigma_data", "rdiag")]
+    for a in (cov, res, o["stats"][b], *per_layer):
+        assert np.isfinite(a).all(), tag
+    off = np.ones(per_layer[0].size, bool); off[idx] = False
+    for a in per_layer:
+        assert not a[off].any(), tag
+    for a in (cov, res):                                                    # rows and columns >= n
+        assert not a[n:, :].any() and not a[:, n:].any(), tag
+    if flag != 0:
+        assert not cov.any() and not res.any() and not o["stats"][b].any() and not any(a.any() for a in per_layer), tag
+        return flag
+    cov, res = cov[:n, :n], res[:n, :n]
+    assert np.array_equal(cov, cov.T), tag
+    A, _ = linearized.normal_equations(G, np.zeros(len(w)), w, np.zeros(n), alpha, Qw, lam)
+    H = G.T @ (w[:, None] * G)
+    na = np.abs(A).sum(axis=1).max()
+    e1, bar1 = np.abs(A @ cov - np.eye(n)).max(), 1e-11 * (na * np.abs(cov).max() + 1)
+    e2, bar2 = np.abs(A @ res - H).max(), 1e-11 * (na * np.abs(res).max() + np.abs(H).max())
+    print(f"{tag}: n {n} rows {used} |A cov - I| {e1:.2e} (bar {bar1:.2e})  |A res - H| {e2:.2e} (bar {bar2:.2e})  "
+          f"rdiag {o['rdiag'][b][idx].min():.3f}..{o['rdiag'][b][idx].max():.3f}")
+    assert e1 <= bar1, (tag, e1, bar1)
+    assert e2 <= bar2, (tag, e2, bar2)
+    for name, got, want in (("rdiag", o["rdiag"][b][idx], ref["rdiag"]),
+                            ("sigma_post^2", o["sigma_post"][b][idx] ** 2, np.diag(ref["cov"])),
+                            ("sigma_data^2", o["sigma_data"][b][idx] ** 2, np.diag(ref["res"] @ ref["cov"]))):
+        err, bar = np.abs(got - want), 1e-9 * np.abs(want) + 1e-12 * np.abs(want).max()
+        print(f"    {name}: worst error / bar {(err / bar).max():.2e}")
+        assert (err <= bar).all(), (tag, name, (err / bar).max())
+    dof, logdet = o["stats"][b]
+    assert abs(dof - ref["dof"]) <= 1e-9 * n, (tag, dof, ref["dof"])
+    assert abs(logdet - ref["logdet"]) <= 1e-10 * (abs(ref["logdet"]) + n), (tag, logdet, ref["logdet"])
+    return flag
+
+
+def _check_launch(c, o, lam, tag):
+    flags, rd = [], []
+    for b in range(c["B"]):
+        idx, Qw, G, _, w = _rows_of(c, b)
+        flags.append(_check_stack(f"{tag} stack {b}", idx, Qw, G, w, c["alpha"], lam[b], o, b, c["N"]))
+        rd.append(o["rdiag"][b][idx])
+    return flags, np.concatenate(rd)
+
+
+def _all_free(c):
+    """The case with every layer of every stack free (n = Lmax: the LDS limit at 128)."""
+    c["free"] = np.ones_like(c["free"])
+    c["nlay"][:] = c["Lmax"]
+    return c
+
+
+@pytest.mark.parametrize("lam_scale", [1.0, 1000.0])
+@pytest.mark.parametrize("B,Lmax,N,every", [s + (False,) for s in CASES] + [(1, 128, 256, True)])
+def test_resolution_kernel_matches_the_reference(B, Lmax, N, every, lam_scale):
+    c = _case(B, Lmax, N, seed=1000 + Lmax)
+    if every:
+        c = _all_free(c)
+    rc, o = _launch(c, lam_scale=lam_scale)
+    assert rc == _lib.SUCCESS, _lib.lib().surfdisp_last_error()
+    flags, rd = _check_launch(c, o, c["lam"] * lam_scale, f"({B},{Lmax},{N}) lam x {lam_scale:g}")
+    if every:
+        assert _rows_of(c, 0)[0].size == 128
+    if c["obs"].ndim == 2 and B >= 3:
+        assert flags[2] == 1 and flags[1] == 0 and flags[3 % B] == 0          # every row masked: flag 1, its neighbours solved
+    assert o["info"][:, 1].sum() > 0 or N == 1                             # rows were dropped somewhere
+    print(f"rdiag median {np.median(rd):.3f}")
+
+
+def _pivot_case():
+    """The construction of test_failed_pivot_is_flag_2_and_leaves_the_neighbours_alone (tests/test_lsq_gpu.py): N < n, alpha = 0,
+    lam = 0 in the middle stack, layers the data do not see."""
+    c = _case(3, 8, 3, seed=77)
+    c["alpha"] = 0.0
+    c["lam"] = np.array([4.0, 0.0, 4.0])
+    c["free"] = np.ones(8, np.uint8)
+    c["nlay"][:] = 8
+    c["obs"], c["uncer"], c["mask"] = np.array([3.0, 3.1, 3.2]), np.array([0.03, 0.03, 0.03]), np.ones(3, np.uint8)
+    for a in c["part"]:
+        if a is not None:
+            a[:, :, 5:] = 0.0
+    return c
+
+
+def test_failed_pivot_is_flag_2_all_zeros_and_leaves_the_neighbours_alone():
+    c = _pivot_case()
+    rc, o = _launch(c)
+    assert rc == _lib.SUCCESS
+    assert o["info"][:, 2].tolist() == [0, 2, 0]
+    for k in NAMES[:-1]:
+        assert not o[k][1].any(), k
+        assert np.isfinite(o[k]).all(), k
+    flags, _ = _check_launch(c, o, c["lam"], "beside a failed pivot")
+    assert flags == [0, 2, 0]
+
+
+def test_null_cov_or_res_leaves_the_other_outputs_bit_identical():
+    c = _case(3, 17, 40, seed=1017)
+    rc, full = _launch(c)
+    assert rc == _lib.SUCCESS
+    for kw, absent in ((dict(no_cov=True), "cov"), (dict(no_res=True), "res")):
+        rc, o = _launch(c, **kw)
+        assert rc == _lib.SUCCESS
+        assert (o[absent] == 7.0).all()
+        for k in NAMES:
+            if k != absent:
+                assert np.array_equal(o[k], full[k]), (absent, k)
+
+
+def test_resolution_entry_refuses_bad_arguments_before_launching():
+    c = _case(1, 200, 6, seed=5)
+    untouched = lambda o: all((o[k] == 7).all() for k in NAMES)
+    rc, o = _launch(c, nfree_max=129)
+    assert rc == _lib.ERR_INVALID and untouched(o)
+    for name in ("lam", "model", "obs", "mask", "cols", "sigma_post", "sigma_data", "rdiag", "stats", "info"):
+        rc, o = _launch(c, nfree_max=128, **{name: True})
+        assert rc == _lib.ERR_INVALID and untouched(o), name
+    c["alpha"] = -1.0
+    rc, o = _launch(c, nfree_max=128)
+    assert rc == _lib.ERR_INVALID and untouched(o)
+    c["alpha"] = 0.8
+    rc, o = _launch(c, nfree_max=128)                                        # 200 free layers against nfree_max 128: not solved
+    assert rc == _lib.SUCCESS and o["info"][0].tolist() == [0, 6, 3]
+    assert not any(o[k].any() for k in NAMES[:-1])
+
+
+def test_resolution_on_real_kernels():
+    """LsqPlan.resolution on the synth_L8 stacks of test_step_on_real_kernels (Rayleigh c + U + H/V, Love c) against the reference
+    formed on the host from the ``part`` and ``pred`` tensors the same call returns; the same bars."""
+    import torch
+    model = synth.synth_models(4, 8, seed=21)
+    B, _, L = model.shape
+    per = synth.default_periods(8)
+    sets = (("R", "c"), ("R", "U"), ("L", "c"), ("R", "E"))
+    truth = model.copy(); truth[:, 1, :] *= 1.03
+    data = _datasets(per, _forward_all(truth, per), sets, 0.01, C=B)
+    dm = torch.from_numpy(model).cuda()
+    free = (model[:, 1, :] > 0)
+    free[:, 3] = False                                                      # a gap in the free mask
+    ps, qs = np.where(model[0, 1] > 0, 1.7, 0.0), np.where(model[0, 1] > 0, 0.3, 0.0)
+    lam = np.array([3.0, 3.0, 300.0, 3.0])
+    plan = linearized.LsqPlan(B, L, data)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()
+    out = plan.resolution(dm, t(lam), free=t(free.astype(np.uint8)), nfree_max=7, vp_slope=t(ps), rho_slope=t(qs), alpha=0.5)
+    assert set(out) >= {"cov", "res", "sigma_post", "sigma_data", "rdiag", "dof", "logdet", "used", "dropped", "flag",
+                        "free_index", "nfree"}
+    f64 = lambda x: None if x is None else x.cpu().numpy()
+    pred, part = out["pred"], out["part"]
+    c = dict(B=B, Lmax=L, nlay=np.full(B, L), free=free.astype(np.uint8), Q=np.ones(L - 1), vp_slope=np.tile(ps, (B, 1)),
+             rho_slope=np.tile(qs, (B, 1)), cols=np.stack([plan.joint.col_src, plan.joint.col_idx], axis=1),
+             weights=plan.joint.col_w, obs=plan.obs.cpu().numpy(), uncer=plan.uncer.cpu().numpy(), mask=plan.mask.cpu().numpy(),
+             part=[f64(a) for a in part], pred=[f64(pred[k]) for k in ("cR", "uR", "cL", "uL", "eR")], alpha=0.5, N=plan.joint.Ptot)
+    o = {k: f64(out[k]) for k in ("cov", "res", "sigma_post", "sigma_data", "rdiag")}
+    o["stats"] = np.stack([f64(out["dof"]), f64(out["logdet"])], axis=1)
+    o["info"] = np.stack([f64(out[k]) for k in ("used", "dropped", "flag")], axis=1)
+    assert o["cov"].shape == (B, 7, 7) and o["res"].shape == (B, 7, 7)
+    flags, _ = _check_launch(c, o, lam, "synth_L8")
+    assert flags == [0] * B and (o["info"][:, 0] == plan.joint.Ptot).all()
+    fi, nf = f64(out["free_index"]), f64(out["nfree"])
+    assert fi.dtype == np.int64 and fi.shape == (B, 7)
+    for b in range(B):
+        idx = np.nonzero(free[b])[0]
+        assert nf[b] == idx.size and fi[b, :idx.size].tolist() == idx.tolist() and (fi[b, idx.size:] == -1).all()
+    # without the matrices: the same per-layer outputs, bit for bit
+    again = plan.resolution(dm, t(lam), free=t(free.astype(np.uint8)), nfree_max=7, vp_slope=t(ps), rho_slope=t(qs), alpha=0.5,
+                            want_cov=False, want_res=False)
+    assert again["cov"] is None and again["res"] is None
+    for k in ("sigma_post", "sigma_data", "rdiag"):
+        assert np.array_equal(f64(again[k]), o[k]), k
+
+
+def test_batch_resolution_does_not_touch_the_iteration():
+    """LinearizedBatch.resolution() after 3 iterations of the recovery problem of tests/test_lsq_gpu.py: model, lam and objective
+    bit-identical, and the next iteration the same as without the call."""
+    import torch
+    true, start = _true_and_start()
+    per = synth.default_periods(12)
+    data = _datasets(per, _forward_all(true, per), SETS3, 0.005)
+    make = lambda: linearized.LinearizedBatch(start, data, alpha=ALPHA, lam0=LAM0, nu=NU, lam_min=LAM_MIN)
+    inv, twin = make(), make()
+    inv.run(3); twin.run(3)
+    before = [x.clone() for x in (inv.model, inv.lam, inv.objective)]
+    out = inv.resolution()
+    for x, y in zip(before, (inv.model, inv.lam, inv.objective)):
+        assert torch.equal(x, y)
+    assert (out["flag"] == 0).all() and (out["nfree"] == 8).all() and tuple(out["cov"].shape) == (16, 8, 8)
+    rd, dof = out["rdiag"].cpu().numpy(), out["dof"].cpu().numpy()
+    assert ((dof > 0) & (dof < 8)).all() and np.allclose(rd.sum(axis=1), dof, rtol=1e-12)
+    sp, sd = out["sigma_post"].cpu().numpy(), out["sigma_data"].cpu().numpy()
+    assert (sd <= sp).all() and (sp > 0).all()
+    # smoothing alone, a scalar, and one value per stack
+    out0 = inv.resolution(lam=0.0, want_cov=False)
+    assert out0["cov"] is None and (out0["flag"] == 0).all() and (out0["dof"] > torch.as_tensor(dof).cuda()).all()
+    lam = inv.lam.clone()
+    outv = inv.resolution(lam=lam.cpu().numpy())
+    assert torch.equal(outv["rdiag"].cpu(), torch.as_tensor(rd))
+    with pytest.raises(ValueError, match="lam"):
+        inv.resolution(lam=np.ones(3))
+    a, b = inv.run(1), twin.run(1)
+    for k in ("model", "objective", "lam", "accepted", "rms", "predicted"):
+        assert torch.equal(a[k], b[k]), k
