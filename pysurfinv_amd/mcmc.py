@@ -178,7 +178,8 @@ class MetropolisBatch:
     """
 
     AUTO_INDEP_CHAINS = 3072        # 64-lane teams of fewer chains leave the chip's 196 608 lanes partly empty
-    PLAN_CACHE = 8                  # plans kept: the speculative lock step alternates between two stack counts, two wave types each
+    COUNTER_LIMIT = 1 << 40         # Philox call counters stay below: from 2^40 on the counter's high word reaches the bits of the stream tags
+    PLAN_CACHE = 8             # plans kept: the speculative lock step alternates between two stack counts, two wave types each
 
     def __init__(self, spec: ParamSpec, to_model, periods=None, c_obs=None, uncer=None, device="cuda:0",
                  isgood=None, proposer=None, seed=None, forward=None, independent=False, fast_scan=False,
@@ -458,11 +459,13 @@ class MetropolisBatch:
     def _fused_call(self, C, row, row_offset, counter):
         """What one launch sequence of the fused path starts from: the buffers, the current stream, this step's Philox
         counter (default: one more than the last call's) and the address of chain 0's mcTrack row."""
-        st = self._fused_buffers(C)
-        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
         if counter is None:
             self._counter += 1
             counter = self._counter
+        if not 0 <= counter < self.COUNTER_LIMIT:
+            raise OverflowError(f"Philox call counter {counter}: the kernels' streams are distinct below 2^40 lock steps only")
+        st = self._fused_buffers(C)
+        stream = ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
         rowp = ctypes.c_void_p(row.data_ptr() + 8 * int(row_offset) if row is not None else 0)
         return st, stream, counter, rowp
 

@@ -260,7 +260,9 @@ def test_fused_device_kernels_proposal_and_accept():
     """csrc/surfdisp_mcmc.hip against the torch formulas: (1) proposals stay inside the bounds with the requested step
     (plain Gaussian where the bounds are far), uniform resets cover the prior box; (2) misfit, likelihood and the
     mcTrack row of the accept kernel equal MetropolisBatch.misfit of the same proposals, the state moves exactly where
-    the row says 'accepted', better models are always accepted, failed solves never."""
+    the row says 'accepted', better models are always accepted, failed solves never.
+    (The exact comparison - every proposal and every accept decision against a host replay of the Philox streams - is
+    tests/test_mcmc_replay.py.)"""
     import ctypes
     from pysurfinv_amd import _lib
     dev = torch.device("cuda:0")
