@@ -36,7 +36,8 @@ extern "C" {
                                        additive, same version: surfdisp_forward_group_kernels_device, surfdisp_group_kernels_workspace_bytes,
                                        surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes,
                                        surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events,
-                                       surfdisp_lsq_step_device, surfdisp_lsq_resolution_device */
+                                       surfdisp_lsq_step_device, surfdisp_lsq_resolution_device,
+                                       surfdisp_forward_atten_device, surfdisp_atten_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -257,6 +258,35 @@ int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const i
                                           float *dcdb, float *dcda, float *dcdr,
                                           float *dedb, float *deda, float *dedr, int *n_nonfinite,
                                           void *workspace, size_t workspace_bytes);
+
+/* ---- (5e) ... and the apparent ATTENUATION of the mode, added within ABI 4.  After every REIGEN / LEIGEN call the reference
+ *          forms the attenuation coefficient and the apparent quality factor of the mode from its phase-velocity partials and
+ *          the layers' 1/Qs (calcul.f:256-265 Love, 341-349 Rayleigh: alphL / alphR, qL_app / qR_app) - in a loop whose bound
+ *          `mmm` is never assigned, into locals that nothing returns; the fp64 toolkit writes them (TEST1/test.R.att, test.L.att).
+ *          With b_i, a_i the attenuation-corrected, earth-flattened velocities of input layer i at the period and dc/db_i, dc/da_i
+ *          the partials with respect to them (what SURFDISP_KERN_REFCOORD returns):
+ *              W_i = b_i (dc/db_i + 4/3 (b_i / a_i) dc/da_i)     (dwx, surfa.f:1207; Love: W_i = b_i dc/db_i, calcul.f:261),
+ *              S = sum_i qsinv_i W_i   over the solid layers down to and including the unit's effective half space,
+ *              gamma = pi S / (T c^2)  in 1/km,      qinv = S U / c^2 = gamma U T / pi = 1 / Q_apparent,
+ *              dqdq_i = W_i U / c^2:   qinv = sum_i dqdq_i qsinv_i.
+ *          1/Q and not Q, so that a stack without attenuation gives 0 and not infinity.  dqdq is the linear kernel of qinv with
+ *          respect to layer i's 1/Qs at FIXED eigenfunction - not the total derivative: 1/Qs also shifts the layer velocities
+ *          through the dispersion correction (calcul.f:122-126), hence c, U and the partials; at T = 1 s that correction vanishes
+ *          and qinv is exactly linear in the 1/Qs row.  The library evaluates W_i from the caller-coordinate rows of (5b) (the
+ *          flattening factor cancels), in fp64; pysurfinv_amd.senskernel.attenuation_from_kernels is the same statement on the host.
+ *          After the launches of (5b) - c, u, status, dcdb, dcda, dcdr bit-identical to surfdisp_forward_kernels_device on the same
+ *          inputs - one more kernel reads the layer-major scratch again: qinv, gamma [B][P]; dqdq [B][P][Lmax].  Zeros for unsolved
+ *          periods and bad stacks; in dqdq also for water layers and layers below the effective half space.  Rayleigh and Love.
+ *          gamma, dqdq, dcda, dcdr may be NULL.  SURFDISP_INDEPENDENT and the other flags as in (5b).  SURFDISP_ERR_INVALID, before
+ *          anything is launched: SURFDISP_PHASE_ONLY, SURFDISP_KERN_REFCOORD, NULL qinv / dcdb, and a workspace smaller than
+ *          surfdisp_atten_workspace_bytes (that of (5b) with its scratch: there is no direct route). */
+size_t surfdisp_atten_workspace_bytes(int B, int Lmax, int P);
+int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay,
+                                  const float *model, int P, const float *per, int kind,
+                                  float *c, float *u, int *status,
+                                  float *dcdb, float *dcda, float *dcdr,
+                                  float *qinv, float *gamma, float *dqdq,
+                                  void *workspace, size_t workspace_bytes);
 
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:
  *          Model1D.seisPropLayers, models.py:72-102 + layers.py:139-284) for models with a static

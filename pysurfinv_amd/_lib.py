@@ -36,7 +36,8 @@ EXPORTS = (
     "surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_forward_batch_device2_events",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
-    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes",
+    "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -123,6 +124,11 @@ def lib() -> ctypes.CDLL:
     L.surfdisp_forward_ellip_kernels_device.restype = ctypes.c_int
     L.surfdisp_forward_ellip_kernels_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
                                                         vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    L.surfdisp_atten_workspace_bytes.restype = ctypes.c_size_t
+    L.surfdisp_atten_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.surfdisp_forward_atten_device.restype = ctypes.c_int
+    L.surfdisp_forward_atten_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
     L.surfdisp_group_kernels_shift_offset.restype = ctypes.c_size_t     # test read-out (not in include/surfdisp.h)
     L.surfdisp_group_kernels_shift_offset.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.surfdisp_thermal_scratch_bytes.restype = ctypes.c_size_t

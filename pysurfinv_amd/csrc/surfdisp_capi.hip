@@ -379,7 +379,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
                                float *c, float *u, int *status,
                                void *workspace, size_t workspace_bytes, hipEvent_t *ev,
                                float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr,
-                               bool force_hist = false)
+                               bool force_hist = false, bool scr_vp = false)
 {
     int rc = check_args(B, Lmax, P, kind, model, per, c, u);
     if (rc) return rc;
@@ -476,8 +476,10 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
         kscale = reinterpret_cast<float *>(q);  q += align_up((size_t)P * B * sizeof(float));
         khs = reinterpret_cast<int *>(q);
     }
-    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, ka, kr, kscr, kscale, khs,
-                     kern_raw ? 1 : 0, 0, 0, kn.group_order};
+    // (on the scratch route kb / ka / kr only say which planes the kernel stores: scr_vp asks for the dc/dVp plane - the
+    // attenuation kernel reads it - also when the caller wants no dc/dVp rows)
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka, kr,
+                     kscr, kscale, khs, kern_raw ? 1 : 0, 0, 0, kn.group_order};
     if (!phase_only) SD_HIP(sd::launch_group(s, kind, ga));
     if (!phase_only && kscr) {
         // one launch for the three arrays: factor 1 / (dL/dk), zeros below each unit's half space, whole rows
@@ -620,6 +622,43 @@ int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const i
                          n_nonfinite};
     sd::EllipTransposeArgs ta{B, P, Lmax, e.xscr, e.fscr, e.gam, e.khs, dedb, deda, dedr};
     SD_HIP(sd::launch_ellip_kern(s, ea, ta));
+    return SURFDISP_SUCCESS;
+}
+
+// The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit), then the apparent attenuation of the
+// mode from the layer-major scratch those launches leave (K2c in surfdisp_kernels.hip).  Workspace: the kernels entry's.
+size_t surfdisp_atten_workspace_bytes(int B, int Lmax, int P) { return surfdisp_kernels_workspace_bytes(B, Lmax, P); }
+
+int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay,
+                                  const float *model, int P, const float *per, int kind,
+                                  float *c, float *u, int *status,
+                                  float *dcdb, float *dcda, float *dcdr,
+                                  float *qinv, float *gamma, float *dqdq,
+                                  void *workspace, size_t workspace_bytes)
+{
+    if (!qinv || !dcdb) { set_err("surfdisp_forward_atten_device: qinv or dcdb is NULL"); return SURFDISP_ERR_INVALID; }
+    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
+        set_err("surfdisp_forward_atten_device: no PHASE_ONLY, no KERN_REFCOORD");
+        return SURFDISP_ERR_INVALID;
+    }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < surfdisp_atten_workspace_bytes(B, Lmax, P)) {
+        set_err("workspace too small (surfdisp_atten_workspace_bytes)");
+        return SURFDISP_ERR_INVALID;
+    }
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, nullptr, false, true);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int wave = kind & ~SD_KIND_FLAGS;
+    const Carve w = carve(workspace, B, Lmax, P);
+    char *q = static_cast<char *>(workspace) + align_up(w.total);               // forward_device_impl's scratch, factors, layers
+    const float *kscr = reinterpret_cast<const float *>(q);    q += align_up((size_t)3 * Lmax * P * B * sizeof(float));
+    const float *kscale = reinterpret_cast<const float *>(q);  q += align_up((size_t)P * B * sizeof(float));
+    const int *khs = reinterpret_cast<const int *>(q);
+    sd::AttenArgs aa{B, P, Lmax, wave, w.mdl, per, kscr, kscale, khs, w.ct, w.ut, qinv, gamma, dqdq};
+    SD_HIP(sd::launch_atten(s, aa));
     return SURFDISP_SUCCESS;
 }
 

@@ -92,6 +92,19 @@ struct KernTransposeArgs {
     const int *khs;       // [P][B]
     float *kb, *ka, *kr;  // the caller's [B][P][Lmax] rows (ka, kr may be nullptr)
 };
+// apparent attenuation of the mode (surfdisp_forward_atten_device) from the same scratch, see K2c
+struct AttenArgs {
+    int B, P, Lmax, kind;
+    const float *mdl;     // SoA staged fields (Vs, Vp, 1/Qs of every layer)
+    const float *per;     // [P]
+    const float *kscr;    // [3][Lmax][P][B] unscaled shares; planes 0 (dc/dVs) and, Rayleigh, 1 (dc/dVp) are read
+    const float *kscale;  // [P][B]
+    const int *khs;       // [P][B]
+    const float *c, *u;   // [P][B] period-major
+    float *qinv, *gamma;  // the caller's [B][P] arrays: 1 / Q_apparent, attenuation coefficient (1/km; may be nullptr)
+    float *dqdq;          // nullptr, or the caller's [B][P][Lmax] rows: d (1 / Q_apparent) / d (1/Qs of layer i)
+};
+hipError_t launch_atten(hipStream_t s, const AttenArgs &a);
 
 // group-velocity kernels (surfdisp_forward_group_kernels_device): the fundamental-mode roots at the shifted periods
 // T (1 -+ dfrac) of every solved (stack, period) unit, found from the first-order prediction without a scan

@@ -3078,6 +3078,91 @@ __global__ __launch_bounds__(256) void surfdisp_kern_transpose_kernel(KernTransp
     }
 }
 
+// K2c: the apparent attenuation of the mode from the same scratch (surfdisp_forward_atten_device).  After REIGEN / LEIGEN the
+// reference forms, from its partials and the layers' 1/Qs (calcul.f:256-265, 341-349; dwx: surfa.f:1207),
+//      W_i = b_i (dc/db_i + 4/3 (b_i / a_i) dc/da_i)   (Love: b_i dc/db_i),        S = sum_i qsinv_i W_i,
+//      alpha = pi S / (T c^2),     1 / Q_app = S U / c^2,
+// in a loop whose bound is never assigned, into locals nothing returns.  Here W_i comes from the caller-coordinate shares
+// kb = dc/dVs, ka = dc/dVp the scratch holds - scaled with the unit's factor in fp32 exactly as K2b scales them, so the
+// result is a function of the rows the caller receives - by undoing the chain factors of chain_of (the flattening factor
+// cancels; qsq = qsinv ln(1/T) / pi, qpq = qsq 4/3 Vs^2 / Vp^2):
+//      W_i = Vs kb - Vs ka (8/3) qsq (Vs/Vp) / (1 - qpq) + (4/3) ka Vs^2 (1 + qsq)^2 / (Vp (1 + qpq) (1 - qpq)),
+// in fp64 (the three terms may cancel; the kernel is bound by its reads).  dqdq_i = W_i U / c^2 is the linear kernel of
+// 1 / Q_app with respect to layer i's 1/Qs at fixed eigenfunction; 1 / Q_app = sum_i dqdq_i qsinv_i.
+// One workgroup = 64 consecutive stacks at one period (a wavefront reads consecutive words of every layer plane) x 4
+// wavefronts that take every fourth layer; per 64-layer tile the dqdq values go through LDS to whole rows as in K2b, the
+// four partial sums (fp64, fixed order) meet in LDS at the end.  Zeros: units without a factor (unsolved periods, bad
+// stacks), water layers, layers below the unit's half space.
+template <int KIND>
+__global__ __launch_bounds__(256) void surfdisp_atten_kernel(AttenArgs A)
+{
+    __shared__ float tile[64][65];
+    __shared__ double part[4][64];
+    const int B = A.B, P = A.P, Lmax = A.Lmax;
+    const int nbb = (B + 63) / 64;
+    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64;
+    const size_t PB = (size_t)P * B, fs = (size_t)Lmax * B;
+    const int bl = threadIdx.x % 64, wv = threadIdx.x / 64;
+    const int b = b0 + bl;
+    const float *__restrict__ scr_b = A.kscr;
+    const float *__restrict__ scr_a = A.kscr + (size_t)Lmax * PB;
+    const float *__restrict__ mdl = A.mdl;
+    float sc = 0.0f; int hs = -1;
+    double uc2 = 0.0, ut = 0.0, lnT = 0.0;
+    if (b < B) {
+        const size_t o = (size_t)k * B + b;
+        const float c = A.c[o], u = A.u[o], T = A.per[k];
+        sc = A.kscale[o];
+        if (sc != 0.0f && c > 0.0f && u > 0.0f) {
+            hs = A.khs[o];
+            uc2 = (double)u / ((double)c * (double)c);
+            ut = (double)u * (double)T;
+            lnT = log(1.0 / (double)T);
+        }
+    }
+    double sum = 0.0;
+    for (int i0 = 0; i0 < Lmax; i0 += 64) {
+        for (int il = wv; il < 64; il += 4) {
+            const int i = i0 + il;
+            double dq = 0.0;
+            if (i <= hs) {
+                const size_t ol = (size_t)i * B + b;
+                const double vs = (double)mdl[F_VS * fs + ol];
+                if (vs > 0.0) {                                          // (a water layer has no share)
+                    const double qs = (double)mdl[F_QS * fs + ol];
+                    double w = vs * (double)(scr_b[(size_t)i * PB + (size_t)k * B + b] * sc);
+                    if (KIND == 2) {
+                        const double vp = (double)mdl[F_VP * fs + ol];
+                        const double ka = (double)(scr_a[(size_t)i * PB + (size_t)k * B + b] * sc);
+                        const double qsq = qs * lnT / 3.14159265358979323846;
+                        const double qpq = qsq * (4.0 / 3.0) * vs * vs / (vp * vp);
+                        w = w - vs * ka * (8.0 / 3.0) * qsq * (vs / vp) / (1.0 - qpq)
+                              + (4.0 / 3.0) * ka * vs * vs * (1.0 + qsq) * (1.0 + qsq) / (vp * (1.0 + qpq) * (1.0 - qpq));
+                    }
+                    dq = w * uc2;
+                    sum += dq * qs;
+                }
+            }
+            if (A.dqdq) tile[il][bl] = (float)dq;
+        }
+        if (A.dqdq) {                                                    // (block-uniform)
+            __syncthreads();
+            for (int t = threadIdx.x; t < 64 * 64; t += 256) {
+                const int bq = t / 64, il = t % 64;
+                if (i0 + il < Lmax && b0 + bq < B) A.dqdq[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
+            }
+            __syncthreads();
+        }
+    }
+    part[wv][bl] = sum;
+    __syncthreads();
+    if (wv == 0 && b < B) {
+        const double q = ((part[0][bl] + part[1][bl]) + part[2][bl]) + part[3][bl];
+        A.qinv[(size_t)b * P + k] = (float)q;                            // (0 for a unit without partials)
+        if (A.gamma) A.gamma[(size_t)b * P + k] = (hs >= 0) ? (float)(3.14159265358979323846 * q / ut) : 0.0f;
+    }
+}
+
 // ====================================================================== K4: group-velocity kernels
 // surfdisp_forward_group_kernels_device, behind the forward + partials launches (whose outputs it leaves as they are).
 // Differentiating U = d omega / dk at fixed omega (Rodi et al. 1975):
@@ -3423,6 +3508,14 @@ hipError_t launch_kern_transpose(hipStream_t s, const KernTransposeArgs &a)
 {
     const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 3u);
     hipLaunchKernelGGL(surfdisp_kern_transpose_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_atten(hipStream_t s, const AttenArgs &a)
+{
+    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)));
+    if (a.kind == 2) hipLaunchKernelGGL((surfdisp_atten_kernel<2>), grid, dim3(256), 0, s, a);
+    else             hipLaunchKernelGGL((surfdisp_atten_kernel<1>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -286,6 +286,43 @@ class BatchPlan:
         _lib.check(rc)
         return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(self.nnonfin.item()) if count else self.nnonfin)
 
+    def run_atten(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, want_kernel=True, want_gamma=True):
+        """``run_kernels`` plus the apparent attenuation of the mode (``surfdisp_forward_atten_device``): returns (c, u, status,
+        dcdb, dcda, dcdr, qinv, gamma, dqdq).  c .. dcdr equal ``run_kernels``' bit for bit; qinv [B, P] = 1 / Q_apparent
+        (calcul.f:256-265, 341-349: what the reference forms from its partials and the layers' 1/Qs and never returns),
+        gamma [B, P] the attenuation coefficient in 1/km, dqdq float32 [B, P, L] = d qinv / d (1/Qs of layer i) at fixed
+        eigenfunction (``None`` with ``want_kernel=False``; gamma ``None`` with ``want_gamma=False``).  Unsolved periods and
+        bad stacks are zeros, as are water layers and layers below the half space in dqdq.  Rayleigh and Love."""
+        torch = self.torch
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        mk2 = lambda: torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
+        dcdb = mk()
+        dcda = mk() if (want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH) else None
+        dcdr = mk() if want_rho else None
+        qinv = mk2()
+        gamma = mk2() if want_gamma else None
+        dqdq = mk() if want_kernel else None
+        if getattr(self, "aworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
+            self.aws_bytes = int(_lib.lib().surfdisp_atten_workspace_bytes(self.B, self.L, self.P))
+            self.aworkspace = torch.empty(self.aws_bytes, dtype=torch.uint8, device=self.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._last_ws = self.aworkspace
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().surfdisp_forward_atten_device(
+                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                ptr(qinv), ptr(gamma), ptr(dqdq), ptr(self.aworkspace), self.aws_bytes)
+        _lib.check(rc)
+        return self.c, self.u, self.status, dcdb, dcda, dcdr, qinv, gamma, dqdq
+
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
         own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""

@@ -163,8 +163,48 @@ def group_from_phase_partials(c, u, k_minus, k_plus, dlnT):
     return r * (2.0 - r) * 0.5 * (km + kp) - r * r * (kp - km) / float(dlnT)
 
 
+def attenuation_from_kernels(model, periods, c, u, kb, ka=None):
+    """Apparent attenuation of the mode from its phase-velocity kernels, in float64 (the host statement of what the HIP
+    attenuation kernel computes; the reference forms the same numbers after REIGEN / LEIGEN, calcul.f:256-265, 341-349,
+    and never returns them).  With W_i = b_i (dc/db_i + 4/3 (b_i/a_i) dc/da_i) in the reference's coordinates
+    (surfa.f:1207 ``dwx``; Love: b_i dc/db_i), rewritten for the caller-coordinate kernels ``kb`` = dc/dVs and ``ka`` =
+    dc/dVp (``None``: Love) - the flattening factor cancels, qsq = qsinv ln(1/T)/pi, qpq = qsq (4/3) Vs^2/Vp^2:
+
+        W_i = Vs kb - Vs ka (8/3) qsq (Vs/Vp) / (1 - qpq) + (4/3) ka Vs^2 (1 + qsq)^2 / (Vp (1 + qpq)(1 - qpq)),
+
+        dqdq_i = W_i U / c^2,   qinv = sum_i dqdq_i qsinv_i  (= 1/Q_apparent),   gamma = pi qinv / (U T)  (1/km).
+
+    model [B, 5, L] (vp, vs, rho, h, 1/Qs) or [5, L]; periods [P]; c, u [B, P]; kb, ka [B, P, L].  Returns (qinv [B, P],
+    gamma [B, P], dqdq [B, P, L]); zeros at unsolved periods (c or U not > 0), water layers (Vs <= 0) and wherever the
+    kernels are zero (layers below the effective half space)."""
+    m = np.asarray(model, np.float64)
+    m = m[None] if m.ndim == 2 else m
+    T = np.asarray(periods, np.float64).ravel()
+    c = np.asarray(c, np.float64).reshape(m.shape[0], T.size)
+    u = np.asarray(u, np.float64).reshape(m.shape[0], T.size)
+    kb = np.asarray(kb, np.float64).reshape(m.shape[0], T.size, m.shape[2])
+    vp, vs, qs = m[:, 0, None, :], m[:, 1, None, :], m[:, 4, None, :]
+    with np.errstate(invalid="ignore", divide="ignore"):            # (a non-finite stack gives zeros: its c is 0)
+        solid = (vs > 0) & (vp > 0)
+        vs = np.where(solid, vs, 0.0)
+        vp = np.where(solid, vp, 1.0)
+        W = vs * kb
+        if ka is not None:
+            ka = np.asarray(ka, np.float64).reshape(kb.shape)
+            qsq = qs * np.log(1.0 / T)[None, :, None] / np.pi
+            qpq = qsq * (4.0 / 3.0) * vs * vs / (vp * vp)
+            W = (W - vs * ka * (8.0 / 3.0) * qsq * (vs / vp) / (1.0 - qpq)
+                 + (4.0 / 3.0) * ka * vs * vs * (1.0 + qsq) ** 2 / (vp * (1.0 + qpq) * (1.0 - qpq)))
+        ok = (c > 0) & (u > 0)
+        uc2 = np.where(ok, u / np.where(ok, c * c, 1.0), 0.0)
+        dqdq = np.where(solid & ok[:, :, None] & (W != 0), W * uc2[:, :, None], 0.0)
+        qinv = np.where(dqdq != 0, dqdq * qs, 0.0).sum(axis=2)
+        gamma = np.where(ok, np.pi * qinv / np.where(ok, u * T[None, :], 1.0), 0.0)
+    return qinv, gamma, dqdq
+
+
 def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01,
-                     ellipticity=False):
+                     ellipticity=False, attenuation=False):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
     the partial derivatives REIGEN / LEIGEN form from their energy integrals and never return
     (surfa.f:1130-1135, 1204-1207; 561-565, 584-585), with the chain factors of the attenuation
@@ -179,18 +219,28 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     failed), grv = dudb * Vs / 100 / h in phv's units, and n_failed.
     ``ellipticity=True`` (``surfdisp_forward_ellip_kernels_device``, Rayleigh only): also ratio [M, P] (the ellipticity chi),
     dedb, deda, dedr [M, P, L] = d chi / d (Vs | Vp | rho), ell = dedb * Vs / 100 / h in phv's units, and n_nonfinite (units
-    whose rows are NaN).  It is one entry of its own: combined with ``group=True`` it is refused (call twice)."""
+    whose rows are NaN).  It is one entry of its own: combined with ``group=True`` it is refused (call twice).
+    ``attenuation=True`` (``surfdisp_forward_atten_device``, both wave types): also qinv [M, P] = 1 / Q_apparent of the mode
+    (0 for a stack without attenuation and at unsolved periods), gamma [M, P] its attenuation coefficient in 1/km, dqdq
+    [M, P, L] = d qinv / d (1/Qs of layer i) at fixed eigenfunction (qinv = sum_i dqdq_i qsinv_i, see
+    ``attenuation_from_kernels``) and Qapp = 1 / qinv (inf where qinv is 0).  One entry of its own as well: refused
+    together with ``group=True`` or ``ellipticity=True``."""
     import torch
     kind = {"R": 2, "L": 1}[wtype]
     if ellipticity and kind != 2:
         raise ValueError("analytic_kernels: ellipticity kernels are Rayleigh only (wtype='R')")
     if ellipticity and group:
         raise ValueError("analytic_kernels: ellipticity=True and group=True are separate entries; call once for each")
+    if attenuation and (group or ellipticity):
+        raise ValueError("analytic_kernels: attenuation=True is an entry of its own; call once more for group / ellipticity")
     M, _, L = model.shape
     plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
     if ellipticity:
         c, u, st, ratio, kb, ka, kr, eb, ea, er, nnf = plan.run_ellip_kernels(model, periods, kind=kind, nlay=nlay,
                                                                              want_vp=want_vp, want_rho=want_rho)
+    elif attenuation:
+        c, u, st, kb, ka, kr, qinv, gamma, dqdq = plan.run_atten(model, periods, kind=kind, nlay=nlay,
+                                                                 want_vp=want_vp, want_rho=want_rho)
     elif group:
         c, u, st, kb, ka, kr, ub, ua, ur, nf = plan.run_group_kernels(model, periods, kind=kind, nlay=nlay, dlnT_frac=dlnT_frac,
                                                                       want_vp=want_vp, want_rho=want_rho)
@@ -204,6 +254,9 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
         out.update(dudb=ub, duda=ua, dudr=ur, grv=per_km(ub), n_failed=nf)
     if ellipticity:
         out.update(ratio=ratio, dedb=eb, deda=ea, dedr=er, ell=per_km(eb), n_nonfinite=nnf)
+    if attenuation:
+        out.update(qinv=qinv, gamma=gamma, dqdq=dqdq,
+                   Qapp=torch.where(qinv != 0, 1.0 / qinv, torch.full_like(qinv, float("inf"))))
     return out
 
 
