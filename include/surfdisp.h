@@ -37,7 +37,8 @@ extern "C" {
                                        surfdisp_forward_ellip_kernels_device, surfdisp_ellip_kernels_workspace_bytes,
                                        surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events,
                                        surfdisp_lsq_step_device, surfdisp_lsq_resolution_device,
-                                       surfdisp_forward_atten_device, surfdisp_atten_workspace_bytes */
+                                       surfdisp_forward_atten_device, surfdisp_atten_workspace_bytes,
+                                       surfdisp_posterior_profile_device, surfdisp_posterior_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -473,6 +474,58 @@ int surfdisp_lsq_resolution_device(void *stream, int B, int Lmax, const int *nla
                                    double alpha, const double *Q, int q_per_stack, const double *lam,
                                    double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
                                    double *stats, int *info);
+
+/* ---- (6f) posterior Vs(z) profiles of a whole Metropolis track on the device, added within ABI 4 (csrc/surfdisp_post.hip): what
+ *          the reference's PostPoint reports per point - the final rows' models as Vs at depth (point.py:317-335 _loadValues(zdeps)),
+ *          their mean, spread and histograms (plotVsProfileShaded, _check_distribution) and, with a prefix, the row subsets of
+ *          _check_convergency - for every point of a track at once.  pysurfinv_amd.posterior.posterior_reference is the same
+ *          statement in numpy.
+ *   in:    track [npoints][R] rows of row_stride >= 3 + N doubles (device): misfit, L, accepted, params[N] - a point's chains one
+ *          after the other, as in the reference's .npz.  idesc: the integer part of the params->stack descriptor of (6), HOST memory,
+ *          idesc_len ints (it is checked here and travels in the kernel arguments); fdesc: its float part, device.  aux: NULL, or
+ *          the [.][K] table of per-point constants (device; slot N + k of a row, Model1DBatch.set_local_info), rows: NULL (point p
+ *          reads aux row p) or [npoints] ints (device).  zdeps [D]: ascending depths in km, HOST memory, 1 <= D <=
+ *          SURFDISP_POST_DEPTHS_MAX.  Models with a static layer structure and no thermal layer, as surfdisp_prior_device.
+ *   select (point.py:152-168), per point over its R rows: a NaN misfit counts as +inf; imin = the first row of the smallest misfit;
+ *          thres = max(2 min, min + 0.5); a row is FINAL when misfit < thres.  true_markov_chain != 0: a row's parameters are those
+ *          of the last row at or before it whose accepted column is > 0.5 (row 0 of a point counts as accepted).  chainL > 0: only
+ *          rows with r % chainL < prefix take part in the minimum, the threshold and the final set (the others count as +inf; the
+ *          parameter substitution still looks at every row); chainL <= 0: every row, prefix is not read.
+ *   value: Vs at zdeps[d] of a final row's model = linear interpolation on the grid points of Model1D.seisPropGrids WITHOUT the
+ *          reference mantle (Model1D.value), with np.interp's bracket z[j] <= zd < z[j+1], largest j: a doubled interface point
+ *          gives the lower layer's top value, zd equal to the last grid depth gives the last value.  NaN above the first or below
+ *          the last grid point; a value that is not finite is not counted.
+ *   out:   min_misfit, thres [npoints] fp64; imin, n_final [npoints] int (n_final: final rows).  count [npoints][D] int: finite
+ *          values; vs_mean, vs_std (population, ddof = 0), vs_min, vs_max [npoints][D] fp64, NaN where count is 0.  pmean, pstd
+ *          [npoints][N] fp64: the same of the final rows' parameters; both NULL: not written.  hist [npoints][D][nbins] int: counts of
+ *          the nbins equal bins of [vlo, vhi) - bin i = [vlo + i w, vlo + (i + 1) w), w = (vhi - vlo) / nbins -, below, above
+ *          [npoints][D] int the counts of values < vlo and >= vhi; hist NULL: none of the three is written, nbins / vlo / vhi are
+ *          not read.  The entry clears the three arrays itself.
+ *   how:   four stream-ordered launches, no host synchronisation, no allocation, graph-capturable.  The sums are fp64 in an order
+ *          fixed by the input: a point's rows go in slabs of SURFDISP_POST_SLAB_ROWS, every slab leaves (n, mean, M2, min, max) per
+ *          depth and parameter in the caller's workspace, and a last launch merges them in slab order (Chan's pairwise update) -
+ *          two calls on one input return the same bits.  Only the histogram counts are (integer) atomics.
+ *          SURFDISP_ERR_INVALID, before anything is launched or written: npoints, R or N below 1, N above 128, R above 2^30,
+ *          npoints x slabs beyond 2^31 - 1, row_stride below 3 + N, K below 0, D outside 1..SURFDISP_POST_DEPTHS_MAX, depths that
+ *          are not finite or not strictly ascending, with hist: nbins below 1, vlo or vhi not finite, vhi <= vlo; with chainL > 0:
+ *          prefix outside 1..chainL, R % chainL != 0; a descriptor that is too short, has no layer or more than 10, a thermal
+ *          layer (kind 6) or an unknown kind, a slot outside the [params | aux] row, grid ranges that do not tile 0..ngrid in
+ *          order with at least two points each; K > 0 without aux; a NULL required pointer (track, idesc, fdesc, zdeps, min_misfit,
+ *          thres, imin, n_final, count, vs_mean, vs_std, vs_min, vs_max, workspace; pmean and pstd only together; below and above
+ *          with hist), a workspace smaller than surfdisp_posterior_workspace_bytes. */
+#define SURFDISP_POST_SLAB_ROWS 4096
+#define SURFDISP_POST_DEPTHS_MAX 256
+size_t surfdisp_posterior_workspace_bytes(int npoints, int R, int N, int D);
+int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, const double *track, long row_stride,
+                                      const int *idesc, int idesc_len, const double *fdesc,
+                                      const double *aux, int K, const int *rows,
+                                      int D, const double *zdeps, int true_markov_chain, int chainL, int prefix,
+                                      int nbins, double vlo, double vhi,
+                                      double *min_misfit, double *thres, int *imin, int *n_final,
+                                      double *pmean, double *pstd,
+                                      int *count, double *vs_mean, double *vs_std, double *vs_min, double *vs_max,
+                                      int *hist, int *below, int *above,
+                                      void *workspace, size_t workspace_bytes);
 
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular

@@ -37,7 +37,8 @@ EXPORTS = (
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
     "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes",
-    "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device",
+    "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -174,6 +175,16 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "surfdisp_lsq_resolution_device"):          # (absent from an older build loaded through SURFDISP_LIB_PATH)
         L.surfdisp_lsq_resolution_device.restype = ctypes.c_int
         L.surfdisp_lsq_resolution_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + [vp] * 7
+    # (stream, npoints, R, N, track, row_stride, idesc (host), idesc_len, fdesc, aux, K, rows, D, zdeps (host), true_markov_chain, chainL,
+    #  prefix, nbins, vlo, vhi, min_misfit, thres, imin, n_final, pmean, pstd, count, vs_mean, vs_std, vs_min, vs_max, hist, below, above,
+    #  workspace, workspace_bytes)
+    if hasattr(L, "surfdisp_posterior_profile_device"):       # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        L.surfdisp_posterior_workspace_bytes.restype = ctypes.c_size_t
+        L.surfdisp_posterior_workspace_bytes.argtypes = [ctypes.c_int] * 4
+        L.surfdisp_posterior_profile_device.restype = ctypes.c_int
+        L.surfdisp_posterior_profile_device.argtypes = ([vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_long, vp, ctypes.c_int, vp,
+                                                         vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int, ctypes.c_double, ctypes.c_double] + [vp] * 14 + [vp, ctypes.c_size_t])
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdint.h>
+#include <cmath>
 #include <atomic>
 #include "surfdisp_internal.h"
 
@@ -739,6 +740,104 @@ int surfdisp_mcmc_propose_tree_device(void *stream, int C, int N, int depth, con
 {
     return mcmc_propose("surfdisp_mcmc_propose_tree_device", stream, C, N, p, vmin, vmax, step, seed, counter, 0, out, chain0, depth,
                         false, nullptr, 0, 0);
+}
+
+// Posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; header section (6f)).  Workspace: the per-slab partials
+// [npoints][nslab][D + N][5] doubles, the slabs' smallest misfits [npoints][nslab] doubles, then four int arrays [npoints][nslab].
+static long post_slabs(int R) { return ((long)R + SURFDISP_POST_SLAB_ROWS - 1) / SURFDISP_POST_SLAB_ROWS; }
+
+size_t surfdisp_posterior_workspace_bytes(int npoints, int R, int N, int D)
+{
+    if (npoints < 1 || R < 1 || N < 1 || D < 1) return 0;
+    const size_t units = (size_t)npoints * (size_t)post_slabs(R);
+    return units * ((size_t)(D + N) * 5 * sizeof(double) + sizeof(double) + 4 * sizeof(int));
+}
+
+// the integer part of the params->stack descriptor (layout: csrc/surfdisp_layers.hip), as the profile kernel walks it
+static const char *post_check_desc(const int *idesc, int len, int width, bool has_aux, int N)
+{
+    if (len < 4) return "descriptor too short";
+    const int nin = idesc[0], ngrid = idesc[1];
+    if (nin < 1 || nin > sd::SD_POST_MAX_LAYERS) return "1..10 input layers";
+    if (len < 4 + 16 * nin) return "descriptor too short";
+    auto slot_ok = [&](int sl) { return sl >= -1 && sl < width && (has_aux || sl < N); };
+    int at = 0;
+    for (int l = 0; l < nin; ++l) {
+        const int *li = idesc + 4 + 8 * l, *ci = idesc + 4 + 8 * nin + 8 * l;
+        if (li[0] == 6) return "a thermal layer (kind 6) is not supported";
+        if (li[0] < 0 || li[0] > 7) return "unknown layer kind";
+        if (!slot_ok(li[1]) || li[3] < 0 || li[3] > 8) return "thickness slot or coefficient count out of range";
+        if (li[4] != at || li[5] < li[4] + 2) return "grid ranges must tile 0..ngrid in order, two points or more each";
+        at = li[5];
+        for (int k = 0; k < li[3]; ++k)
+            if (!slot_ok(ci[k])) return "coefficient slot out of range";
+    }
+    if (at != ngrid) return "grid ranges must tile 0..ngrid in order, two points or more each";
+    if (idesc[4 + 6] < 0 || !slot_ok(idesc[4 + 6] - 1)) return "topography slot out of range";
+    return nullptr;
+}
+
+int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, const double *track, long row_stride,
+                                      const int *idesc, int idesc_len, const double *fdesc,
+                                      const double *aux, int K, const int *rows,
+                                      int D, const double *zdeps, int true_markov_chain, int chainL, int prefix,
+                                      int nbins, double vlo, double vhi,
+                                      double *min_misfit, double *thres, int *imin, int *n_final,
+                                      double *pmean, double *pstd,
+                                      int *count, double *vs_mean, double *vs_std, double *vs_min, double *vs_max,
+                                      int *hist, int *below, int *above,
+                                      void *workspace, size_t workspace_bytes)
+{
+    const char *name = "surfdisp_posterior_profile_device";
+    if (npoints < 1 || R < 1 || R > (1 << 30) || N < 1 || N > sd::SD_POST_MAX_PARAMS || row_stride < 3 + (long)N || K < 0 ||
+        D < 1 || D > SURFDISP_POST_DEPTHS_MAX || (long)npoints * post_slabs(R) > 0x7fffffffL) {
+        set_err("%s: invalid size (npoints, R, N >= 1; N <= 128; R <= 2^30; row_stride >= 3 + N; K >= 0; 1 <= D <= 256)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (!track || !idesc || !fdesc || !zdeps || !min_misfit || !thres || !imin || !n_final || !count || !vs_mean || !vs_std ||
+        !vs_min || !vs_max || !workspace || (!pmean != !pstd) || (hist && (!below || !above)) || (K > 0 && !aux)) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    for (int d = 0; d < D; ++d)
+        if (!std::isfinite(zdeps[d]) || (d > 0 && !(zdeps[d] > zdeps[d - 1]))) {
+            set_err("%s: invalid depths: finite and strictly ascending", name); return SURFDISP_ERR_INVALID;
+        }
+    if (hist && (nbins < 1 || !std::isfinite(vlo) || !std::isfinite(vhi) || !(vhi > vlo))) {
+        set_err("%s: invalid histogram: nbins >= 1, finite vlo < vhi", name); return SURFDISP_ERR_INVALID;
+    }
+    if (chainL > 0 && (prefix < 1 || prefix > chainL || R % chainL != 0)) {
+        set_err("%s: invalid prefix: 1 <= prefix <= chainL and R a multiple of chainL", name); return SURFDISP_ERR_INVALID;
+    }
+    if (const char *why = post_check_desc(idesc, idesc_len, N + K, aux != nullptr, N)) {
+        set_err("%s: invalid descriptor: %s", name, why); return SURFDISP_ERR_INVALID;
+    }
+    if (workspace_bytes < surfdisp_posterior_workspace_bytes(npoints, R, N, D)) {
+        set_err("%s: invalid workspace: smaller than surfdisp_posterior_workspace_bytes", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::PostArgs a{};
+    a.npoints = npoints; a.R = R; a.N = N; a.K = K; a.D = D; a.nslab = (int)post_slabs(R);
+    a.tmc = true_markov_chain ? 1 : 0; a.chainL = chainL > 0 ? chainL : 0; a.prefix = prefix;
+    a.row_stride = row_stride; a.track = track; a.fdesc = fdesc; a.aux = aux; a.rows = aux ? rows : nullptr;
+    a.min_misfit = min_misfit; a.thres = thres; a.imin = imin; a.n_final = n_final; a.pmean = pmean; a.pstd = pstd;
+    a.count = count; a.vs_mean = vs_mean; a.vs_std = vs_std; a.vs_min = vs_min; a.vs_max = vs_max;
+    const size_t units = (size_t)npoints * a.nslab;
+    a.ws_part = static_cast<double *>(workspace);
+    a.ws_mis = a.ws_part + units * (size_t)(D + N) * 5;
+    a.ws_row = reinterpret_cast<int *>(a.ws_mis + units);
+    a.ws_last = a.ws_row + units; a.ws_carry = a.ws_last + units; a.ws_nfin = a.ws_carry + units;
+    const int nin = idesc[0];
+    for (int i = 0; i < 4 + 16 * nin; ++i) a.idesc[i] = idesc[i];
+    for (int d = 0; d < D; ++d) a.zdeps[d] = zdeps[d];
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hist) {
+        a.hist = hist; a.below = below; a.above = above; a.nbins = nbins; a.vlo = vlo; a.vhi = vhi;
+        a.bin_w = (vhi - vlo) / nbins; a.inv_w = nbins / (vhi - vlo);
+        SD_HIP(hipMemsetAsync(hist, 0, (size_t)npoints * D * nbins * sizeof(int), s));
+        SD_HIP(hipMemsetAsync(below, 0, (size_t)npoints * D * sizeof(int), s));
+        SD_HIP(hipMemsetAsync(above, 0, (size_t)npoints * D * sizeof(int), s));
+    }
+    SD_HIP(sd::launch_posterior(s, a));
+    return SURFDISP_SUCCESS;
 }
 
 // The generic prior predicates on the device (csrc/surfdisp_layers.hip, surfdisp_prior_kernel): tags[c] = mark_tag where chain c's

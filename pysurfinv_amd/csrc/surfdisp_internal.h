@@ -275,6 +275,34 @@ struct LsqArgs {
     double *cov, *res;      // [B][nmax][nmax] or nullptr
     double *sigma_post, *sigma_data, *rdiag;   // [B][Lmax]
 };
+// posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; include/surfdisp.h section (6f)).  The descriptor's
+// integer part and the depths travel in the kernel arguments: the entry has checked them on the host.
+constexpr int SD_POST_SLAB = SURFDISP_POST_SLAB_ROWS;   // rows of one point a workgroup walks: the unit of the per-slab partials
+constexpr int SD_POST_MAX_LAYERS = 10;                  // input layers of the descriptor (Model1DBatch.native_descriptor's own cap)
+constexpr int SD_POST_MAX_PARAMS = 128;                 // two parameters per lane of the profile kernel
+struct PostArgs {
+    int npoints, R, N, K, D, nslab;
+    int tmc, chainL, prefix;   // true_markov_chain; chainL > 0: only rows with r % chainL < prefix are selected
+    int nbins;
+    long row_stride;           // doubles between the rows of the track; a point's rows are R * row_stride apart
+    const double *track;       // [npoints][R][row_stride]: misfit, L, accepted, params[N]
+    const double *fdesc;       // the descriptor's float part (device)
+    const double *aux;         // nullptr, or [.][K] per-point constants: slot N + k of a row
+    const int *rows;           // nullptr (point p reads aux row p), or [npoints] the aux row of each point
+    double vlo, vhi, bin_w, inv_w;
+    double *min_misfit, *thres;   // [npoints]
+    int *imin, *n_final;          // [npoints]
+    double *pmean, *pstd;         // nullptr, or [npoints][N]
+    int *count;                   // [npoints][D]
+    double *vs_mean, *vs_std, *vs_min, *vs_max;   // [npoints][D]
+    int *hist, *below, *above;    // nullptr, or [npoints][D][nbins], [npoints][D], [npoints][D]
+    double *ws_part;           // workspace: [npoints][nslab][D + N][5] (n, mean, M2, min, max)
+    double *ws_mis;            // [npoints][nslab] smallest misfit of the slab
+    int *ws_row, *ws_last, *ws_carry, *ws_nfin;   // [npoints][nslab] its row, the slab's last accepted row, the one it starts from, final rows
+    int idesc[4 + 16 * SD_POST_MAX_LAYERS];
+    double zdeps[SURFDISP_POST_DEPTHS_MAX];
+};
+hipError_t launch_posterior(hipStream_t s, const PostArgs &a);
 size_t lsq_lds_bytes(int nmax);
 size_t lsq_resolution_lds_bytes(int nmax);
 hipError_t launch_lsq_step(hipStream_t s, const LsqArgs &a);

@@ -32,7 +32,8 @@ def summary_columns(n_params, n_periods):
 
 def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, chainL, outdir=None,
              rank=0, world=1, device="cuda:0", seed=0, forward=None, isgood=None, fast_scan=False,
-             writer_threads=4, keep_tracks=True, local_info=None, chain_groups=None, spec_depth=None):
+             writer_threads=4, keep_tracks=True, local_info=None, chain_groups=None, spec_depth=None,
+             profile_depths=None):
     """Invert the points owned by ``rank``.
 
     model_batch : layers_batch.Model1DBatch (one setting for the grid)
@@ -45,6 +46,11 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
                   ``MetropolisBatch.chain_groups``) or their number; the random numbers of every chain do not depend on it
     spec_depth  : None (the sampler's default: speculative lock steps of depth 4 / 3 / 2 for up to 136 / 292 / 682 chains per rank,
                   ``MetropolisBatch.auto_spec_depth``) or the depth (1 = one step per forward solve)
+    profile_depths: None, or ascending depths (km): every point's posterior Vs(z) profile over its final rows (``pysurfinv_amd.posterior``:
+                  one call of the device entry on a HIP device for a model with a native descriptor and no thermal layer, the
+                  numpy statement ``posterior_reference`` otherwise), formed from the tracks before they leave the device, inside
+                  ``elapsed``, and gathered like the summaries: the result then carries ``profiles = dict(zdeps, count, mean, std,
+                  min, max)``, [n_points, D] each, on every rank.
     Returns dict(points=(lo, hi), mcTrack=[n_local, chains*chainL, 3+N] or None, summaries=[n_points, 6+2N+P]
     (every rank holds all rows, point order), columns, elapsed (sampling + summaries + gather, this rank),
     elapsed_write, report).  ``report`` carries the MAX over ranks of ``elapsed`` and the summed counters."""
@@ -81,9 +87,23 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
         first_chain = torch.arange(n_local, device=dev) * chains_per_point     # observation row of each point
         summ = mc.summarise_points(tracks_dev, first_chain)
         n_forward = mc.n_forward
+    prof = None
+    if profile_depths is not None:
+        from . import posterior
+        zd = np.asarray(profile_depths, float).ravel()
+        prof = torch.zeros((n_local, 5 * zd.size), dtype=torch.float64, device=dev)
+        if n_local > 0:
+            native = dev.type == "cuda" and model_batch.native_descriptor() is not None and not model_batch._native_thermal
+            fn, trk = (posterior.posterior_profiles, tracks_dev) if native else (posterior.posterior_reference, tracks_dev.cpu())
+            pr = fn(model_batch, trk, zd, rows=np.arange(n_local) if local_info is not None else None)
+            prof = torch.cat([pr[k].to(torch.float64) for k in ("count", "vs_mean", "vs_std", "vs_min", "vs_max")], dim=1).to(dev)
     # the one data exchange of the flow: every rank gets every point's summary row (a few hundred bytes per point)
     parts = shard.gather_rows(summ, device=cdev)
     summaries = torch.cat(parts, dim=0).cpu().numpy()
+    profiles = None
+    if prof is not None:
+        allp = torch.cat(shard.gather_rows(prof, device=cdev), dim=0).cpu().numpy().reshape(n_points, 5, zd.size)
+        profiles = dict(zdeps=zd, count=allp[:, 0].astype(np.int64), mean=allp[:, 1], std=allp[:, 2], min=allp[:, 3], max=allp[:, 4])
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
@@ -103,9 +123,12 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     elapsed_write = time.perf_counter() - t1
     max_elapsed, (tot_forward, tot_points) = shard.reduce_report(elapsed, [n_forward, n_local], device=cdev)
     steps = tot_points * chains_per_point * chainL
-    return dict(points=(lo, hi), mcTrack=tracks if keep_tracks else None, summaries=summaries,
-                columns=summary_columns(N, P), elapsed=elapsed, elapsed_write=elapsed_write,
-                report=dict(elapsed_max=max_elapsed, forward_solves=tot_forward, points=tot_points,
-                            metropolis_steps=steps,
-                            steps_per_s=steps / max_elapsed if max_elapsed > 0 else 0.0,
-                            solves_per_s=tot_forward / max_elapsed if max_elapsed > 0 else 0.0))
+    res = dict(points=(lo, hi), mcTrack=tracks if keep_tracks else None, summaries=summaries,
+               columns=summary_columns(N, P), elapsed=elapsed, elapsed_write=elapsed_write,
+               report=dict(elapsed_max=max_elapsed, forward_solves=tot_forward, points=tot_points,
+                           metropolis_steps=steps,
+                           steps_per_s=steps / max_elapsed if max_elapsed > 0 else 0.0,
+                           solves_per_s=tot_forward / max_elapsed if max_elapsed > 0 else 0.0))
+    if profiles is not None:
+        res["profiles"] = profiles
+    return res

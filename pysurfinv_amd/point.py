@@ -132,6 +132,7 @@ class PostPoint(Point):
                  device="cuda:0", _forward=None):
         self.MCparas_pri = None
         self._forward = _forward
+        self.trueMarkovChain, self._post_device = bool(trueMarkovChain), device
         if npzMC is not None:
             tmp = np.load(npzMC, allow_pickle=True)
             self.MC, setting, obs = np.array(tmp["mcTrack"], float), tmp["setting"][()], tmp["obs"][()]
@@ -191,3 +192,28 @@ class PostPoint(Point):
         indVars = range(self.MCparas.shape[1]) if isinstance(indVars, str) and indVars == "all" else indVars
         paras = self.MCparas[self.accFinal] if not priori else self.MCparas_pri[self.accFinal]
         return np.array([mc[list(indVars)] for mc in paras]).T
+
+    def profile(self, zdeps, hist=None, quantiles=(0.16, 0.5, 0.84)):
+        """The point's posterior Vs(z) profile as host arrays: dict(zdeps, count, mean, std, min, max [D]; pmean, pstd [N];
+        min_misfit, thres, n_final; with ``hist=(vlo, vhi, nbins)`` also hist [D, nbins], below, above [D], quantiles [D, Q]).
+        ``std`` is what ``plotVsProfileShaded`` shades with: ``_loadValues(zdeps=zdeps).std(axis=1)``.  One call of the device
+        entry (``posterior.posterior_profiles``) when the point has a HIP device and its model a native descriptor without a
+        thermal layer; ``posterior.posterior_reference`` otherwise (``device=None``, non-static layer structures)."""
+        import torch
+        from . import posterior
+        mb = self.initMod
+        on_dev = (self._post_device is not None and torch.device(self._post_device).type == "cuda"
+                  and mb.native_descriptor() is not None and not mb._native_thermal)
+        track = torch.as_tensor(self.MC[None, :, :], dtype=torch.float64)
+        fn = posterior.posterior_reference
+        if on_dev:
+            track, fn = track.to(mb.device), posterior.posterior_profiles
+        r = fn(mb, track, zdeps, true_markov_chain=self.trueMarkovChain, hist=hist, quantiles=quantiles)
+        r = {k: v[0].cpu().numpy() for k, v in r.items()}
+        out = dict(zdeps=np.asarray(zdeps, float), count=r["count"], mean=r["vs_mean"], std=r["vs_std"], min=r["vs_min"],
+                   max=r["vs_max"], pmean=r["pmean"], pstd=r["pstd"], min_misfit=float(r["min_misfit"]), thres=float(r["thres"]),
+                   n_final=int(r["n_final"]))
+        for k in ("hist", "below", "above", "quantiles"):
+            if k in r:
+                out[k] = r[k]
+        return out
