@@ -32,6 +32,33 @@ def host_group(model, per, kind, c, ratio, dbg=None):
     return u
 
 
+def host_prep_rows(model, kind, nlay=None):
+    """prep_stack compiled for the host: (rows float32 [B, 9, L] = vp, vs, rho, 1/Qs, dif, qqq, dfl, hsf, hsr; nl int32 [B])."""
+    model = np.ascontiguousarray(model, np.float32)
+    B, _, L = model.shape
+    rows = np.zeros((B, 9, L), np.float32)
+    nl = np.zeros(B, np.int32)
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    nlay = None if nlay is None else np.ascontiguousarray(nlay, np.int32)
+    H.sd_hostcheck_prep_rows(B, L, None if nlay is None else ip(nlay), fp(model), int(kind), fp(rows), ip(nl))
+    return rows, nl
+
+
+def host_kernels(model, per, kind, c, ratio, nlay=None, refcoord=False):
+    """The KERN instantiation of group_rayleigh / group_love compiled for the host, at the roots c and ellipticities ratio
+    [B, P]: (u [B, P], dcdb, dcda, dcdr [B, P, L]; dcda None for Love).  ``refcoord``: unit chain factors."""
+    model = np.ascontiguousarray(model, np.float32)
+    per = np.ascontiguousarray(per, np.float32)
+    B, _, L = model.shape; P = per.size
+    u = np.zeros((B, P), np.float32)
+    kb, ka, kr = (np.zeros((B, P, L), np.float32) for _ in range(3))
+    nlay = None if nlay is None else np.ascontiguousarray(nlay, np.int32)
+    H.sd_hostcheck_kernels(B, L, None if nlay is None else nlay.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), fp(model), P, fp(per),
+                           int(kind), int(bool(refcoord)), fp(np.ascontiguousarray(c, np.float32)),
+                           fp(np.ascontiguousarray(ratio, np.float32)), fp(u), fp(kb), fp(ka), fp(kr))
+    return u, kb, (ka if int(kind) == 2 else None), kr
+
+
 if __name__ == "__main__":
     cases = load_cases()
     sel = sys.argv[1:] or sorted(cases)
