@@ -38,6 +38,7 @@ extern "C" {
                                        surfdisp_mcmc_accept_joint5_device, surfdisp_mcmc_accept_tree_joint5_device, surfdisp_forward_batch_device2_events,
                                        surfdisp_lsq_step_device, surfdisp_lsq_resolution_device,
                                        surfdisp_forward_atten_device, surfdisp_atten_workspace_bytes,
+                                       surfdisp_forward_eigen_device, surfdisp_eigen_workspace_bytes,
                                        surfdisp_posterior_profile_device, surfdisp_posterior_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
@@ -287,6 +288,45 @@ int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay
                                   float *c, float *u, int *status,
                                   float *dcdb, float *dcda, float *dcdr,
                                   float *qinv, float *gamma, float *dqdq,
+                                  void *workspace, size_t workspace_bytes);
+
+/* ---- (5f) ... and the mode's EIGENFUNCTION and energy integrals, added within ABI 4: what REIGEN / LEIGEN leave in COMMON
+ *          /rar/ (dept1, ampur, ampuz, stresz, stresr; Love amp, stress), /rco1/ (sumi0..2) and /rco/ (are / ale) and the
+ *          reference never returns (surfa.f:389, 728, 1105-1108, 1145-1148, 1213-1245; Love 499-500, 554-555, 571-628).
+ *          The launches of surfdisp_forward_batch_device with the group-velocity kernel's eigenfunction instantiation in place
+ *          of the plain one - c, u, status bit-identical to surfdisp_forward_batch_device on the same inputs and flags - then
+ *          one transposition kernel.  ur, uz, tz, tr [B][P][Lmax]: the horizontal and vertical displacement and the normal
+ *          and shear traction AT THE TOP OF CALLER LAYER i (the depth sum of the thicknesses above it), fp32 as the
+ *          reference's arrays; energy [B][P][4] = (I0, I1, I2, amp).  Conventions:
+ *            - Rayleigh is normalised to uz = 1 at the top of the first solid layer, Love to ut = 1 there (amp(l) / ut,
+ *              surfa.f:580-581).  Love: ur holds the transverse displacement, tr the shear traction, uz and tz are zeros.
+ *            - the entry at that top is SET, not integrated: Rayleigh (ellipticity, 1, 0, 0) (surfa.f:1233-1245), Love (1, 0)
+ *              (surfa.f:627-628).  Under a water layer it is entry 1 - the sea floor, the reference's dept1(1) = d(1) - and
+ *              Rayleigh's normal traction there is the water's, tzz (surfa.f:910, 1244); entry 0, the sea surface, which
+ *              the reference does not form, is zero.
+ *            - the last non-zero entry is the top of the unit's effective half space (layer dropping, surfa.f:853-866 /
+ *              475-487; when the cut falls inside a layer, that layer's top); deeper layers, layers beyond nlay, unsolved
+ *              periods, bad stacks and the degenerate exits (surfa.f label 7006; Love's overflow retries exhausted) are zeros,
+ *              integrals included.
+ *            - Love's low-amplitude exclusion (surfa.f:588-596): an entry of a layer at least as fast as the effective
+ *              half space whose normalised displacement is below 1e-20 is zero, displacement and traction.
+ *            - I0, I1, I2 are the sums U is formed from: Rayleigh U = (k I1 + I2) / (omega I0) (surfa.f:1186), Love
+ *              U = I1 / (c I0) after the division by ut^2 (surfa.f:600-606), I2 = 0.  amp = 1 / (2 c U I0), 0 where c is not
+ *              a solved value: the surface-wave amplification factor; the reference's are / ale (surfa.f:1191, 608) is
+ *              amp x 1e-15 / sqrt(6.28318).
+ *            - all values are those of the earth-flattened, attenuation-corrected stack at the period, as the reference's
+ *              are; no inverse flattening of amplitudes is applied.  The reference's own /rar/ entries sit at the MIDDLE of
+ *              its sublayers (kk = 3, surfa.f:1104-1108, 553-555), half a sublayer below these.
+ *          uz, tz, tr and energy may be NULL.  SURFDISP_INDEPENDENT, SURFDISP_STRICT and the scan flags as in (5).
+ *          SURFDISP_ERR_INVALID, before anything is launched: SURFDISP_PHASE_ONLY, SURFDISP_KERN_REFCOORD, a NULL c, u, status or
+ *          ur, and a workspace smaller than surfdisp_eigen_workspace_bytes (the forward workspace + a layer-major scratch
+ *          [4][Lmax][P][B] + five words per unit: there is no direct route). */
+size_t surfdisp_eigen_workspace_bytes(int B, int Lmax, int P);
+int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay,
+                                  const float *model, int P, const float *per, int kind,
+                                  float *c, float *u, int *status,
+                                  float *ur, float *uz, float *tz, float *tr,   /* [B][P][Lmax] */
+                                  float *energy,                                 /* [B][P][4]    */
                                   void *workspace, size_t workspace_bytes);
 
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:

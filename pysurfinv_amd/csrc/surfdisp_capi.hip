@@ -375,12 +375,32 @@ int surfdisp_workspace_counters(void *stream, const void *workspace, int B, int 
     return SURFDISP_SUCCESS;
 }
 
+// the eigenfunction entry's part of the workspace, behind the forward solve's: the layer-major scratch [4][Lmax][P][B] and
+// per unit the divisor, the deepest layer and the three energy integrals
+struct EigCarve {
+    float *escr, *ediv, *esum;
+    int *ehs;
+    size_t total;
+};
+static EigCarve eigcarve(void *base, int B, int Lmax, int P)
+{
+    char *p = static_cast<char *>(base);
+    size_t off = align_up(carve(nullptr, B, Lmax, P).total);
+    EigCarve e;
+    e.escr = reinterpret_cast<float *>(p + off);  off += align_up((size_t)4 * Lmax * P * B * sizeof(float));
+    e.ediv = reinterpret_cast<float *>(p + off);  off += align_up((size_t)P * B * sizeof(float));
+    e.ehs = reinterpret_cast<int *>(p + off);     off += align_up((size_t)P * B * sizeof(int));
+    e.esum = reinterpret_cast<float *>(p + off);  off += align_up((size_t)3 * P * B * sizeof(float));
+    e.total = off;
+    return e;
+}
+
 static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
                                const float *model, int P, const float *per, int kind,
                                float *c, float *u, int *status,
                                void *workspace, size_t workspace_bytes, hipEvent_t *ev,
                                float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr,
-                               bool force_hist = false, bool scr_vp = false)
+                               bool force_hist = false, bool scr_vp = false, const EigCarve *eig = nullptr)
 {
     int rc = check_args(B, Lmax, P, kind, model, per, c, u);
     if (rc) return rc;
@@ -481,6 +501,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // attenuation kernel reads it - also when the caller wants no dc/dVp rows)
     sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka, kr,
                      kscr, kscale, khs, kern_raw ? 1 : 0, 0, 0, kn.group_order};
+    if (eig) { ga.escr = eig->escr; ga.ediv = eig->ediv; ga.ehs = eig->ehs; ga.esum = eig->esum; }   // (the EIG instantiation)
     if (!phase_only) SD_HIP(sd::launch_group(s, kind, ga));
     if (!phase_only && kscr) {
         // one launch for the three arrays: factor 1 / (dL/dk), zeros below each unit's half space, whole rows
@@ -660,6 +681,44 @@ int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay
     const int *khs = reinterpret_cast<const int *>(q);
     sd::AttenArgs aa{B, P, Lmax, wave, w.mdl, per, kscr, kscale, khs, w.ct, w.ut, qinv, gamma, dqdq};
     SD_HIP(sd::launch_atten(s, aa));
+    return SURFDISP_SUCCESS;
+}
+
+// The launches of surfdisp_forward_batch_device with the group-velocity kernel's EIG instantiation in place of the plain one
+// (c, u, status bit for bit), then the transposition of the layer-top eigenfunctions and the energy integrals (K2d in
+// surfdisp_kernels.hip).  Workspace: the forward solve's + the layer-major scratch and the per-unit words; no direct route.
+size_t surfdisp_eigen_workspace_bytes(int B, int Lmax, int P)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    return eigcarve(nullptr, B, Lmax, P).total;
+}
+
+int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay,
+                                  const float *model, int P, const float *per, int kind,
+                                  float *c, float *u, int *status,
+                                  float *ur, float *uz, float *tz, float *tr, float *energy,
+                                  void *workspace, size_t workspace_bytes)
+{
+    if (!c || !u || !status || !ur) { set_err("surfdisp_forward_eigen_device: c, u, status or ur is NULL"); return SURFDISP_ERR_INVALID; }
+    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
+        set_err("surfdisp_forward_eigen_device: no PHASE_ONLY, no KERN_REFCOORD");
+        return SURFDISP_ERR_INVALID;
+    }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < surfdisp_eigen_workspace_bytes(B, Lmax, P)) {
+        set_err("workspace too small (surfdisp_eigen_workspace_bytes)");
+        return SURFDISP_ERR_INVALID;
+    }
+    const EigCarve e = eigcarve(workspace, B, Lmax, P);
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                             workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &e);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int wave = kind & ~SD_KIND_FLAGS;
+    const Carve w = carve(workspace, B, Lmax, P);
+    sd::EigenTransposeArgs ta{B, P, Lmax, wave, w.mdl, w.nl, per, e.escr, e.ediv, e.ehs, e.esum, w.ct, w.ut, ur, uz, tz, tr, energy};
+    SD_HIP(sd::launch_eigen_transpose(s, ta));
     return SURFDISP_SUCCESS;
 }
 

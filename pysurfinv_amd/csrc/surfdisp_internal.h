@@ -84,7 +84,27 @@ struct GroupArgs {
     int xcd_order;        // set by launch_group: workgroup -> (stack block, period) order that keeps a stack block's periods on one XCD
     int krev;             // (developer knob, SURFDISP_GROUP_ORDER + 100: periods in descending order)
     int group_order;      // SURFDISP_GROUP_ORDER: < 0 the library's rule (launch_group), 0 plain period-major order, g > 0: an XCD takes g stack blocks at a time
+    // eigenfunctions (surfdisp_forward_eigen_device; the EIG instantiations only, which write no partials)
+    float *escr;          // nullptr, or the layer-major scratch [4][Lmax][P][B] (Love: 2 planes) of the layer-top values
+    float *ediv;          // with escr: [P][B] the unit's divisor (Rayleigh 1, Love ut at the top)
+    int *ehs;             // with escr: [P][B] deepest layer the unit wrote (-1: none - unsolved, bad stack, degenerate exit)
+    float *esum;          // with escr: [3][P][B] the energy integrals I0, I1, I2 the group velocity is formed from
 };
+// eigenfunctions from the layer-major scratch to the caller's rows, see K2d
+struct EigenTransposeArgs {
+    int B, P, Lmax, kind;
+    const float *mdl;     // SoA staged fields (Love: the layers' Vs of the low-amplitude exclusion)
+    const int *nl;        // [B]
+    const float *per;     // [P]
+    const float *escr;    // [4][Lmax][P][B] (Love: planes 0, 1)
+    const float *ediv;    // [P][B]
+    const int *ehs;       // [P][B]
+    const float *esum;    // [3][P][B]
+    const float *c, *u;   // [P][B] period-major
+    float *ur, *uz, *tz, *tr;   // the caller's [B][P][Lmax] rows (all but ur may be nullptr)
+    float *energy;        // nullptr, or the caller's [B][P][4]: I0, I1, I2, 1 / (2 c U I0)
+};
+hipError_t launch_eigen_transpose(hipStream_t s, const EigenTransposeArgs &a);
 struct KernTransposeArgs {
     int B, P, Lmax, kind;
     const float *kscr;    // [3][Lmax][P][B]

@@ -2189,6 +2189,29 @@ struct KOut {
         if (off_r) *reinterpret_cast<float *>(reinterpret_cast<char *>(q) + off_r) = vr;
     }
 };
+// Eigenfunctions (the EIG instantiations; surfdisp_forward_eigen_device, K2d): the displacement-stress vector the sweep holds
+// at the TOP of every caller layer i <= hs_layer - a knot of every split (fast_sublayers, the reference's ndiv) and of both
+// Rayleigh paths - stored fp32 like the reference's real*4 COMMON /rar/ (surfa.f:389, 728), one plain store per component
+// into a layer-major scratch [4][Lmax][P*B] (Love: [2]), the layout of the partials' scratch: the lanes of a wavefront
+// write consecutive words.  Entry (component q, layer i) of this unit sits at p[q * plane + i * stride].
+struct EOut {
+    float *p;
+    size_t stride, plane;
+    SD_HD void put(int i, float ur, float uz, float tz, float tr) const
+    {
+        float *q = p + (size_t)i * stride;
+        q[0] = ur; q[plane] = uz; q[2 * plane] = tz; q[3 * plane] = tr;
+    }
+    SD_HD void put2(int i, float ut, float tq) const
+    {
+        float *q = p + (size_t)i * stride;
+        q[0] = ut; q[plane] = tq;
+    }
+};
+// ... and per unit: the divisor of the stored values (Rayleigh 1: the sweep is normalised to uz = 1 at the top of the first
+// solid layer; Love: ut at the top, known only after the last layer, surfa.f:580-581), the deepest layer written (-1: none -
+// the degenerate exits leave zero rows and zero integrals) and the three sums exactly as the U expression consumes them.
+struct EUnit { float div; int hs; float i0, i1, i2; };
 struct K3 { float b, a, r; };
 struct Chain { float dbdb, dadb, dada, rfac; };
 SD_HD __forceinline__ Chain chain_of(const LayerRaw &r, float lnT, bool is_halfspace, bool raw)
@@ -2451,14 +2474,15 @@ SD_HD __forceinline__ int fast_sublayers(const RCoef &q, float wvnosq, float dsu
 // MODE 2: energy integrals.  two_vec = false: z[] is the combined solution itself (fast path);
 //         two_vec = true: y[] and z[] are stepped separately and combined at every knot with the
 //         fitted xnorm / bb, exactly like the reference's stored knots (surfa.f:1092-1095).
-template <int MODE, bool KERN = false>
+// EIG (MODE 2): also store the combined vector at the top of every layer the sweep steps through (EOut).
+template <int MODE, bool KERN = false, bool EIG = false>
 SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t fs, int B, int b,
                                                int n, float lnT, int ndiv, bool water, float div,
                                                const Drop dr, float wvno, float wvnosq, float omegsq,
                                                double y[4], double z[4], bool do_y, bool own,
                                                double xnorm, double bbn, RInt &acc,
                                                const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float cw = 0.0f, K3 *hold = nullptr,
-                                               bool *shorter = nullptr)
+                                               bool *shorter = nullptr, const EOut eo = EOut{nullptr, 1, 0})
 {
 #pragma clang fp contract(off)   // both sweeps must see identical coefficients
     LayerRaw nraw = layer_load(mdl, fs, (size_t)dr.hs_layer * B + b);
@@ -2531,6 +2555,7 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
         float f_sz[5], f_sr[5];
 #endif
         const double ibb = 1.0 / bbn;
+        float e_ur = 0.0f, e_uz = 0.0f, e_tz = 0.0f, e_tr = 0.0f;    // (EIG) the last knot's vector
         auto knot = [&](int kk) {
             // fast path: z[] is the combined, normalised solution (xnorm*y + z)/bb itself;
             // robust path: combine the separately integrated solutions at the knot
@@ -2541,6 +2566,7 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
             } else {
                 aur = (float)z[0]; auz = (float)z[1]; atz = (float)z[2]; atr = (float)z[3];
             }
+            if constexpr (EIG) { e_ur = aur; e_uz = auz; e_tz = atz; e_tr = atr; }
             const float durdz = atr * ixmu - wvno * auz;
             const float duzdz = (atz + wvno * xlamb * aur) * il2m;
             f_mr[kk] = aur * aur; f_mz[kk] = auz * auz;
@@ -2590,6 +2616,8 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
             acc.i1 += (double)(l2m * dmmr + xmu * dmmz);
             acc.i2 += (double)(xmu * dzsr - xlamb * drsz);
         }
+        // the layer's last knot (kk = 0 of its last sublayer) is the top of layer jl
+        if constexpr (EIG) eo.put(jl, e_ur, e_uz, e_tz, e_tr);
         if (kern) {
             const K3 sh = kern_layer_rayleigh(kc, v.rho, xlamb, xmu, wvno, wvnosq, omegsq, k_mr, k_mz, k_rz, k_zr, k_sz, k_sr);
             if (jl == dr.hs_layer) *hold = sh;                       // the half-space terms join it (group_rayleigh)
@@ -2604,10 +2632,11 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
 __device__ unsigned long long sd_restart_count[2];
 #endif
 
-template <bool KERN = false>
+template <bool KERN = false, bool EIG = false>
 SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int b, int n,
                                 float T, float c, float ratio, double *dbg = nullptr,
-                                const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float *kscale = nullptr, int *khs = nullptr)
+                                const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float *kscale = nullptr, int *khs = nullptr,
+                                const EOut eo = EOut{nullptr, 1, 0}, EUnit *eu = nullptr)
 {
 #pragma clang fp contract(off)
     const float lnT = logf(1.0f / T);
@@ -2629,6 +2658,7 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     const float cw = c / wvno;                                        // (KERN) c / k
     K3 hold{0.0f, 0.0f, 0.0f};                                        // (KERN) share of the layer that holds the half space
     if (KERN) { *kscale = 0.0f; *khs = dr.hs_layer; }                 // no factor yet: the consumer writes zeros
+    if constexpr (EIG) *eu = EUnit{1.0f, -1, 0.0f, 0.0f, 0.0f};       // nothing yet: zero rows, zero integrals
     float wat_a = 0.0f, wat_r = 0.0f;                                 // (KERN) the water layer's own share
     if (wet) {                                                        // surfa.f:879-910
         const float d1 = top.d;
@@ -2759,8 +2789,10 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         // rounding noise the fastest-growing solution picks up on the way (<= 1e7 * 1e-16).
         for (int i = 0; i < 4; ++i) { z[i] = (xnorm * y0[i] + z0[i]) / bbn; y[i] = 0.0; }
         aur = (float)z[0]; auz = (float)z[1];
-        rayleigh_sweep<2, KERN>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                y, z, false, own, xnorm, bbn, acc, ko, cw, &hold);
+        // (EIG) the top of the effective half space is the start vector itself: the reference's entry mmax (surfa.f:1145-1148)
+        if constexpr (EIG) if (dr.nreg_hs <= 0) eo.put(dr.hs_layer, aur, auz, (float)z[2], (float)z[3]);
+        rayleigh_sweep<2, KERN, EIG>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, false, own, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo);
     } else {
         // Robust path (thick structure / short period: the solutions grow by up to ~1e27 and the
         // rounding noise excited on the way up is far larger than the answer).  The reference stays
@@ -2773,8 +2805,11 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         for (int i = 0; i < 4; ++i) { y[i] = y0[i]; z[i] = z0[i]; }
         aur = (float)((xnorm * y0[0] + z0[0]) / bbn);
         auz = (float)((xnorm * y0[1] + z0[1]) / bbn);
-        rayleigh_sweep<2, KERN>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                y, z, true, false, xnorm, bbn, acc, ko, cw, &hold);
+        if constexpr (EIG)
+            if (dr.nreg_hs <= 0)
+                eo.put(dr.hs_layer, aur, auz, (float)((xnorm * y0[2] + z0[2]) / bbn), (float)((xnorm * y0[3] + z0[3]) / bbn));
+        rayleigh_sweep<2, KERN, EIG>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, true, false, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo);
     }
     if (wet && !any_solid) { aur = ratio; auz = 1.0f; }              // label 77777, surfa.f:1140-1144
     {   // label 7002, surfa.f:1145-1186
@@ -2806,13 +2841,26 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     if (dbg) { dbg[10] = acc.i0; dbg[11] = acc.i1; dbg[15] = acc.i2; }
     const float s0 = (float)acc.i0, s1 = (float)acc.i1, s2 = (float)acc.i2;
     if (KERN) *kscale = 1.0f / (-2.0f * (wvno * s1 + s2));           // 1 / (dL/dk), surfa.f:1203-1207: applied by the consumer
+    if constexpr (EIG) {
+        // The surface entry is SET, not integrated: (ratio, 1, 0, 0) (surfa.f:1231-1245).  Under a water layer the
+        // reference's first entry is the sea floor, dept1(1) = d(1), with the water's normal traction: (ratio, 1, tzz, 0)
+        // (surfa.f:1232, 1244) - caller layer 1; the sea surface itself, which the reference does not form, is zero.
+        if (wet) {
+            eo.put(0, 0.0f, 0.0f, 0.0f, 0.0f);
+            if (dr.hs_layer >= 1) eo.put(1, ratio, 1.0f, tzz, 0.0f);
+        } else {
+            eo.put(0, ratio, 1.0f, 0.0f, 0.0f);
+        }
+        *eu = EUnit{1.0f, dr.hs_layer, s0, s1, s2};
+    }
     return (wvno * s1 + s2) / (omega * s0);                           // surfa.f:1186
 }
 
 // ---- Love, surfa.f:374-606 (all fp32, as the reference) --------------------------------------
-template <bool KERN = false>
+template <bool KERN = false, bool EIG = false>
 SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, int n,
-                            float T, float c, const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float *kscale = nullptr, int *khs = nullptr)
+                            float T, float c, const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float *kscale = nullptr, int *khs = nullptr,
+                            const EOut eo = EOut{nullptr, 1, 0}, EUnit *eu = nullptr)
 {
     const float lnT = logf(1.0f / T);
     int ndiv = 5;
@@ -2837,6 +2885,7 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
         return K3{2.0f * v.rho * v.b * cw * dldm * ch.dbdb, 0.0f, cw * (dldr + v.b * v.b * dldm) * ch.rfac};
     };
     if (kern) { *kscale = 0.0f; *khs = dr.hs_layer; }
+    if constexpr (EIG) *eu = EUnit{1.0f, -1, 0.0f, 0.0f, 0.0f};       // nothing yet (attempts exhausted: zero rows, zero integrals)
     float ut0 = 1.0f;
     for (int attempt = 0; attempt < 16; ++attempt) {
         float ut = ut0;
@@ -2853,6 +2902,9 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
         // the half space itself (surfa.f:502-512): int u^2 = 1/(2 rb), int (du/dz)^2 = rb/2 - like the reference's sumi0 /
         // sumi1 start values not scaled with ut0^2
         if (kern && rbh > 0.0f) hold = kern_layer(dr.hs_layer, nraw, hsv, dm0, 0.5f * rbh);
+        // (EIG) the top of the effective half space: amp(mmax), stress(mmax) (surfa.f:499-500).  A retry after an overflow
+        // (ut0 / 1e5) rewrites every store of the failed attempt.
+        if constexpr (EIG) if (dr.nreg_hs <= 0) eo.put2(dr.hs_layer, ut, tq);
         for (int jl = dr.hs_layer; jl >= 0 && !overflow; --jl) {
             const LayerRaw raw = nraw;
             if (jl > 0) nraw = layer_load(mdl, fs, (size_t)(jl - 1) * B + b);
@@ -2911,6 +2963,7 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
                     k_sm += (dz / 22.5f) * (7.0f * (smm[0] + smm[4]) + 32.0f * (smm[1] + smm[3]) + 12.0f * smm[2]);
                 }
             }
+            if constexpr (EIG) if (!overflow) eo.put2(jl, ut, tq);   // after the layer's last sublayer: its top
             if (kern && !overflow) {
                 const K3 sh = kern_layer(jl, raw, v, k_dm, k_sm);
                 if (jl == dr.hs_layer) { hold.b += sh.b; hold.r += sh.r; }
@@ -2924,14 +2977,26 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
         }
         sumi0 = sumi0 / (ut * ut);
         sumi1 = sumi1 / (ut * ut);
+        if constexpr (EIG) {
+            // The surface entry is SET: (1, 0) (surfa.f:627-628) - stored as (ut, 0), which the consumer's division by ut
+            // makes exactly (1, 0).  Under a water layer, which LEIGEN skips (surfa.f:524, 579), ut is the value at the sea
+            // floor, the reference's first entry (dept1(1) = d(1), surfa.f:626): caller layer 1; the sea surface is zero.
+            if (!(top.b > 0.0f)) {
+                eo.put2(0, 0.0f, 0.0f);
+                if (dr.hs_layer >= 1) eo.put2(1, ut, 0.0f);
+            } else {
+                eo.put2(0, ut, 0.0f);
+            }
+            if (ut != 0.0f && fin(ut)) *eu = EUnit{ut, dr.hs_layer, sumi0, sumi1, 0.0f};
+        }
         return sumi1 / (c * sumi0);                                   // surfa.f:606
     }
     return 0.0f;
 }
 
 // KERN: also write the analytic partials (A.kb/ka/kr).  The plain variant is held to 168 VGPRs (three
-// wavefronts per SIMD instead of two).
-template <int KIND, bool KERN>
+// wavefronts per SIMD instead of two).  EIG: also store the eigenfunction at every layer top and the energy integrals (K2d).
+template <int KIND, bool KERN, bool EIG = false>
 #ifndef SD_GROUP_WAVES
 #define SD_GROUP_WAVES 3
 #endif
@@ -2988,13 +3053,27 @@ void surfdisp_group_kernel(GroupArgs A)
     float kscale = 0.0f;
     int khs = -1;
     float ugr = 0.0f;
+    EOut eo{nullptr, 1, 0};
+    EUnit eu{1.0f, -1, 0.0f, 0.0f, 0.0f};
+    if constexpr (EIG) {                                    // layer-major scratch [4][Lmax][P][B]: coalesced
+        eo.p = A.escr + idx;
+        eo.stride = (size_t)P * B;
+        eo.plane = (size_t)A.Lmax * P * B;
+    }
     if (n >= 2 && k < A.nsolved[b]) {
         const size_t fs = (size_t)A.Lmax * B;
         const float T = A.per[k];
         const float c = A.c[o];
-        if (KIND == 2) ugr = group_rayleigh<KERN>(A.mdl, fs, B, b, n, T, c, A.ratio[(size_t)k * B + b],
-                                                  A.dbg ? A.dbg + 16 * o : nullptr, ko, &kscale, &khs);
-        else           ugr = group_love<KERN>(A.mdl, fs, B, b, n, T, c, ko, &kscale, &khs);
+        if (KIND == 2) ugr = group_rayleigh<KERN, EIG>(A.mdl, fs, B, b, n, T, c, A.ratio[(size_t)k * B + b],
+                                                       A.dbg ? A.dbg + 16 * o : nullptr, ko, &kscale, &khs, eo, &eu);
+        else           ugr = group_love<KERN, EIG>(A.mdl, fs, B, b, n, T, c, ko, &kscale, &khs, eo, &eu);
+    }
+    if constexpr (EIG) {
+        // (no finite integrals: zeros, as for an unsolved unit)
+        if (!(fabsf(eu.i0) <= 3.0e38f) || !(fabsf(eu.i1) <= 3.0e38f) || !(fabsf(eu.i2) <= 3.0e38f)) eu = EUnit{1.0f, -1, 0.0f, 0.0f, 0.0f};
+        const size_t PB = (size_t)P * B;
+        A.ediv[o] = eu.div; A.ehs[o] = eu.hs;
+        A.esum[o] = eu.i0; A.esum[PB + o] = eu.i1; A.esum[2 * PB + o] = eu.i2;
     }
     if (KERN) {
         if (!(fabsf(kscale) <= 3.0e38f)) kscale = 0.0f;     // (no finite factor: zeros, as for an unsolved unit)
@@ -3071,6 +3150,72 @@ __global__ __launch_bounds__(256) void surfdisp_kern_transpose_kernel(KernTransp
     if (b0 + bl < B && !zero_only) { sc = A.kscale[(size_t)k * B + b0 + bl]; hs = A.khs[(size_t)k * B + b0 + bl]; }
     for (int il = threadIdx.x / 64; il < 64; il += 4)
         tile[il][bl] = (i0 + il <= hs) ? scr[(size_t)(i0 + il) * PB + (size_t)k * B + b0 + bl] * sc : 0.0f;
+    __syncthreads();
+    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
+        const int bq = t / 64, il = t % 64;
+        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
+    }
+}
+
+// K2d: the eigenfunctions (surfdisp_forward_eigen_device) from the layer-major scratch [4][Lmax][P*B] the EIG group-velocity
+// kernel leaves (EOut / EUnit) to the caller's [B][P][Lmax] rows, through the 64 units x 64 layers LDS tile of K2b (row stride
+// 65 words: the stores run along a row, the loads down a column whose words fall into 64 different banks).  Divides by the
+// unit's divisor as the reference does (amp(l) / ut, surfa.f:580-581; Rayleigh: 1), writes zeros below the unit's deepest
+// layer and for units without one (unsolved periods, bad stacks, degenerate exits), and whole rows.  blockIdx.z: 0 ur (Love:
+// the transverse displacement), 1 uz, 2 tz, 3 tr (Love: the shear traction); Love's uz and tz are rows of zeros.
+// Love's low-amplitude exclusion (surfa.f:588-596): an entry whose layer is at least as fast as the effective half space and
+// whose normalised displacement is below xxmin = 1e-20 is zero, displacement and traction.
+// energy [B][P][4] = (I0, I1, I2, amp), amp = 1 / (2 c U I0) rounded once to fp32, 0 where c is not a solved value: the
+// surface-wave amplification factor.  The reference's amplitude response (surfa.f:608, 1191) is are = ale = amp x
+// 1e-15 / sqrt(6.28318): a constant factor away.
+__global__ __launch_bounds__(256) void surfdisp_eigen_transpose_kernel(EigenTransposeArgs A)
+{
+    __shared__ float tile[64][65];
+    const int B = A.B, P = A.P, Lmax = A.Lmax;
+    const int z = blockIdx.z;
+    float *__restrict__ out = (z == 0) ? A.ur : ((z == 1) ? A.uz : ((z == 2) ? A.tz : A.tr));
+    if (!out) return;                                        // (block-uniform)
+    const bool love = A.kind != 2;
+    const bool zero_only = love && (z == 1 || z == 2);
+    const size_t PB = (size_t)P * B;
+    const float *__restrict__ scr = A.escr + (size_t)(love ? (z == 3 ? 1 : 0) : z) * Lmax * PB;
+    const int nbb = (B + 63) / 64;
+    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
+    const int bl = threadIdx.x % 64;
+    const bool live = b0 + bl < B;
+    const size_t un = (size_t)k * B + b0 + bl;               // (read only where live)
+    float dv = 1.0f; int hs = -1;
+    if (live && !zero_only) { dv = A.ediv[un]; hs = A.ehs[un]; }
+    for (int il = threadIdx.x / 64; il < 64; il += 4) {
+        const int i = i0 + il;
+        float v = 0.0f;
+        if (i <= hs) {
+            v = scr[(size_t)i * PB + un] / dv;
+            if (love) {
+                const float amp = (z == 0) ? v : A.escr[(size_t)i * PB + un] / dv;
+                if (fabsf(amp) < 1.0e-20f) {                 // (rare: only then are the two velocities formed)
+                    const float lnT = logf(1.0f / A.per[k]);
+                    const size_t fs = (size_t)Lmax * B;
+                    const int n = A.nl[b0 + bl];
+                    const float vb = layer_at(A.mdl, fs, (size_t)i * B + b0 + bl, lnT, i == n - 1).b;
+                    const float vh = layer_at(A.mdl, fs, (size_t)hs * B + b0 + bl, lnT, hs == n - 1).b;
+                    if (vb >= vh) v = 0.0f;
+                }
+            }
+        }
+        tile[il][bl] = v;
+    }
+    if (z == 0 && blockIdx.y == 0 && A.energy && threadIdx.x < 64 && live) {
+        float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, amp = 0.0f;
+        if (hs >= 0) {
+            e0 = A.esum[un]; e1 = A.esum[PB + un]; e2 = A.esum[2 * PB + un];
+            const float c = A.c[un], u = A.u[un];
+            if (c > 0.0f) amp = (float)(1.0 / (2.0 * (double)c * (double)u * (double)e0));
+            if (!fin(amp)) amp = 0.0f;
+        }
+        float *e = A.energy + ((size_t)(b0 + bl) * P + k) * 4;
+        e[0] = e0; e[1] = e1; e[2] = e2; e[3] = amp;
+    }
     __syncthreads();
     for (int t = threadIdx.x; t < 64 * 64; t += 256) {
         const int bq = t / 64, il = t % 64;
@@ -3511,6 +3656,13 @@ hipError_t launch_kern_transpose(hipStream_t s, const KernTransposeArgs &a)
     return hipGetLastError();
 }
 
+hipError_t launch_eigen_transpose(hipStream_t s, const EigenTransposeArgs &a)
+{
+    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 4u);
+    hipLaunchKernelGGL(surfdisp_eigen_transpose_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_atten(hipStream_t s, const AttenArgs &a)
 {
     const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)));
@@ -3569,6 +3721,13 @@ hipError_t launch_group(hipStream_t s, int kind, const GroupArgs &a_in)
     g %= 100;
     a.xcd_order = (nblk >= 8 && a.B % 256 == 0 && g > 0) ? g : 0;
     if (a.xcd_order) grid = (((nblk + 7) / 8 + a.xcd_order - 1) / a.xcd_order) * a.xcd_order * 8 * a.P;
+    // (the eigenfunction entry: the plain kernel's EIG instantiation; it writes no partials)
+    if (a.escr && !kern) {
+        if (kind == 2) hipLaunchKernelGGL((surfdisp_group_kernel<2, false, true>), dim3(grid), dim3(256), 0, s, a);
+        else           hipLaunchKernelGGL((surfdisp_group_kernel<1, false, true>), dim3(grid), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    if (a.escr) return hipErrorInvalidValue;
     if (kind == 2 && kern)  hipLaunchKernelGGL((surfdisp_group_kernel<2, true>), dim3(grid), dim3(256), 0, s, a);
     else if (kind == 2)     hipLaunchKernelGGL((surfdisp_group_kernel<2, false>), dim3(grid), dim3(256), 0, s, a);
     else if (kern)          hipLaunchKernelGGL((surfdisp_group_kernel<1, true>), dim3(grid), dim3(256), 0, s, a);

@@ -323,6 +323,43 @@ class BatchPlan:
         _lib.check(rc)
         return self.c, self.u, self.status, dcdb, dcda, dcdr, qinv, gamma, dqdq
 
+    def run_eigen(self, model, periods, kind=2, nlay=None, want_uz=True, want_tz=True, want_tr=True, want_energy=True):
+        """``run`` plus the mode's eigenfunction at the top of every input layer and its energy integrals
+        (``surfdisp_forward_eigen_device``): returns (c, u, status, ur, uz, tz, tr, energy).  c, u, status equal ``run``'s bit
+        for bit (``kind`` may carry the INDEPENDENT / STRICT / scan flags); ur, uz, tz, tr float32 [B, P, L] = horizontal and
+        vertical displacement, normal and shear traction at the TOP of layer i of the earth-flattened, attenuation-corrected
+        stack at the period (Love: ur the transverse displacement, tr the shear traction, uz and tz zeros), normalised to
+        uz = 1 (Love ut = 1) at the top of the first solid layer; energy [B, P, 4] = (I0, I1, I2, 1 / (2 c U I0)).  Zeros below
+        the unit's effective half space, beyond nlay, for unsolved periods and bad stacks.  ``None`` where not requested.
+        The conventions are those of include/surfdisp.h section (5f)."""
+        torch = self.torch
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        ur = mk()
+        uz = mk() if want_uz else None
+        tz = mk() if want_tz else None
+        tr = mk() if want_tr else None
+        energy = torch.empty((self.B, self.P, 4), dtype=torch.float32, device=self.device) if want_energy else None
+        if getattr(self, "eigworkspace", None) is None:        # kept for reuse, as run_kernels' workspace
+            self.eigws_bytes = int(_lib.lib().surfdisp_eigen_workspace_bytes(self.B, self.L, self.P))
+            self.eigworkspace = torch.empty(self.eigws_bytes, dtype=torch.uint8, device=self.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._last_ws = self.eigworkspace
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().surfdisp_forward_eigen_device(
+                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                ptr(self.c), ptr(self.u), ptr(self.status), ptr(ur), ptr(uz), ptr(tz), ptr(tr), ptr(energy),
+                ptr(self.eigworkspace), self.eigws_bytes)
+        _lib.check(rc)
+        return self.c, self.u, self.status, ur, uz, tz, tr, energy
+
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
         own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""

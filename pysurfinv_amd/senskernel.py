@@ -203,8 +203,130 @@ def attenuation_from_kernels(model, periods, c, u, kb, ka=None):
     return qinv, gamma, dqdq
 
 
+_R0 = 6371.0
+_TWOPI32 = float(np.float32(6.2831853072))          # the wavenumber's constant as the solver holds it (surfa.f:871, 874)
+
+
+def flattened_layers(model, period, wtype="R", nlay=None):
+    """The earth-flattened, attenuation-corrected values of every layer of ONE stack at ``period``, float64, from the
+    library's documented formulas (flat1.f:44-68; calcul.f:122-126) on the fp32 inputs: dict(a, b, rho, d) [L] in the
+    regular role - layer i between r_i = R0 - sum_{j<i} h_j and r_n = r_i - h_i:
+
+        dif = (1/r_n - 1/r_i) R0 / ln(r_i/r_n),  qqq = (r_i^p - r_n^p) / (ln(r_i/r_n) R0^p p),  d = R0 ln(r_i / r_n),
+        qsq = qsinv ln(1/T) / pi,  b = Vs (1 + qsq) dif,  a = Vp (1 + qsq (4/3) Vs^2 / Vp^2) dif,  rho = rho qqq,
+
+    p = 2.275 (Rayleigh) | 5 (Love), R0 = 6371; the last layer (index nlay - 1, the half space) has d = 0 and the factors
+    R0 / r_i and (r_i / R0)^p.  model [5, L] (vp, vs, rho, h, 1/Qs)."""
+    m = np.asarray(model, np.float32).astype(np.float64)
+    L = m.shape[1]
+    n = L if nlay is None else int(nlay)
+    p = float(np.float32(5.0 if wtype == "L" else 2.275))
+    vp, vs, rho, h, qs = m
+    bot = np.cumsum(h)
+    r_i, r_n = _R0 - (bot - h), _R0 - bot
+    idx = np.arange(L)
+    with np.errstate(all="ignore"):
+        fltd = np.log(r_i / r_n)
+        dif = np.where(idx < n - 1, (1.0 / r_n - 1.0 / r_i) * _R0 / fltd, _R0 / r_i)
+        qqq = np.where(idx < n - 1, (r_i ** p - r_n ** p) / (fltd * _R0 ** p * p), (r_i / _R0) ** p)
+        d = np.where(idx < n - 1, _R0 * fltd, 0.0)
+        qsq = qs * np.log(1.0 / float(np.float32(period))) / np.pi
+        qpq = qsq * (4.0 / 3.0) * vs * vs / (vp * vp)
+    live = idx < n
+    z = np.zeros(L)
+    return dict(a=np.where(live, vp * (1.0 + qpq) * dif, z), b=np.where(live, vs * (1.0 + qsq) * dif, z),
+                rho=np.where(live, rho * qqq, z), d=np.where(live, d, z))
+
+
+def _expm(A):
+    """exp(A) of a small real matrix: scaling and squaring around a Taylor series, float64."""
+    A = np.asarray(A, np.float64)
+    nrm = np.abs(A).sum(axis=1).max()
+    s = max(0, int(np.ceil(np.log2(max(nrm, 1e-300)))) + 2)
+    X = A / (2.0 ** s)
+    E = np.eye(A.shape[0]); term = np.eye(A.shape[0])
+    for k in range(1, 25):
+        term = term @ X / k
+        E = E + term
+    for _ in range(s):
+        E = E @ E
+    return E
+
+
+def eigen_layer_matrix(lay, i, period, c, wtype="R", frac=1.0, rk4_steps=0):
+    """The exact propagator of layer ``i`` of ``flattened_layers``' dict ``lay``: the matrix that carries the
+    displacement-stress vector of the mode with phase velocity ``c`` at ``period`` UPWARD through ``frac`` of the layer's
+    (flattened) thickness H, exp(-frac H A), float64.  Rayleigh, v = (ur, uz, tz, tr), the system REIGEN integrates
+    (surfa.f:933-940, 960-963; k = omega / c):
+
+        ur' = -k uz + tr / mu,   uz' = k lam ur / (lam + 2 mu) + tz / (lam + 2 mu),
+        tz' = -omega^2 rho uz + k tr,   tr' = (4 k^2 mu (lam + mu) / (lam + 2 mu) - omega^2 rho) ur - k lam tz / (lam + 2 mu);
+
+    Love, v = (ut, tq) (surfa.f:549-550):  ut' = tq / mu,  tq' = (k^2 mu - omega^2 rho) ut.
+
+    ``rk4_steps`` > 0: not the exact map but the one REIGEN itself applies over that distance - that many classical
+    Runge-Kutta steps (surfa.f:955-968: the polynomial I + X + X^2/2 + X^3/6 + X^4/24 of X = -h A per step)."""
+    a, b, rho, H = (float(lay[k][i]) for k in ("a", "b", "rho", "d"))
+    om = _TWOPI32 / float(np.float32(period))
+    k = _TWOPI32 / (float(np.float32(c)) * float(np.float32(period)))
+    mu = rho * b * b
+    if wtype == "L":
+        A = np.array([[0.0, 1.0 / mu], [k * k * mu - om * om * rho, 0.0]])
+    else:
+        lam = rho * (a * a - 2.0 * b * b)
+        a12 = 1.0 / (lam + 2.0 * mu)
+        a13 = k * lam * a12
+        a21 = -om * om * rho
+        a43 = a21 + 4.0 * k * k * mu * (lam + mu) * a12
+        A = np.array([[0.0, -k, 0.0, 1.0 / mu], [a13, 0.0, a12, 0.0], [0.0, a21, 0.0, k], [a43, 0.0, -a13, 0.0]])
+    if rk4_steps:
+        X = -float(frac) * H / int(rk4_steps) * A
+        I = np.eye(A.shape[0])
+        return np.linalg.matrix_power(I + X @ (I + X @ (I + X @ (I + X / 4.0) / 3.0) / 2.0), int(rk4_steps))
+    return _expm(-float(frac) * H * A)
+
+
+def eigen_layer_propagate(model, period, c, layer, v, wtype="R", nlay=None, frac=1.0):
+    """Carry the displacement-stress vector ``v`` ((ur, uz, tz, tr); Love (ut, tq)) given at a depth inside or at the bottom
+    of input layer ``layer`` upward through ``frac`` of that layer's thickness, with the exact propagator of the
+    earth-flattened, attenuation-corrected layer (``flattened_layers``, ``eigen_layer_matrix``), in float64: with
+    ``frac=1`` from the top of layer ``layer + 1`` to the top of layer ``layer`` - what relates consecutive entries of
+    ``eigenfunctions``.  Returns the vector at the upper depth."""
+    lay = flattened_layers(model, period, wtype, nlay)
+    return eigen_layer_matrix(lay, int(layer), period, c, wtype, frac) @ np.asarray(v, np.float64)
+
+
+def eigenfunctions(model, periods, wtype="R", nlay=None):
+    """The mode's eigenfunction at the top of every input layer and its energy integrals, for a whole batch, from ONE
+    forward solve (``surfdisp_forward_eigen_device``): what REIGEN / LEIGEN leave in COMMON /rar/, /rco1/ and /rco/ and
+    the reference never returns.  model: torch float32 [M, 5, L] on a HIP device; periods float32 [P].  Returns a dict:
+    c, u [M, P]; status [M]; Rayleigh ur, uz, tz, tr [M, P, L] (horizontal / vertical displacement, normal / shear traction,
+    uz = 1 at the top of the first solid layer), Love ut, tt (transverse displacement, shear traction, ut = 1 there);
+    I0, I1, I2, amp [M, P] (the energy integrals U is formed from and the amplification factor 1 / (2 c U I0));
+    ztop [M, L] the cumulative depth of every layer's top.  Values are those of the earth-flattened, attenuation-corrected
+    stack at the period; zeros below a unit's effective half space, for unsolved periods and bad stacks."""
+    kind = {"R": 2, "L": 1}[wtype]
+    M, _, L = model.shape
+    plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
+    c, u, st, ur, uz, tz, tr, en = plan.run_eigen(model, periods, kind=kind, nlay=nlay,
+                                                  want_uz=(kind == 2), want_tz=(kind == 2))
+    return _eigen_dict(model, kind, c, u, st, ur, uz, tz, tr, en)
+
+
+def _eigen_dict(model, kind, c, u, st, ur, uz, tz, tr, en):
+    import torch
+    h = model[:, 3, :]
+    out = dict(c=c, u=u, status=st, I0=en[..., 0], I1=en[..., 1], I2=en[..., 2], amp=en[..., 3],
+               ztop=torch.cumsum(h, dim=1) - h)
+    if kind == 2:
+        out.update(ur=ur, uz=uz, tz=tz, tr=tr)
+    else:
+        out.update(ut=ur, tt=tr)
+    return out
+
+
 def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01,
-                     ellipticity=False, attenuation=False):
+                     ellipticity=False, attenuation=False, eigen=False):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
     the partial derivatives REIGEN / LEIGEN form from their energy integrals and never return
     (surfa.f:1130-1135, 1204-1207; 561-565, 584-585), with the chain factors of the attenuation
@@ -224,7 +346,9 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     (0 for a stack without attenuation and at unsolved periods), gamma [M, P] its attenuation coefficient in 1/km, dqdq
     [M, P, L] = d qinv / d (1/Qs of layer i) at fixed eigenfunction (qinv = sum_i dqdq_i qsinv_i, see
     ``attenuation_from_kernels``) and Qapp = 1 / qinv (inf where qinv is 0).  One entry of its own as well: refused
-    together with ``group=True`` or ``ellipticity=True``."""
+    together with ``group=True`` or ``ellipticity=True``.
+    ``eigen=True`` (``surfdisp_forward_eigen_device``, one more solve on the same plan): also the keys of
+    ``eigenfunctions`` - ur, uz, tz, tr (Love ut, tt), I0, I1, I2, amp, ztop."""
     import torch
     kind = {"R": 2, "L": 1}[wtype]
     if ellipticity and kind != 2:
@@ -257,6 +381,12 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     if attenuation:
         out.update(qinv=qinv, gamma=gamma, dqdq=dqdq,
                    Qapp=torch.where(qinv != 0, 1.0 / qinv, torch.full_like(qinv, float("inf"))))
+    if eigen:
+        c0, u0 = c.clone(), u.clone()                       # (the plan's c, u are rewritten by the second solve: same bits)
+        out.update(c0=c0, u0=u0)
+        e = plan.run_eigen(model, periods, kind=kind, nlay=nlay, want_uz=(kind == 2), want_tz=(kind == 2))
+        ed = _eigen_dict(model, kind, *e)
+        out.update({k: v for k, v in ed.items() if k not in ("c", "u", "status")})
     return out
 
 
