@@ -22,20 +22,16 @@ std::atomic<double *> g_dbg{nullptr};    // developer hook, see surfdisp_debug_b
 struct EnvKnobs {
     int team = 0;                 // SURFDISP_TEAM
     int team_love = 0;            // SURFDISP_TEAM_LOVE (developer knob): lanes per stack of Love root searches only
-    size_t overlap_max = 64u * 1024u;   // SURFDISP_OVERLAP_MAX
     size_t lds_budget = 44u * 1024u;    // SURFDISP_LDS_BUDGET (developer knob): root-search LDS per 256 lanes
     size_t lds_budget_pipelined = 44u * 1024u;   // SURFDISP_LDS_BUDGET_PIPELINED (developer knob): ... of a SURFDISP_PIPELINED launch (64 KB until r03)
     float refine_wtol = 1.2e-3f;  // SURFDISP_WTOL
     float refine_atol = 1.0e-6f;  // SURFDISP_ATOL
-    float phimax = 0.7853982f;    // SURFDISP_SCAN_PHASE (fast scan only; developer knob)
-    float ambig = 3.0e-5f;        // SURFDISP_AMBIG (developer knob): scan trials below this fraction of their terms' magnitude are
-                                  // evaluated again with the reference's arithmetic (0 = off)
     float ell_ambig = 3.0e-3f;    // SURFDISP_ELL_AMBIG (developer knob): ellipticity closures below this fraction of their terms' magnitude are
                                   // evaluated again with the reference's arithmetic (0 = off)
     float ell_gmax = 25.0f;       // SURFDISP_ELL_GMAX (developer knob): ... and where 2 b^2 / c^2 of the stack's fastest layer exceeds this
     int group_order = -1;         // SURFDISP_GROUP_ORDER (developer knob): workgroup order of the group-velocity kernel (-1: the library's rule; 0: plain period-major; g: XCD-aware, g stack blocks at a time)
     float phimulti = 1.0f;        // SURFDISP_PHIMULTI (developer knob): vertical-phase growth (rad) across a bracket beyond which NEVILL refines it
-    bool fastscan = false;        // SURFDISP_FASTSCAN=1: opt every call of the process into the heuristic scan
+    bool fastscan = false;        // SURFDISP_FASTSCAN=1: opt every call of the process into the count-guided coarse scan
     int device = 0;               // SURFDISP_DEVICE (fast_surf_)
     int balance = -1;             // SURFDISP_BALANCE (developer knob): wavefront priority by progress, -1 = automatic
     int lockstep = -1;            // SURFDISP_LOCKSTEP (developer knob): -1 = automatic (on), 0 / 1, 2 = also for (stack, period) units
@@ -45,22 +41,14 @@ struct EnvKnobs {
     long host_chunk_layers = 327680;   // SURFDISP_HOST_CHUNK (developer knob): layers' worth of stacks per chunk
     int host_pipeline = 1;        // SURFDISP_HOST_PIPELINE (developer knob): 0 = large host-buffer calls as one chunk
     int rows_min_team = 8;        // SURFDISP_ROWS_MIN_TEAM (developer knob): teams of at least this many lanes rebuild from the row copy
-#ifdef SD_ELL_INKERNEL_WIDE
-    int ell_kernel = 0;           // A/B build: the ellipticity recursions inside the root search for every team size (r02)
-#else
-    int ell_kernel = 1;           // the ellipticity kernel for teams of >= 4 lanes
-#endif
     EnvKnobs()
     {
         if (const char *e = getenv("SURFDISP_TEAM")) team = atoi(e);
         if (const char *e = getenv("SURFDISP_TEAM_LOVE")) team_love = atoi(e);
-        if (const char *e = getenv("SURFDISP_OVERLAP_MAX")) overlap_max = (size_t)atol(e);
         if (const char *e = getenv("SURFDISP_LDS_BUDGET")) lds_budget = lds_budget_pipelined = (size_t)atol(e);
         if (const char *e = getenv("SURFDISP_LDS_BUDGET_PIPELINED")) lds_budget_pipelined = (size_t)atol(e);
         if (const char *e = getenv("SURFDISP_WTOL")) refine_wtol = (float)atof(e);
         if (const char *e = getenv("SURFDISP_ATOL")) refine_atol = (float)atof(e);
-        if (const char *e = getenv("SURFDISP_SCAN_PHASE")) phimax = (float)atof(e);
-        if (const char *e = getenv("SURFDISP_AMBIG")) ambig = (float)atof(e);
         if (const char *e = getenv("SURFDISP_PHIMULTI")) phimulti = (float)atof(e);
         if (const char *e = getenv("SURFDISP_GROUP_ORDER")) group_order = atoi(e);
         if (const char *e = getenv("SURFDISP_ELL_AMBIG")) ell_ambig = (float)atof(e);
@@ -103,7 +91,7 @@ struct Carve {
     int *nl, *nsolved, *hist;
     float *fsafe, *ovf;
     int *fb_count, *fb_list;
-    int *amb_count;       // [1] scan trials evaluated again with the reference's arithmetic (behind fb_count: zeroed with it)
+    int *amb_count;       // [2] brackets sent to NEVILL by the phase rule, ellipticities evaluated again (behind fb_count: zeroed with it)
     size_t total;
 };
 
@@ -128,7 +116,7 @@ Carve carve(void *base, int B, int Lmax, int P)
     return c;
 }
 
-int pick_team(int B, int Lmax, bool need_ratio = true, bool pipelined = false, int kind = SURFDISP_KIND_RAYLEIGH)
+int pick_team(int B, int Lmax, bool pipelined = false, int kind = SURFDISP_KIND_RAYLEIGH)
 {
     int G = g_team_override.load(std::memory_order_relaxed);
     if (G == 0 && kind == SURFDISP_KIND_LOVE) G = knobs().team_love;
@@ -168,9 +156,9 @@ int pick_team(int B, int Lmax, bool need_ratio = true, bool pipelined = false, i
     while (p2 * 2 <= G) p2 *= 2;
     G = p2;
     // The working stacks of a workgroup's 256/G teams are what limits the workgroups per CU (one slot each: since r03 the
-    // ellipticities of teams of >= 4 lanes come from their own kernel; need_ratio only sizes the second slot of an A/B build
-    // with -DSD_ELL_INKERNEL_WIDE): keep them within 44 KB per 256 lanes, i.e. at least three workgroups = wavefronts per
-    // SIMD, normally four - a wider team wastes fewer evaluations than a half-empty SIMD costs (scripts/sweep_team.py,
+    // ellipticities of teams of >= 4 lanes come from their own kernel): keep them within 44 KB per 256 lanes, i.e. at least
+    // three workgroups = wavefronts per SIMD, normally four - a wider team wastes fewer evaluations than a half-empty SIMD
+    // costs (scripts/sweep_team.py,
     // profiles/r02e/sweep_team.txt; re-checked on the r03 kernels, every auto choice within 1 % of the best forced size).
     const size_t per256 = 256 / SD_PHASE_BLOCK;        // the budget is per 256 lanes
     // (until r03 a caller that keeps another batch in flight - SURFDISP_PIPELINED, the joint Rayleigh + Love plan - got 64 KB =
@@ -178,18 +166,9 @@ int pick_team(int B, int Lmax, bool need_ratio = true, bool pipelined = false, i
     // (r03: with the teams of a wavefront in lock step the wider team wins there too - joint solve of 16 384 x L64, Rayleigh
     // teams of 16 instead of 8: 5.59 -> 5.32 ms - so the budget is the same 44 KB; SURFDISP_LDS_BUDGET_PIPELINED restores 64 KB)
     const size_t budget = pipelined ? knobs().lds_budget_pipelined : knobs().lds_budget;
-    auto lds_of = [&](int g) { return sd::phase_lds_bytes(Lmax, g, need_ratio && g >= 4, kind) * per256; };
+    auto lds_of = [&](int g) { return sd::phase_lds_bytes(Lmax, g, kind) * per256; };
     while (G < 64 && lds_of(G) > budget) G *= 2;
     return G;
-}
-
-// A/B builds with -DSD_ELL_INKERNEL_WIDE only (the r02 arrangement): the second LDS slot (ellipticity of period k
-// evaluated inside the first scan pass of period k+1) saves one pass per period but doubles the workgroup's LDS
-// (measured in r02: on at 49 KB is 7-19 % faster than off, on at 74 KB / 147 KB is 9 % / 38 % slower).
-static bool use_overlap(int Lmax, int G)
-{
-    const size_t cap = knobs().overlap_max;
-    return G >= 4 && sd::phase_lds_bytes(Lmax, G, true, SURFDISP_KIND_RAYLEIGH) * (256 / SD_PHASE_BLOCK) <= cap;
 }
 
 int check_args(int B, int Lmax, int P, int kind, const void *model, const void *per,
@@ -247,13 +226,10 @@ int surfdisp_get_team(int B, int Lmax) { return surfdisp_get_team2(B, Lmax, 1, S
 // OR'd in; P: periods, used by the independent decomposition) - what forward_device_impl computes
 int surfdisp_get_team2(int B, int Lmax, int P, int kind)
 {
-    const bool phase_only = (kind & SURFDISP_PHASE_ONLY) != 0, indep = (kind & SURFDISP_INDEPENDENT) != 0;
-    const bool pipelined = (kind & SURFDISP_PIPELINED) != 0, strict = (kind & SURFDISP_STRICT) != 0;
+    const bool indep = (kind & SURFDISP_INDEPENDENT) != 0, pipelined = (kind & SURFDISP_PIPELINED) != 0;
     const int wave = kind & ~SD_KIND_FLAGS;
-    const bool want_ell = (wave == SURFDISP_KIND_RAYLEIGH) && !phase_only;
     const long units = (indep ? (long)B * (P > 0 ? P : 1) : (long)B) * ((pipelined && wave != SURFDISP_KIND_LOVE) ? 2 : 1);
-    const bool ell_k_ok = want_ell && knobs().ell_kernel != 0 && !strict;
-    return pick_team((int)(units > 0x3fffffff ? 0x3fffffff : units), Lmax, want_ell && !ell_k_ok, pipelined, wave);
+    return pick_team((int)(units > 0x3fffffff ? 0x3fffffff : units), Lmax, pipelined, wave);
 }
 
 // developer hook (not in include/surfdisp.h): device buffer of B*P*16 doubles receiving
@@ -363,7 +339,7 @@ int surfdisp_workspace_fallback_count(void *stream, const void *workspace, int B
 }
 
 // introspection: {stacks handed to the exact fallback kernel, brackets sent to NEVILL because the vertical phase grows by more
-// than SURFDISP_PHIMULTI across them (-DSD_AMBIG builds: + scan trials evaluated again), ellipticities evaluated again with the
+// than SURFDISP_PHIMULTI across them, ellipticities evaluated again with the
 // reference's arithmetic} of the last solve on `workspace`.  Waits for `stream`.
 int surfdisp_workspace_counters(void *stream, const void *workspace, int B, int Lmax, int P, int *counts3)
 {
@@ -413,7 +389,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     const bool indep = (kind & SURFDISP_INDEPENDENT) != 0;
     const bool pipelined = (kind & SURFDISP_PIPELINED) != 0;
     // the reference's point-by-point scan unless the caller (flag) or the process (environment) opted into the
-    // heuristic one; SURFDISP_EXACTSCAN (ABI 1) is accepted and wins over both
+    // count-guided coarse one; SURFDISP_EXACTSCAN (ABI 1) is accepted and wins over both
     const EnvKnobs &kn = knobs();
     const bool strict = (kind & SURFDISP_STRICT) != 0;
     const bool exactscan = (kind & SURFDISP_EXACTSCAN) != 0;
@@ -422,11 +398,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     kind &= ~SD_KIND_FLAGS;
     // Love: the coarse scan with its Sturm-count certificate (phase_body, CERT) is the DEFAULT - it returns the bracket the
     // point-by-point scan returns, by a theorem, not a heuristic; SURFDISP_EXACTSCAN / SURFDISP_CERTSCAN=0 walk every point
-#if defined(SD_RCERT) && SD_RCERT
-    fastscan = !exactscan && !strict && (kn.certscan != 0 || fastscan);      // (experimental build: the Rayleigh count drives the scan too)
-#else
     if (kind == SURFDISP_KIND_LOVE) fastscan = !exactscan && !strict && (kn.certscan != 0 || fastscan);
-#endif
     // the ellipticity recursions (two more evaluations per period) feed the group-velocity kernel - and the caller who
     // asked for the ratio itself (ABI 3), also in a phase-only call
     const bool want_ell = (kind == SURFDISP_KIND_RAYLEIGH) && (!phase_only || ratio != nullptr);
@@ -439,8 +411,8 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // (and SURFDISP_STRICT) keeps them in-kernel.
     // Teams of two lanes keep them too: their ellipticity pass has both lanes busy, one start vector each (three batches in
     // flight, 65 536 x L10: 34.0 M solves/s in-kernel against 33.6 M with the extra kernel).
-    const bool ell_k_ok = want_ell && kn.ell_kernel != 0 && !strict;
-    const int G = pick_team((int)(units > 0x3fffffff ? 0x3fffffff : units), Lmax, want_ell && !ell_k_ok, pipelined, kind);
+    const bool ell_k_ok = want_ell && !strict;
+    const int G = pick_team((int)(units > 0x3fffffff ? 0x3fffffff : units), Lmax, pipelined, kind);
     const bool ell_k = ell_k_ok && G >= 4;
     const bool ell_in = want_ell && !ell_k;
 
@@ -457,10 +429,9 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     if (ev) SD_HIP(hipEventRecord(ev[0], s));
     SD_HIP(sd::launch_prep(s, kind, pa));
     if (ev) SD_HIP(hipEventRecord(ev[1], s));
-    const float wtol = kn.refine_wtol, atol = kn.refine_atol, phimax = kn.phimax;
+    const float wtol = kn.refine_wtol, atol = kn.refine_atol;
     sd::PhaseArgs ph{B, Lmax, P, w.mdl, w.nl, per, w.ct, ell_in ? w.ratio : nullptr, w.nsolved, status, wtol, atol,
-                     fastscan ? 1 : 0, w.fsafe, (ell_in && use_overlap(Lmax, G)) ? 1 : 0, phimax,
-                     w.ovf, w.fb_count, w.fb_list, kn.balance >= 0 ? kn.balance : ((pipelined && G < 8) ? 0 : 1), strict ? 1 : 0};
+                     fastscan ? 1 : 0, w.fsafe, /* overlap, phimax: layout only */ 0, 0.0f, w.ovf, w.fb_count, w.fb_list, kn.balance >= 0 ? kn.balance : ((pipelined && G < 8) ? 0 : 1), strict ? 1 : 0};
 #ifdef SD_WAVECLOCK
     ph.wclk = reinterpret_cast<unsigned long long *>(g_dbg.load(std::memory_order_relaxed));
 #endif
@@ -468,14 +439,14 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     else          { ph.msrc = w.mdl;  ph.ms_b = 1;         ph.ms_f = (long)Lmax * B; ph.ms_i = B; }
     // (two-lane teams compute their ellipticities themselves but record the history too: the pairs whose closure cancels
     // are redone by the ellipticity kernel)
-    const bool ell_fix = ell_in && !strict && kn.ell_kernel != 0 && kn.ell_ambig != 0.0f;
+    const bool ell_fix = ell_in && !strict && kn.ell_ambig != 0.0f;
     ph.hist = (ell_k || ell_fix || force_hist) ? w.hist : nullptr;   // (force_hist: the ellipticity kernels replay it too)
     ph.lockstep = kn.lockstep >= 0 ? kn.lockstep : 1;
-    ph.ambig = kn.ambig; ph.phimulti = kn.phimulti; ph.amb_count = w.amb_count; ph.ell_ambig = ell_fix ? kn.ell_ambig : 0.0f; ph.ell_gmax = kn.ell_gmax;
+    ph.phimulti = kn.phimulti; ph.amb_count = w.amb_count; ph.ell_ambig = ell_fix ? kn.ell_ambig : 0.0f; ph.ell_gmax = kn.ell_gmax;
     ph.scan_general = kn.leanscan ? 0 : 1;
     SD_HIP(sd::launch_phase(s, kind, G, indep, ph));
     // the exact fallback re-solves what the production kernel listed (normally nothing: idle blocks exit at once)
-    ph.overlap = 0; ph.fast = 0;
+    ph.fast = 0;
     if (ell_k) ph.ratio = w.ratio;                         // ... with its ellipticities in-kernel (marked -1 in hist)
     SD_HIP(sd::launch_phase_exact(s, kind, indep, ph));
     if (ev) SD_HIP(hipEventRecord(ev[2], s));              // [ev1, ev2] = the root search (+ its idle fallback launch)

@@ -36,10 +36,13 @@ struct PhaseArgs {
     int *status;          // [B] or nullptr
     float wtol;           // bracket width below which the root may be read off by interpolation
     float atol;           // ... provided secant and 3-point estimates agree to this (km/s)
-    int fast;             // opt-in heuristic coarse-to-fine scan (SURFDISP_FASTSCAN); 0 = every grid point, the default
+    int fast;             // count-guided coarse-to-fine scan (Love's default, Rayleigh's opt-in SURFDISP_FASTSCAN); 0 = every grid point
     const float *fsafe;   // [B], see PrepArgs
-    int overlap;          // second LDS slot: the ellipticity passes ride in the next period's first scan pass
-    float phimax;         // fast scan: largest vertical-phase increment (rad) of an interval that may be skipped
+    // (always 0 since the r02 second LDS slot and the r01 phase rule went; the two words keep the argument block's layout:
+    // taking them out regroups the kernels' argument loads and changes their instruction counts, which the committed
+    // counter profiles are tagged with - see profiles/variants_removed/README.md)
+    int overlap;
+    float phimax;
     const float *ovf;     // [3][B], see PrepArgs
     int *fb_count;        // [1] number of entries of fb_list
     int *fb_list;         // [teams]: team indices (stack, or period * B + stack in independent mode) for the exact kernel
@@ -54,10 +57,9 @@ struct PhaseArgs {
     // was computed in the kernel itself (exact fallback; the two fields are still recorded for the ellipticity kernels)
     int *hist;
     int lockstep;         // the teams of a wavefront refine and end their periods together (see the root search's main loop)
-    float ambig;          // a scan trial with |value| below this fraction of its terms' magnitude is evaluated again with the
-                          // reference's own arithmetic (0: never)
+    float ambig;          // (always 0, unread: kept for the layout like overlap / phimax)
     float phimulti;       // a bracket across which the vertical phase grows by more than this (rad) goes to NEVILL
-    int *amb_count;       // nullptr, or [2]: number of scan trials / of ellipticities evaluated again (statistics)
+    int *amb_count;       // nullptr, or [2]: brackets sent to NEVILL by the phase rule / ellipticities evaluated again (statistics)
     float ell_ambig;      // in-kernel ellipticity passes: a closure below this fraction of its terms marks the pair for the ellipticity kernel
     float ell_gmax;       // ... and so does g = 2 b^2 / c^2 of the stack's fastest layer beyond this
     int scan_general;     // 1: pure scan passes also run the general pass body (SURFDISP_LEANSCAN=0, for A/B and the tests)
@@ -340,7 +342,7 @@ hipError_t launch_thermal(hipStream_t s, const LayersArgs &a);
 #ifndef SD_PHASE_BLOCK
 #define SD_PHASE_BLOCK 256
 #endif
-size_t phase_lds_bytes(int Lmax, int G, bool overlap, int kind);   // per workgroup of SD_PHASE_BLOCK lanes (kind: 1 Love, 2 Rayleigh)
+size_t phase_lds_bytes(int Lmax, int G, int kind);   // per workgroup of SD_PHASE_BLOCK lanes (kind: 1 Love, 2 Rayleigh)
 size_t phase_exact_lds_bytes(int Lmax, int G, int kind);
 int phase_exact_team(int Lmax, int kind);                // lanes per stack of the exact fallback kernel
 hipError_t launch_phase_exact(hipStream_t s, int kind, bool independent, const PhaseArgs &a);

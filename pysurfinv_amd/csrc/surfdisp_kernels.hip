@@ -18,8 +18,8 @@
 //                               recursion state in registers.  Periods are walked in order inside the
 //                               team (faithful start rule c1 = 0.9*c(k-1), mmax carry-over, failure
 //                               guards, NaN semantics: calcul.f:104-220).  Template flags: INDEP (one
-//                               team per (stack, period), SURFDISP_INDEPENDENT), FAST (opt-in heuristic
-//                               scan, SURFDISP_FASTSCAN), EXACT (the fallback instantiation that restates
+//                               team per (stack, period), SURFDISP_INDEPENDENT), FAST (count-guided coarse
+//                               scan: Love's default, Rayleigh's opt-in SURFDISP_FASTSCAN), EXACT (the fallback instantiation that restates
 //                               DLTAR4 / DLTAR1 / NEVILL statement by statement for the stacks the
 //                               production arithmetic cannot treat faithfully); phase-only calls skip
 //                               the ellipticity recursions.  The teams of a wavefront run in LOCK STEP: all
@@ -468,7 +468,7 @@ __device__ __forceinline__ RState ray_start(const RTrial &t, const int start, co
 // makes the motion-stress system Hamiltonian and Z symmetric).  The zeros are counted LAYER BY LAYER, inside each layer, by
 // Wittrick and Williams' rule (below) - exact in exact arithmetic while every oscillatory layer's S phase stays below pi
 // (scripts/analysis/rayleigh_count_ww*.py: equal to the brute-force count on every such trial of 50 random stacks).  The first
-// attempt (SD_RCERT == 2) looked at the sign of b1 at the interfaces only and missed pairs of zeros inside one layer
+// attempt looked at the sign of b1 at the interfaces only and missed pairs of zeros inside one layer
 // (profiles/r04a/rayleigh_count.txt: 25 of 1.3e8 soak stacks on another root).
 // What the count is NOT: a proof that an interval between two trials with equal counts holds no root.  Along the scan's line
 // omega = const the count rises where the line crosses a branch whose group velocity is positive and FALLS where it is negative:
@@ -477,15 +477,9 @@ __device__ __forceinline__ RState ray_start(const RTrial &t, const int start, co
 // theorem); Rayleigh ones can, and two soak stacks in 1.2e9 did (profiles/r04b/rayleigh_count_ww.txt).  Hence opt-in.
 // kc accumulates the count, kunc flags a trial whose count is not safe (a sign within rounding, an S phase beyond the bound, a
 // liquid layer).
-#ifndef SD_RCERT_PHASE
-#define SD_RCERT_PHASE 3.0f
-#endif
 #ifndef SD_RCERT_SPHASE
 #define SD_RCERT_SPHASE 3.0f    // S phase (rad) of an oscillatory layer up to which its in-layer count is taken (the theorem's bound: pi)
 #endif
-#ifndef SD_RCERT
-#define SD_RCERT 1              // 1: the Rayleigh FAST instantiations (opt-in, SURFDISP_FASTSCAN) are the count-guided scan; 0: the r01
-#endif                          // heuristic scan; 2: the first attempt (interface-only count; profiles/r04a/rayleigh_count.txt)
 // mid(0) and mid(1): called once the step has read all of the layer's values and again after the P coefficients - where the
 // single-register-set loop of delta_rayleigh issues the next layer's loads into the registers the step has freed (not
 // called by a liquid top layer)
@@ -539,12 +533,6 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
     const float E2 = fmaf(sinpr, t2, fmaf(Cy, h2, D * u1));
     const float n1 = (b1 - E1) - E2;
     if (CERT) {
-#if SD_RCERT == 2
-        // (first attempt, kept for the record: sign changes of b1 at the interfaces only - misses pairs of zeros inside a layer)
-        *kc += ((n1 < 0.0f) != (b1 < 0.0f)) ? 1 : 0;
-        *kunc = *kunc || !(fabsf(P.x) + fabsf(qm) < SD_RCERT_PHASE) ||
-                !(fabsf(n1) > 1.0e-4f * (fabsf(b1) + fabsf(E1) + fabsf(E2)));
-#else
         // Zeros of det U_s INSIDE this layer (Wittrick-Williams).  With the surface pair's impedance Z_t at the layer's top and the
         // layer's propagator in blocks, det U_s at depth z below the top vanishes where M(z) = Z_t - K11(z) is singular, K11 = the
         // impedance of the slab clamped at z seen from its top; M(0+) is positive definite and - as long as no clamped-clamped
@@ -571,12 +559,6 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
                 !(fabsf(n1) > 1.0e-4f * (fabsf(b1) + fabsf(E1) + fabsf(E2))) ||
                 !(fabsf(c5) > 1.0e-4f * (fabsf(p1) + fabsf(p2) + 2.0f * fabsf(D))) ||
                 (!dneg && !(fabsf(m11n) > 1.0e-4f * (fabsf(m11a) + fabsf(m11b)))) || !(fabsf(bc) > 0.0f);
-#ifdef SD_DEBUG_COUNT
-        if (csq > SD_DEBUG_COUNT * SD_DEBUG_COUNT && csq < (SD_DEBUG_COUNT + 0.07f) * (SD_DEBUG_COUNT + 0.07f))
-            printf("   layer c %.6f: b1 % .5e n1 % .5e c5 % .5e (p1 % .3e p2 % .3e 2D % .3e) m11n % .5e (%.3e, %.3e) det<0 %d m11<0 %d count %d qm %.3f pm %.3f unsafe %d\n",
-                   sqrtf(csq), b1, n1, c5, p1, p2, D + D, m11n, m11a, m11b, (int)dneg, (int)mneg, *kc, qm, pm, (int)*kunc);
-#endif
-#endif
     }
     const float n3 = fmaf(g, E1, fmaf(g1, E2, h3));
     const float n5 = fmaf(g2, E1, fmaf(g12, E2, h5));
@@ -588,7 +570,7 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
 // (a itself is not needed: every occurrence is a^2, available as 1/ia2); A = the values of layer mmax - 1, rho_last its
 // density, rho_prev the density of layer mmax - 2 (0 when there is none: the state is in that layer's scale)
 // *mag (if given): the sum of the magnitudes of the closure's five terms - |value| far below it means the value is the
-// remainder of a cancellation, i.e. its SIGN is within the rounding of this arithmetic (the scan's ambiguity test)
+// remainder of a cancellation, i.e. its SIGN is within the rounding of this arithmetic (the ellipticity passes' test)
 __device__ __forceinline__ float ray_close(const RState &s, const RTrial &t, const RLyr &A, const float rho_last,
                                            const float rho_prev, const int start, float *mag = nullptr, const bool want_mag = true,
                                            int *kc = nullptr, bool *kunc = nullptr)
@@ -626,11 +608,6 @@ __device__ __forceinline__ float ray_close(const RState &s, const RTrial &t, con
         const float S11 = -zf * rap - sf * s.h4, S12 = zf * zo + sf * s.h3, S22 = -zf * rbp + sf * s.h2;
         const float dq = S11 * S22 - S12 * S12, tp = S11 + S22;
         *kc += (dq < 0.0f) ? 1 : ((tp > 0.0f) ? 2 : 0);
-#ifdef SD_DEBUG_COUNT
-        if (csq > SD_DEBUG_COUNT * SD_DEBUG_COUNT && csq < (SD_DEBUG_COUNT + 0.07f) * (SD_DEBUG_COUNT + 0.07f))
-            printf("   half space c %.6f: S11 % .5e (%.3e - %.3e) S12 % .5e S22 % .5e (%.3e + %.3e) det % .5e trace % .5e count %d\n",
-                   sqrtf(csq), S11, -zf * rap, sf * s.h4, S12, S22, -zf * rbp, sf * s.h2, dq, tp, *kc);
-#endif
         // unsafe: the half space not evanescent in P and S, a determinant or - where it matters - a trace within rounding, not finite
         *kunc = *kunc || !(arga > 0.0f) || !(argb > 0.0f) || !(fabsf(dq) > 1.0e-4f * (fabsf(S11 * S22) + S12 * S12)) ||
                 (dq > 0.0f && !(fabsf(tp) > 1.0e-4f * (fabsf(S11) + fabsf(S22)))) || !fin(dq) || !fin(s.b1) || s.b1 == 0.0f;
@@ -649,8 +626,8 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
     int kc_ = 0; bool kunc_ = !count;
     int *const kc = &kc_; bool *const kunc = &kunc_;
     // phi: vertical phase sum_i k d_i sqrt(c^2/v_i^2 - 1) over the layers (and wave types) that are oscillatory
-    // at c -- the WKB mode counter the opt-in fast scan bounds between two coarse points (free: pm and qm are
-    // the recursion's own arguments)
+    // at c -- the WKB mode counter (free: pm and qm are the recursion's own arguments; read by tests/probe only since the
+    // r01 scan that bounded it between two coarse points is gone)
     phi = 0.0f;
     const RTrial t = ray_trial(c, T);
     RState s = ray_start(t, start, (start == 1) ? 0.0f : W_IR(0));
@@ -675,7 +652,7 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
             m += 2;
         }
     } else {
-        // (also the opt-in fast scan's instantiations: their extra scan state put teams of four at 133 VGPRs = three
+        // (also the count-guided scan's instantiations: their extra scan state put teams of four at 133 VGPRs = three
         // wavefronts per SIMD, 27 M solves/s with one batch in flight; single-buffered 122 = four, 36 M.)
         // Teams of two lanes - what a caller with several batches in flight gets (SURFDISP_PIPELINED) - keep ONE register
         // set in flight: their wavefronts share SIMDs with the group-velocity kernel's (168 VGPRs), and three of them
@@ -712,11 +689,6 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
 // overflows to inf, and every inf - inf turns NaN, exactly where the reference's does (which decides the "roots" the
 // reference returns next to the overflowed region).  Working stack of that kernel: a in the W_IA2 slot.
 // start = 1 -> dispersion (-bb1); 2 / 3 -> the two ellipticity passes (bb1), combined by the caller (surfa.f:360-363).
-// AINV: called on the PRODUCTION kernel's working stack, whose W_IA2 slot holds 1/a^2 (to 1 ulp) instead of a: a is taken
-// as 1/sqrt of it (IEEE) - the reference's arithmetic on a P velocity that may differ from its own in the last bit, which
-// moves the value ten times less than the production recursion's rounding does (the scan's ambiguity re-evaluation).
-// (The production kernel inlines the body: a call would cost its wavefronts a fourth of their registers - the calling
-// convention's - and with them the fourth wavefront per SIMD.)
 struct RefLyr { float a, b, rho, d; };
 // GET: m -> the working stack's values of layer m (called for m = 0 .. mmax - 1, once each, in order)
 template <class GET>
@@ -807,17 +779,10 @@ __device__ __forceinline__ float delta_rayleigh_ref_gen(GET get, const int mmax,
     const float bb1 = h11 * b1 + h12 * b2 + 2.0f * h13 * b3 + h14 * b4 + h15 * b5;
     return (start == 1) ? -bb1 : bb1;
 }
-template <bool AINV>
-__device__ __forceinline__ float delta_rayleigh_ref_body(const float *wq, const int LS, const int S,
-                                                         const int mmax, const float c, const float t, const int start)
-{
-    return delta_rayleigh_ref_gen([&](int m) { return RefLyr{AINV ? 1.0f / sqrtf(W_IA2(m)) : W_IA2(m), W_B(m), W_R(m), W_D(m)}; },
-                                  mmax, c, t, start);
-}
 __device__ __noinline__ float delta_rayleigh_ref(const float *wq, const int LS, const int S,
                                                  const int mmax, const float c, const float t, const int start)
 {
-    return delta_rayleigh_ref_body<false>(wq, LS, S, mmax, c, t, start);
+    return delta_rayleigh_ref_gen([&](int m) { return RefLyr{W_IA2(m), W_B(m), W_R(m), W_D(m)}; }, mmax, c, t, start);
 }
 
 // Love: Thomson-Haskell 2-vector from the half space up, surfa.f:143-179 (production kernel; the reference's own
@@ -984,8 +949,8 @@ enum { ST_SCAN = 0, ST_REFINE = 1, ST_ELLIP = 2, ST_DONE = 3, ST_NEVILL = 4, ST_
 //   period, on a freshly built full stack.  P times more teams, P times shorter dependency chain:
 //   the mode for small batches; equal to the faithful mode to ~1e-6 on well-behaved (monotone)
 //   stacks, NOT on rough ones (defects 2 and 9) - the caller opts in.
-// FAST = true: opt-in heuristic coarse-to-fine scan (SURFDISP_FASTSCAN; instantiated for teams of 2, 4 and 8 lanes
-// only); FAST = false: every grid point, as the reference - the default, and all larger teams.
+// FAST = true: the count-guided coarse-to-fine scan (Love's default, Rayleigh's opt-in SURFDISP_FASTSCAN; instantiated for
+// teams of 2, 4 and 8 lanes only); FAST = false: every grid point, as the reference - the default, and all larger teams.
 // EXACT = false: the production root search - factorised Rayleigh recursion, team subdivision + interpolation
 //   instead of NEVILL.  Two things those cannot reproduce faithfully:
 //   * a bracket with more than one visible sign change - which of several roots NEVILL lands on depends on its
@@ -1029,24 +994,19 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     const int b = INDEP ? (int)(tg % B) : (int)tg;         // consecutive teams = consecutive stacks
     const int k_own = INDEP ? (int)(tg / B) : 0;           // INDEP: the one period this team solves
     float *wq = w_lds + slot;
-    // second slot: a snapshot of the layers the ellipticity recursion of period k still needs while
-    // the main slot already holds period k+1 (only for teams of >= 4 lanes, see OVERLAP below)
     // the ellipticity (two more recursions per period, surfa.f:360-363) only feeds the group-velocity
     // kernel: a phase-only call (A.ratio == nullptr) skips it altogether
     // Production teams of >= 4 lanes never compute them: surfdisp_ellip_kernel does (one lane per (stack, period)), and
     // their instantiations carry no ellipticity state at all.  In-kernel: the exact fallback and two-lane teams (an
-    // ellipticity pass with both lanes busy).  -DSD_ELL_INKERNEL_WIDE restores the r02 arrangement for A/B builds (two
-    // lanes of a wide team riding in the next period's first scan pass, reading a snapshot in a second LDS slot).
-#ifdef SD_ELL_INKERNEL_WIDE
-    const bool want_ratio = (KIND == 2) && (A.ratio != nullptr);
-    const bool OVERLAP = !EXACT && want_ratio && (G >= 4) && !INDEP && (A.overlap != 0);
-#else
+    // ellipticity pass with both lanes busy).
     constexpr bool ELL_HERE = EXACT || (G < 4);
     const bool want_ratio = ELL_HERE && (KIND == 2) && (A.ratio != nullptr);
+    // What is left of two removed arrangements - OVERLAP / ell_pend / js / had_ell (r02: ellipticity passes riding in the next
+    // period's first scan pass, a snapshot in a second LDS slot) and q0* / p0phi / back0 (r01: the heuristic coarse scan's
+    // look-back) - is constant or never read.  The compiler folds it away, but deleting these statements changes what it
+    // generates for up to 48 instantiations (profiles/variants_removed/README.md): they go with the next counter pass.
     constexpr bool OVERLAP = false;
-#endif
-    float *wq2 = w_lds + (size_t)LS * Lcap + slot;
-    // NEVILL's interpolation table x(1..11), y(1..11) (surfa.f:8) of this team, behind the working stacks
+    // NEVILL's interpolation table x(1..11), y(1..11) (surfa.f:8) of this team, behind the working stacks (A.overlap is 0)
     float *nvx = w_lds + (size_t)((!EXACT && G >= 4 && A.overlap != 0) ? 2 : 1) * LS * Lcap + (size_t)slot * 24, *nvy = nvx + 12;
     // staged fields of this team's stack (SoA copy or rows, see PhaseArgs): field f of layer i at M_AT(f, i)
     const float *__restrict__ mrow = A.msrc + (size_t)b * A.ms_b;
@@ -1067,12 +1027,11 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     bool p0ok = false;                 // p0d was computed with mm_frozen (usable for interpolation)
     bool first = true;
     int status = SURFDISP_OK;
-    // opt-in fast scan (teams of 2..8 lanes): after the first pass of a period the scan advances
-    // FSTRIDE grid points per lane; an interval between two coarse points is skipped only if it is
-    // judged free of sign changes (see below), otherwise its fine points are scanned as usual
-    constexpr int FSTRIDE = (FAST && (KIND == 1 || SD_RCERT) && G <= 4) ? SD_CERT_STRIDE : 4;
-    constexpr bool fastok = FAST && (G >= 2) && (G <= 8);
-    // CERT (Love): the coarse scan's certificate is a theorem IN EXACT ARITHMETIC (instead of the heuristics below) behind fp32
+    // coarse scan (teams of 2..8 lanes): a coarse pass advances FSTRIDE grid points per lane; an interval between two coarse
+    // points is skipped only if the mode counts at its ends certify it (see below), otherwise its fine points are scanned
+    // as usual
+    constexpr int FSTRIDE = (FAST && G <= 4) ? SD_CERT_STRIDE : 4;
+    // CERT (Love): the coarse scan's certificate is a theorem IN EXACT ARITHMETIC behind fp32
     // guards - the "unsafe count" tests - whose margins are soaked, not proved.  At fixed frequency the angle of
     // the pair (displacement, stress) at the surface, followed continuously up from the half space, falls monotonically as
     // the trial velocity rises (Sturm / Pruefer), and a mode sits wherever it passes a multiple of pi: the number of modes
@@ -1087,22 +1046,14 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     // bit on 5.7e8 random stacks (scripts/soak_cert.py).
     // (Rayleigh: the FAST instantiations are opt-in - SURFDISP_FASTSCAN - and run the same coarse scan on the count of ray_step /
     // ray_close, which is exact but not monotone along the scan line where a branch has a zero-group-velocity point: see there.)
-    constexpr bool CERT = fastok && (KIND == 1 || SD_RCERT) && !EXACT;
+    static_assert(!(FAST && EXACT), "the exact fallback walks every grid point");
+    constexpr bool CERT = FAST && (G >= 2) && (G <= 8);
     int p0Kp = 0x40000000;             // Sturm count at p0 (CERT), packed: count + 4096, bit 30 = unsafe
-    // ... and only on stacks where two modes cannot sit within one coarse interval: velocities that never
-    // decrease with depth (no channel waves) and no layer thicker than three wavelengths of the period at
-    // hand (overtones of a thick layer crowd together as (c T / 2h)^2)
-    const float fsafe = (fastok && team_valid) ? A.fsafe[b] : 1.0e30f;
     bool coarse = false;               // this pass scans on the coarse grid
     int fine_left = 1;                 // fine points still to scan before going (back) to coarse
-    // q0ok: the coarse point before p0 (for lane 0); !q0ok (first coarse pass after fine ones): the fine point p0 - dc
-    float q0c = 0.0f, q0d = 0.0f; int q0mm = 0; bool q0ok = false;
-    float p0phi = 0.0f;                // vertical phase (delta_rayleigh) at p0c, valid whenever coarse is set
-    // pending ellipticity of the previous period (OVERLAP): evaluated by lanes 0-1 of the first
-    // scan pass of the next period instead of costing a pass of its own
+    float q0c = 0.0f, q0d = 0.0f; int q0mm = 0; [[maybe_unused]] bool q0ok = false;   // (left over, see OVERLAP)
+    [[maybe_unused]] float p0phi = 0.0f;
     bool ell_pend = false;
-    int ell_k = 0, ell_mm = 2;
-    float ell_c = 1.0f, ell_T = 1.0f;
     // NEVILL's state between two evaluations (c1, del1 = p0c, p0d; c2, del2 = cb, db; c3 = croot)
     int nv_nev = 1, nv_m = 1, nv_ic = 0;
     bool defer = false;                // !EXACT: this stack goes to the exact fallback kernel
@@ -1261,7 +1212,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     // teams only (the headline's pipelined launch: root search 1.39 -> 1.36 ms, profiles/r08a); teams of 4 .. 32 lanes
     // gained nothing measurable from it and the deep-stack c5 leg lost 1 % to the larger kernel, 64 lanes lost a wavefront per
     // SIMD (Love: six more VGPRs).
-#if defined(SD_AMBIG) || defined(SD_DEBUG_TRIALS)
+#ifdef SD_DEBUG_TRIALS
     constexpr bool LEAN = false;
 #else
     constexpr bool LEAN = !FAST && !EXACT && !INDEP && (G == 2);
@@ -1297,22 +1248,17 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 else __builtin_amdgcn_s_setprio(0);
             }
         }
-        const bool lean = LEAN && !OVERLAP && A.scan_general == 0 && __all(st == ST_SCAN || st == ST_WREF || st == ST_DONE);
+        const bool lean = LEAN && A.scan_general == 0 && __all(st == ST_SCAN || st == ST_WREF || st == ST_DONE);
         // ---------------------------------------------------------------- choose the trial point
         float cj = 1.0f;
         int mmj = 2, start = 1;
         bool eval = (st != ST_DONE) && (st != ST_WREF) && (st != ST_WEND);
-        const float *wl = wq;                                  // the stack this lane's recursion reads
-        float Tl = T;
-        const bool ell_lane = OVERLAP && ell_pend && (st == ST_SCAN) && (j < 2);
         const int js = (OVERLAP && ell_pend && st == ST_SCAN) ? j - 2 : j;   // scan-lane index in the team
-        if (ell_lane) {
-            cj = ell_c; mmj = ell_mm; start = 2 + j; wl = wq2; Tl = ell_T;
-        } else if (st == ST_SCAN) {
+        if (st == ST_SCAN) {
             // exact fp32 grid of the reference: c2 = c1 + dc repeatedly (calcul.f:157,161)
-            const int nadd = (fastok && coarse) ? FSTRIDE * (first ? js : js + 1) : (first ? js : js + 1);   // (CERT may start a period on the coarse grid)
+            const int nadd = (CERT && coarse) ? FSTRIDE * (first ? js : js + 1) : (first ? js : js + 1);   // (CERT may start a period on the coarse grid)
             cj = p0c;
-            if (fastok) {
+            if (CERT) {
 #pragma unroll
                 for (int i = 0; i < FSTRIDE * G; ++i) if (i < nadd) cj = cj + DC;
             } else {
@@ -1369,64 +1315,26 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         }
 #endif
         float vmag = 0.0f;                                     // magnitude of the terms the value is the sum of (production recursion)
-#if defined(SD_AMBIG) && SD_AMBIG == 2
-        bool amb_defer = false;
-#endif
         if (eval) {
-#ifdef SD_AMBIG
-            const bool want_mag = true;
-#else
             const bool want_mag = want_ratio && st == ST_ELLIP;   // (the in-kernel ellipticity passes' cancellation test)
-#endif
-            if (KIND == 2) val = EXACT ? delta_rayleigh_ref(wl, LS, S, mmj, cj, Tl, start)
-                                       : delta_rayleigh<(G != 2) && !FAST, CERT>(wl, LS, S, mmj, cj, Tl, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse);
+            if (KIND == 2) val = EXACT ? delta_rayleigh_ref(wq, LS, S, mmj, cj, T, start)
+                                       : delta_rayleigh<(G != 2) && !FAST, CERT>(wq, LS, S, mmj, cj, T, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse);
             // Love, NEVILL passes of the production kernel: DLTAR1 statement by statement on the production working stack (it holds
             // b, rho, d as the exact kernel's does).  A bracket goes to NEVILL because it may hold several roots, and which of them
             // NEVILL lands on depends on the VALUES it sees (its 10 x rule, its interpolation) - with e^{kd} of hundreds of km of
             // layer the production recursion's values differ from the reference's by whole orders of magnitude, or are inf where
             // those are finite (r04 soak, thick-layer family, Love: 2e-4 of the stacks on another overtone with the production
             // values, 1.4e-2 before there was a NEVILL for such brackets at all).
-#ifndef SD_NO_LOVE_REFNEV
-            else if (!EXACT && (st == ST_NEVILL || st == ST_NEVILL0)) val = delta_love_ref_body(wl, LS, S, mmj, cj, Tl);
-#endif
-            else           val = EXACT ? delta_love_ref(wl, LS, S, mmj, cj, Tl) : delta_love<CERT>(wl, LS, S, mmj, cj, Tl, phj, kcj, kuncj, coarse,
-#ifdef SD_AMBIG
-                                                                                                      &vmag
-#else
-                                                                                                      nullptr
-#endif
-                                                                                                      );   // counts only where they are compared: coarse passes
+            else if (!EXACT && (st == ST_NEVILL || st == ST_NEVILL0)) val = delta_love_ref_body(wq, LS, S, mmj, cj, T);
+            else           val = EXACT ? delta_love_ref(wq, LS, S, mmj, cj, T)
+                                       : delta_love<CERT>(wq, LS, S, mmj, cj, T, phj, kcj, kuncj, coarse);   // counts only where they are compared: coarse passes
         }
-        // (-DSD_AMBIG builds only, see DESIGN.md.)  A scan trial whose value is the remainder of a cancellation - |value| below A.ambig of the terms it is the sum of -
-        // has a SIGN within the rounding of the production recursion, and the scan decides on signs (calcul.f:157-167): a
-        // flipped sign moves the bracket by one grid step onto a neighbouring root or past a pair of close roots (the zero
-        // pattern mismatches of the soaks, 2e-5 of random stacks).  Such a trial is evaluated again with the reference's own
-        // arithmetic (DLTAR4 / DLTAR1 statement by statement) and that value's sign is used.  Rare by construction (counted in
-        // A.amb_count); the wavefront's other lanes wait for it.
-#ifdef SD_AMBIG
-        if (!EXACT && eval && st == ST_SCAN && !ell_lane && A.ambig > 0.0f && fabsf(val) < A.ambig * vmag) {
-#if SD_AMBIG == 2   // (second experiment: the whole stack to the exact fallback kernel - the reference's arithmetic on the reference's own inputs)
-            amb_defer = true;
-#else
-            val = (KIND == 2) ? delta_rayleigh_ref_body<true>(wl, LS, S, mmj, cj, Tl, 1) : delta_love_ref_body(wl, LS, S, mmj, cj, Tl);
-#endif
-            if (A.amb_count) atomicAdd(A.amb_count, 1);
-        }
-#if SD_AMBIG == 2
-        if ((__ballot(amb_defer) & tmask) != 0ull) defer = true;
-        amb_defer = false;
-#endif
-#endif
-        // ... and the in-kernel ellipticity passes (two-lane teams) likewise: a closure that is the remainder of a cancellation
-        // marks the (stack, period) for the ellipticity kernel, which evaluates both passes with the reference's arithmetic
-        // on the replayed working stack (see there)
-#ifdef SD_NO_ELLG
-        const bool ell_amb = false;
-#else
+        // The in-kernel ellipticity passes (two-lane teams): a closure that is the remainder of a cancellation - |value| below
+        // A.ell_ambig of the terms it is the sum of - marks the (stack, period) for the ellipticity kernel, which evaluates both
+        // passes with the reference's arithmetic on the replayed working stack (see there)
         const bool ell_amb = !EXACT && want_ratio && eval && st == ST_ELLIP && A.ell_ambig != 0.0f &&
                              (A.ell_ambig < 0.0f || fabsf(val) < A.ell_ambig * vmag ||
                               cj * cj < ell_c2min);                                       // see surfdisp_ellip_kernel
-#endif
 #ifdef SD_WAVECLOCK
         wcyc_eval += __builtin_readcyclecounter() - we0;
 #endif
@@ -1481,9 +1389,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                     p0ok = (q_pmm == q_mm);
                     passes = 0;
                     st = LOCK ? ST_WREF : ST_REFINE;
-#ifndef SD_NO_PHASEMULTI
                     if (!LOCK && bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
-#endif
                 } else if (fl >= 0) {
                     failed = true;                             // label 250
                 } else {
@@ -1501,9 +1407,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             }
             if (LOCK && !__any(st == ST_SCAN) && st == ST_WREF) {   // (no team ends its period in a scan pass)
                 st = ST_REFINE;
-#ifndef SD_NO_PHASEMULTI
                 if (bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
-#endif
             }
             continue;
         }
@@ -1517,7 +1421,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         const int kpk = CERT ? ((kcj + 4096) | (kuncj ? 0x40000000 : 0)) : 0;          // count | unsafe flag, packed
         const int sKp = CERT ? __shfl(kpk, lm1) : 0;                                   // ... of the previous lane
         const int pKp = (j == 0) ? p0Kp : sKp;
-        const bool searching = ((st == ST_SCAN) || (st == ST_REFINE)) && !ell_lane;
+        const bool searching = ((st == ST_SCAN) || (st == ST_REFINE)) ;
         const bool has_prev = !((st == ST_SCAN) && first && (js == 0));
         auto negnan = [](float x) { return signbit(x) && !(x != x); };   // a NaN compares as positive, see below
         const bool cross = has_prev && (negnan(val) != negnan(pd));
@@ -1528,10 +1432,8 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         bool guard = false;
         if (st == ST_SCAN && has_prev && !cross)               // calcul.f:165-166
             guard = (cj < 0.8f * b1top) || !(cj < W_B(mmj - 1) + 0.3f);
-        // coarse pass: the interval (previous coarse point, this one) may be skipped only if the
-        // secular function has the same sign at both ends, was evaluated with the same effective
-        // half space at the coarse points around it, and ln|Delta| bends so little at BOTH ends of the
-        // interval that no pair of roots can hide in it.  Anything else is rescanned point by point.
+        // coarse pass: the interval (previous coarse point, this one) may be skipped only if both ends were evaluated with the
+        // same effective half space and carry equal, safe mode counts.  Anything else is rescanned point by point.
         bool uncert = false, back0 = false;
         if (CERT) {
             if (coarse && st == ST_SCAN) {
@@ -1542,58 +1444,6 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 const bool low_guard = (pc + DC) < 0.8f * b1top;
                 uncert = has_prev && (near_hs || low_guard || !((pmm == mmj) && fin(pd) && fin(val) && !kuncj && (pKp == kpk)));
             }
-        } else if (fastok) {
-        const int ln1 = (lane + 1) & 63, lm2 = (lane + 62) & 63;
-        const float nx_d = __shfl(val, ln1), sp_d = __shfl(val, lm2);
-        const int nx_mm = __shfl(mmj, ln1), sp_mm = __shfl(mmj, lm2);
-        const float sphi = __shfl(phj, lm1), nphi = __shfl(phj, ln1);
-        // ln(p n / m^2) < 1 for three same-sign values: the second difference of ln|Delta| at the middle point.
-        // A pair of roots between two coarse points lifts it to >= 2.2 at one of them whatever exponential
-        // envelope multiplies the function (soft layers: e^{k d} factors change Delta by orders of magnitude per
-        // coarse step; a test on the second difference of Delta itself, r01i-r01l, is blind there and fires
-        // before most simple roots instead)
-        auto logsd_ok = [](float p, float m, float n) {
-            const float rm = __builtin_amdgcn_rcpf(m);
-            const float a = p * rm, b = n * rm;
-            return (a > 0.0f) && (b > 0.0f) && (a * b < 2.7182818f);
-        };
-        if (coarse && st == ST_SCAN) {
-            const bool has_next = (j < G - 1);
-            const bool has_pp = (j >= 1) || q0ok;
-            const float pp_d = (j >= 2) ? sp_d : ((j == 1) ? p0d : q0d);
-            const int pp_mm = (j >= 2) ? sp_mm : ((j == 1) ? p0mm : q0mm);
-            // right end: with the next point (a last lane's right end is looked at by lane 0 of the next pass, back0
-            // below).  A next point of the other sign means a root in the NEXT interval; two more in this one
-            // would be three modes within two intervals, which the phase rule excludes.
-            const bool nx_same = (negnan(nx_d) == negnan(val));
-            const bool okf = !has_next || ((pmm == mmj) && (mmj == nx_mm) && fin(nx_d) &&
-                                           (nx_same ? logsd_ok(pd, val, nx_d) : (fabsf(nphi - phj) < A.phimax)));
-            // left end: with the coarse point before ...
-            const bool oklog_b = has_pp && logsd_ok(pp_d, pd, val);
-            const bool okb = !has_pp || ((pp_mm == pmm) && (pmm == mmj) && fin(pp_d) && oklog_b);
-            // ... or, in the first coarse pass after fine ones, with the fine point before p0: the slope of
-            // ln|Delta| over the last fine step against the slope over this interval (a pair close behind p0
-            // bends it by 1.2-2.3 per fine step; 0.5 is allowed)
-            bool oke = true;
-            if (j == 0 && !q0ok) {
-                const float rf = pd * __builtin_amdgcn_rcpf(q0d), rc = val * __builtin_amdgcn_rcpf(pd);
-                const float rf2 = rf * rf;
-                const float x = rc * __builtin_amdgcn_rcpf(rf2 * rf2);
-                oke = (q0mm == pmm) && (pmm == mmj) && (rf > 0.0f) && (rc > 0.0f) && (x > 0.135f) && (x < 7.39f);
-            }
-            // the secular function is analytic in c except at the half-space velocity (its closure is
-            // linear in sqrt|c^2/b^2 - 1|): within two coarse steps of that branch point nothing is skipped
-            const bool near_hs = !(cj < W_B(mmj - 1) - 2.0f * (float)FSTRIDE * DC);
-            // ... and the interval must be too short for two modes: consecutive modes are ~pi apart in the
-            // vertical phase summed over the oscillatory layers, however the stack is built (thick or slow
-            // layers, short periods); the interval may add at most A.phimax (pi/4 by default) to it
-            const float pphi = (j == 0) ? p0phi : sphi;
-            const bool okphi = fabsf(phj - pphi) < A.phimax;
-            uncert = near_hs || !(okf && okb && oke && okphi && fin(pd) && fin(val));
-            // lane 0 also holds the right end of the previous pass's last interval (q0, p0): if that fails the
-            // rescan starts at q0
-            back0 = (j == 0) && q0ok && (cross ? !okphi : !oklog_b);
-        }
         }
         const bool ev = searching && (cross || guard || uncert);
         const unsigned long long em = __ballot(ev) & tmask;
@@ -1605,28 +1455,28 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         const int e_pmm = __shfl(pmm, src);
         const int l_mm = __shfl(mmj, tbase + G - 1);
         const int e_cross = __shfl((int)cross, src);
-        const int t_back0 = fastok ? __shfl((int)back0, tbase) : 0;
+        const int t_back0 = CERT ? __shfl((int)back0, tbase) : 0;
         const int lastl = tbase + G - 1;
         const float l_c = __shfl(cj, lastl), l_d = __shfl(val, lastl);
-        const float l_phi = fastok ? __shfl(phj, lastl) : 0.0f;
+        const float l_phi = CERT ? __shfl(phj, lastl) : 0.0f;
         const int l_Kp = CERT ? __shfl(kpk, lastl) : 0;
         const int e_pKp = CERT ? __shfl(pKp, src) : 0;
         // the values of the team's first two lanes: the two ellipticity recursions, and NEVILL's del3 (every lane of the team
         // evaluated the same c3) - only where some team of the wavefront needs them (not in a scan or refine pass of a c+U call)
         float v0 = 0.0f, v1 = 0.0f;
-        if (__any(st == ST_ELLIP || st == ST_NEVILL || st == ST_NEVILL0 || (OVERLAP && ell_pend && st == ST_SCAN))) { v0 = __shfl(val, tbase); v1 = __shfl(val, (G > 1) ? tbase + 1 : tbase); }
+        if (__any((st == ST_ELLIP) | (st == ST_NEVILL) | (st == ST_NEVILL0))) { v0 = __shfl(val, tbase); v1 = __shfl(val, (G > 1) ? tbase + 1 : tbase); }
         // what only a REFINE pass reads (wavefront-uniform test: in lock step most passes have no refining team):
         // the right neighbour of the crossing lane, the lane before the last one, and - the fourth point of the second
         // three-point estimate - two lanes below / above the crossing lane and two before the last one
         float e_nc = 0.0f, e_nd = 0.0f, pl_c = 0.0f, pl_d = 0.0f, e_ppc = 0.0f, e_ppd = 0.0f, e_n2c = 0.0f, e_n2d = 0.0f,
               pl2_c = 0.0f, pl2_d = 0.0f;
         int pl_mm = 0;
-        if (fastok || __any(st == ST_REFINE)) {
+        if (CERT || __any(st == ST_REFINE)) {
             const int nxt = (src < lastl) ? src + 1 : lastl;
             e_nc = __shfl(cj, nxt); e_nd = __shfl(val, nxt);
             const int pl = (G > 1) ? lastl - 1 : lastl;
             pl_c = __shfl(cj, pl); pl_d = __shfl(val, pl);
-            if (fastok) pl_mm = __shfl(mmj, pl);
+            if (CERT) pl_mm = __shfl(mmj, pl);
             const int lm2s = (src - 2 >= tbase) ? src - 2 : tbase;
             e_ppc = __shfl(cj, lm2s); e_ppd = __shfl(val, lm2s);
             const int nx2 = (src + 2 <= lastl) ? src + 2 : lastl;
@@ -1660,11 +1510,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 multi = ncross >= 2;                           // -> NEVILL for this period
             }
         }
-        if (OVERLAP && ell_pend && st == ST_SCAN) {
-            if (j == 0) A.ratio[(size_t)ell_k * B + b] = 0.5f * v1 / v0;   // surfa.f:363
-            ell_pend = false;
-        }
-        if (fastok && st == ST_SCAN && coarse) {
+        if (CERT && st == ST_SCAN && coarse) {
             ++passes;
             if (fl >= 0) {                                     // rescan this interval point by point
                 p0c = e_pc; p0d = e_pd; p0mm = e_pmm;
@@ -1701,21 +1547,17 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 // lanes.  The phase is summed by the team, once per bracket (a layer per lane and turn).
                 // (Lock step: the teams of a wavefront find their brackets in different passes, and a block run for one team
                 // costs the wavefront as much as for all - the phase is summed when all of them leave ST_WREF together, below.)
-#ifdef SD_NO_PHASEMULTI
-                if (EXACT) nevill_start();
-#else
                 if (EXACT || (!LOCK && bracket_phase(p0c, cb, mm_frozen) > A.phimulti)) nevill_start();
-#endif
             } else if (fl >= 0) {
                 failed = true;                                 // label 250
             } else {
                 p0c = l_c; p0d = l_d; p0mm = l_mm; first = false;
                 if (CERT) p0Kp = l_Kp;
-                if (fastok) { p0phi = l_phi; q0d = pl_d; q0mm = pl_mm; }    // pl: the fine point p0 - dc
+                if (CERT) { p0phi = l_phi; q0d = pl_d; q0mm = pl_mm; }    // pl: the fine point p0 - dc
                 if (passes > 100000) failed = true;            // cannot happen: c grows by dc/pass
-                if (fastok) {
+                if (CERT) {
                     fine_left -= had_ell ? G - 2 : G;
-                    if (fine_left <= 0 && (CERT ? nodrop : (fsafe <= 3.0f * p0c * T))) { coarse = true; q0ok = false; }
+                    if (fine_left <= 0 && nodrop) { coarse = true; q0ok = false; }
                     // (CERT: fine passes carry no counts, so the coarse pass starts AT p0 - its first lane evaluates it again)
                     if (CERT && coarse) first = true;
                 }
@@ -1824,12 +1666,8 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 // lanes).  The values are brought to order one by a common power of two first (exact).
                 const float fm = fmaxf(fabsf(p0d), fabsf(db));
                 const int fex = (fm > 0.0f && fin(fm)) ? __builtin_amdgcn_frexp_expf(fm) : 0;
-#ifdef SD_NO_FSCALE
-                const float f0 = p0d, f1 = db, f2 = td;
-#else
                 const float f0 = ldexpf(p0d, -fex), f1 = ldexpf(db, -fex), f2 = ldexpf(td, -fex);
                 ud = ldexpf(ud, -fex);
-#endif
                 auto qt = [](float a, float bq) { return a * __builtin_amdgcn_rcpf(bq); };
                 float ts = qt(-f0 * w, f1 - f0);
                 float t = qt(w * (f0 * f2), (f1 - f0) * (f1 - f2)) + qt(sx * (f0 * f1), (f2 - f0) * (f2 - f1));
@@ -1870,33 +1708,16 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 // cut-off is subdivided until it no longer does (roots lie below it, calcul.f:191).
                 bool accept = !(w > 1.0e-6f) || passes > 64;
                 if (!accept && !(w > A.wtol) && agree) {
-#ifndef SD_NO_KINK
                     accept = !(W_B(mm_frozen - 1) <= cb * 1.000001f);
 #ifdef SD_COUNT_KINK
                     if (j == 0 && A.amb_count && !accept) atomicAdd(A.amb_count + 1, 1);   // (developer statistics: refine passes added by the kink test)
-#endif
-#else
-                    accept = true;
 #endif
                 }
                 if (accept) {
                     croot = p0c + (inside ? t : ts);
                     if (p0c >= 16.0f) fatal = true;                // NEVILL's 50 cycles, see above
                     else if (croot <= W_B(mm_frozen - 1)) {        // calcul.f:191
-                        if (want_ratio) {
-                            if (OVERLAP && k + 1 < P) {
-                                // snapshot the layers the ellipticity recursion reads, then move on:
-                                // the next build overwrites exactly these (first mm_frozen) layers
-                                for (int i = j; i < mm_frozen; i += G) {
-#pragma unroll
-                                    for (int f = 0; f < NFK; ++f)
-                                        wq2[i * LS + f * S] = wq[i * LS + f * S];
-                                }
-                                ell_pend = true; ell_k = k; ell_mm = mm_frozen; ell_c = croot; ell_T = T;
-                                solved = true;
-                            } else { st = ST_ELLIP; sub = 0; }
-                        }
-                        else solved = true;
+                        if (want_ratio) { st = ST_ELLIP; sub = 0; } else solved = true;
                     } else failed = true;
                 }
             }
@@ -1912,7 +1733,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         }
         if (!EXACT && defer) {
             if (j == 0) A.fb_list[atomicAdd(A.fb_count, 1)] = (int)tg;
-            defer = false; st = ST_DONE; ell_pend = false; solved = false; failed = false; fatal = false;
+            defer = false; st = ST_DONE; solved = false; failed = false; fatal = false;
         }
         if (fatal) {
             nsolved = 0; k = 0; status = SURFDISP_NUMERIC; st = ST_DONE; ell_pend = false; solved = false; failed = false;
@@ -1931,9 +1752,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             if (solved) { st = ST_WEND; solved = false; }
             if (!__any(st == ST_SCAN) && st == ST_WREF) {
                 st = ST_REFINE;
-#ifndef SD_NO_PHASEMULTI
                 if (bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();      // (see the bracket branch of the scan)
-#endif
             }
             if (!__any(st == ST_SCAN || st == ST_WREF || st == ST_REFINE || st == ST_NEVILL || st == ST_NEVILL0 || st == ST_ELLIP) && st == ST_WEND)
                 solved = true;
@@ -1944,7 +1763,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         if (solved) {
             if (j == 0) {
                 A.c[(size_t)k * B + b] = croot;                // period-major: coalesced across teams
-                if (want_ratio && !ell_pend) A.ratio[(size_t)k * B + b] = r12;
+                if (want_ratio) A.ratio[(size_t)k * B + b] = r12;
                 // (exact kernel: negative - its ellipticity is final - with the same two fields, for the ellipticity kernels' replay)
                 if (A.hist) A.hist[(size_t)k * B + b] = EXACT ? (int)(0x80000000u | (unsigned)nflat_cur | ((unsigned)mm_frozen << 16))
                                                               : (nflat_cur | (mm_frozen << 16) | (ell_flag ? 0x40000000 : 0));
@@ -2242,10 +2061,7 @@ SD_HD __forceinline__ KC kern_coef(const LayerRaw &raw, const LayerV &v, float l
 // KR: the type the six sums are carried and combined in.  dc/drho is the difference of the kinetic and the two elastic
 // terms, which cancel to ~1e-3 of their size (equipartition): combined in fp32 it came out 6e-4 of a period's peak off
 // the reference's value (tests/golden/ref_partials.npz) - the reference carries them DOUBLE PRECISION (surfa.f:717-722).
-#ifndef SD_KERN_REAL
-#define SD_KERN_REAL double
-#endif
-typedef SD_KERN_REAL KR;
+typedef double KR;
 SD_HD __forceinline__ K3 kern_layer_rayleigh(const KC &kc, float rho, float xlamb, float xmu, float wvno, float wvnosq,
                                              float omegsq, KR dmmr, KR dmmz, KR drsz, KR dzsr, KR smmz, KR smmr)
 {
@@ -2547,13 +2363,7 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
         float f_mr[5], f_mz[5], f_rz[5], f_zr[5];
         constexpr bool kern = KERN;
         KR k_mr = 0, k_mz = 0, k_rz = 0, k_zr = 0, k_sz = 0, k_sr = 0;   // this layer's sums
-#ifdef SD_KERN_BOOLE_INCR
-        // the two strain integrals only the partials need: Boole sums formed knot by knot (weights 7 32 12 32 7), the
-        // knot shared with the next sublayer kept - no five-entry arrays alive across the RK4 steps
-        float w_sz = 0.0f, w_sr = 0.0f, t_sz = 0.0f, t_sr = 0.0f;
-#else
         float f_sz[5], f_sr[5];
-#endif
         const double ibb = 1.0 / bbn;
         float e_ur = 0.0f, e_uz = 0.0f, e_tz = 0.0f, e_tr = 0.0f;    // (EIG) the last knot's vector
         auto knot = [&](int kk) {
@@ -2572,24 +2382,14 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
             f_mr[kk] = aur * aur; f_mz[kk] = auz * auz;
             f_rz[kk] = aur * duzdz; f_zr[kk] = auz * durdz;
             if (kern) {
-#ifdef SD_KERN_BOOLE_INCR
-                t_sz = duzdz * duzdz; t_sr = durdz * durdz;
-                const float wk = (kk == 2) ? 12.0f : ((kk & 1) ? 32.0f : 7.0f);
-                w_sz = fmaf(wk, t_sz, w_sz); w_sr = fmaf(wk, t_sr, w_sr);
-#else
                 f_sz[kk] = duzdz * duzdz; f_sr[kk] = durdz * durdz;
-#endif
             }
         };
         for (int s = 0; s < nstep; ++s) {
             // bottom knot: the top knot of the sublayer below when it belongs to the same layer
             if (s == 0) knot(4);
             else { f_mr[4] = f_mr[0]; f_mz[4] = f_mz[0]; f_rz[4] = f_rz[0]; f_zr[4] = f_zr[0];
-#ifdef SD_KERN_BOOLE_INCR
-                   if (kern) { w_sz = 7.0f * t_sz; w_sr = 7.0f * t_sr; }
-#else
                    if (kern) { f_sz[4] = f_sz[0]; f_sr[4] = f_sr[0]; }
-#endif
             }
 #pragma unroll
             for (int kk = 3; kk >= 0; --kk) {
@@ -2603,11 +2403,7 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
             const float drsz = SD_BOOLE(f_rz), dzsr = SD_BOOLE(f_zr);
             if (kern) {
                 k_mr += dmmr; k_mz += dmmz; k_rz += drsz; k_zr += dzsr;
-#ifdef SD_KERN_BOOLE_INCR
-                k_sz += hq * w_sz; k_sr += hq * w_sr;
-#else
                 k_sz += SD_BOOLE(f_sz); k_sr += SD_BOOLE(f_sr);
-#endif
             }
 #undef SD_BOOLE
             // the sublayer's contributions in fp32 as in the reference (surfa.f:1126-1128); only the
@@ -3540,7 +3336,7 @@ template <int KIND, int G, bool INDEP, bool FAST = false, bool EXACT = false>
 hipError_t launch_phase_g(hipStream_t s, const sd::PhaseArgs &a)
 {
     constexpr int S = SD_PHASE_BLOCK / G;
-    const size_t lds = EXACT ? sd::phase_exact_lds_bytes(a.Lmax, G, KIND) : sd::phase_lds_bytes(a.Lmax, G, a.overlap != 0, KIND);
+    const size_t lds = EXACT ? sd::phase_exact_lds_bytes(a.Lmax, G, KIND) : sd::phase_lds_bytes(a.Lmax, G, KIND);
     auto kern = sd::surfdisp_phase_kernel<KIND, G, INDEP, FAST, EXACT>;
     // raise the dynamic-LDS limit of this instantiation only when a launch needs more than any before it (per
     // device): the attribute call costs ~10 us, visible in launch-bound Metropolis loops
@@ -3575,7 +3371,7 @@ hipError_t launch_phase_x(hipStream_t s, const sd::PhaseArgs &a)
 template <int KIND, bool INDEP>
 hipError_t launch_phase_k(hipStream_t s, const sd::PhaseArgs &a, int G)
 {
-    if (a.fast) {                                  // opt-in fast scan: teams of 2..8 lanes only
+    if (a.fast) {                                  // count-guided coarse scan: teams of 2..8 lanes only
         switch (G) {
             case 2:  return launch_phase_g<KIND, 2, INDEP, true>(s, a);
             case 4:  return launch_phase_g<KIND, 4, INDEP, true>(s, a);
@@ -3599,11 +3395,9 @@ hipError_t launch_phase_k(hipStream_t s, const sd::PhaseArgs &a, int G)
 
 namespace sd {
 
-// working stack per team (+ the ellipticity snapshot slot for teams of >= 4 lanes; allocated for
-// Love too so that one number describes a launch)
-// NEVILL's table x(12), y(12) per team behind the working stack(s)
-size_t phase_lds_bytes(int Lmax, int G, bool overlap, int kind) { const int S = SD_PHASE_BLOCK / G; return ((size_t)((G >= 4 && overlap) ? 2 : 1) * lds_ls(S, kind == 1 ? NFW_LOVE : NFW) * Lmax + (size_t)24 * S) * sizeof(float); }
-// exact fallback: one working stack per team + NEVILL's table x(12), y(12)
+// one working stack per team + NEVILL's table x(12), y(12) behind the working stacks
+size_t phase_lds_bytes(int Lmax, int G, int kind) { const int S = SD_PHASE_BLOCK / G; return ((size_t)lds_ls(S, kind == 1 ? NFW_LOVE : NFW) * Lmax + (size_t)24 * S) * sizeof(float); }
+// exact fallback: the same layout
 size_t phase_exact_lds_bytes(int Lmax, int G, int kind) { const int S = SD_PHASE_BLOCK / G; return ((size_t)lds_ls(S, kind == 1 ? NFW_LOVE : NFW) * Lmax + (size_t)24 * S) * sizeof(float); }
 int phase_exact_team(int Lmax, int kind)
 {

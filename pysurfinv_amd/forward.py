@@ -47,13 +47,13 @@ def forward_batch(model, periods, kind=2, nlay=None, device=0, independent=False
     Host buffers in, host buffers out (C ABI surfdisp_forward_batch).  ``independent=True`` ORs
     SURFDISP_INDEPENDENT into ``kind`` (one team per (stack, period); see include/surfdisp.h).
     The scan evaluates every 0.01 km/s grid point as the reference does; ``fast_scan=True`` opts into the
-    heuristic coarse-to-fine scan (SURFDISP_FASTSCAN); ``strict=True`` solves every stack with the kernel that restates
+    count-guided coarse-to-fine scan (SURFDISP_FASTSCAN); ``strict=True`` solves every stack with the kernel that restates
     the reference's arithmetic statement by statement (SURFDISP_STRICT: a verification mode, several times slower)."""
     if independent:
         kind = int(kind) | _lib.INDEPENDENT
     if strict:
         kind = int(kind) | _lib.STRICT
-    if fast_scan:                                  # opt-in heuristic scan (SURFDISP_FASTSCAN); default: every grid point
+    if fast_scan:                                  # opt-in count-guided scan (SURFDISP_FASTSCAN); default: every grid point
         kind = int(kind) | _lib.FASTSCAN
     L = _lib.lib()
     model = np.ascontiguousarray(model, dtype=np.float32)
@@ -114,7 +114,7 @@ class BatchPlan:
             kind = int(kind) | _lib.INDEPENDENT
         if pipelined:
             kind = int(kind) | _lib.PIPELINED
-        if fast_scan:                                  # opt-in heuristic scan (SURFDISP_FASTSCAN)
+        if fast_scan:                                  # opt-in count-guided scan (SURFDISP_FASTSCAN)
             kind = int(kind) | _lib.FASTSCAN
         if strict:                                     # verification mode (SURFDISP_STRICT): the exact kernel for every stack
             kind = int(kind) | _lib.STRICT

@@ -216,7 +216,7 @@ class MetropolisBatch:
         if independent not in (True, False, "auto"):
             raise ValueError("independent must be True, False or 'auto'")
         self.independent = independent
-        # fast_scan=True: opt into the heuristic coarse-to-fine scan (SURFDISP_FASTSCAN); the default walks every
+        # fast_scan=True: opt into the count-guided coarse-to-fine scan (SURFDISP_FASTSCAN); the default walks every
         # grid point of the reference's scan, so root selection and failures are the reference's on every input
         self.fast_scan = bool(fast_scan)
         # local_rows [C]: row of the model's per-point local-information table (Model1DBatch.set_local_info) each chain

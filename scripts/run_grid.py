@@ -35,7 +35,7 @@ def main():
     ap.add_argument("--chains", type=int, default=50)
     ap.add_argument("--chainL", type=int, default=1000)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--fast-scan", action="store_true", help="opt into the heuristic scan (SURFDISP_FASTSCAN)")
+    ap.add_argument("--fast-scan", action="store_true", help="opt into the count-guided scan (SURFDISP_FASTSCAN)")
     ap.add_argument("--local-keys", default="", help="comma-separated per-point constants (topo, lithoAge, period, <Layer>.<key>): "
                                                      "columns of local_info[n, K] in --input")
     ap.add_argument("--chain-groups", type=int, default=None, help="chain groups per rank (default: 2 from 4 096 chains on)")
