@@ -39,7 +39,9 @@ extern "C" {
                                        surfdisp_lsq_step_device, surfdisp_lsq_resolution_device,
                                        surfdisp_forward_atten_device, surfdisp_atten_workspace_bytes,
                                        surfdisp_forward_eigen_device, surfdisp_eigen_workspace_bytes,
-                                       surfdisp_posterior_profile_device, surfdisp_posterior_workspace_bytes */
+                                       surfdisp_posterior_profile_device, surfdisp_posterior_workspace_bytes,
+                                       surfdisp_posterior_sources_device, surfdisp_posterior_sources_workspace_bytes,
+                                       surfdisp_posterior_predictive_device, surfdisp_posterior_predictive_workspace_bytes */
 #define SURFDISP_NPER_MAX 200      /* fast_surf.pyf:14-19: cvper and outputs are real*4[200] */
 #define SURFDISP_NLAY_MAX 200      /* layers per stack accepted by this library */
 
@@ -566,6 +568,64 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
                                       int *count, double *vs_mean, double *vs_std, double *vs_min, double *vs_max,
                                       int *hist, int *below, int *above,
                                       void *workspace, size_t workspace_bytes);
+
+/* ---- (6g) posterior predictive curves of a whole Metropolis track, added within ABI 4 (csrc/surfdisp_pred.hip): the data-space view
+ *          of the reference's PostPoint.plotDisp(ensemble=True) / Model3D.checkPhaseVelocity - the predicted curves of the final
+ *          rows' models against the observations.  Two entries around the forward solve of (2): the first finds the DISTINCT
+ *          models among the final rows, the second forms weighted statistics of their predictions.
+ *          pysurfinv_amd.posterior.posterior_predictive drives both; predictive_reference is the same statement in numpy.
+ *
+ *   surfdisp_posterior_sources_device
+ *   in:    track, row_stride (>= 3: only misfit and the accepted column are read), true_markov_chain, chainL, prefix as in (6f).
+ *   out:   min_misfit, thres [npoints] fp64, imin, n_final [npoints] int: as in (6f), from the same rules and the same two
+ *          selection kernels.  weight [npoints][R] int: the number of FINAL rows of the point whose parameters are those of row r
+ *          (true_markov_chain != 0: r is the last accepted row at or before them, row 0 counting as accepted; otherwise the final
+ *          flag of row r itself); 0 for every row that is not a source; weight sums to n_final over a point.  n_sources [npoints]
+ *          int: rows with weight > 0.  imin_source [npoints] int: the source row of row imin (the row whose parameters minMod has).
+ *   how:   weight is cleared on the stream, then filled with integer atomics: the result does not depend on their order.  Four
+ *          launches, no host synchronisation, no allocation.  SURFDISP_ERR_INVALID, before anything is launched or written:
+ *          npoints or R below 1, R above 2^30, npoints x slabs beyond 2^31 - 1, row_stride below 3, with chainL > 0: prefix
+ *          outside 1..chainL, R % chainL != 0; a NULL pointer; a workspace smaller than
+ *          surfdisp_posterior_sources_workspace_bytes.
+ *
+ *   surfdisp_posterior_predictive_device
+ *   in:    pred [total] rows of ld >= P floats (device), P <= SURFDISP_PRED_COLS_MAX columns used; failed NULL or [total] bytes
+ *          (nonzero: the row's solve failed); w [total] int weights (a weight <= 0: the row is ignored altogether); offsets
+ *          [npoints + 1] int (device): the rows of point p are offsets[p] .. offsets[p+1] - 1 (clamped to 0..total); total = 0 is
+ *          allowed (pred and w are then not read).  Histogram: vlo, vhi [P] HOST arrays, one range per column (c, U and H/V live
+ *          on different scales), nbins equal bins of [vlo[c], vhi[c]) as in (6f); the ranges travel in the kernel arguments, so the
+ *          arrays may be released when the entry returns.
+ *   out:   an entry COUNTS when its row is not failed, its weight is positive and its value is finite.  count [npoints][P] int:
+ *          the summed weight of the entries that count; mean, std (population: sqrt(sum w (v - mean)^2 / sum w)), min, max
+ *          [npoints][P] fp64, NaN where count is 0 - the unweighted statistics of the list with row i repeated w[i] times.
+ *          n_failed [npoints] int: the summed weight of the failed rows.  hist [npoints][P][nbins], below, above [npoints][P] int
+ *          (summed weights; hist NULL: none of the three is written, nbins / vlo / vhi are not read); the entry clears them.
+ *   how:   two launches (with hist: one launch of the statistics kernel per 64 columns, then the finish), no host
+ *          synchronisation, no allocation, graph-capturable.  A lane is a column; a point's list goes in slabs of SURFDISP_PRED_SLAB_ROWS rows over
+ *          min(ceil(total / SURFDISP_PRED_SLAB_ROWS), SURFDISP_PRED_SLABS_MAX) workgroups per point and chunk of 64 columns
+ *          (workgroup s walks slabs s, s + that number, ...); each keeps fp64 sums about the first counted value, the wavefronts
+ *          and then the workgroups are merged in a fixed order (weighted Chan update): two calls on one input return the same
+ *          bits.  Only the histogram counts are (integer) atomics.  SURFDISP_ERR_INVALID, before anything is launched or written:
+ *          npoints below 1, total below 0, P outside 1..SURFDISP_PRED_COLS_MAX, ld below P; with hist: nbins below 1, a vlo or
+ *          vhi that is not finite, vhi[c] <= vlo[c], vlo / vhi / below / above NULL; a NULL required pointer (pred and w when
+ *          total > 0, offsets, count, mean, std, min, max, n_failed, workspace); a workspace smaller than
+ *          surfdisp_posterior_predictive_workspace_bytes. */
+#define SURFDISP_PRED_SLAB_ROWS 4096
+#define SURFDISP_PRED_SLABS_MAX 16
+#define SURFDISP_PRED_COLS_MAX 1024
+size_t surfdisp_posterior_sources_workspace_bytes(int npoints, int R);
+int surfdisp_posterior_sources_device(void *stream, int npoints, int R, const double *track, long row_stride,
+                                      int true_markov_chain, int chainL, int prefix,
+                                      double *min_misfit, double *thres, int *imin, int *n_final,
+                                      int *weight, int *n_sources, int *imin_source,
+                                      void *workspace, size_t workspace_bytes);
+size_t surfdisp_posterior_predictive_workspace_bytes(int npoints, int total, int P);
+int surfdisp_posterior_predictive_device(void *stream, int npoints, int total, int P, const float *pred, long ld,
+                                         const unsigned char *failed, const int *w, const int *offsets,
+                                         int nbins, const double *vlo, const double *vhi,
+                                         int *count, double *mean, double *std, double *vmin, double *vmax, int *n_failed,
+                                         int *hist, int *below, int *above,
+                                         void *workspace, size_t workspace_bytes);
 
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular

@@ -39,7 +39,9 @@ EXPORTS = (
     "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes",
     "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_forward_eigen_device", "surfdisp_eigen_workspace_bytes",
     "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device",
-    "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
+    "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes",
+    "surfdisp_posterior_sources_device", "surfdisp_posterior_sources_workspace_bytes",
+    "surfdisp_posterior_predictive_device", "surfdisp_posterior_predictive_workspace_bytes", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
     "surfdisp_device_count", "surfdisp_abi_version", "surfdisp_last_error",
     "surfdisp_kernel_name",
 )
@@ -193,6 +195,21 @@ def lib() -> ctypes.CDLL:
         L.surfdisp_posterior_profile_device.argtypes = ([vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_long, vp, ctypes.c_int, vp,
                                                          vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                          ctypes.c_int, ctypes.c_double, ctypes.c_double] + [vp] * 14 + [vp, ctypes.c_size_t])
+    if hasattr(L, "surfdisp_posterior_sources_device"):       # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        # (stream, npoints, R, track, row_stride, true_markov_chain, chainL, prefix, min_misfit, thres, imin, n_final, weight, n_sources,
+        #  imin_source, workspace, workspace_bytes)
+        L.surfdisp_posterior_sources_workspace_bytes.restype = ctypes.c_size_t
+        L.surfdisp_posterior_sources_workspace_bytes.argtypes = [ctypes.c_int] * 2
+        L.surfdisp_posterior_sources_device.restype = ctypes.c_int
+        L.surfdisp_posterior_sources_device.argtypes = ([vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int] + [vp] * 7 + [vp, ctypes.c_size_t])
+        # (stream, npoints, total, P, pred, ld, failed, w, offsets, nbins, vlo (host), vhi (host), count, mean, std, min, max, n_failed,
+        #  hist, below, above, workspace, workspace_bytes)
+        L.surfdisp_posterior_predictive_workspace_bytes.restype = ctypes.c_size_t
+        L.surfdisp_posterior_predictive_workspace_bytes.argtypes = [ctypes.c_int] * 3
+        L.surfdisp_posterior_predictive_device.restype = ctypes.c_int
+        L.surfdisp_posterior_predictive_device.argtypes = ([vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_long, vp, vp, vp,
+                                                            ctypes.c_int, vp, vp] + [vp] * 9 + [vp, ctypes.c_size_t])
     L.surfdisp_thread_release.restype = None
     L.surfdisp_thread_release.argtypes = []
     L.surfdisp_workspace_fallback_count.restype = ctypes.c_int

@@ -870,6 +870,109 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
     return SURFDISP_SUCCESS;
 }
 
+// Source rows of a Metropolis track (csrc/surfdisp_pred.hip; header section (6g)).  Workspace: the slabs' smallest misfits
+// [npoints][nslab] doubles, then four int arrays [npoints][nslab] (as the tail of the (6f) workspace).
+size_t surfdisp_posterior_sources_workspace_bytes(int npoints, int R)
+{
+    if (npoints < 1 || R < 1) return 0;
+    return (size_t)npoints * (size_t)post_slabs(R) * (sizeof(double) + 4 * sizeof(int));
+}
+
+int surfdisp_posterior_sources_device(void *stream, int npoints, int R, const double *track, long row_stride,
+                                      int true_markov_chain, int chainL, int prefix,
+                                      double *min_misfit, double *thres, int *imin, int *n_final,
+                                      int *weight, int *n_sources, int *imin_source,
+                                      void *workspace, size_t workspace_bytes)
+{
+    const char *name = "surfdisp_posterior_sources_device";
+    if (npoints < 1 || R < 1 || R > (1 << 30) || row_stride < 3 || (long)npoints * post_slabs(R) > 0x7fffffffL) {
+        set_err("%s: invalid size (npoints, R >= 1; R <= 2^30; row_stride >= 3; npoints x slabs <= 2^31 - 1)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (!track || !min_misfit || !thres || !imin || !n_final || !weight || !n_sources || !imin_source || !workspace) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    if (chainL > 0 && (prefix < 1 || prefix > chainL || R % chainL != 0)) {
+        set_err("%s: invalid prefix: 1 <= prefix <= chainL and R a multiple of chainL", name); return SURFDISP_ERR_INVALID;
+    }
+    if (workspace_bytes < surfdisp_posterior_sources_workspace_bytes(npoints, R)) {
+        set_err("%s: invalid workspace: smaller than surfdisp_posterior_sources_workspace_bytes", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::PostSourcesArgs S{};
+    sd::PostArgs &a = S.sel;
+    a.npoints = npoints; a.R = R; a.nslab = (int)post_slabs(R);
+    a.tmc = true_markov_chain ? 1 : 0; a.chainL = chainL > 0 ? chainL : 0; a.prefix = prefix;
+    a.row_stride = row_stride; a.track = track;
+    a.min_misfit = min_misfit; a.thres = thres; a.imin = imin; a.n_final = n_final;
+    const size_t units = (size_t)npoints * a.nslab;
+    a.ws_mis = static_cast<double *>(workspace);
+    a.ws_row = reinterpret_cast<int *>(a.ws_mis + units);
+    a.ws_last = a.ws_row + units; a.ws_carry = a.ws_last + units; a.ws_nfin = a.ws_carry + units;
+    S.weight = weight; S.n_sources = n_sources; S.imin_source = imin_source;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SD_HIP(hipMemsetAsync(weight, 0, (size_t)npoints * R * sizeof(int), s));
+    SD_HIP(sd::launch_post_sources(s, S));
+    return SURFDISP_SUCCESS;
+}
+
+// Weighted column statistics of a list of predictions (csrc/surfdisp_pred.hip; header section (6g)).  Workspace: the partials
+// [npoints][nslab][P][5] doubles, then the slabs' failed weights [npoints][nslab] ints.
+static long pred_slabs(long total)
+{
+    const long n = (total + SURFDISP_PRED_SLAB_ROWS - 1) / SURFDISP_PRED_SLAB_ROWS;
+    return n < 1 ? 1 : (n > SURFDISP_PRED_SLABS_MAX ? SURFDISP_PRED_SLABS_MAX : n);
+}
+
+size_t surfdisp_posterior_predictive_workspace_bytes(int npoints, int total, int P)
+{
+    if (npoints < 1 || total < 0 || P < 1) return 0;
+    const size_t units = (size_t)npoints * (size_t)pred_slabs(total);
+    return units * ((size_t)P * 5 * sizeof(double) + sizeof(int));
+}
+
+int surfdisp_posterior_predictive_device(void *stream, int npoints, int total, int P, const float *pred, long ld,
+                                         const unsigned char *failed, const int *w, const int *offsets,
+                                         int nbins, const double *vlo, const double *vhi,
+                                         int *count, double *mean, double *std, double *vmin, double *vmax, int *n_failed,
+                                         int *hist, int *below, int *above,
+                                         void *workspace, size_t workspace_bytes)
+{
+    const char *name = "surfdisp_posterior_predictive_device";
+    if (npoints < 1 || total < 0 || P < 1 || P > SURFDISP_PRED_COLS_MAX || ld < (long)P ||
+        (long)npoints * pred_slabs(total) > 0x7fffffffL) {
+        set_err("%s: invalid size (npoints >= 1; total >= 0; 1 <= P <= 1024; ld >= P; npoints x slabs <= 2^31 - 1)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if ((total > 0 && (!pred || !w)) || !offsets || !count || !mean || !std || !vmin || !vmax || !n_failed || !workspace ||
+        (hist && (!below || !above || !vlo || !vhi))) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    if (hist) {
+        bool ok = nbins >= 1;
+        for (int c = 0; ok && c < P; ++c) ok = std::isfinite(vlo[c]) && std::isfinite(vhi[c]) && vhi[c] > vlo[c];
+        if (!ok) { set_err("%s: invalid histogram: nbins >= 1, finite vlo < vhi in every column", name); return SURFDISP_ERR_INVALID; }
+    }
+    if (workspace_bytes < surfdisp_posterior_predictive_workspace_bytes(npoints, total, P)) {
+        set_err("%s: invalid workspace: smaller than surfdisp_posterior_predictive_workspace_bytes", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::PredArgs a{};
+    a.npoints = npoints; a.total = total; a.P = P; a.nslab = (int)pred_slabs(total); a.ld = ld;
+    a.pred = pred; a.failed = failed; a.w = w; a.offsets = offsets;
+    a.count = count; a.mean = mean; a.std = std; a.mn = vmin; a.mx = vmax; a.n_failed = n_failed;
+    const size_t units = (size_t)npoints * a.nslab;
+    a.ws_part = static_cast<double *>(workspace);
+    a.ws_nfail = reinterpret_cast<int *>(a.ws_part + units * (size_t)P * 5);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hist) {
+        a.hist = hist; a.below = below; a.above = above; a.nbins = nbins;
+        SD_HIP(hipMemsetAsync(hist, 0, (size_t)npoints * P * nbins * sizeof(int), s));
+        SD_HIP(hipMemsetAsync(below, 0, (size_t)npoints * P * sizeof(int), s));
+        SD_HIP(hipMemsetAsync(above, 0, (size_t)npoints * P * sizeof(int), s));
+    }
+    SD_HIP(sd::launch_pred_stats(s, a, vlo, vhi));
+    return SURFDISP_SUCCESS;
+}
+
 // The generic prior predicates on the device (csrc/surfdisp_layers.hip, surfdisp_prior_kernel): tags[c] = mark_tag where chain c's
 // model breaks a rule; only_tag >= 0: only chains with tags[c] >= only_tag are looked at.  Static-structure models, no thermal layer.
 int surfdisp_prior_device(void *stream, int C, int N, int L, const double *params, const int *idesc, const double *fdesc,

@@ -325,6 +325,32 @@ struct PostArgs {
     double zdeps[SURFDISP_POST_DEPTHS_MAX];
 };
 hipError_t launch_posterior(hipStream_t s, const PostArgs &a);
+hipError_t launch_post_selection(hipStream_t s, const PostArgs &a);   // K1 and K2 of launch_posterior alone
+// source rows of a track and weighted statistics of a list of predictions (csrc/surfdisp_pred.hip; include/surfdisp.h section (6g))
+constexpr int SD_PRED_SLAB = SURFDISP_PRED_SLAB_ROWS;   // list rows a workgroup of the statistics kernel walks at a time
+struct PostSourcesArgs {
+    PostArgs sel;              // what launch_post_selection reads and writes; its ws_nfin holds the slabs' final rows
+    int *weight;               // [npoints][R]
+    int *n_sources, *imin_source;   // [npoints]
+};
+struct PredArgs {
+    int npoints, total, P, nslab, nbins;
+    long ld;                   // floats between the rows of pred
+    const float *pred;         // [total][ld]
+    const unsigned char *failed;   // nullptr, or [total]
+    const int *w;              // [total]
+    const int *offsets;        // [npoints + 1]
+    int chunk0;                // the chunk of 64 columns of blockIdx.y = 0 (with a histogram: one launch per chunk)
+    double vlo[64], vhi[64];   // with hist: the histogram ranges of this launch's 64 columns, by value
+    int *count;                // [npoints][P]
+    double *mean, *std, *mn, *mx;   // [npoints][P]
+    int *n_failed;             // [npoints]
+    int *hist, *below, *above; // nullptr, or [npoints][P][nbins], [npoints][P], [npoints][P]
+    double *ws_part;           // [npoints][nslab][P][5] (n, mean, M2, min, max)
+    int *ws_nfail;             // [npoints][nslab]
+};
+hipError_t launch_post_sources(hipStream_t s, const PostSourcesArgs &a);
+hipError_t launch_pred_stats(hipStream_t s, PredArgs a, const double *vlo, const double *vhi);   // vlo, vhi: host [P], read with a.hist
 size_t lsq_lds_bytes(int nmax);
 size_t lsq_resolution_lds_bytes(int nmax);
 hipError_t launch_lsq_step(hipStream_t s, const LsqArgs &a);

@@ -19,24 +19,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "surfdisp_internal.h"
+#include "surfdisp_post_common.h"
 
 #pragma clang fp contract(off)
 
 namespace sd {
 
-constexpr int POST_BLOCK = 256, POST_WAVES = POST_BLOCK / 64;
 constexpr int POST_TOPS = SD_POST_MAX_LAYERS + 1;
-
-__device__ __forceinline__ bool min_before(double ma, int ra, double mb, int rb) { return ma < mb || (ma == mb && ra < rb); }
-
-// misfit of a row as the selection sees it: NaN = +inf, a row outside the prefix = +inf
-__device__ __forceinline__ double row_misfit(const PostArgs &A, const double *row, int r)
-{
-    double m = row[0];
-    if (m != m) m = INFINITY;
-    if (A.chainL > 0 && (r % A.chainL) >= A.prefix) m = INFINITY;
-    return m;
-}
 
 // running figures of one column (a depth, or a parameter) over the final rows, in row order
 struct Acc { double n, piv, s1, s2, mn, mx; };
@@ -49,7 +38,6 @@ __device__ __forceinline__ void acc_add(Acc &a, double v)
     a.s1 += d; a.s2 += d * d; a.n += 1.0;
     a.mn = fmin(a.mn, v); a.mx = fmax(a.mx, v);
 }
-struct Part { double n, mean, m2, mn, mx; };
 __device__ __forceinline__ Part acc_part(const Acc &a)
 {
     Part p{a.n, 0.0, 0.0, a.mn, a.mx};
@@ -60,18 +48,6 @@ __device__ __forceinline__ Part acc_part(const Acc &a)
     }
     return p;
 }
-// Chan, Golub & LeVeque: b joins a
-__device__ __forceinline__ void part_merge(Part &a, const Part &b)
-{
-    if (b.n == 0.0) return;
-    if (a.n == 0.0) { a = b; return; }
-    const double n = a.n + b.n, delta = b.mean - a.mean;
-    a.mean = a.mean + delta * (b.n / n);
-    a.m2 = a.m2 + b.m2 + delta * delta * (a.n * b.n / n);
-    a.mn = fmin(a.mn, b.mn); a.mx = fmax(a.mx, b.mx);
-    a.n = n;
-}
-
 // value `sl` of the [params | aux] row of track row `prow`
 __device__ __forceinline__ double slot_value(const PostArgs &A, const double *prow, const double *arow, int sl)
 {
@@ -307,6 +283,15 @@ __global__ __launch_bounds__(POST_BLOCK) void post_finish_kernel(PostArgs A)
         const size_t o = (size_t)pt * A.N + (col - A.D);
         A.pmean[o] = mean; A.pstd[o] = sd;
     }
+}
+
+// K1 and K2 alone (also the first two launches of surfdisp_posterior_sources_device, csrc/surfdisp_pred.hip): reads track, R, nslab,
+// row_stride, chainL, prefix; writes ws_mis, ws_row, ws_last, ws_carry, min_misfit, imin, thres
+hipError_t launch_post_selection(hipStream_t s, const PostArgs &a)
+{
+    hipLaunchKernelGGL(post_select_kernel, dim3(a.npoints * a.nslab), dim3(POST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(post_threshold_kernel, dim3((a.npoints + 63) / 64), dim3(64), 0, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_posterior(hipStream_t s, const PostArgs &a)

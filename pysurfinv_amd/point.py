@@ -217,3 +217,31 @@ class PostPoint(Point):
             if k in r:
                 out[k] = r[k]
         return out
+
+    def predictive(self, hist=None, quantiles=(0.16, 0.5, 0.84)):
+        """The point's posterior predictive curves as host arrays - what ``plotDisp(ensemble=True)`` draws against the
+        observations: dict(count, mean, std, min, max, min_pred, fit [P] over the point's data columns; min_misfit, thres,
+        misfit_dev; n_final, n_sources, n_failed; with ``hist=(vlo, vhi, nbins)`` - scalars or one range per column - also hist
+        [P, nbins], below, above [P], quantiles [P, Q]).  The device route (``posterior.posterior_predictive``: every distinct
+        final model solved once) when the point has a HIP device, ``posterior.predictive_reference`` otherwise
+        (``device=None`` with a ``_forward`` hook)."""
+        import torch
+        from . import posterior
+        on_dev = (self._post_device is not None and torch.device(self._post_device).type == "cuda" and self._forward is None)
+        if not on_dev and self._forward is None:
+            raise ValueError("PostPoint.predictive needs a HIP device or a _forward hook")
+        mc = self._sampler()
+        track = torch.as_tensor(self.MC[None, :, :], dtype=torch.float64)
+        fn = posterior.predictive_reference
+        if on_dev:
+            track, fn = track.to(mc.device), posterior.posterior_predictive
+        r = fn(mc, track, true_markov_chain=self.trueMarkovChain, hist=hist, quantiles=quantiles)
+        r = {k: v[0].cpu().numpy() for k, v in r.items()}
+        out = dict(count=r["count"], mean=r["pred_mean"], std=r["pred_std"], min=r["pred_min"], max=r["pred_max"],
+                   min_pred=r["min_pred"], fit=r["fit"], min_misfit=float(r["min_misfit"]), thres=float(r["thres"]),
+                   misfit_dev=float(r["misfit_dev"]), n_final=int(r["n_final"]), n_sources=int(r["n_sources"]),
+                   n_failed=int(r["n_failed"]))
+        for k in ("hist", "below", "above", "quantiles"):
+            if k in r:
+                out[k] = r[k]
+        return out

@@ -8,6 +8,9 @@ models as Vs at depth (``_loadValues(zdeps=...)``, point.py:317-335), their mean
   device track, read in place; every result is tested against the reference function.  Models with a static layer structure
   (``Model1DBatch.native_descriptor()``) and no thermal layer.
 * ``convergence`` runs either for the row prefixes of ``_check_convergency``.
+* ``posterior_predictive`` / ``predictive_reference`` are the data-space half (``PostPoint.plotDisp(ensemble=True)``,
+  ``Model3D.checkPhaseVelocity``): the predicted curves of the final rows' models, their mean, spread and histograms per data
+  column, held against the observations - for any parameterisation, since the models come from the sampler's own ``to_model``.
 
 Selection (point.py:152-168, as ``MetropolisBatch.summarise_points`` states it), per point over its R rows
 ``[misfit, L, accepted, *params]``: a NaN misfit counts as +inf; ``imin`` = the first row of the smallest misfit;
@@ -238,3 +241,291 @@ def convergence(model_batch, track, zdeps, chainL, rows=None, true_markov_chain=
     prefixes = [max(int(l), 1) for l in np.linspace(chainL / 10, chainL, int(n_tests))]
     res = [fn(model_batch, track, zdeps, rows=rows, true_markov_chain=true_markov_chain, chainL=chainL, prefix=p) for p in prefixes]
     return dict(prefixes=prefixes, mean=torch.stack([r["vs_mean"] for r in res]), std=torch.stack([r["vs_std"] for r in res]))
+
+
+# ------------------------------------------------------------------ posterior predictive curves (header section (6g))
+PRED_SLAB_ROWS = 4096     # SURFDISP_PRED_SLAB_ROWS: list rows a workgroup of the statistics kernel walks at a time
+PRED_SLABS_MAX = 16       # SURFDISP_PRED_SLABS_MAX
+PRED_COLS_MAX = 1024      # SURFDISP_PRED_COLS_MAX
+
+
+def quantiles_from_hist_cols(hist, vlo, vhi, quantiles):
+    """``quantiles_from_hist`` with one range per column: ``hist`` ``[..., P, nbins]``, ``vlo``, ``vhi`` ``[P]`` -> ``[..., P, Q]``."""
+    import torch
+    h = hist.to(torch.float64)
+    nb = h.shape[-1]
+    lo = torch.as_tensor(np.asarray(vlo, np.float64), device=h.device)[:, None]
+    w = (torch.as_tensor(np.asarray(vhi, np.float64), device=h.device)[:, None] - lo) / nb
+    cum = h.cumsum(dim=-1)
+    n = cum[..., -1:]
+    out = []
+    for q in quantiles:
+        target = float(q) * n
+        b = ((cum >= target) & (cum > 0)).to(torch.int8).argmax(dim=-1, keepdim=True)
+        hb = h.gather(-1, b)
+        before = cum.gather(-1, b) - hb
+        v = lo + w * (b.to(torch.float64) + (target - before) / hb)
+        out.append(torch.where(n > 0, v, torch.full_like(v, float("nan"))))
+    return torch.cat(out, dim=-1) if out else h.new_zeros(h.shape[:-1] + (0,))
+
+
+def _pred_hist_args(hist, P):
+    """None, or (vlo [P], vhi [P] float64 arrays, nbins) of ``hist = (vlo, vhi, nbins)`` with scalars or [P] arrays."""
+    if hist is None:
+        return None
+    try:
+        vlo = np.array(np.broadcast_to(np.asarray(hist[0], np.float64), (P,)))
+        vhi = np.array(np.broadcast_to(np.asarray(hist[1], np.float64), (P,)))
+    except ValueError:
+        raise ValueError(f"hist = (vlo, vhi, nbins): vlo and vhi scalars or arrays of the {P} data columns") from None
+    nbins = int(hist[2])
+    if not (np.isfinite(vlo).all() and np.isfinite(vhi).all() and (vhi > vlo).all() and nbins >= 1):
+        raise ValueError("hist = (vlo, vhi, nbins) with finite vlo < vhi in every column and nbins >= 1")
+    return vlo, vhi, nbins
+
+
+def _predictive_args(sampler, shape, obs_rows, chainL, prefix, hist, max_batch):
+    """The checks both predictive functions share: (P, obs_rows as an int64 array or None, chainL, prefix, hist)."""
+    if len(shape) != 3 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("track must be [points, R, 3 + N]")
+    npnt, R, W = shape
+    if W != 3 + sampler.spec.n:
+        raise ValueError(f"track rows have {W} columns, the sampler's model has {sampler.spec.n} parameters")
+    if int(max_batch) < 1:
+        raise ValueError("max_batch >= 1")
+    P = int(sampler.c_obs.shape[-1])
+    if P > PRED_COLS_MAX:
+        raise ValueError(f"{P} data columns: at most {PRED_COLS_MAX}")
+    # rows of the sampler's per-chain observations / local information (None: the same data for every model)
+    nrows = (int(sampler.c_obs.shape[0]) if sampler.c_obs.ndim == 2 else
+             int(sampler.local_rows.shape[0]) if sampler.local_rows is not None else None)
+    if obs_rows is not None:
+        obs_rows = np.asarray(obs_rows.cpu().numpy() if hasattr(obs_rows, "cpu") else obs_rows, dtype=np.int64)
+        if obs_rows.shape != (npnt,):
+            raise ValueError("obs_rows must be [points]")
+        if nrows is not None and (obs_rows.min() < 0 or obs_rows.max() >= nrows):
+            raise ValueError(f"obs_rows outside the sampler's {nrows} rows of observations")
+    elif nrows is not None:
+        if nrows != npnt:
+            raise ValueError(f"{npnt} points against {nrows} rows of observations: pass obs_rows=")
+        obs_rows = np.arange(npnt, dtype=np.int64)
+    chainL, prefix = _prefix_args(R, chainL, prefix)
+    return P, obs_rows, chainL, prefix, _pred_hist_args(hist, P)
+
+
+def _predict(sampler, params, rows, max_batch):
+    """The sampler's own prediction of every row of ``params`` (a tensor on its device), ``max_batch`` rows per solve:
+    (pred float64 [n, P], misfit [n], failed bool [n]).  ``MetropolisBatch.misfit`` marks a failed solve with 88888."""
+    import torch
+    from .mcmc import FAIL
+    n, P = params.shape[0], int(sampler.c_obs.shape[-1])
+    pred = torch.empty((n, P), dtype=torch.float64, device=params.device)
+    mis = torch.empty(n, dtype=torch.float64, device=params.device)
+    for a in range(0, n, int(max_batch)):
+        b = min(n, a + int(max_batch))
+        m, _, _, cP = sampler.misfit(params[a:b].contiguous(), rows=None if rows is None else rows[a:b], return_c=True)
+        pred[a:b], mis[a:b] = cP, m
+    return pred, mis, mis == FAIL
+
+
+def _fit(torch, sampler, mean, obs_rows_t):
+    """(pred_mean - obs) / uncer where the observation is used, NaN elsewhere."""
+    c_obs, uncer, mask = sampler.c_obs, sampler.uncer, sampler.mask
+    if c_obs.ndim == 2:
+        i = obs_rows_t.to(c_obs.device)
+        c_obs, uncer, mask = c_obs[i], uncer[i], mask[i]
+    c_obs, uncer, mask = (t.to(mean.device) for t in (c_obs, uncer, mask))
+    return torch.where(mask.expand_as(mean), (mean - c_obs) / uncer, torch.full_like(mean, float("nan")))
+
+
+def predictive_reference(sampler, track, obs_rows=None, true_markov_chain=True, chainL=None, prefix=None, hist=None,
+                         quantiles=(0.16, 0.5, 0.84), max_batch=65536):
+    """The statement of ``posterior_predictive`` in numpy float64, without deduplication: ``select_reference`` expands every final
+    row to its source parameters, all of them are predicted by ``sampler.misfit`` (a sampler on any device, or one with the
+    ``forward=`` hook), and ``np.mean / np.std / np.min / np.max / np.histogram`` run over the rows that are not failed (per
+    column: over their finite values).  ``min_pred`` is the prediction of the source of ``imin``; ``misfit_dev`` the largest
+    ``|recomputed - recorded|`` misfit over the source rows (a recorded NaN counts as inf).  ``track``: CPU tensor or array.
+    Returns the dict of ``posterior_predictive``, CPU tensors."""
+    import torch
+    tr = track.detach().cpu().numpy() if isinstance(track, torch.Tensor) else np.asarray(track)
+    tr = np.asarray(tr, dtype=np.float64)
+    P, obs_rows, _, _, hist = _predictive_args(sampler, tr.shape, obs_rows, chainL, prefix, hist, max_batch)
+    npnt, R, W = tr.shape
+    mis, imin, thres, final, src = select_reference(tr, true_markov_chain, chainL, prefix)
+    pts, fin_rows = np.nonzero(final)                                     # (point, row) order
+    src_rows = src[pts, fin_rows]
+    dev = sampler.device
+    params = torch.as_tensor(tr[pts, src_rows, 3:], dtype=torch.float64, device=dev)
+    rows_t = None if obs_rows is None else torch.as_tensor(obs_rows[pts], device=dev)
+    pred, rmis, failed = _predict(sampler, params, rows_t, max_batch)
+    pred, rmis, failed = pred.cpu().numpy(), rmis.cpu().numpy(), failed.cpu().numpy()
+    out = dict(min_misfit=mis[np.arange(npnt), imin], thres=thres, imin=imin.astype(np.int64),
+               n_final=final.sum(axis=1).astype(np.int64), n_sources=np.zeros(npnt, np.int64), n_failed=np.zeros(npnt, np.int64),
+               count=np.zeros((npnt, P), np.int32), min_pred=np.full((npnt, P), np.nan), misfit_dev=np.full(npnt, np.nan))
+    for k in ("pred_mean", "pred_std", "pred_min", "pred_max"):
+        out[k] = np.full((npnt, P), np.nan)
+    if hist is not None:
+        vlo, vhi, nbins = hist
+        out.update(hist=np.zeros((npnt, P, nbins), np.int32), below=np.zeros((npnt, P), np.int32),
+                   above=np.zeros((npnt, P), np.int32))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                  # all-NaN columns: NaN is the answer
+        for p in range(npnt):
+            sel = pts == p
+            if not sel.any():
+                continue
+            out["n_sources"][p] = np.unique(src_rows[sel]).size
+            out["n_failed"][p] = failed[sel].sum()
+            d = np.abs(rmis[sel] - tr[p, src_rows[sel], 0])
+            out["misfit_dev"][p] = np.where(np.isnan(d), np.inf, d).max()
+            at = np.nonzero(fin_rows[sel] == imin[p])[0]
+            if at.size:
+                out["min_pred"][p] = pred[sel][at[0]]
+            vals = pred[sel][~failed[sel]]
+            vals = np.where(np.isfinite(vals), vals, np.nan)
+            out["count"][p] = np.isfinite(vals).sum(axis=0)
+            if vals.shape[0] == 0:
+                continue
+            out["pred_mean"][p], out["pred_std"][p] = np.nanmean(vals, axis=0), np.nanstd(vals, axis=0)
+            out["pred_min"][p], out["pred_max"][p] = np.nanmin(vals, axis=0), np.nanmax(vals, axis=0)
+            if hist is not None:
+                for c in range(P):
+                    edges = np.arange(nbins + 1) * ((vhi[c] - vlo[c]) / nbins) + vlo[c]
+                    v = vals[:, c][np.isfinite(vals[:, c])]
+                    out["below"][p, c], out["above"][p, c] = (v < vlo[c]).sum(), (v >= vhi[c]).sum()
+                    v = v[(v >= vlo[c]) & (v < vhi[c])]
+                    out["hist"][p, c] = np.histogram(v, edges)[0] if v.size else 0
+    out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items()}
+    out["fit"] = _fit(torch, sampler, out["pred_mean"], None if obs_rows is None else torch.as_tensor(obs_rows))
+    if hist is not None:
+        out["quantiles"] = quantiles_from_hist_cols(out["hist"], vlo, vhi, quantiles)
+    return out
+
+
+def posterior_sources(track, true_markov_chain=True, chainL=None, prefix=None):
+    """One call of ``surfdisp_posterior_sources_device`` on a float64 device track ``[points, R, >= 3]`` (read in place): dict of
+    device tensors ``min_misfit, thres`` float64, ``imin, n_final, n_sources, imin_source`` int32 ``[points]`` and ``weight`` int32
+    ``[points, R]`` - how many final rows carry the parameters of row r."""
+    import torch
+    npnt, R, W = track.shape
+    chainL, prefix = _prefix_args(R, chainL, prefix)
+    dev = track.device
+    L = _lib.lib()
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    o = dict(min_misfit=torch.empty(npnt, **f64), thres=torch.empty(npnt, **f64), imin=torch.empty(npnt, **i32),
+             n_final=torch.empty(npnt, **i32), weight=torch.empty((npnt, R), **i32), n_sources=torch.empty(npnt, **i32),
+             imin_source=torch.empty(npnt, **i32))
+    ws = torch.empty(max(int(L.surfdisp_posterior_sources_workspace_bytes(npnt, R)), 8), dtype=torch.uint8, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.surfdisp_posterior_sources_device(
+            ctypes.c_void_p(stream), npnt, R, ptr(track), W, 1 if true_markov_chain else 0, chainL, prefix,
+            ptr(o["min_misfit"]), ptr(o["thres"]), ptr(o["imin"]), ptr(o["n_final"]), ptr(o["weight"]), ptr(o["n_sources"]),
+            ptr(o["imin_source"]), ptr(ws), ws.numel()))
+    return o
+
+
+def predictive_statistics(pred, failed, w, offsets, hist=None):
+    """One call of ``surfdisp_posterior_predictive_device``: ``pred`` float32 ``[total, P]`` (rows ``pred.stride(0)`` apart),
+    ``failed`` uint8 ``[total]`` or None, ``w`` int32 ``[total]``, ``offsets`` int32 ``[points + 1]``, all on one device;
+    ``hist`` None or ``(vlo [P], vhi [P], nbins)`` as ``_pred_hist_args`` returns it.  Dict of device tensors ``count`` int32 and
+    ``pred_mean, pred_std, pred_min, pred_max`` float64 ``[points, P]``, ``n_failed`` int32 ``[points]``, and with ``hist``
+    ``hist [points, P, nbins]``, ``below``, ``above``."""
+    import torch
+    total, P = pred.shape
+    npnt = offsets.numel() - 1
+    dev = pred.device
+    L = _lib.lib()
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    o = dict(count=torch.empty((npnt, P), **i32), n_failed=torch.empty(npnt, **i32))
+    for k in ("pred_mean", "pred_std", "pred_min", "pred_max"):
+        o[k] = torch.empty((npnt, P), **f64)
+    vlo, vhi, nbins = hist if hist is not None else (None, None, 0)
+    if hist is not None:
+        vlo, vhi = np.ascontiguousarray(vlo, np.float64), np.ascontiguousarray(vhi, np.float64)
+        o.update(hist=torch.empty((npnt, P, nbins), **i32), below=torch.empty((npnt, P), **i32), above=torch.empty((npnt, P), **i32))
+    ws = torch.empty(max(int(L.surfdisp_posterior_predictive_workspace_bytes(npnt, total, P)), 8), dtype=torch.uint8, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
+    host = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(L.surfdisp_posterior_predictive_device(
+            ctypes.c_void_p(stream), npnt, total, P, ptr(pred), pred.stride(0) if total else P, ptr(failed), ptr(w), ptr(offsets),
+            nbins, host(vlo), host(vhi), ptr(o["count"]), ptr(o["pred_mean"]), ptr(o["pred_std"]), ptr(o["pred_min"]),
+            ptr(o["pred_max"]), ptr(o["n_failed"]), ptr(o.get("hist")), ptr(o.get("below")), ptr(o.get("above")), ptr(ws), ws.numel()))
+    return o
+
+
+def posterior_predictive(sampler, track, obs_rows=None, true_markov_chain=True, chainL=None, prefix=None, hist=None,
+                         quantiles=(0.16, 0.5, 0.84), max_batch=65536):
+    """Posterior predictive curves of every point of a device track ``[points, R, 3 + N]`` (float64, read in place) under the
+    data of ``sampler``, a ``MetropolisBatch`` on the track's device (``(periods, c_obs, uncer)`` or ``data=``; P = its data
+    columns).  ``obs_rows`` ``[points]``: the row of the sampler's per-chain observations / local information each point
+    belongs to (default: point p reads row p).
+
+    1. ``surfdisp_posterior_sources_device``: the selection (module docstring) and ``weight [points, R]`` - with
+       ``true_markov_chain`` a rejected row carries the parameters of the last accepted row before it, so the distinct models
+       among the final rows are about (accept rate) of them;
+    2. ``torch.nonzero(weight)`` - the ONE host synchronisation of the call (the host must know the batch size) - lists the
+       source rows in (point, row) order; their parameters are gathered from the track;
+    3. every source row is solved once by ``sampler.misfit(..., return_c=True)`` - ``to_model`` and the batched solver, exactly as
+       the sampler fitted it - in slices of ``max_batch`` rows;
+    4. ``surfdisp_posterior_predictive_device``: weighted statistics per point and data column.  A row is FAILED when the
+       sampler's misfit rule fails it (88888); an entry counts when its row is not failed and its value is finite; the result
+       equals the unweighted statistics of the list with every row repeated ``weight`` times (std: population).
+
+    ``hist``: None or ``(vlo, vhi, nbins)`` with scalars or ``[P]`` arrays - one range per data column.
+    Returns a dict of device tensors: ``min_misfit, thres`` float64, ``imin, n_final, n_sources, n_failed`` int64 ``[points]``;
+    ``count`` int32, ``pred_mean, pred_std, pred_min, pred_max`` float64 ``[points, P]`` (NaN where count is 0); ``min_pred``
+    ``[points, P]``: the curve of ``minMod``, taken from the list; ``fit`` ``[points, P]``: ``(pred_mean - obs) / uncer`` where the
+    observation is used, NaN elsewhere; ``misfit_dev`` ``[points]``: the largest ``|recomputed - recorded|`` misfit over the
+    solved source rows (each is an accepted row, or row 0, so its recorded misfit is that of its own parameters: the staleness
+    check of a loaded track; a recorded NaN counts as inf); with ``hist``: ``hist [points, P, nbins]``, ``below``, ``above``,
+    ``quantiles [points, P, Q]``.  Raises ``ValueError`` for shapes that do not fit (checked first, so also without a device)
+    and for a sampler with the ``forward=`` hook or on another device, ``SurfdispError`` for a track that is not on a HIP device."""
+    import torch
+    if not isinstance(track, torch.Tensor):
+        raise ValueError("track must be a float64 tensor [points, R, 3 + N]")
+    P, obs_rows, _, _, hist = _predictive_args(sampler, tuple(track.shape), obs_rows, chainL, prefix, hist, max_batch)
+    if track.dtype != torch.float64:
+        raise ValueError("track must be float64 [points, R, 3 + N]")
+    if getattr(sampler, "_forward", None) is not None:
+        raise ValueError("posterior_predictive solves on the device: a sampler with the forward= hook goes through predictive_reference")
+    if track.device.type != "cuda":
+        raise _lib.SurfdispError("posterior_predictive needs a track on a HIP device (no CPU fallback: predictive_reference is the host statement)")
+    if sampler.device != track.device:
+        raise ValueError(f"the sampler is on {sampler.device}, the track on {track.device}")
+    track = track.contiguous()
+    npnt, R, W = track.shape
+    dev = track.device
+    src = posterior_sources(track, true_markov_chain, chainL, prefix)
+    weight = src["weight"]
+    nz = torch.nonzero(weight)                                            # (point, row) order; the one host synchronisation
+    pt, row = nz[:, 0], nz[:, 1]
+    total = int(nz.shape[0])
+    w = weight[pt, row].contiguous()
+    offsets = torch.zeros(npnt + 1, dtype=torch.int32, device=dev)
+    offsets[1:] = torch.cumsum(src["n_sources"], dim=0)
+    rows_all = None if obs_rows is None else torch.as_tensor(obs_rows, device=dev)
+    pred64, mis, failed = _predict(sampler, track[pt, row, 3:], None if rows_all is None else rows_all[pt], max_batch)
+    pred = pred64.to(torch.float32).contiguous()                          # (the solver's own fp32 values: exact)
+    o = predictive_statistics(pred, failed.to(torch.uint8).contiguous(), w, offsets, hist)
+    d = torch.nan_to_num((mis - track[pt, row, 0]).abs(), nan=float("inf"))
+    o["misfit_dev"] = torch.full((npnt,), float("nan"), dtype=torch.float64, device=dev).scatter_reduce(0, pt, d, "amax", include_self=False)
+    key = pt * R + row                                                    # ascending: the list position of (point, imin_source)
+    want = torch.arange(npnt, device=dev) * R + src["imin_source"].to(torch.int64)
+    at = torch.searchsorted(key, want).clamp(max=max(total - 1, 0))
+    o["min_pred"] = torch.full((npnt, P), float("nan"), dtype=torch.float64, device=dev)
+    if total:
+        found = key[at] == want
+        o["min_pred"] = torch.where(found[:, None], pred[at].to(torch.float64), o["min_pred"])
+    o["fit"] = _fit(torch, sampler, o["pred_mean"], rows_all)
+    for k in ("min_misfit", "thres"):
+        o[k] = src[k]
+    for k in ("imin", "n_final", "n_sources"):
+        o[k] = src[k].to(torch.int64)
+    o["n_failed"] = o["n_failed"].to(torch.int64)
+    if hist is not None:
+        o["quantiles"] = quantiles_from_hist_cols(o["hist"], hist[0], hist[1], quantiles)
+    return o
