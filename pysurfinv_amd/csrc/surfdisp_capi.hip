@@ -41,6 +41,7 @@ struct EnvKnobs {
     long host_chunk_layers = 327680;   // SURFDISP_HOST_CHUNK (developer knob): layers' worth of stacks per chunk
     int host_pipeline = 1;        // SURFDISP_HOST_PIPELINE (developer knob): 0 = large host-buffer calls as one chunk
     int rows_min_team = 8;        // SURFDISP_ROWS_MIN_TEAM (developer knob): teams of at least this many lanes rebuild from the row copy
+    int group_stash = 1;          // SURFDISP_GROUP_STASH (developer knob): 0 = the Rayleigh group-velocity kernel derives every layer again in each sweep (no LDS stash)
     EnvKnobs()
     {
         if (const char *e = getenv("SURFDISP_TEAM")) team = atoi(e);
@@ -62,6 +63,7 @@ struct EnvKnobs {
         if (const char *e = getenv("SURFDISP_CERTSCAN")) certscan = atoi(e);
         if (const char *e = getenv("SURFDISP_LEANSCAN")) leanscan = atoi(e);
         if (const char *e = getenv("SURFDISP_HOST_SLOTS")) host_slots = atoi(e);
+        if (const char *e = getenv("SURFDISP_GROUP_STASH")) group_stash = atoi(e);
         if (const char *e = getenv("SURFDISP_HOST_CHUNK")) { host_chunk_layers = atol(e); if (host_chunk_layers < 1024) host_chunk_layers = 1024; }
     }
 };
@@ -473,6 +475,8 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka, kr,
                      kscr, kscale, khs, kern_raw ? 1 : 0, 0, 0, kn.group_order};
     if (eig) { ga.escr = eig->escr; ga.ediv = eig->ediv; ga.ehs = eig->ehs; ga.esum = eig->esum; }   // (the EIG instantiation)
+    // (not beside other batches: the stash's 50 KB per workgroup would keep their root-search workgroups off the CU)
+    ga.stash = (kn.group_stash && !pipelined) ? 0 : -1;
     if (!phase_only) SD_HIP(sd::launch_group(s, kind, ga));
     if (!phase_only && kscr) {
         // one launch for the three arrays: factor 1 / (dL/dk), zeros below each unit's half space, whole rows

@@ -91,6 +91,7 @@ struct GroupArgs {
     float *ediv;          // with escr: [P][B] the unit's divisor (Rayleigh 1, Love ut at the top)
     int *ehs;             // with escr: [P][B] deepest layer the unit wrote (-1: none - unsolved, bad stack, degenerate exit)
     float *esum;          // with escr: [3][P][B] the energy integrals I0, I1, I2 the group velocity is formed from
+    int stash;            // in: < 0 never keep the fit's layer values in LDS (SURFDISP_GROUP_STASH=0), 0 the library's rule; set by launch_group: 1 = this launch keeps them
 };
 // eigenfunctions from the layer-major scratch to the caller's rows, see K2d
 struct EigenTransposeArgs {

@@ -393,6 +393,7 @@ __device__ __forceinline__ float wk_ilove(const float rho, const float b) { retu
 // with r signed before the branch wherever k d |r| != 0 (tests/test_layer_coef_bits.py); k d |r| = 0 needs a layer of zero
 // thickness, which the prep kernel rejects.
 struct LCoef { float r, rsin, sinr, cs, x, ph; };
+template <bool SKIP = true>
 SD_HD __forceinline__ LCoef layer_coef(const float arg, const float wd)
 {
     const float xs = fmaxf(fabsf(arg), 1.0e-30f), y = rsq_hw(xs);
@@ -405,10 +406,29 @@ SD_HD __forceinline__ LCoef layer_coef(const float arg, const float wd)
         // sinh of a small argument: the difference of the two exponentials carries their absolute error (~6e-8), i.e. a
         // relative error 6e-8 / |x| that sinr = sinh(x) / r passes on - 1 % one float below a thin layer's velocity, a jump
         // of the secular function where c crosses it.  Below |x| = 1/4 the odd series to x^5 (truncation < 5e-8 relative;
-        // above, the exponentials' error is < 4e-7 relative).  Cost: 4-6 % of the root search, 5.6 % of the headline.
-        const float x2 = o.x * o.x;
-        const float shs = fmaf(o.x * x2, fmaf(x2, 8.33333333e-3f, 1.66666667e-1f), o.x);
-        if (fabsf(o.x) < 0.25f) sh = shs;
+        // above, the exponentials' error is < 4e-7 relative).  Cost: 4-6 % of the root search, 5.6 % of the headline, when
+        // every lane evaluates it.  SKIP (device): the series and its select run only where some active lane of the
+        // wavefront takes them (one compare into vcc, one scalar branch; the lanes that take them see the same
+        // expressions, so every lane's value is the bits it was).  On the bench stacks a P coefficient needs the series
+        // in under 2 % of the lane slots and a wavefront of 64 stacks in a quarter of its S coefficients: root search of
+        // four-lane teams 1.364 -> 1.312 ms (-3.8 %), 993 -> 931 M wave-level VALU instructions per launch (-6.3 %),
+        // 16-lane teams of 96-layer stacks 5.2 -> 4.9 ms (profiles/r10a).  Not for 64-lane teams (SKIP = false, phase_body):
+        // the lanes of a wavefront are then 64 trial velocities of ONE stack, some lane nearly always needs the series,
+        // and the branch only splits the block the scheduler hides the exponentials' latency in - the Metropolis lock
+        // step of 1 500 x 96-layer stacks 1.43 -> 1.48 ms with it.  32-lane teams were not measured: off.
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SD_NO_SINH_SKIP)
+        if (!SKIP || __builtin_amdgcn_ballot_w64(fabsf(o.x) < 0.25f) != 0ull)
+#endif
+        {
+            const float x2 = o.x * o.x;
+            const float shs = fmaf(o.x * x2, fmaf(x2, 8.33333333e-3f, 1.66666667e-1f), o.x);
+            if (fabsf(o.x) < 0.25f) sh = shs;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(SD_NO_SINH_SKIP)
+            // (an empty statement the compiler may not move: without it the five instructions are hoisted above the
+            // branch again and every wavefront pays for them)
+            if (SKIP) asm volatile("" : "+v"(sh));
+#endif
+        }
         o.rsin = ra * sh; o.sinr = sh * -y; o.cs = ch;
         o.ph = 0.0f;
     } else {
@@ -484,7 +504,7 @@ __device__ __forceinline__ RState ray_start(const RTrial &t, const int start, co
 // single-register-set loop of delta_rayleigh issues the next layer's loads into the registers the step has freed (not
 // called by a liquid top layer)
 struct NoMid { __device__ void operator()(int) const {} };
-template <bool FIRST, bool CERT = false, class Mid = NoMid>
+template <bool FIRST, bool CERT = false, bool SKIP = true, class Mid = NoMid>
 __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr &y, const int start, float &phi, int *kc = nullptr,
                                          bool *kunc = nullptr, const Mid &mid = Mid())
 {
@@ -502,7 +522,7 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
         // a21 = rhoc sinpr are non-zero (surfa.f:236-250)
         if (start != 1) return;
         if (CERT) *kunc = true;                            // (a liquid layer: no certificate)
-        const LCoef P = layer_coef(arga, wd);
+        const LCoef P = layer_coef<SKIP>(arga, wd);
         const float sinpr = P.sinr, cosp = P.cs;
         phi += P.ph;
         const float n1 = cosp * b1;
@@ -515,9 +535,9 @@ __device__ __forceinline__ void ray_step(RState &s, const RTrial &t, const RLyr 
     const float argb = fmaf(-csq, ib2, 1.0f);
     const float g = 2.0f * (sv * sv) * icsq;
     const float g1 = g - 1.0f;
-    const LCoef P = layer_coef(arga, wd);                              // surfa.f:263-279
+    const LCoef P = layer_coef<SKIP>(arga, wd);                              // surfa.f:263-279
     mid(1);
-    const LCoef Q = layer_coef(argb, wd);
+    const LCoef Q = layer_coef<SKIP>(argb, wd);
     const float rsinp = P.rsin, sinpr = P.sinr, cosp = P.cs;
     const float rsinq = Q.rsin, sinqr = Q.sinr, cosq = Q.cs, qm = Q.x;
     phi += P.ph;
@@ -617,7 +637,7 @@ __device__ __forceinline__ float ray_close(const RState &s, const RTrial &t, con
     return (start == 1) ? -bb1 : bb1;
 }
 
-template <bool PIPE2 = true, bool CERT = false>
+template <bool PIPE2 = true, bool CERT = false, bool SKIP = true>
 __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, const int S,
                                                 const int mmax, const float c, const float T,
                                                 const int start, float &phi, float *mag = nullptr, const bool want_mag = true,
@@ -639,16 +659,16 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
     int m = 0;
     if (last >= 1) {                                                 // layer 0: the one that may be water
         const RLyr Bq = load(1);
-        if (CERT && count) ray_step<true, true>(s, t, A, start, phi, kc, kunc); else ray_step<true>(s, t, A, start, phi);
+        if (CERT && count) ray_step<true, true, SKIP>(s, t, A, start, phi, kc, kunc); else ray_step<true, false, SKIP>(s, t, A, start, phi);
         A = Bq;
         m = 1;
     }
     if (PIPE2) {
         while (m + 2 <= last) {
             const RLyr Bq = load(m + 1);
-            if (CERT && count) ray_step<false, true>(s, t, A, start, phi, kc, kunc); else ray_step<false>(s, t, A, start, phi);
+            if (CERT && count) ray_step<false, true, SKIP>(s, t, A, start, phi, kc, kunc); else ray_step<false, false, SKIP>(s, t, A, start, phi);
             A = load(m + 2);
-            if (CERT && count) ray_step<false, true>(s, t, Bq, start, phi, kc, kunc); else ray_step<false>(s, t, Bq, start, phi);
+            if (CERT && count) ray_step<false, true, SKIP>(s, t, Bq, start, phi, kc, kunc); else ray_step<false, false, SKIP>(s, t, Bq, start, phi);
             m += 2;
         }
     } else {
@@ -667,14 +687,14 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
             auto mid = [&](int stage) {
                 if (stage == 0) { A.d = W_D(n); A.ia2 = W_IA2(n); } else { A.ib2 = W_IB2(n); }
             };
-            if (CERT && count) ray_step<false, true>(s, t, A, start, phi, kc, kunc, mid); else ray_step<false>(s, t, A, start, phi, nullptr, nullptr, mid);
+            if (CERT && count) ray_step<false, true, SKIP>(s, t, A, start, phi, kc, kunc, mid); else ray_step<false, false, SKIP>(s, t, A, start, phi, nullptr, nullptr, mid);
             A.sv = W_B(n); A.rat = W_IR(n);
             m = n;
         }
     }
     if (m < last) {
         const RLyr Bq = load(m + 1);
-        if (CERT && count) ray_step<false, true>(s, t, A, start, phi, kc, kunc); else ray_step<false>(s, t, A, start, phi);
+        if (CERT && count) ray_step<false, true, SKIP>(s, t, A, start, phi, kc, kunc); else ray_step<false, false, SKIP>(s, t, A, start, phi);
         A = Bq;
     }
     // A holds layer mmax-1 here; the state is in the scale of the last layer stepped through
@@ -795,7 +815,7 @@ __device__ __noinline__ float delta_rayleigh_ref(const float *wq, const int LS, 
 // safe (a sign or a multiple of pi within rounding).  In a layer where c > b the pair (ut, tt / (h rb)) ROTATES by
 // q = -k d rb: floor(|q| / pi) or one more crossings, the parity being whether tt changed sign; where c < b it moves along
 // a hyperbola towards the diagonal and can cross at most once, counter-clockwise.
-template <bool CERT = false>
+template <bool CERT = false, bool SKIP = true>
 __device__ __forceinline__ float delta_love(const float *wq, const int LS, const int S,
                                             const int mmax, const float c, const float T, float &phi, int &kc, bool &kunc,
                                             const bool count = true, float *mag = nullptr)
@@ -825,7 +845,7 @@ __device__ __forceinline__ float delta_love(const float *wq, const int LS, const
         h = rho * bm * bm;
         // the layer's coefficients at q = -k d rb: y = sin(q) / rb = -sinr, z = rb sin q = -rsin = -rb^2 y (rsin, sinr of
         // layer_coef at 1 - c^2/b^2 = -arg and +k d)
-        const LCoef Q = layer_coef(-arg, wvno * d);
+        const LCoef Q = layer_coef<SKIP>(-arg, wvno * d);
         rb = fabsf(Q.r);
         const float q = -Q.x;
         const float yv = -Q.sinr, z = -Q.rsin, cosq = Q.cs;
@@ -1318,7 +1338,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         if (eval) {
             const bool want_mag = want_ratio && st == ST_ELLIP;   // (the in-kernel ellipticity passes' cancellation test)
             if (KIND == 2) val = EXACT ? delta_rayleigh_ref(wq, LS, S, mmj, cj, T, start)
-                                       : delta_rayleigh<(G != 2) && !FAST, CERT>(wq, LS, S, mmj, cj, T, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse);
+                                       : delta_rayleigh<(G != 2) && !FAST, CERT, (G <= 16)>(wq, LS, S, mmj, cj, T, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse);
             // Love, NEVILL passes of the production kernel: DLTAR1 statement by statement on the production working stack (it holds
             // b, rho, d as the exact kernel's does).  A bracket goes to NEVILL because it may hold several roots, and which of them
             // NEVILL lands on depends on the VALUES it sees (its 10 x rule, its interpolation) - with e^{kd} of hundreds of km of
@@ -1327,7 +1347,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             // values, 1.4e-2 before there was a NEVILL for such brackets at all).
             else if (!EXACT && (st == ST_NEVILL || st == ST_NEVILL0)) val = delta_love_ref_body(wq, LS, S, mmj, cj, T);
             else           val = EXACT ? delta_love_ref(wq, LS, S, mmj, cj, T)
-                                       : delta_love<CERT>(wq, LS, S, mmj, cj, T, phj, kcj, kuncj, coarse);   // counts only where they are compared: coarse passes
+                                       : delta_love<CERT, (G <= 16)>(wq, LS, S, mmj, cj, T, phj, kcj, kuncj, coarse);   // counts only where they are compared: coarse passes
         }
         // The in-kernel ellipticity passes (two-lane teams): a closure that is the remainder of a cancellation - |value| below
         // A.ell_ambig of the terms it is the sum of - marks the (stack, period) for the ellipticity kernel, which evaluates both
@@ -1974,6 +1994,36 @@ SD_HD __forceinline__ Drop drop_group(const float *__restrict__ mdl, size_t fs, 
     return r;
 }
 
+// No cut possible: the walk above cuts only where its running sum of evanescent sublayer thicknesses exceeds
+// dmax = FACT T c, and that sum cannot exceed the thickness of everything above the half space.  tot = sum |dfl| over
+// the layers 0 .. n-2 (period-independent: one load and one add per layer, against nine loads, a layer_derive with two
+// IEEE divisions and up to ndiv adds per layer of the walk); where tot (1 + 1e-4) <= dmax the walk returns {n - 1, 0},
+// and so does drop_or_none without walking.  On 200 km stacks that is every period from ~15 s up.
+// Why 1e-4 is enough.  The walk adds m = ndiv (n - 1) terms dsub = fl(d / div) in fp32, in layer order, over a SUBSET of
+// the layers: m <= 99 for Rayleigh (ndiv <= 99 / (n - 1); 199 where ndiv = 1), m <= 5 x 199 = 995 for Love at
+// SURFDISP_NLAY_MAX layers.  Its sum is at most sum |d| (1 + u)^m, u = 2^-24 (each dsub <= |d| / div (1 + u), each
+// addition another (1 + u); terms of either sign: the error of a running sum is bounded by the sum of the magnitudes).
+// tot, n - 1 <= 199 additions of the magnitudes, is at least sum |d| (1 - u)^(n - 2).  So the walk's sum is
+// <= tot (1 + (m + n) u + ...) <= tot (1 + 7.2e-5) (1.8e-5 for Rayleigh), and the product tot (1 + 1e-4) rounds by one
+// more u.  The test is one-sided: it only ever says "no cut" where the walk says so; anything else (a NaN included) walks.
+#define SD_NO_DROP_SLACK 1.0e-4f
+SD_HD __forceinline__ bool group_no_cut(const float *__restrict__ mdl, size_t fs, int B, int b, int n, float c, float T)
+{
+    float tot = 0.0f;
+    for (int jl = 0; jl + 1 < n; ++jl) tot = tot + fabsf(mdl[F_DFL * fs + (size_t)jl * B + b]);
+    return tot * (1.0f + SD_NO_DROP_SLACK) <= FACT * T * c;
+}
+template <int KIND>
+SD_HD __forceinline__ Drop drop_or_none(const float *__restrict__ mdl, size_t fs, int B, int b,
+                                             int n, float lnT, float c, float T, int ndiv, bool water,
+                                             float div)
+{
+#ifndef SD_NO_DROP_SHORTCUT
+    if (group_no_cut(mdl, fs, B, b, n, c, T)) return Drop{n - 1, 0};
+#endif
+    return drop_group<KIND>(mdl, fs, B, b, n, lnT, c, T, ndiv, water, div);
+}
+
 // Analytic partial derivatives of the phase velocity (the quantities REIGEN / LEIGEN form from their
 // energy integrals and leave in COMMON /rar1/: surfa.f:1130-1135, 1180-1184, 1204-1207 / 509-512, 561-565, 581-583).
 // The eigenproblem is solved for the attenuation-dispersed, earth-flattened layer values; the
@@ -2291,39 +2341,79 @@ SD_HD __forceinline__ int fast_sublayers(const RCoef &q, float wvnosq, float dsu
 //         two_vec = true: y[] and z[] are stepped separately and combined at every knot with the
 //         fitted xnorm / bb, exactly like the reference's stored knots (surfa.f:1092-1095).
 // EIG (MODE 2): also store the combined vector at the top of every layer the sweep steps through (EOut).
-template <int MODE, bool KERN = false, bool EIG = false>
+//
+// LStash: a lane's own copy of what the fit (MODE 0) derives for every layer it steps through and the later sweeps
+// (MODE 1, MODE 2) would derive again, bit for bit, from nine loads, layer_derive's two IEEE divisions and the IEEE
+// reciprocals 1 / (lambda + 2 mu) and 1 / mu: rho, mu, lambda and the two reciprocals, word f of layer jl at
+// p[(jl * SD_STASH_W + f) * str] (the group kernel: dynamic LDS, str = 256 lanes, p = base + lane - lane-private, one
+// bank per lane).  Only values that do not depend on the sweep's split (own, nstep) are kept: the fit may run twice, and
+// writes the same words both times.  A liquid layer, which the sweeps skip before they derive anything else, is marked
+// by SD_STASH_LIQUID in its first word: a quiet NaN with a payload, which no arithmetic on the finite values the prep
+// kernel lets through can produce (operations on finite operands give the default NaN, payload zero) - so no derived rho
+// is mistaken for it.  p == nullptr: every sweep derives its own values (the KERN sweep, which needs the raw layer for
+// its chain factors, always does).
+#define SD_STASH_W 5
+#define SD_STASH_LIQUID 0x7fc0dead
+struct LStash { float *p; int str; };
+template <int MODE, bool KERN = false, bool EIG = false, bool STASH = false>
 SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t fs, int B, int b,
                                                int n, float lnT, int ndiv, bool water, float div,
                                                const Drop dr, float wvno, float wvnosq, float omegsq,
                                                double y[4], double z[4], bool do_y, bool own,
                                                double xnorm, double bbn, RInt &acc,
                                                const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float cw = 0.0f, K3 *hold = nullptr,
-                                               bool *shorter = nullptr, const EOut eo = EOut{nullptr, 1, 0})
+                                               bool *shorter = nullptr, const EOut eo = EOut{nullptr, 1, 0},
+                                               LStash *st = nullptr)
 {
 #pragma clang fp contract(off)   // both sweeps must see identical coefficients
-    LayerRaw nraw = layer_load(mdl, fs, (size_t)dr.hs_layer * B + b);
+    // (STASH: the instantiations that may be handed a stash - the others compile to the code they were without it)
+    const bool keep = STASH && (MODE == 0) && st && st->p;          // the fit: leave the layer values for the sweeps
+    const bool kept = STASH && (MODE != 0) && !KERN && st && st->p; // a later sweep: take them
+#ifdef SD_SWEEP_PROBE
+    SD_SWEEP_PROBE(MODE, own, kept);                                // host test builds only (tests/hostcheck/trimscheck.hip)
+#endif
+    LayerRaw nraw{};
+    if (!kept) nraw = layer_load(mdl, fs, (size_t)dr.hs_layer * B + b);
     for (int jl = dr.hs_layer; jl >= 0; --jl) {
         const LayerRaw raw = nraw;
-        if (jl > 0) nraw = layer_load(mdl, fs, (size_t)(jl - 1) * B + b);   // in flight during this layer
+        if (!kept && jl > 0) nraw = layer_load(mdl, fs, (size_t)(jl - 1) * B + b);   // in flight during this layer
         const int nsub = (jl == 0 && water) ? 1 : ndiv;
         const int nreg = (jl == dr.hs_layer) ? dr.nreg_hs : nsub;
         if (nreg <= 0) continue;
-        const LayerV v = layer_derive(raw, lnT, jl == n - 1);
-        if (v.b <= 0.0f) {                                           // water: surfa.f:930
-            if (MODE == 2 && KERN && jl > 0) ko.put(jl, 0.0f, 0.0f, 0.0f);   // (the top layer's entry: group_rayleigh)
-            continue;
+        LayerV v;
+        float xmu, xlamb;
+        RCoef q;
+        if (kept) {
+            const float *sp = st->p + (size_t)(jl * SD_STASH_W) * st->str;
+            v.rho = sp[0];
+            if (__builtin_bit_cast(uint32_t, v.rho) == (uint32_t)SD_STASH_LIQUID) continue;   // water (no partials on this path: nothing to put)
+            v.a = 0.0f; v.b = 0.0f;                                  // (unused from here on without KERN)
+            v.d = mdl[F_DFL * fs + (size_t)jl * B + b];              // (a stepped layer is never the true half space: d = dfl)
+            xmu = sp[st->str]; xlamb = sp[2 * st->str];
+            q.a12 = sp[3 * st->str]; q.a34 = sp[4 * st->str];
+        } else {
+            v = layer_derive(raw, lnT, jl == n - 1);
+            if (v.b <= 0.0f) {                                       // water: surfa.f:930
+                if (MODE == 2 && KERN && jl > 0) ko.put(jl, 0.0f, 0.0f, 0.0f);   // (the top layer's entry: group_rayleigh)
+                if (keep) st->p[(size_t)(jl * SD_STASH_W) * st->str] = __builtin_bit_cast(float, (uint32_t)SD_STASH_LIQUID);
+                continue;
+            }
+            xmu = v.rho * v.b * v.b;                                 // surfa.f:831-832
+            xlamb = v.rho * (v.a * v.a - 2.0f * v.b * v.b);
+            q.a12 = 1.0f / (xlamb + 2.0f * xmu);
+            q.a34 = 1.0f / xmu;
+            if (keep) {
+                float *sp = st->p + (size_t)(jl * SD_STASH_W) * st->str;
+                sp[0] = v.rho; sp[st->str] = xmu; sp[2 * st->str] = xlamb;
+                sp[3 * st->str] = q.a12; sp[4 * st->str] = q.a34;
+            }
         }
         float dsub = (ndiv > 1 && !(jl == 0 && water)) ? v.d / div : v.d;
-        const float xmu = v.rho * v.b * v.b;                         // surfa.f:831-832
-        const float xlamb = v.rho * (v.a * v.a - 2.0f * v.b * v.b);
         KC kc{};
         if (MODE == 2 && KERN) kc = kern_coef(raw, v, lnT, jl == n - 1, cw, ko.raw != 0);
-        RCoef q;
-        q.a12 = 1.0f / (xlamb + 2.0f * xmu);
         q.a13 = wvno * xlamb * q.a12;
         q.a21 = -omegsq * v.rho;
         q.a24 = wvno; q.a31 = -wvno;
-        q.a34 = 1.0f / xmu;
         q.a42 = -q.a13;
         q.a43 = q.a21 + 4.0f * wvnosq * xmu * (xlamb + xmu) * q.a12;
         int nstep = nreg;                                            // sublayers this sweep steps through the layer
@@ -2428,11 +2518,11 @@ SD_HD __forceinline__ void rayleigh_sweep(const float *__restrict__ mdl, size_t 
 __device__ unsigned long long sd_restart_count[2];
 #endif
 
-template <bool KERN = false, bool EIG = false>
+template <bool KERN = false, bool EIG = false, bool STASH = false>
 SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int b, int n,
                                 float T, float c, float ratio, double *dbg = nullptr,
                                 const KOut ko = KOut{nullptr, 1, 0, 0, 0}, float *kscale = nullptr, int *khs = nullptr,
-                                const EOut eo = EOut{nullptr, 1, 0}, EUnit *eu = nullptr)
+                                const EOut eo = EOut{nullptr, 1, 0}, EUnit *eu = nullptr, LStash *st = nullptr)
 {
 #pragma clang fp contract(off)
     const float lnT = logf(1.0f / T);
@@ -2444,7 +2534,7 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     const LayerV top = layer_at(mdl, fs, (size_t)b, lnT, false);
     const bool water = (ndiv > 1) ? (top.b <= 0.1e-10f) : false;      // jj=2 only when splitting
     const bool wet = !(top.b > 0.0f);
-    const Drop dr = drop_group<2>(mdl, fs, B, b, n, lnT, c, T, ndiv, water, div);
+    const Drop dr = drop_or_none<2>(mdl, fs, B, b, n, lnT, c, T, ndiv, water, div);
     const float wvno = 6.2831853072f / (c * T);
     const float wvnosq = wvno * wvno;
     const float omega = 6.2831853072f / T;
@@ -2519,8 +2609,9 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
     auto fit = [&](auto step_tag, bool own) -> double {
         constexpr int STEP = decltype(step_tag)::value;
         for (int i = 0; i < 4; ++i) { y[i] = y0[i]; z[i] = z0[i]; }
-        rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                             y, z, true, own, 0.0, 1.0, acc, KOut{nullptr, 1, 0, 0, 0}, 0.0f, nullptr, &shorter);
+        rayleigh_sweep<STEP, false, false, STASH>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                             y, z, true, own, 0.0, 1.0, acc, KOut{nullptr, 1, 0, 0, 0}, 0.0f, nullptr, &shorter,
+                             EOut{nullptr, 1, 0}, st);
         const double yt0 = y[0], yt1 = y[1];
         double aa = z[0] - ratio * z[1];
         double bb = ratio * yt1 - yt0;
@@ -2545,8 +2636,9 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
                 for (int i = 0; i < 4; ++i) z[i] = z[i] + xnorm * y[i];
             } else {
                 for (int i = 0; i < 4; ++i) z[i] = z0[i];
-                rayleigh_sweep<STEP>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                     y, z, false, false, 0.0, 1.0, acc);
+                rayleigh_sweep<STEP, false, false, STASH>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, false, false, 0.0, 1.0, acc, KOut{nullptr, 1, 0, 0, 0}, 0.0f, nullptr, nullptr,
+                                     EOut{nullptr, 1, 0}, st);
             }
             aa = z[0] - ratio * z[1];
             bb = ratio * yt1 - yt0;
@@ -2587,8 +2679,8 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         aur = (float)z[0]; auz = (float)z[1];
         // (EIG) the top of the effective half space is the start vector itself: the reference's entry mmax (surfa.f:1145-1148)
         if constexpr (EIG) if (dr.nreg_hs <= 0) eo.put(dr.hs_layer, aur, auz, (float)z[2], (float)z[3]);
-        rayleigh_sweep<2, KERN, EIG>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                     y, z, false, own, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo);
+        rayleigh_sweep<2, KERN, EIG, STASH>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, false, own, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo, st);
     } else {
         // Robust path (thick structure / short period: the solutions grow by up to ~1e27 and the
         // rounding noise excited on the way up is far larger than the answer).  The reference stays
@@ -2604,8 +2696,8 @@ SD_HD float group_rayleigh(const float *__restrict__ mdl, size_t fs, int B, int 
         if constexpr (EIG)
             if (dr.nreg_hs <= 0)
                 eo.put(dr.hs_layer, aur, auz, (float)((xnorm * y0[2] + z0[2]) / bbn), (float)((xnorm * y0[3] + z0[3]) / bbn));
-        rayleigh_sweep<2, KERN, EIG>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
-                                     y, z, true, false, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo);
+        rayleigh_sweep<2, KERN, EIG, STASH>(mdl, fs, B, b, n, lnT, ndiv, water, div, dr, wvno, wvnosq, omegsq,
+                                     y, z, true, false, xnorm, bbn, acc, ko, cw, &hold, nullptr, eo, st);
     }
     if (wet && !any_solid) { aur = ratio; auz = 1.0f; }              // label 77777, surfa.f:1140-1144
     {   // label 7002, surfa.f:1145-1186
@@ -2666,7 +2758,7 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
     const float div = (float)ndiv;
     const LayerV top = layer_at(mdl, fs, (size_t)b, lnT, false);
     const bool water = (ndiv > 1) ? (top.b <= 0.1e-10f) : false;
-    const Drop dr = drop_group<1>(mdl, fs, B, b, n, lnT, c, T, ndiv, water, div);
+    const Drop dr = drop_or_none<1>(mdl, fs, B, b, n, lnT, c, T, ndiv, water, div);
     const float wvno = 6.2831853f / (c * T);
     const LayerV hsv = layer_at(mdl, fs, (size_t)dr.hs_layer * B + b, lnT, dr.hs_layer == n - 1);
     constexpr bool kern = KERN;
@@ -2792,15 +2884,16 @@ SD_HD float group_love(const float *__restrict__ mdl, size_t fs, int B, int b, i
 
 // KERN: also write the analytic partials (A.kb/ka/kr).  The plain variant is held to 168 VGPRs (three
 // wavefronts per SIMD instead of two).  EIG: also store the eigenfunction at every layer top and the energy integrals (K2d).
-template <int KIND, bool KERN, bool EIG = false>
+// STASH (surfdisp_group_kernel_stash, the default Rayleigh launch of a shallow batch: launch_group): gstash is the
+// workgroup's dynamic LDS, [Lmax][SD_STASH_W][256] - the lanes' layer values from the fit for the later sweeps (LStash).
 #ifndef SD_GROUP_WAVES
 #define SD_GROUP_WAVES 3
 #endif
 #ifndef SD_KERN_WAVES
 #define SD_KERN_WAVES 1
 #endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KERN ? SD_KERN_WAVES : SD_GROUP_WAVES, 8)))
-void surfdisp_group_kernel(GroupArgs A)
+template <int KIND, bool KERN, bool EIG, bool STASH>
+__device__ __forceinline__ void group_kernel_body(const GroupArgs &A, float *gstash)
 {
     const int B = A.B, P = A.P;
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2860,7 +2953,11 @@ void surfdisp_group_kernel(GroupArgs A)
         const size_t fs = (size_t)A.Lmax * B;
         const float T = A.per[k];
         const float c = A.c[o];
-        if (KIND == 2) ugr = group_rayleigh<KERN, EIG>(A.mdl, fs, B, b, n, T, c, A.ratio[(size_t)k * B + b],
+                if (KIND == 2 && STASH) {    // (launch_group: the default Rayleigh launch of a shallow batch)
+            LStash st{gstash + threadIdx.x, 256};
+            ugr = group_rayleigh<false, false, true>(A.mdl, fs, B, b, n, T, c, A.ratio[(size_t)k * B + b],
+                                               A.dbg ? A.dbg + 16 * o : nullptr, ko, &kscale, &khs, eo, &eu, &st);
+        } else if (KIND == 2) ugr = group_rayleigh<KERN, EIG>(A.mdl, fs, B, b, n, T, c, A.ratio[(size_t)k * B + b],
                                                        A.dbg ? A.dbg + 16 * o : nullptr, ko, &kscale, &khs, eo, &eu);
         else           ugr = group_love<KERN, EIG>(A.mdl, fs, B, b, n, T, c, ko, &kscale, &khs, eo, &eu);
     }
@@ -2885,6 +2982,20 @@ void surfdisp_group_kernel(GroupArgs A)
         }
     }
     A.u[o] = ugr;
+}
+template <int KIND, bool KERN, bool EIG = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KERN ? SD_KERN_WAVES : SD_GROUP_WAVES, 8)))
+void surfdisp_group_kernel(GroupArgs A)
+{
+    group_kernel_body<KIND, KERN, EIG, false>(A, nullptr);
+}
+// the plain Rayleigh kernel, KIND = 2, with the layer stash (a kernel of its own: with both paths in one kernel the
+// register allocation of either spills at the 168 VGPRs that three wavefronts per SIMD allow)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SD_GROUP_WAVES, 8)))
+void surfdisp_group_kernel_stash(GroupArgs A)
+{
+    extern __shared__ float gstash[];
+    group_kernel_body<2, false, false, true>(A, gstash);
 }
 
 // K3: period-major internal results -> the caller's [B][P] arrays, through an LDS tile so that both
@@ -3522,7 +3633,21 @@ hipError_t launch_group(hipStream_t s, int kind, const GroupArgs &a_in)
         return hipGetLastError();
     }
     if (a.escr) return hipErrorInvalidValue;
+    // The default Rayleigh launch keeps the fit's layer values in LDS for the later sweeps (LStash) while the three
+    // workgroups per CU that its registers allow still fit in the CU's 160 KB: Lmax x SD_STASH_W KB each, Lmax <= 10.
+    // Deeper batches, and a.stash < 0 (SURFDISP_GROUP_STASH=0, or a SURFDISP_PIPELINED call: beside other batches the
+    // stash's LDS keeps their root-search workgroups off the CU - 65 536 x L10 x P20 with three batches in flight
+    // 40.9 -> 36.5 M solves/s with it, profiles/r10a), derive them again in every sweep - the same bits.
+    size_t lds = 0;
+    a.stash = 0;
+#ifndef SD_NO_GROUP_STASH
+    if (kind == 2 && !kern && a_in.stash >= 0 && (size_t)a.Lmax * SD_STASH_W * 1024 * SD_GROUP_WAVES <= 160u * 1024u) {
+        a.stash = 1;
+        lds = (size_t)a.Lmax * SD_STASH_W * 256 * sizeof(float);
+    }
+#endif
     if (kind == 2 && kern)  hipLaunchKernelGGL((surfdisp_group_kernel<2, true>), dim3(grid), dim3(256), 0, s, a);
+    else if (kind == 2 && a.stash) hipLaunchKernelGGL(surfdisp_group_kernel_stash, dim3(grid), dim3(256), lds, s, a);
     else if (kind == 2)     hipLaunchKernelGGL((surfdisp_group_kernel<2, false>), dim3(grid), dim3(256), 0, s, a);
     else if (kern)          hipLaunchKernelGGL((surfdisp_group_kernel<1, true>), dim3(grid), dim3(256), 0, s, a);
     else                    hipLaunchKernelGGL((surfdisp_group_kernel<1, false>), dim3(grid), dim3(256), 0, s, a);
