@@ -331,6 +331,56 @@ int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay
                                   float *energy,                                 /* [B][P][4]    */
                                   void *workspace, size_t workspace_bytes);
 
+/* ---- (5g) ... and the derivatives of the phase velocity with respect to the LAYER THICKNESSES and the INTERFACE DEPTHS, added
+ *          within ABI 4: what a model built from a Moho depth, a water depth or a sediment thickness needs, and what 2 L perturbed
+ *          solves give only badly (an fp32 thickness step is quantised).  In the conventions of (5f) - v_j the vector at the top of
+ *          caller layer j as returned there, (a, b, rho)_m the earth-flattened, attenuation-corrected values of layer m, lam =
+ *          rho (a^2 - 2 b^2), mu = rho b^2, k = omega / c - the Hamiltonian of the depth equations,
+ *              Love      E(v; m) = rho omega^2 ut^2 - mu k^2 ut^2 + tq^2 / mu,
+ *              Rayleigh  uz' = (tz + k lam ur) / (lam + 2 mu), ur' = tr / mu - k uz,
+ *                        W2 = lam (uz' - k ur)^2 + 2 mu (k^2 ur^2 + uz'^2) + mu (ur' + k uz)^2,
+ *                        E(v; m) = rho omega^2 (ur^2 + uz^2) - W2 + 2 tr ur' + 2 tz uz',
+ *              the liquid layer above the sea floor (lam = rho a^2; uz, tz of the sea-floor entry):
+ *                        urw = -k tz / (rho omega^2), uz' = tz / lam + k urw, E = rho omega^2 (urw^2 + uz^2) - tz^2 / lam + 2 tz uz'
+ *                        (Love: E = 0, the sea floor is its free surface),
+ *          is constant through a homogeneous layer and jumps at an interface by the kernel of that interface's flattened depth:
+ *              K_j = -amp (c^3 / omega^2) [E(v_j; j-1) - E(v_j; j)],   amp = 1 / (2 c U I0),   1 <= j <= hs (the effective half space),
+ *          with U the structural group velocity the library returns (formed from I0, I1, I2 at fixed layer values).  In the caller's
+ *          coordinates (flat1.f: r_j = R0 - sum_{m<j} h_m; rt, rb a layer's top and bottom radius, x = ln(rt / rb), p = 2.275 | 5) the
+ *          interface also moves the flattening factors of the two layers it bounds; with the rows of (5b), Sv_m = Vs dcdb + Vp dcda
+ *          (Love: Vs dcdb), Sr_m = rho dcdr:
+ *              d ln dif/d rt =  1 / (rt^2 (1/rb - 1/rt)) - 1 / (x rt),     d ln dif/d rb = -1 / (rb^2 (1/rb - 1/rt)) + 1 / (x rb),
+ *              d ln qqq/d rt =  p rt^(p-1) / (rt^p - rb^p) - 1 / (x rt),   d ln qqq/d rb = -p rb^(p-1) / (rt^p - rb^p) + 1 / (x rb),
+ *              (layer nlay - 1, the half-space role: d ln dif/d rt = -1 / rt, d ln qqq/d rt = p / rt),
+ *              dcdz_j = K_j R0 / r_j - [Sv_{j-1} d ln dif_{j-1}/d rb + Sr_{j-1} d ln qqq_{j-1}/d rb]
+ *                                    - [Sv_j d ln dif_j/d rt + Sr_j d ln qqq_j/d rt],
+ *              dcdh_i = sum_{j>i} dcdz_j.
+ *          dcdz [B][P][Lmax]: d c(period) / d (depth of the top of input layer j), the other interfaces fixed; dcdh [B][P][Lmax]:
+ *          d c(period) / d (thickness of input layer i), everything below shifted rigidly - what a change of model[:, 3, i] does.
+ *          Evaluated in fp64 from the fp32 rows (the layer-top values as (5f) returns them, the shares as (5b) returns them), so
+ *          pysurfinv_amd.senskernel.thickness_kernels_reference, the same statement in numpy, can be fed with the returned rows.
+ *          Left out: the flattening-factor term of a liquid layer itself (the rows of a water layer are not read; it would enter only
+ *          dcdh[0] and dcdz[1] of a water-covered stack, whose jump term - the water depth - is formed), the dependence of the layer
+ *          dropping on the thicknesses (every other row ignores it too), the share of a layer without thickness.
+ *          After the launches of (5b) - c, u, status, dcdb, dcda, dcdr bit-identical to surfdisp_forward_kernels_device on the same
+ *          inputs - the eigenfunction instantiation of the group-velocity kernel runs on the roots already found (no second root
+ *          search) and one more kernel combines the two layer-major scratches.  Zeros: below the effective half space, beyond nlay,
+ *          unsolved periods, bad stacks and degenerate exits, dcdh[nlay - 1], dcdz[0].  Every entry NaN for a solved unit with a value
+ *          that is not finite (amp, a jump: e.g. a liquid layer below the top) - *n_nonfinite (device int, may be NULL) counts those
+ *          units, as in (5d).  dcda, dcdr, dcdz may be NULL; dcdh has the same bits whichever of them are.  Rayleigh and Love.
+ *          SURFDISP_INDEPENDENT, SURFDISP_STRICT and the scan flags as in (5b) and (5f).  SURFDISP_ERR_INVALID, before anything is
+ *          launched: SURFDISP_PHASE_ONLY, SURFDISP_KERN_REFCOORD, a NULL c, u, status, dcdb or dcdh, and a workspace smaller than
+ *          surfdisp_thickness_kernels_workspace_bytes (that of (5b) plus the eigenfunction scratch of (5f) and one word per unit:
+ *          there is no direct route). */
+size_t surfdisp_thickness_kernels_workspace_bytes(int B, int Lmax, int P);
+int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                              const float *model, int P, const float *per, int kind,
+                                              float *c, float *u, int *status,
+                                              float *dcdb, float *dcda, float *dcdr,
+                                              float *dcdh, float *dcdz,                 /* [B][P][Lmax] */
+                                              int *n_nonfinite,
+                                              void *workspace, size_t workspace_bytes);
+
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:
  *          Model1D.seisPropLayers, models.py:72-102 + layers.py:139-284) for models with a static
  *          layer structure.  params [C][N] fp64, model [C][5][L] fp32 (rows vp, vs, rho, h, 1/Qs);

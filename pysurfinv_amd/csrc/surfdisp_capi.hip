@@ -360,10 +360,10 @@ struct EigCarve {
     int *ehs;
     size_t total;
 };
-static EigCarve eigcarve(void *base, int B, int Lmax, int P)
+static EigCarve eigcarve(void *base, int B, int Lmax, int P, size_t behind = 0)
 {
     char *p = static_cast<char *>(base);
-    size_t off = align_up(carve(nullptr, B, Lmax, P).total);
+    size_t off = behind ? align_up(behind) : align_up(carve(nullptr, B, Lmax, P).total);   // (behind: the thickness entry's, after the partials' scratch)
     EigCarve e;
     e.escr = reinterpret_cast<float *>(p + off);  off += align_up((size_t)4 * Lmax * P * B * sizeof(float));
     e.ediv = reinterpret_cast<float *>(p + off);  off += align_up((size_t)P * B * sizeof(float));
@@ -378,7 +378,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
                                float *c, float *u, int *status,
                                void *workspace, size_t workspace_bytes, hipEvent_t *ev,
                                float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr,
-                               bool force_hist = false, bool scr_vp = false, const EigCarve *eig = nullptr)
+                               bool force_hist = false, bool scr_vp = false, const EigCarve *eig = nullptr, bool scr_rho = false)
 {
     int rc = check_args(B, Lmax, P, kind, model, per, c, u);
     if (rc) return rc;
@@ -471,8 +471,9 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
         khs = reinterpret_cast<int *>(q);
     }
     // (on the scratch route kb / ka / kr only say which planes the kernel stores: scr_vp asks for the dc/dVp plane - the
-    // attenuation kernel reads it - also when the caller wants no dc/dVp rows)
-    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka, kr,
+    // attenuation kernel reads it - also when the caller wants no dc/dVp rows; scr_rho: the same for dc/drho, the thickness kernel)
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka,
+                     (scr_rho && kscr && !kr) ? kb : kr,
                      kscr, kscale, khs, kern_raw ? 1 : 0, 0, 0, kn.group_order};
     if (eig) { ga.escr = eig->escr; ga.ediv = eig->ediv; ga.ehs = eig->ehs; ga.esum = eig->esum; }   // (the EIG instantiation)
     // (not beside other batches: the stash's 50 KB per workgroup would keep their root-search workgroups off the CU)
@@ -694,6 +695,77 @@ int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay
     const Carve w = carve(workspace, B, Lmax, P);
     sd::EigenTransposeArgs ta{B, P, Lmax, wave, w.mdl, w.nl, per, e.escr, e.ediv, e.ehs, e.esum, w.ct, w.ut, ur, uz, tz, tr, energy};
     SD_HIP(sd::launch_eigen_transpose(s, ta));
+    return SURFDISP_SUCCESS;
+}
+
+// The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit), then the EIG instantiation of the
+// group-velocity kernel on the roots and ellipticities those launches left (no second root search; its U goes to a scratch
+// plane), then the thickness kernel on both layer-major scratches (K2e in surfdisp_kernels.hip).  Workspace: the kernels
+// entry's, then the eigenfunction scratch and its per-unit words, then the scratch plane; no direct route.
+struct ThickCarve {
+    EigCarve e;
+    float *us;
+    size_t total;
+};
+static ThickCarve thickcarve(void *base, int B, int Lmax, int P)
+{
+    ThickCarve t;
+    t.e = eigcarve(base, B, Lmax, P, surfdisp_kernels_workspace_bytes(B, Lmax, P));
+    size_t off = t.e.total;
+    t.us = reinterpret_cast<float *>(static_cast<char *>(base) + off);  off += align_up((size_t)P * B * sizeof(float));
+    t.total = off;
+    return t;
+}
+
+size_t surfdisp_thickness_kernels_workspace_bytes(int B, int Lmax, int P)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    return thickcarve(nullptr, B, Lmax, P).total;
+}
+
+int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                              const float *model, int P, const float *per, int kind,
+                                              float *c, float *u, int *status,
+                                              float *dcdb, float *dcda, float *dcdr,
+                                              float *dcdh, float *dcdz, int *n_nonfinite,
+                                              void *workspace, size_t workspace_bytes)
+{
+    if (!c || !u || !status || !dcdb || !dcdh) {
+        set_err("surfdisp_forward_thickness_kernels_device: c, u, status, dcdb or dcdh is NULL");
+        return SURFDISP_ERR_INVALID;
+    }
+    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
+        set_err("surfdisp_forward_thickness_kernels_device: no PHASE_ONLY, no KERN_REFCOORD");
+        return SURFDISP_ERR_INVALID;
+    }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (!workspace || workspace_bytes < surfdisp_thickness_kernels_workspace_bytes(B, Lmax, P)) {
+        set_err("workspace too small (surfdisp_thickness_kernels_workspace_bytes)");
+        return SURFDISP_ERR_INVALID;
+    }
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
+                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, nullptr, false, true, nullptr, true);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int wave = kind & ~SD_KIND_FLAGS;
+    const EnvKnobs &kn = knobs();
+    const Carve w = carve(workspace, B, Lmax, P);
+    const ThickCarve t = thickcarve(workspace, B, Lmax, P);
+    char *q = static_cast<char *>(workspace) + align_up(w.total);               // forward_device_impl's scratch, factors, layers
+    const float *kscr = reinterpret_cast<const float *>(q);    q += align_up((size_t)3 * Lmax * P * B * sizeof(float));
+    const float *kscale = reinterpret_cast<const float *>(q);  q += align_up((size_t)P * B * sizeof(float));
+    const int *khs = reinterpret_cast<const int *>(q);
+    if (n_nonfinite) SD_HIP(hipMemsetAsync(n_nonfinite, 0, sizeof(int), s));
+    // (kb = nullptr: the EIG instantiation, which writes no partials)
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, t.us, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, 0, 0, 0, kn.group_order};
+    ga.escr = t.e.escr; ga.ediv = t.e.ediv; ga.ehs = t.e.ehs; ga.esum = t.e.esum;
+    ga.stash = -1;
+    SD_HIP(sd::launch_group(s, wave, ga));
+    sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, per, t.e.escr, t.e.ediv, t.e.ehs, t.e.esum, kscr, kscale, khs,
+                     w.ct, w.ut, dcdh, dcdz, n_nonfinite};
+    SD_HIP(sd::launch_thickness(s, ta));
     return SURFDISP_SUCCESS;
 }
 

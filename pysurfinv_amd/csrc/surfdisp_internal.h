@@ -128,6 +128,25 @@ struct AttenArgs {
     float *dqdq;          // nullptr, or the caller's [B][P][Lmax] rows: d (1 / Q_apparent) / d (1/Qs of layer i)
 };
 hipError_t launch_atten(hipStream_t s, const AttenArgs &a);
+// thickness and interface-depth kernels of c (surfdisp_forward_thickness_kernels_device) from both scratches, see K2e
+struct ThickArgs {
+    int B, P, Lmax, kind;
+    const float *model;   // the caller's [B][5][Lmax]: row 3, the thicknesses (the staged fields hold only the flattened ones)
+    const float *mdl;     // SoA staged fields
+    const int *nl;        // [B]
+    const float *per;     // [P]
+    const float *escr;    // [4][Lmax][P][B] layer-top values (Love: planes 0, 1)
+    const float *ediv;    // [P][B]
+    const int *ehs;       // [P][B]
+    const float *esum;    // [3][P][B]: plane 0, I0, is read
+    const float *kscr;    // [3][Lmax][P][B] unscaled shares (Love: planes 0, 2)
+    const float *kscale;  // [P][B]
+    const int *khs;       // [P][B]
+    const float *c, *u;   // [P][B] period-major
+    float *dcdh, *dcdz;   // the caller's [B][P][Lmax] rows (dcdz may be nullptr)
+    int *n_nonfinite;     // nullptr, or [1]: solved units with NaN rows
+};
+hipError_t launch_thickness(hipStream_t s, const ThickArgs &a);
 
 // group-velocity kernels (surfdisp_forward_group_kernels_device): the fundamental-mode roots at the shifted periods
 // T (1 -+ dfrac) of every solved (stack, period) unit, found from the first-order prediction without a scan

@@ -30,6 +30,8 @@
 //                               integration + energy integrals (surfa.f:714-1192 / 374-606), fp64 state
 //                               for Rayleigh as in the reference (surfa.f:717-722); the KERN
 //                               instantiation also writes the analytic partials dc/d(Vs, Vp, rho).
+//   K2e surfdisp_thickness_kernel (surfdisp_forward_thickness_kernels_device only): dc/d(layer thickness, interface depth) from
+//                               the layer-top eigenfunctions of the EIG instantiation and the partials' scratch (see K2e below).
 //   K3 surfdisp_finish_kernel : period-major internal results -> the caller's [B][P] arrays.
 //   K4 (surfdisp_forward_group_kernels_device only) surfdisp_shift_kernel + K2 + surfdisp_group_combine_kernel: roots at
 //                               T (1 -+ d) from the first-order prediction, the phase partials there, and the analytic
@@ -3215,6 +3217,267 @@ __global__ __launch_bounds__(256) void surfdisp_atten_kernel(AttenArgs A)
     }
 }
 
+// K2e: the thickness and interface-depth kernels of the phase velocity (surfdisp_forward_thickness_kernels_device) from the two
+// layer-major scratches: the layer-top eigenfunctions of the EIG group-velocity kernel (K2d) and the unscaled shares of
+// dc/d(Vs, Vp, rho) (K2b).  With v_j the displacement-stress vector at the top of caller layer j, normalised as K2d returns it,
+// (a, b, rho)_m the values layer_at gives, lam = rho (a^2 - 2 b^2), mu = rho b^2, k = omega / c, the Hamiltonian of the depth ODE
+//      Love      E(v; m) = rho omega^2 ut^2 - mu k^2 ut^2 + tq^2 / mu
+//      Rayleigh  uz' = (tz + k lam ur) / (lam + 2 mu), ur' = tr / mu - k uz,
+//                W2 = lam (uz' - k ur)^2 + 2 mu (k^2 ur^2 + uz'^2) + mu (ur' + k uz)^2,
+//                E(v; m) = rho omega^2 (ur^2 + uz^2) - W2 + 2 tr ur' + 2 tz uz'
+//      liquid layer above the sea floor (lam = rho a^2): urw = -k tz / (rho omega^2), uz' = tz / lam + k urw,
+//                E = rho omega^2 (urw^2 + uz^2) - tz^2 / lam + 2 tz uz'             (Love: 0, the sea floor is its free surface)
+// is constant through a homogeneous layer, and its jump is the kernel of the flattened depth of interface j (1 <= j <= hs, the
+// unit's effective half space), the other interfaces and omega fixed:
+//      K_j = -amp (c^3 / omega^2) [E(v_j; j-1) - E(v_j; j)],      amp = 1 / (2 c U I0).
+// The caller's depth of interface j also moves the flattening factors of the two layers it bounds (flat1.f:44-62; r_j = R0 -
+// sum_{m<j} h_m, rt / rb a layer's top / bottom radius, x = ln(rt / rb), p = pwr_of; q^p = (rb / rt)^p = exp(-p x)):
+//      d ln dif/d rt =  1 / (rt^2 (1/rb - 1/rt)) - 1 / (x rt),      d ln dif/d rb = -1 / (rb^2 (1/rb - 1/rt)) + 1 / (x rb),
+//      d ln qqq/d rt =  p / (rt (1 - q^p)) - 1 / (x rt),            d ln qqq/d rb = -p q^p / (rb (1 - q^p)) + 1 / (x rb),
+//      (the layer nlay - 1 in its half-space role: -1 / rt and p / rt),
+// which act on c through the caller-coordinate shares Sv_m = Vs dc/dVs + Vp dc/dVp, Sr_m = rho dc/drho - the scratch values
+// times the unit's factor in fp32, exactly the rows K2b writes (a' is homogeneous of degree 1 in (Vp, Vs), so Sv is the share
+// of ln dif):
+//      dcdz_j = K_j R0 / r_j - [Sv_{j-1} d ln dif_{j-1}/d rb + Sr_{j-1} d ln qqq_{j-1}/d rb] - [Sv_j d ln dif_j/d rt + Sr_j d ln qqq_j/d rt],
+//      dcdh_i = sum_{j>i} dcdz_j       (layer i thicker, everything below shifted rigidly).
+// All in fp64 (the 1/h-sized terms of the factor derivatives cancel down to 1/r).  Left out: the factor term of a liquid
+// layer (its shares are not read), the dependence of the layer dropping on the thicknesses (as in every other row), and the
+// share of a layer without thickness (it holds no energy).
+// ThickUnit: what one (stack, period) unit needs; entry (component q, layer i) of its layer-top values sits at
+// ev[q * e_plane + i * e_layer], its shares (0 Vs, 1 Vp, 2 rho) at kv[q * k_plane + i * k_layer].
+struct ThickUnit {
+    const float *mdl; size_t fs; int B, b, n;
+    int hs;                       // deepest interface with a kernel; < 1: a unit of zeros
+    int khs;                      // deepest layer with shares
+    bool wet;
+    float lnT, dv, ksc;
+    double k, om2, fac;           // wavenumber, omega^2, -amp c^3 / omega^2
+    const float *ev; size_t e_layer, e_plane;
+    const float *kv; size_t k_layer, k_plane;
+};
+SD_HD inline ThickUnit thick_unit(const float *mdl, size_t fs, int B, int b, int n, float T, float c, float u, float i0,
+                                  float dv, int ehs, float ksc, int khs, const float *ev, size_t e_layer, size_t e_plane,
+                                  const float *kv, size_t k_layer, size_t k_plane)
+{
+    ThickUnit q;
+    q.mdl = mdl; q.fs = fs; q.B = B; q.b = b; q.n = n;
+    q.ev = ev; q.e_layer = e_layer; q.e_plane = e_plane; q.kv = kv; q.k_layer = k_layer; q.k_plane = k_plane;
+    q.dv = dv; q.ksc = ksc; q.khs = khs;
+    q.hs = (n >= 2 && ksc != 0.0f && c > 0.0f && ehs <= n - 1) ? ehs : -1;
+    q.wet = false; q.lnT = 0.0f; q.k = 0.0; q.om2 = 0.0; q.fac = 0.0;
+    if (q.hs >= 1) {
+        const double om = (double)6.2831853072f / (double)T;
+        q.lnT = logf(1.0f / T);
+        q.k = om / (double)c;
+        q.om2 = om * om;
+        q.fac = -(1.0 / (2.0 * (double)c * (double)u * (double)i0)) * ((double)c * (double)c * (double)c) / q.om2;
+        q.wet = !(mdl[F_VS * fs + (size_t)b] > 0.0f);
+    }
+    return q;
+}
+SD_HD __forceinline__ double thick_energy_love(double ut, double tq, const LayerV &v, double k, double om2)
+{
+#pragma clang fp contract(off)
+    const double rho = v.rho, mu = rho * ((double)v.b * (double)v.b);
+    return rho * om2 * (ut * ut) - mu * (k * k) * (ut * ut) + tq * tq / mu;
+}
+SD_HD __forceinline__ double thick_energy_rayleigh(double ur, double uz, double tz, double tr, const LayerV &v, double k, double om2)
+{
+#pragma clang fp contract(off)
+    const double rho = v.rho, b2 = (double)v.b * (double)v.b, mu = rho * b2;
+    const double lam = rho * ((double)v.a * (double)v.a - 2.0 * b2);
+    const double duz = (tz + k * lam * ur) / (lam + 2.0 * mu);
+    const double dur = tr / mu - k * uz;
+    const double e1 = duz - k * ur, e2 = dur + k * uz;
+    const double w2 = lam * (e1 * e1) + 2.0 * mu * (k * k * (ur * ur) + duz * duz) + mu * (e2 * e2);
+    return rho * om2 * (ur * ur + uz * uz) - w2 + 2.0 * tr * dur + 2.0 * tz * duz;
+}
+SD_HD __forceinline__ double thick_energy_liquid(double uz, double tz, const LayerV &v, double k, double om2)
+{
+#pragma clang fp contract(off)
+    const double rho = v.rho, lam = rho * ((double)v.a * (double)v.a);
+    const double urw = -k * tz / (rho * om2);
+    const double duz = tz / lam + k * urw;
+    return rho * om2 * (urw * urw + uz * uz) - tz * tz / lam + 2.0 * tz * duz;
+}
+// the caller-coordinate shares (Sv, Sr) of layer m: K2b's fp32 products; a liquid layer and a layer below khs have none
+template <int KIND>
+SD_HD __forceinline__ void thick_shares(const ThickUnit &q, int m, double *sv, double *sr)
+{
+#pragma clang fp contract(off)
+    *sv = 0.0; *sr = 0.0;
+    if (m > q.khs) return;
+    const size_t ol = (size_t)m * q.B + q.b;
+    const float vs = q.mdl[F_VS * q.fs + ol];
+    if (!(vs > 0.0f)) return;
+    const float *p = q.kv + (size_t)m * q.k_layer;
+    const float kb = p[0] * q.ksc, kr = p[2 * q.k_plane] * q.ksc;
+    double s = (double)vs * (double)kb;
+    if (KIND == 2) {
+        const float ka = p[q.k_plane] * q.ksc;
+        s = s + (double)q.mdl[F_VP * q.fs + ol] * (double)ka;
+    }
+    *sv = s;
+    *sr = (double)q.mdl[F_RHO * q.fs + ol] * (double)kr;
+}
+// dcdz_j of interface j (1 <= j <= q.hs): z_up the depth of the top of layer j - 1 (the fp64 sum of the thicknesses above
+// it, in layer order), h_up and h_dn the thicknesses of the layers j - 1 and j.  *kj: the flattened-depth kernel K_j.
+template <int KIND>
+SD_HD inline double thick_interface(const ThickUnit &q, int j, double z_up, float h_up, float h_dn, double *kj)
+{
+#pragma clang fp contract(off)
+    const float *e = q.ev + (size_t)j * q.e_layer;
+    const LayerV up = layer_at(q.mdl, q.fs, (size_t)(j - 1) * q.B + q.b, q.lnT, false);
+    const LayerV dn = layer_at(q.mdl, q.fs, (size_t)j * q.B + q.b, q.lnT, j == q.n - 1);
+    const bool sea_floor = q.wet && j == 1;
+    double jump;
+    if (KIND == 2) {
+        // (the fp32 quotients K2d writes; Rayleigh's divisor is 1)
+        const double ur = e[0] / q.dv, uz = e[q.e_plane] / q.dv, tz = e[2 * q.e_plane] / q.dv, tr = e[3 * q.e_plane] / q.dv;
+        const double eu = sea_floor ? thick_energy_liquid(uz, tz, up, q.k, q.om2) : thick_energy_rayleigh(ur, uz, tz, tr, up, q.k, q.om2);
+        jump = eu - thick_energy_rayleigh(ur, uz, tz, tr, dn, q.k, q.om2);
+    } else {
+        float ut = e[0] / q.dv, tq = e[q.e_plane] / q.dv;
+        if (fabsf(ut) < 1.0e-20f) {                          // Love's low-amplitude exclusion, as K2d applies it
+            const float vh = layer_at(q.mdl, q.fs, (size_t)q.hs * q.B + q.b, q.lnT, q.hs == q.n - 1).b;
+            if (dn.b >= vh) { ut = 0.0f; tq = 0.0f; }
+        }
+        const double eu = sea_floor ? 0.0 : thick_energy_love(ut, tq, up, q.k, q.om2);
+        jump = eu - thick_energy_love(ut, tq, dn, q.k, q.om2);
+    }
+    *kj = q.fac * jump;
+    const double r0 = (double)R0, p = (double)pwr_of(KIND);
+    const double z_j = z_up + (double)h_up;
+    const double r_up = r0 - z_up, r_j = r0 - z_j;
+    double sv, sr, chain = 0.0;
+    if (h_up > 0.0f) {                                       // the layer above, regular role: its bottom radius moves
+        thick_shares<KIND>(q, j - 1, &sv, &sr);
+        const double x = log(r_up / r_j), inv = 1.0 / r_j - 1.0 / r_up, d = -expm1(-p * x);      // d = 1 - (rb / rt)^p
+        const double dif_rb = -1.0 / (r_j * r_j * inv) + 1.0 / (x * r_j);
+        const double qqq_rb = -p * (1.0 - d) / (r_j * d) + 1.0 / (x * r_j);
+        chain = sv * dif_rb + sr * qqq_rb;
+    }
+    thick_shares<KIND>(q, j, &sv, &sr);                      // the layer below: its top radius moves
+    if (j == q.n - 1) {
+        chain = chain + (sv * (-1.0 / r_j) + sr * (p / r_j));
+    } else if (h_dn > 0.0f) {
+        const double r_dn = r0 - (z_j + (double)h_dn);
+        const double x = log(r_j / r_dn), inv = 1.0 / r_dn - 1.0 / r_j, d = -expm1(-p * x);
+        const double dif_rt = 1.0 / (r_j * r_j * inv) - 1.0 / (x * r_j);
+        const double qqq_rt = p / (r_j * d) - 1.0 / (x * r_j);
+        chain = chain + (sv * dif_rt + sr * qqq_rt);
+    }
+    return *kj * r0 / r_j - chain;
+}
+
+// One workgroup = 64 consecutive stacks at one period (a lane is one unit; a wavefront reads consecutive words of every plane
+// of both scratches and of the staged fields) x 4 wavefronts that take every fourth interface of a 64-layer tile.  The
+// thicknesses come from the caller's model rows through LDS (read along the layers); every lane forms the depth of each
+// interface for itself, the fp64 sum in layer order from the tile's base depth (ascending pre-pass, wavefront 0).  Tiles run
+// from the deepest to the top: the four wavefronts leave dcdz_j (fp64) of the interfaces i0 + 1 .. i0 + 64 in LDS, wavefront 0
+// adds them from the deepest up into the running sum it carries across the tiles in a register - dcdh[i] is the sum after
+// interface i + 1 - and the rows leave through the 64 x 64 tile (row stride 65) as in K2b; dcdz one word further (dcdz[0] is
+// zero).  No atomics on floating-point values, no per-thread arrays; the order of every sum is fixed.
+// Zeros: below the unit's effective half space and beyond nlay, unsolved periods, bad stacks, degenerate exits (no deepest
+// layer or no factor), dcdh[nlay - 1], dcdz[0].  A unit with a value that is not finite: both rows NaN, counted.
+template <int KIND>
+__global__ __launch_bounds__(256) void surfdisp_thickness_kernel(ThickArgs A)
+{
+    static_assert(SURFDISP_NLAY_MAX <= 256, "zbase holds four 64-layer tiles");
+    __shared__ double dzt[64][65];
+    __shared__ float ht[65][65];
+    __shared__ double zbase[4][64];
+    __shared__ int badf[64];
+    const int B = A.B, P = A.P, Lmax = A.Lmax;
+    const int nbb = (B + 63) / 64;
+    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64;
+    const size_t PB = (size_t)P * B, fs = (size_t)Lmax * B;
+    const int bl = threadIdx.x % 64, wv = threadIdx.x / 64;
+    const int b = b0 + bl;
+    const bool live = b < B;
+    const size_t un = (size_t)k * B + (live ? b : b0);        // (read only where live)
+    const int ntile = (Lmax + 63) / 64;
+    ThickUnit q = thick_unit(A.mdl, fs, B, live ? b : b0, 0, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f, -1, 0.0f, -1, nullptr, 0, 0, nullptr, 0, 0);
+    if (live) {
+        const int ehs = A.ehs[un];
+        q = thick_unit(A.mdl, fs, B, b, A.nl[b], A.per[k], A.c[un], A.u[un], ehs >= 0 ? A.esum[un] : 0.0f,
+                       ehs >= 0 ? A.ediv[un] : 1.0f, ehs, A.kscale[un], A.khs[un],
+                       A.escr + un, PB, (size_t)Lmax * PB, A.kscr + un, PB, (size_t)Lmax * PB);
+    }
+    if (threadIdx.x < 64) badf[threadIdx.x] = 0;
+    // thicknesses of the tile's layers (and the first of the next tile) -> ht[layer][stack]; 0 beyond nlay
+    auto load_h = [&](int i0, int rows) {
+        for (int t = threadIdx.x; t < rows * 64; t += 256) {
+            const int il = t % rows, bq = t / rows;
+            float h = 0.0f;
+            if (b0 + bq < B && i0 + il < A.nl[b0 + bq]) h = A.model[((size_t)(b0 + bq) * 5 + 3) * Lmax + i0 + il];
+            ht[il][bq] = h;
+        }
+    };
+    double zrun = 0.0;
+    for (int t = 0; t < ntile; ++t) {                        // base depth of every tile
+        load_h(t * 64, 64);
+        __syncthreads();
+        if (wv == 0) {
+            zbase[t][bl] = zrun;
+            for (int il = 0; il < 64; ++il) zrun = zrun + (double)ht[il][bl];
+        }
+        __syncthreads();
+    }
+    double carry = 0.0;                                      // (wavefront 0) sum of dcdz over the interfaces below
+    bool bad = false;
+    for (int t = ntile - 1; t >= 0; --t) {
+        const int i0 = t * 64;
+        load_h(i0, 65);
+        __syncthreads();
+        double z = zbase[t][bl];                             // depth of the top of layer i0 + il
+        for (int il = 0; il < 64; ++il) {
+            const float h_up = ht[il][bl];
+            if ((il & 3) == wv) {
+                const int j = i0 + il + 1;
+                double dz = 0.0, kj;
+                if (j <= q.hs) {
+                    dz = thick_interface<KIND>(q, j, z, h_up, ht[il + 1][bl], &kj);
+                    if (!(fabs(dz) <= 1.0e300)) bad = true;
+                }
+                dzt[il][bl] = dz;
+            }
+            z = z + (double)h_up;
+        }
+        __syncthreads();
+        if (wv == 0) {
+            for (int il = 63; il >= 0; --il) {
+                carry = carry + dzt[il][bl];
+                ht[il][bl] = (float)carry;                   // dcdh[i0 + il]
+            }
+        }
+        __syncthreads();
+        for (int s = threadIdx.x; s < 64 * 64; s += 256) {
+            const int bq = s / 64, il = s % 64;
+            if (b0 + bq < B) {
+                const size_t row = ((size_t)(b0 + bq) * P + k) * Lmax;
+                if (i0 + il < Lmax) A.dcdh[row + i0 + il] = ht[il][bq];
+                if (A.dcdz) {
+                    if (i0 + il + 1 < Lmax) A.dcdz[row + i0 + il + 1] = (float)dzt[il][bq];
+                    if (i0 + il == 0) A.dcdz[row] = 0.0f;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (bad) badf[bl] = 1;                                   // (every writer stores the same value)
+    __syncthreads();
+    if (wv == 0 && live && badf[bl] && A.n_nonfinite) atomicAdd(A.n_nonfinite, 1);
+    for (int s = threadIdx.x; s < 64 * Lmax; s += 256) {     // (rare) NaN rows
+        const int bq = s / Lmax, i = s % Lmax;
+        if (b0 + bq < B && badf[bq]) {
+            const size_t o = ((size_t)(b0 + bq) * P + k) * Lmax + i;
+            A.dcdh[o] = __builtin_nanf("");
+            if (A.dcdz) A.dcdz[o] = __builtin_nanf("");
+        }
+    }
+}
+
 // ====================================================================== K4: group-velocity kernels
 // surfdisp_forward_group_kernels_device, behind the forward + partials launches (whose outputs it leaves as they are).
 // Differentiating U = d omega / dk at fixed omega (Rodi et al. 1975):
@@ -3573,6 +3836,14 @@ hipError_t launch_atten(hipStream_t s, const AttenArgs &a)
     const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)));
     if (a.kind == 2) hipLaunchKernelGGL((surfdisp_atten_kernel<2>), grid, dim3(256), 0, s, a);
     else             hipLaunchKernelGGL((surfdisp_atten_kernel<1>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_thickness(hipStream_t s, const ThickArgs &a)
+{
+    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)));
+    if (a.kind == 2) hipLaunchKernelGGL((surfdisp_thickness_kernel<2>), grid, dim3(256), 0, s, a);
+    else             hipLaunchKernelGGL((surfdisp_thickness_kernel<1>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -360,6 +360,44 @@ class BatchPlan:
         _lib.check(rc)
         return self.c, self.u, self.status, ur, uz, tz, tr, energy
 
+    def run_thickness_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, want_dcdz=True, count=True):
+        """``run_kernels`` plus the derivatives of the phase velocity with respect to the layer thicknesses and the interface
+        depths (``surfdisp_forward_thickness_kernels_device``): returns (c, u, status, dcdb, dcda, dcdr, dcdh, dcdz,
+        n_nonfinite).  c .. dcdr equal ``run_kernels``' bit for bit; dcdh float32 [B, P, L] = d c(period) / d (thickness of input
+        layer i), everything below shifted rigidly - what a change of ``model[:, 3, i]`` does; dcdz [B, P, L] = d c(period) /
+        d (depth of the top of layer j), the other interfaces fixed (``None`` with ``want_dcdz=False``); dcdh[i] = sum_{j>i}
+        dcdz[j].  Zeros below a unit's effective half space, beyond nlay, for unsolved periods and bad stacks, in
+        dcdh[nlay - 1] and dcdz[0]; rows of a unit with a value that is not finite are NaN and ``n_nonfinite`` (int,
+        synchronises the stream; ``count=False``: the device tensor itself) counts them.  Rayleigh and Love; the
+        conventions are those of include/surfdisp.h section (5g)."""
+        torch = self.torch
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        dcdb, dcdh = mk(), mk()
+        dcda = mk() if (want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH) else None
+        dcdr = mk() if want_rho else None
+        dcdz = mk() if want_dcdz else None
+        if getattr(self, "tworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
+            self.tws_bytes = int(_lib.lib().surfdisp_thickness_kernels_workspace_bytes(self.B, self.L, self.P))
+            self.tworkspace = torch.empty(self.tws_bytes, dtype=torch.uint8, device=self.device)
+            self.tnonfin = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        self._last_ws = self.tworkspace
+        with torch.cuda.device(self.device):
+            rc = _lib.lib().surfdisp_forward_thickness_kernels_device(
+                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                ptr(dcdh), ptr(dcdz), ptr(self.tnonfin), ptr(self.tworkspace), self.tws_bytes)
+        _lib.check(rc)
+        return (self.c, self.u, self.status, dcdb, dcda, dcdr, dcdh, dcdz, int(self.tnonfin.item()) if count else self.tnonfin)
+
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
         own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""

@@ -253,7 +253,7 @@ def _expm(A):
     return E
 
 
-def eigen_layer_matrix(lay, i, period, c, wtype="R", frac=1.0, rk4_steps=0):
+def eigen_layer_matrix(lay, i, period, c, wtype="R", frac=1.0, rk4_steps=0, fp32_inputs=True):
     """The exact propagator of layer ``i`` of ``flattened_layers``' dict ``lay``: the matrix that carries the
     displacement-stress vector of the mode with phase velocity ``c`` at ``period`` UPWARD through ``frac`` of the layer's
     (flattened) thickness H, exp(-frac H A), float64.  Rayleigh, v = (ur, uz, tz, tr), the system REIGEN integrates
@@ -265,10 +265,15 @@ def eigen_layer_matrix(lay, i, period, c, wtype="R", frac=1.0, rk4_steps=0):
     Love, v = (ut, tq) (surfa.f:549-550):  ut' = tq / mu,  tq' = (k^2 mu - omega^2 rho) ut.
 
     ``rk4_steps`` > 0: not the exact map but the one REIGEN itself applies over that distance - that many classical
-    Runge-Kutta steps (surfa.f:955-968: the polynomial I + X + X^2/2 + X^3/6 + X^4/24 of X = -h A per step)."""
+    Runge-Kutta steps (surfa.f:955-968: the polynomial I + X + X^2/2 + X^3/6 + X^4/24 of X = -h A per step).
+    ``fp32_inputs=False``: ``period`` and ``c`` are not rounded to the solver's float32 first."""
     a, b, rho, H = (float(lay[k][i]) for k in ("a", "b", "rho", "d"))
-    om = _TWOPI32 / float(np.float32(period))
-    k = _TWOPI32 / (float(np.float32(c)) * float(np.float32(period)))
+    if not fp32_inputs:                                # (float64 checkers: period and c as they are given)
+        om = _TWOPI32 / float(period)
+        k = om / float(c)
+    else:
+        om = _TWOPI32 / float(np.float32(period))
+        k = _TWOPI32 / (float(np.float32(c)) * float(np.float32(period)))
     mu = rho * b * b
     if wtype == "L":
         A = np.array([[0.0, 1.0 / mu], [k * k * mu - om * om * rho, 0.0]])
@@ -294,6 +299,117 @@ def eigen_layer_propagate(model, period, c, layer, v, wtype="R", nlay=None, frac
     ``eigenfunctions``.  Returns the vector at the upper depth."""
     lay = flattened_layers(model, period, wtype, nlay)
     return eigen_layer_matrix(lay, int(layer), period, c, wtype, frac) @ np.asarray(v, np.float64)
+
+
+def interface_energy(v, a, b, rho, k, omega, wtype="R", liquid=False):
+    """E(v; m): the Hamiltonian of the depth ODE of ``eigen_layer_matrix`` for the displacement-stress vector ``v`` ((ur, uz,
+    tz, tr); Love (ut, tq)) in the material (a, b, rho) - constant through a homogeneous layer; its jump across an
+    interface is that interface's depth kernel (``thickness_kernels_reference``).  lam = rho (a^2 - 2 b^2), mu = rho b^2.
+
+        Love:      E = rho omega^2 ut^2 - mu k^2 ut^2 + tq^2 / mu
+        Rayleigh:  uz' = (tz + k lam ur) / (lam + 2 mu),  ur' = tr / mu - k uz,
+                   W2 = lam (uz' - k ur)^2 + 2 mu (k^2 ur^2 + uz'^2) + mu (ur' + k uz)^2,
+                   E = rho omega^2 (ur^2 + uz^2) - W2 + 2 tr ur' + 2 tz uz'
+        ``liquid`` (the water layer above the sea floor, lam = rho a^2; of v only uz and tz are read):
+                   urw = -k tz / (rho omega^2),  uz' = tz / lam + k urw,
+                   E = rho omega^2 (urw^2 + uz^2) - tz^2 / lam + 2 tz uz';      Love: E = 0 (the sea floor is its free surface)."""
+    a, b, rho, k, om2 = float(a), float(b), float(rho), float(k), float(omega) ** 2
+    v = np.asarray(v, np.float64)
+    if wtype == "L":
+        if liquid:
+            return 0.0
+        mu = rho * b * b
+        return rho * om2 * v[0] ** 2 - mu * k * k * v[0] ** 2 + v[1] ** 2 / mu
+    ur, uz, tz, tr = v
+    if liquid:
+        lam = rho * a * a
+        urw = -k * tz / (rho * om2)
+        duz = tz / lam + k * urw
+        return rho * om2 * (urw * urw + uz * uz) - tz * tz / lam + 2.0 * tz * duz
+    mu = rho * b * b
+    lam = rho * (a * a - 2.0 * b * b)
+    duz = (tz + k * lam * ur) / (lam + 2.0 * mu)
+    dur = tr / mu - k * uz
+    w2 = lam * (duz - k * ur) ** 2 + 2.0 * mu * (k * k * ur * ur + duz * duz) + mu * (dur + k * uz) ** 2
+    return rho * om2 * (ur * ur + uz * uz) - w2 + 2.0 * tr * dur + 2.0 * tz * duz
+
+
+def thickness_kernels_reference(layers, model, period, c, u, I0, v_tops, dcdb, dcda, dcdr, wtype, nlay=None, hs=None):
+    """The derivatives of the phase velocity of ONE (stack, period) unit with respect to the layer thicknesses and the
+    interface depths, in numpy float64: the host statement of what ``surfdisp_forward_thickness_kernels_device`` computes
+    (include/surfdisp.h section (5g)).  ``layers``: the dict of ``flattened_layers`` (the values the mode was computed on;
+    the layer used as half space in that role); ``model`` [5, L]; ``c``, ``u`` (the structural group velocity), ``I0`` and
+    ``v_tops`` [4 | 2][L] (the vector at the top of every layer, section (5f)) as ``eigenfunctions`` returns them; ``dcdb``,
+    ``dcda`` (``None``: Love), ``dcdr`` [L] the unit's rows of ``analytic_kernels``.  ``hs``: the unit's effective half space
+    (default: the deepest layer with a non-zero entry in v_tops, dcdb or dcdr).
+
+        K_j = -amp (c^3 / omega^2) [E(v_j; j-1) - E(v_j; j)],  amp = 1 / (2 c U I0),  1 <= j <= hs
+
+    (``interface_energy``; the layer above a sea floor in its liquid form) is dc / d(flattened depth of interface j).  In the
+    caller's coordinates (flat1.f; r_j = R0 - sum_{m<j} h_m, rt / rb the top / bottom radius of a layer, x = ln(rt/rb),
+    p = 2.275 | 5, Sv_m = Vs dcdb + Vp dcda, Sr_m = rho dcdr):
+
+        d ln dif/d rt =  1 / (rt^2 (1/rb - 1/rt)) - 1/(x rt),      d ln dif/d rb = -1 / (rb^2 (1/rb - 1/rt)) + 1/(x rb),
+        d ln qqq/d rt =  p rt^(p-1) / (rt^p - rb^p) - 1/(x rt),    d ln qqq/d rb = -p rb^(p-1) / (rt^p - rb^p) + 1/(x rb),
+        (half-space role, layer nlay - 1: d ln dif/d rt = -1/rt, d ln qqq/d rt = p/rt)
+        dcdz_j = K_j R0 / r_j - [Sv_{j-1} d ln dif_{j-1}/d rb + Sr_{j-1} d ln qqq_{j-1}/d rb]
+                              - [Sv_j d ln dif_j/d rt + Sr_j d ln qqq_j/d rt],
+        dcdh_i = sum_{j>i} dcdz_j.
+
+    Returns (dcdh [L], dcdz [L], K [L]); K alone is the result for a flat stack.  A water layer's own flattening-factor term
+    is left out (the rows of a liquid layer are not read), and so is the dependence of the layer dropping on the thicknesses."""
+    m = np.asarray(model, np.float64)
+    L = m.shape[1]
+    n = L if nlay is None else int(nlay)
+    vt = np.asarray(v_tops, np.float64)
+    kb = np.asarray(dcdb, np.float64).ravel()
+    kr = np.asarray(dcdr, np.float64).ravel()
+    ka = np.zeros(L) if dcda is None else np.asarray(dcda, np.float64).ravel()
+    if hs is None:
+        nz = np.flatnonzero((vt != 0).any(axis=0) | (kb != 0) | (kr != 0))
+        hs = int(nz.max()) if nz.size else -1
+    hs = min(int(hs), n - 1)
+    dcdh, dcdz, K = np.zeros(L), np.zeros(L), np.zeros(L)
+    c, u, I0, T = float(c), float(u), float(I0), float(period)
+    if hs < 1 or not (c > 0):
+        return dcdh, dcdz, K
+    om = _TWOPI32 / T
+    k = om / c
+    fac = -(1.0 / (2.0 * c * u * I0)) * c ** 3 / (om * om)
+    p = float(np.float32(5.0 if wtype == "L" else 2.275))
+    vp, vs, rho, h = m[0], m[1], m[2], m[3]
+    wet = not (vs[0] > 0)
+    r = _R0 - np.concatenate([[0.0], np.cumsum(h)[:-1]])
+    solid = vs > 0                                          # (a water layer's own factor term is left out)
+    Sv = np.where(solid, vs * kb + vp * ka, 0.0)
+    Sr = np.where(solid, rho * kr, 0.0)
+    mat = lambda i: (layers["a"][i], layers["b"][i], layers["rho"][i])
+    for j in range(1, hs + 1):
+        v = vt[:, j]
+        K[j] = fac * (interface_energy(v, *mat(j - 1), k, om, wtype, liquid=(wet and j == 1)) - interface_energy(v, *mat(j), k, om, wtype))
+        # the layer above, regular role: its bottom radius moves
+        rt, rb = r[j - 1], r[j]
+        chain = 0.0
+        if h[j - 1] > 0:                                    # (a layer without thickness holds no energy: no share)
+            x = np.log(rt / rb)
+            dif_rb = -1.0 / (rb * rb * (1.0 / rb - 1.0 / rt)) + 1.0 / (x * rb)
+            qqq_rb = -p * rb ** (p - 1.0) / (rt ** p - rb ** p) + 1.0 / (x * rb)
+            chain = Sv[j - 1] * dif_rb + Sr[j - 1] * qqq_rb
+        # the layer below: its top radius moves
+        rt = r[j]
+        if j == n - 1:
+            dif_rt, qqq_rt = -1.0 / rt, p / rt
+        elif not h[j] > 0:
+            dif_rt = qqq_rt = 0.0
+        else:
+            rb = r[j + 1]
+            x = np.log(rt / rb)
+            dif_rt = 1.0 / (rt * rt * (1.0 / rb - 1.0 / rt)) - 1.0 / (x * rt)
+            qqq_rt = p * rt ** (p - 1.0) / (rt ** p - rb ** p) - 1.0 / (x * rt)
+        chain += Sv[j] * dif_rt + Sr[j] * qqq_rt
+        dcdz[j] = K[j] * _R0 / r[j] - chain
+    dcdh[:-1] = np.cumsum(dcdz[::-1])[::-1][1:]
+    return dcdh, dcdz, K
 
 
 def eigenfunctions(model, periods, wtype="R", nlay=None):
@@ -326,7 +442,7 @@ def _eigen_dict(model, kind, c, u, st, ur, uz, tz, tr, en):
 
 
 def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01,
-                     ellipticity=False, attenuation=False, eigen=False):
+                     ellipticity=False, attenuation=False, eigen=False, thickness=False):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
     the partial derivatives REIGEN / LEIGEN form from their energy integrals and never return
     (surfa.f:1130-1135, 1204-1207; 561-565, 584-585), with the chain factors of the attenuation
@@ -347,6 +463,11 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     [M, P, L] = d qinv / d (1/Qs of layer i) at fixed eigenfunction (qinv = sum_i dqdq_i qsinv_i, see
     ``attenuation_from_kernels``) and Qapp = 1 / qinv (inf where qinv is 0).  One entry of its own as well: refused
     together with ``group=True`` or ``ellipticity=True``.
+    ``thickness=True`` (``surfdisp_forward_thickness_kernels_device``, both wave types): also dcdh [M, P, L] = d c / d (thickness
+    of layer i), everything below shifted rigidly (what a change of ``model[:, 3, i]`` does), dcdz [M, P, L] = d c / d (depth of
+    the top of layer j) with the other interfaces fixed, and n_nonfinite (units whose rows are NaN); see
+    ``thickness_kernels_reference``.  One entry of its own as well: refused together with ``group=True``, ``ellipticity=True``
+    or ``attenuation=True``.
     ``eigen=True`` (``surfdisp_forward_eigen_device``, one more solve on the same plan): also the keys of
     ``eigenfunctions`` - ur, uz, tz, tr (Love ut, tt), I0, I1, I2, amp, ztop."""
     import torch
@@ -357,9 +478,14 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
         raise ValueError("analytic_kernels: ellipticity=True and group=True are separate entries; call once for each")
     if attenuation and (group or ellipticity):
         raise ValueError("analytic_kernels: attenuation=True is an entry of its own; call once more for group / ellipticity")
+    if thickness and (group or ellipticity or attenuation):
+        raise ValueError("analytic_kernels: thickness=True is an entry of its own; call once more for group / ellipticity / attenuation")
     M, _, L = model.shape
     plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
-    if ellipticity:
+    if thickness:
+        c, u, st, kb, ka, kr, kh, kz, nnf = plan.run_thickness_kernels(model, periods, kind=kind, nlay=nlay,
+                                                                       want_vp=want_vp, want_rho=want_rho)
+    elif ellipticity:
         c, u, st, ratio, kb, ka, kr, eb, ea, er, nnf = plan.run_ellip_kernels(model, periods, kind=kind, nlay=nlay,
                                                                              want_vp=want_vp, want_rho=want_rho)
     elif attenuation:
@@ -381,6 +507,8 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     if attenuation:
         out.update(qinv=qinv, gamma=gamma, dqdq=dqdq,
                    Qapp=torch.where(qinv != 0, 1.0 / qinv, torch.full_like(qinv, float("inf"))))
+    if thickness:
+        out.update(dcdh=kh, dcdz=kz, n_nonfinite=nnf)
     if eigen:
         c0, u0 = c.clone(), u.clone()                       # (the plan's c, u are rewritten by the second solve: same bits)
         out.update(c0=c0, u0=u0)
