@@ -88,34 +88,178 @@ constexpr int SD_KIND_FLAGS = SURFDISP_PHASE_ONLY | SURFDISP_INDEPENDENT | SURFD
 
 size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// Workspace layout.  A bump carver hands out the arrays of a region one after the other, each padded to 256 bytes; on a null
+// base it only counts.  Every region is written once, below, and an entry's workspace is a composition of regions
+// (layout()), so a size function and the pointers its entry uses come from the same code.
+struct Carver {
+    uintptr_t base;
+    size_t off;
+    explicit Carver(void *b, size_t at = 0) : base(reinterpret_cast<uintptr_t>(b)), off(at) {}
+    template <typename T> T *take(size_t count)
+    {
+        T *p = reinterpret_cast<T *>(base + off);
+        off += align_up(count * sizeof(T));
+        return p;
+    }
+};
+
+// the forward solve's region
 struct Carve {
     float *mdl, *rows, *ratio, *ct, *ut;
     int *nl, *nsolved, *hist;
     float *fsafe, *ovf;
     int *fb_count, *fb_list;
     int *amb_count;       // [2] brackets sent to NEVILL by the phase rule, ellipticities evaluated again (behind fb_count: zeroed with it)
+};
+Carve carve(Carver &cv, int B, int Lmax, int P)
+{
+    const size_t PB = (size_t)P * B;
+    Carve c;
+    c.mdl = cv.take<float>((size_t)9 * Lmax * B);      // sd::NF staged fields, SoA
+    c.rows = cv.take<float>((size_t)9 * Lmax * B);     // ... and one row per stack and field
+    c.ratio = cv.take<float>(PB);
+    c.ct = cv.take<float>(PB);
+    c.ut = cv.take<float>(PB);
+    c.hist = cv.take<int>(PB);
+    c.nl = cv.take<int>(B);
+    c.nsolved = cv.take<int>(B);
+    c.fsafe = cv.take<float>(B);
+    c.ovf = cv.take<float>((size_t)3 * B);
+    c.fb_count = cv.take<int>(3);  c.amb_count = c.fb_count + 1;
+    c.fb_list = cv.take<int>(PB);
+    return c;
+}
+
+// the partials' scratch: layer-major [3][Lmax][P][B] the analytic partials are accumulated in (the lanes of a wavefront -
+// consecutive stacks, one period - then touch consecutive words instead of rows 4 P Lmax bytes apart), and per unit its
+// factor 1 / (dL/dk) and the deepest layer it wrote
+struct KCarve {
+    float *kscr, *kscale;
+    int *khs;
+};
+KCarve kcarve(Carver &cv, int B, int Lmax, int P)
+{
+    const size_t PB = (size_t)P * B;
+    KCarve k;
+    k.kscr = cv.take<float>((size_t)3 * Lmax * PB);
+    k.kscale = cv.take<float>(PB);
+    k.khs = cv.take<int>(PB);
+    return k;
+}
+
+// the group entry's region: a second scratch for T (1 + dfrac) (the partials' scratch, free once the phase partials are
+// transposed, takes T (1 - dfrac)), and per shift and unit the factor, deepest layer, root, ellipticity, group velocity and
+// failure flag
+struct GCarve {
+    float *kscr_p, *ksc, *cs, *ratio, *us, *pers;
+    int *khs;
+    unsigned char *fail;
+};
+GCarve gcarve(Carver &cv, int B, int Lmax, int P)
+{
+    const size_t PB = (size_t)P * B;
+    GCarve g;
+    g.kscr_p = cv.take<float>((size_t)3 * Lmax * PB);
+    g.ksc = cv.take<float>(2 * PB);
+    g.khs = cv.take<int>(2 * PB);
+    g.cs = cv.take<float>(2 * PB);
+    g.ratio = cv.take<float>(2 * PB);
+    g.us = cv.take<float>(2 * PB);
+    g.pers = cv.take<float>((size_t)2 * P);
+    g.fail = cv.take<unsigned char>(2 * PB);
+    return g;
+}
+
+// the ellipticity entry's region: per layer and unit the refreshing period (int), the adjoint row (5 doubles) and the two
+// shares (3 + 3 floats), and per unit gamma and the deepest layer
+struct ECarve {
+    int *kpk;
+    double *wscr;
+    float *xscr, *fscr, *gam;
+    int *khs;
+};
+ECarve ecarve(Carver &cv, int B, int Lmax, int P)
+{
+    const size_t PB = (size_t)P * B, LPB = (size_t)Lmax * PB;
+    ECarve e;
+    e.kpk = cv.take<int>(LPB);
+    e.wscr = cv.take<double>(5 * LPB);
+    e.xscr = cv.take<float>(3 * LPB);
+    e.fscr = cv.take<float>(3 * LPB);
+    e.gam = cv.take<float>(PB);
+    e.khs = cv.take<int>(PB);
+    return e;
+}
+
+// the eigenfunction region: the layer-major scratch [4][Lmax][P][B] and per unit the divisor, the deepest layer and the three
+// energy integrals
+struct EigCarve {
+    float *escr, *ediv, *esum;
+    int *ehs;
+};
+EigCarve eigcarve(Carver &cv, int B, int Lmax, int P)
+{
+    const size_t PB = (size_t)P * B;
+    EigCarve e;
+    e.escr = cv.take<float>((size_t)4 * Lmax * PB);
+    e.ediv = cv.take<float>(PB);
+    e.ehs = cv.take<int>(PB);
+    e.esum = cv.take<float>(3 * PB);
+    return e;
+}
+
+// The entries' workspaces: the forward region, then (all but WS_FORWARD and WS_EIGEN) the partials' scratch, then the entry's
+// own region(s).  Regions an entry does not have stay null.  The attenuation entry's workspace is WS_KERNELS.
+enum WsEntry { WS_FORWARD, WS_KERNELS, WS_GROUP, WS_ELLIP, WS_EIGEN, WS_THICK };
+struct Layout {
+    Carve w;
+    KCarve k;
+    GCarve g;
+    ECarve e;
+    EigCarve eig;
+    float *thick_us;      // the thickness entry's plane [P][B]: the U of its second group-velocity launch
     size_t total;
 };
-
-Carve carve(void *base, int B, int Lmax, int P)
+Layout layout(void *base, int B, int Lmax, int P, WsEntry entry)
 {
-    char *p = static_cast<char *>(base);
-    size_t off = 0;
-    Carve c;
-    c.mdl = reinterpret_cast<float *>(p + off);     off += align_up((size_t)9 * Lmax * B * sizeof(float));      // sd::NF staged fields, SoA
-    c.rows = reinterpret_cast<float *>(p + off);    off += align_up((size_t)9 * Lmax * B * sizeof(float));      // ... and one row per stack and field
-    c.ratio = reinterpret_cast<float *>(p + off);   off += align_up((size_t)P * B * sizeof(float));
-    c.ct = reinterpret_cast<float *>(p + off);      off += align_up((size_t)P * B * sizeof(float));
-    c.ut = reinterpret_cast<float *>(p + off);      off += align_up((size_t)P * B * sizeof(float));
-    c.hist = reinterpret_cast<int *>(p + off);      off += align_up((size_t)P * B * sizeof(int));
-    c.nl = reinterpret_cast<int *>(p + off);        off += align_up((size_t)B * sizeof(int));
-    c.nsolved = reinterpret_cast<int *>(p + off);   off += align_up((size_t)B * sizeof(int));
-    c.fsafe = reinterpret_cast<float *>(p + off);   off += align_up((size_t)B * sizeof(float));
-    c.ovf = reinterpret_cast<float *>(p + off);     off += align_up((size_t)3 * B * sizeof(float));
-    c.fb_count = reinterpret_cast<int *>(p + off);  c.amb_count = c.fb_count + 1;  off += align_up(3 * sizeof(int));
-    c.fb_list = reinterpret_cast<int *>(p + off);   off += align_up((size_t)P * B * sizeof(int));
-    c.total = off;
-    return c;
+    Carver cv(base);
+    Layout l{};
+    l.w = carve(cv, B, Lmax, P);
+    if (entry != WS_FORWARD && entry != WS_EIGEN) l.k = kcarve(cv, B, Lmax, P);
+    if (entry == WS_GROUP) l.g = gcarve(cv, B, Lmax, P);
+    if (entry == WS_ELLIP) l.e = ecarve(cv, B, Lmax, P);
+    if (entry == WS_EIGEN || entry == WS_THICK) l.eig = eigcarve(cv, B, Lmax, P);
+    if (entry == WS_THICK) l.thick_us = cv.take<float>((size_t)P * B);
+    l.total = cv.off;
+    return l;
+}
+size_t layout_bytes(int B, int Lmax, int P, WsEntry entry)
+{
+    if (B < 1 || Lmax < 2 || P < 1) return 0;
+    return layout(nullptr, B, Lmax, P, entry).total;
+}
+
+// The device buffer of one host-buffer batch (a chunk's slot, or the whole call): inputs [model | per | nlay] and outputs
+// [c | u | status] contiguous, each padded as the workspace's arrays are, then the forward solve's workspace.
+struct HostSlot {
+    size_t nm, np, ni, no, ws;                                   // bytes of model, per, nlay = status, c = u, workspace
+    size_t o_model, o_per, o_nl, o_c, o_u, o_st, o_ws, bytes;    // their offsets, and the slot's size
+    template <typename T> static T *at(char *d, size_t off) { return reinterpret_cast<T *>(d + off); }
+};
+HostSlot host_slot(int B, int Lmax, int P)
+{
+    HostSlot h;
+    Carver cv(nullptr);
+    auto put = [&cv](size_t bytes, size_t &at) { at = cv.off; cv.take<char>(bytes); return bytes; };
+    h.nm = put((size_t)B * 5 * Lmax * sizeof(float), h.o_model);
+    h.np = put((size_t)P * sizeof(float), h.o_per);
+    h.ni = put((size_t)B * sizeof(int), h.o_nl);
+    h.no = put((size_t)B * P * sizeof(float), h.o_c);
+    put(h.no, h.o_u);
+    put(h.ni, h.o_st);
+    h.ws = put(layout_bytes(B, Lmax, P, WS_FORWARD), h.o_ws);
+    h.bytes = cv.off;
+    return h;
 }
 
 int pick_team(int B, int Lmax, bool pipelined = false, int kind = SURFDISP_KIND_RAYLEIGH)
@@ -238,148 +382,60 @@ int surfdisp_get_team2(int B, int Lmax, int P, int kind)
 // group-velocity intermediates of the next launches; nullptr switches it off.
 void surfdisp_debug_buffer(double *dev) { g_dbg.store(dev, std::memory_order_relaxed); }
 
-size_t surfdisp_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    return carve(nullptr, B, Lmax, P).total;
-}
-
-// workspace of surfdisp_forward_kernels_device with room for the layer-major scratch [3][Lmax][P][B] the analytic
-// partials are accumulated in (the lanes of a wavefront - consecutive stacks, one period - then touch consecutive
-// words instead of rows 4 P Lmax bytes apart); a workspace of only surfdisp_workspace_bytes still works, slower
-size_t surfdisp_kernels_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    // + per unit its factor 1 / (dL/dk) and the deepest layer it wrote
-    return align_up(carve(nullptr, B, Lmax, P).total) + align_up((size_t)3 * Lmax * P * B * sizeof(float)) +
-           2 * align_up((size_t)P * B * sizeof(float));
-}
-
-// workspace of surfdisp_forward_group_kernels_device: that of the kernels entry (whose layer-major scratch, free once the
-// phase partials are transposed, takes the T (1 - dfrac) partials), a second scratch for T (1 + dfrac), and per shift and
-// unit the root, ellipticity, group velocity, factor, deepest layer and failure flag
-struct GCarve {
-    float *kscr_p, *ksc, *cs, *ratio, *us, *pers;
-    int *khs;
-    unsigned char *fail;
-    size_t total;
-};
-static GCarve gcarve(void *base, int B, int Lmax, int P)
-{
-    char *p = static_cast<char *>(base);
-    const size_t PB = (size_t)P * B;
-    size_t off = align_up(surfdisp_kernels_workspace_bytes(B, Lmax, P));
-    GCarve g;
-    g.kscr_p = reinterpret_cast<float *>(p + off);  off += align_up((size_t)3 * Lmax * PB * sizeof(float));
-    g.ksc = reinterpret_cast<float *>(p + off);     off += align_up(2 * PB * sizeof(float));
-    g.khs = reinterpret_cast<int *>(p + off);       off += align_up(2 * PB * sizeof(int));
-    g.cs = reinterpret_cast<float *>(p + off);      off += align_up(2 * PB * sizeof(float));
-    g.ratio = reinterpret_cast<float *>(p + off);   off += align_up(2 * PB * sizeof(float));
-    g.us = reinterpret_cast<float *>(p + off);      off += align_up(2 * PB * sizeof(float));
-    g.pers = reinterpret_cast<float *>(p + off);    off += align_up((size_t)2 * P * sizeof(float));
-    g.fail = reinterpret_cast<unsigned char *>(p + off);  off += align_up(2 * PB);
-    g.total = off;
-    return g;
-}
-
-// workspace of surfdisp_forward_ellip_kernels_device: that of the kernels entry, then per layer and unit the refreshing period
-// (int), the adjoint row (5 doubles) and the two shares (3 + 3 floats), and per unit gamma and the deepest layer
-struct ECarve {
-    int *kpk;
-    double *wscr;
-    float *xscr, *fscr, *gam;
-    int *khs;
-    size_t total;
-};
-static ECarve ecarve(void *base, int B, int Lmax, int P)
-{
-    char *p = static_cast<char *>(base);
-    const size_t PB = (size_t)P * B, LPB = (size_t)Lmax * PB;
-    size_t off = align_up(surfdisp_kernels_workspace_bytes(B, Lmax, P));
-    ECarve e;
-    e.kpk = reinterpret_cast<int *>(p + off);      off += align_up(LPB * sizeof(int));
-    e.wscr = reinterpret_cast<double *>(p + off);  off += align_up(5 * LPB * sizeof(double));
-    e.xscr = reinterpret_cast<float *>(p + off);   off += align_up(3 * LPB * sizeof(float));
-    e.fscr = reinterpret_cast<float *>(p + off);   off += align_up(3 * LPB * sizeof(float));
-    e.gam = reinterpret_cast<float *>(p + off);    off += align_up(PB * sizeof(float));
-    e.khs = reinterpret_cast<int *>(p + off);      off += align_up(PB * sizeof(int));
-    e.total = off;
-    return e;
-}
-
-size_t surfdisp_ellip_kernels_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    return ecarve(nullptr, B, Lmax, P).total;
-}
-
-size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    return gcarve(nullptr, B, Lmax, P).total;
-}
+// The workspace sizes: each is the end of the composition its entry carves (layout()).  The kernels entry also works, slower,
+// on a workspace of only surfdisp_workspace_bytes.
+size_t surfdisp_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_FORWARD); }
+size_t surfdisp_kernels_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_KERNELS); }
+size_t surfdisp_ellip_kernels_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_ELLIP); }
+size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_GROUP); }
+size_t surfdisp_atten_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_KERNELS); }
+size_t surfdisp_eigen_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_EIGEN); }
+size_t surfdisp_thickness_kernels_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_THICK); }
 
 // developer / test read-out (not in include/surfdisp.h): byte offset, inside that workspace, of the shifted roots
 // [2][P][B] (float; T (1 - dfrac) first) of the last surfdisp_forward_group_kernels_device call on it
 size_t surfdisp_group_kernels_shift_offset(int B, int Lmax, int P)
 {
     if (B < 1 || Lmax < 2 || P < 1) return 0;
-    const GCarve g = gcarve(nullptr, B, Lmax, P);
-    return (size_t)reinterpret_cast<uintptr_t>(g.cs);
+    return (size_t)reinterpret_cast<uintptr_t>(layout(nullptr, B, Lmax, P, WS_GROUP).g.cs);   // (null base: the pointer is the offset)
 }
 
-// introspection: how many stacks (or (stack, period) units in independent mode) the last solve that used this
-// workspace handed to the exact fallback kernel.  Waits for `stream`.
-int surfdisp_workspace_fallback_count(void *stream, const void *workspace, int B, int Lmax, int P, int *count)
+// introspection: n words from fb_count on of the last solve that used this workspace.  Waits for `stream`.
+static int read_counters(void *stream, const void *workspace, int B, int Lmax, int P, int *counts, int n)
 {
-    if (!workspace || !count || B < 1 || Lmax < 2 || P < 1) { set_err("bad argument"); return SURFDISP_ERR_INVALID; }
-    const Carve w = carve(const_cast<void *>(workspace), B, Lmax, P);
+    if (!workspace || !counts || B < 1 || Lmax < 2 || P < 1) { set_err("bad argument"); return SURFDISP_ERR_INVALID; }
+    const Carve w = layout(const_cast<void *>(workspace), B, Lmax, P, WS_FORWARD).w;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    SD_HIP(hipMemcpyAsync(count, w.fb_count, sizeof(int), hipMemcpyDeviceToHost, s));
+    SD_HIP(hipMemcpyAsync(counts, w.fb_count, n * sizeof(int), hipMemcpyDeviceToHost, s));
     SD_HIP(hipStreamSynchronize(s));
     return SURFDISP_SUCCESS;
 }
 
-// introspection: {stacks handed to the exact fallback kernel, brackets sent to NEVILL because the vertical phase grows by more
-// than SURFDISP_PHIMULTI across them, ellipticities evaluated again with the
-// reference's arithmetic} of the last solve on `workspace`.  Waits for `stream`.
-int surfdisp_workspace_counters(void *stream, const void *workspace, int B, int Lmax, int P, int *counts3)
-{
-    if (!workspace || !counts3 || B < 1 || Lmax < 2 || P < 1) { set_err("bad argument"); return SURFDISP_ERR_INVALID; }
-    const Carve w = carve(const_cast<void *>(workspace), B, Lmax, P);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    SD_HIP(hipMemcpyAsync(counts3, w.fb_count, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
-    SD_HIP(hipStreamSynchronize(s));
-    return SURFDISP_SUCCESS;
-}
+// how many stacks (or (stack, period) units in independent mode) the solve handed to the exact fallback kernel
+int surfdisp_workspace_fallback_count(void *stream, const void *workspace, int B, int Lmax, int P, int *count) { return read_counters(stream, workspace, B, Lmax, P, count, 1); }
 
-// the eigenfunction entry's part of the workspace, behind the forward solve's: the layer-major scratch [4][Lmax][P][B] and
-// per unit the divisor, the deepest layer and the three energy integrals
-struct EigCarve {
-    float *escr, *ediv, *esum;
-    int *ehs;
-    size_t total;
+// {stacks handed to the exact fallback kernel, brackets sent to NEVILL because the vertical phase grows by more than
+// SURFDISP_PHIMULTI across them, ellipticities evaluated again with the reference's arithmetic}
+int surfdisp_workspace_counters(void *stream, const void *workspace, int B, int Lmax, int P, int *counts3) { return read_counters(stream, workspace, B, Lmax, P, counts3, 3); }
+
+// What a caller of forward_device_impl asks for beyond c, u and status.
+struct ForwardOpts {
+    hipEvent_t *events = nullptr;         // four events, recorded before prep, between the kernels and after finish
+    float *dcdb = nullptr, *dcda = nullptr, *dcdr = nullptr;   // rows [B][P][Lmax] of the analytic partials of c (dcdb switches them on)
+    float *ratio = nullptr;               // the caller's ellipticity array [B][P]
+    bool record_history = false;          // record the refresh history also where the solve itself needs none (the ellipticity kernels replay it)
+    bool keep_vp_plane = false;           // keep the dc/dVp plane in the partials' scratch also without dcda rows (the attenuation kernel reads it)
+    bool keep_rho_plane = false;          // ... and the dc/drho plane without dcdr rows (the thickness kernel)
+    const EigCarve *eigen = nullptr;      // the eigen region: the group-velocity kernel's EIG instantiation fills it
 };
-static EigCarve eigcarve(void *base, int B, int Lmax, int P, size_t behind = 0)
-{
-    char *p = static_cast<char *>(base);
-    size_t off = behind ? align_up(behind) : align_up(carve(nullptr, B, Lmax, P).total);   // (behind: the thickness entry's, after the partials' scratch)
-    EigCarve e;
-    e.escr = reinterpret_cast<float *>(p + off);  off += align_up((size_t)4 * Lmax * P * B * sizeof(float));
-    e.ediv = reinterpret_cast<float *>(p + off);  off += align_up((size_t)P * B * sizeof(float));
-    e.ehs = reinterpret_cast<int *>(p + off);     off += align_up((size_t)P * B * sizeof(int));
-    e.esum = reinterpret_cast<float *>(p + off);  off += align_up((size_t)3 * P * B * sizeof(float));
-    e.total = off;
-    return e;
-}
 
 static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
                                const float *model, int P, const float *per, int kind,
                                float *c, float *u, int *status,
-                               void *workspace, size_t workspace_bytes, hipEvent_t *ev,
-                               float *kb = nullptr, float *ka = nullptr, float *kr = nullptr, float *ratio = nullptr,
-                               bool force_hist = false, bool scr_vp = false, const EigCarve *eig = nullptr, bool scr_rho = false)
+                               void *workspace, size_t workspace_bytes, const ForwardOpts &o)
 {
+    hipEvent_t *const ev = o.events;
+    float *const kb = o.dcdb, *const ka = o.dcda, *const kr = o.dcdr, *const ratio = o.ratio;
     int rc = check_args(B, Lmax, P, kind, model, per, c, u);
     if (rc) return rc;
     if (!workspace || workspace_bytes < surfdisp_workspace_bytes(B, Lmax, P)) {
@@ -404,7 +460,8 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // the ellipticity recursions (two more evaluations per period) feed the group-velocity kernel - and the caller who
     // asked for the ratio itself (ABI 3), also in a phase-only call
     const bool want_ell = (kind == SURFDISP_KIND_RAYLEIGH) && (!phase_only || ratio != nullptr);
-    const Carve w = carve(workspace, B, Lmax, P);
+    const Layout lay = layout(workspace, B, Lmax, P, WS_KERNELS);
+    const Carve &w = lay.w;
     // independent mode has B*P root searches in flight: size the teams for that many; a caller that
     // keeps a second batch in flight (SURFDISP_PIPELINED) has twice the stacks on the chip
     const long units = (indep ? (long)B * P : (long)B) * ((pipelined && kind != SURFDISP_KIND_LOVE) ? 2 : 1);
@@ -442,7 +499,7 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // (two-lane teams compute their ellipticities themselves but record the history too: the pairs whose closure cancels
     // are redone by the ellipticity kernel)
     const bool ell_fix = ell_in && !strict && kn.ell_ambig != 0.0f;
-    ph.hist = (ell_k || ell_fix || force_hist) ? w.hist : nullptr;   // (force_hist: the ellipticity kernels replay it too)
+    ph.hist = (ell_k || ell_fix || o.record_history) ? w.hist : nullptr;
     ph.lockstep = kn.lockstep >= 0 ? kn.lockstep : 1;
     ph.phimulti = kn.phimulti; ph.amb_count = w.amb_count; ph.ell_ambig = ell_fix ? kn.ell_ambig : 0.0f; ph.ell_gmax = kn.ell_gmax;
     ph.scan_general = kn.leanscan ? 0 : 1;
@@ -464,18 +521,13 @@ static int forward_device_impl(void *stream, int B, int Lmax, const int *nlay,
     // analytic partials: through the layer-major scratch when the caller's workspace has room for it
     float *kscr = nullptr, *kscale = nullptr;
     int *khs = nullptr;
-    if (kb && workspace_bytes >= surfdisp_kernels_workspace_bytes(B, Lmax, P)) {
-        char *q = static_cast<char *>(workspace) + align_up(w.total);
-        kscr = reinterpret_cast<float *>(q);    q += align_up((size_t)3 * Lmax * P * B * sizeof(float));
-        kscale = reinterpret_cast<float *>(q);  q += align_up((size_t)P * B * sizeof(float));
-        khs = reinterpret_cast<int *>(q);
-    }
-    // (on the scratch route kb / ka / kr only say which planes the kernel stores: scr_vp asks for the dc/dVp plane - the
-    // attenuation kernel reads it - also when the caller wants no dc/dVp rows; scr_rho: the same for dc/drho, the thickness kernel)
-    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (scr_vp && kscr && !ka) ? kb : ka,
-                     (scr_rho && kscr && !kr) ? kb : kr,
+    if (kb && workspace_bytes >= lay.total) { kscr = lay.k.kscr; kscale = lay.k.kscale; khs = lay.k.khs; }
+    // (on the scratch route kb / ka / kr only say which planes the kernel stores: keep_vp_plane / keep_rho_plane ask for a
+    // plane also when the caller wants no rows of it)
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, w.ut, gdbg, kb, (o.keep_vp_plane && kscr && !ka) ? kb : ka,
+                     (o.keep_rho_plane && kscr && !kr) ? kb : kr,
                      kscr, kscale, khs, kern_raw ? 1 : 0, 0, 0, kn.group_order};
-    if (eig) { ga.escr = eig->escr; ga.ediv = eig->ediv; ga.ehs = eig->ehs; ga.esum = eig->esum; }   // (the EIG instantiation)
+    if (o.eigen) { ga.escr = o.eigen->escr; ga.ediv = o.eigen->ediv; ga.ehs = o.eigen->ehs; ga.esum = o.eigen->esum; }   // (the EIG instantiation)
     // (not beside other batches: the stash's 50 KB per workgroup would keep their root-search workgroups off the CU)
     ga.stash = (kn.group_stash && !pipelined) ? 0 : -1;
     if (!phase_only) SD_HIP(sd::launch_group(s, kind, ga));
@@ -499,7 +551,7 @@ int surfdisp_forward_batch_device(void *stream, int B, int Lmax, const int *nlay
                                   void *workspace, size_t workspace_bytes)
 {
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                               workspace, workspace_bytes, nullptr);
+                               workspace, workspace_bytes, ForwardOpts());
 }
 
 // ABI 3: the same solve, also returning the Rayleigh ellipticity the reference keeps in COMMON /o/ (calcul.f:195).
@@ -508,8 +560,29 @@ int surfdisp_forward_batch_device2(void *stream, int B, int Lmax, const int *nla
                                    float *c, float *u, float *ratio, int *status,
                                    void *workspace, size_t workspace_bytes)
 {
+    ForwardOpts o;
+    o.ratio = ratio;
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                               workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, ratio);
+                               workspace, workspace_bytes, o);
+}
+
+// The preamble of the entries below, in the order each performs it: required pointers (`have`; `required` names them in the
+// error text), refused kind flags, the entry's own extra test (`extra`: its error text where it failed, else null), check_args,
+// workspace size.  `ws`: the composition the entry needs at least, `ws_fn` the size function the error text names (null: none),
+// `ws_rc` the return code for a smaller workspace (it differs between the entries).
+static int entry_preamble(const char *name, bool have, const char *required, int refused, const char *refused_text,
+                          const char *extra, int B, int Lmax, int P, int kind, const void *model, const void *per,
+                          const void *c, const void *u, const void *workspace, size_t workspace_bytes, WsEntry ws,
+                          const char *ws_fn, int ws_rc)
+{
+    if (!have) { set_err("%s: %s is NULL", name, required); return SURFDISP_ERR_INVALID; }
+    if (kind & refused) { set_err("%s: %s", name, refused_text); return SURFDISP_ERR_INVALID; }
+    if (extra) { set_err("%s: %s", name, extra); return SURFDISP_ERR_INVALID; }
+    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    if (rc) return rc;
+    if (workspace && workspace_bytes >= layout_bytes(B, Lmax, P, ws)) return SURFDISP_SUCCESS;
+    set_err(ws_fn ? "workspace too small (%s)" : "workspace too small", ws_fn ? ws_fn : "");
+    return ws_rc;
 }
 
 // Forward solve + analytic partial derivatives of the phase velocity with respect to each layer's
@@ -521,13 +594,14 @@ int surfdisp_forward_kernels_device(void *stream, int B, int Lmax, const int *nl
                                     float *dcdb, float *dcda, float *dcdr,
                                     void *workspace, size_t workspace_bytes)
 {
-    if (!dcdb) { set_err("surfdisp_forward_kernels_device: dcdb is NULL"); return SURFDISP_ERR_INVALID; }
-    if (kind & SURFDISP_PHASE_ONLY) {
-        set_err("surfdisp_forward_kernels_device: the partials come from the group-velocity kernel (no PHASE_ONLY)");
-        return SURFDISP_ERR_INVALID;
-    }
-    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                               workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr);
+    // (a workspace of only the forward solve's size is accepted: the direct route into the rows)
+    int rc = entry_preamble("surfdisp_forward_kernels_device", dcdb != nullptr, "dcdb", SURFDISP_PHASE_ONLY,
+                            "the partials come from the group-velocity kernel (no PHASE_ONLY)", nullptr, B, Lmax, P, kind, model, per,
+                            c, u, workspace, workspace_bytes, WS_FORWARD, nullptr, SURFDISP_ERR_WORKSPACE);
+    if (rc) return rc;
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
 }
 
 // The same launches, then the analytic partials of the GROUP velocity (K4 in surfdisp_kernels.hip): the roots at
@@ -540,33 +614,24 @@ int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const i
                                           float *dudb, float *duda, float *dudr, int *n_shift_failed,
                                           void *workspace, size_t workspace_bytes)
 {
-    if (!dcdb || !dudb) { set_err("surfdisp_forward_group_kernels_device: dcdb or dudb is NULL"); return SURFDISP_ERR_INVALID; }
-    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
-        set_err("surfdisp_forward_group_kernels_device: no PHASE_ONLY, no KERN_REFCOORD");
-        return SURFDISP_ERR_INVALID;
-    }
-    if (!(dlnT_frac >= 1.0e-3f && dlnT_frac <= 0.05f)) {
-        set_err("surfdisp_forward_group_kernels_device: dlnT_frac outside [1e-3, 0.05]");
-        return SURFDISP_ERR_INVALID;
-    }
-    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    int rc = entry_preamble("surfdisp_forward_group_kernels_device", dcdb && dudb, "dcdb or dudb",
+                            SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD, "no PHASE_ONLY, no KERN_REFCOORD",
+                            (dlnT_frac >= 1.0e-3f && dlnT_frac <= 0.05f) ? nullptr : "dlnT_frac outside [1e-3, 0.05]",
+                            B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_GROUP,
+                            "surfdisp_group_kernels_workspace_bytes", SURFDISP_ERR_WORKSPACE);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < surfdisp_group_kernels_workspace_bytes(B, Lmax, P)) {
-        set_err("workspace too small (surfdisp_group_kernels_workspace_bytes)");
-        return SURFDISP_ERR_WORKSPACE;
-    }
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr);
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave = kind & ~SD_KIND_FLAGS;
     const EnvKnobs &kn = knobs();
-    const Carve w = carve(workspace, B, Lmax, P);
+    const Layout lay = layout(workspace, B, Lmax, P, WS_GROUP);
+    const Carve &w = lay.w;
+    const GCarve &g = lay.g;
     const size_t PB = (size_t)P * B;
-    char *q = static_cast<char *>(workspace) + align_up(w.total);
-    float *kscr = reinterpret_cast<float *>(q);                                  // forward_device_impl's scratch ...
-    float *kscale0 = reinterpret_cast<float *>(q + align_up((size_t)3 * Lmax * PB * sizeof(float)));   // ... and factors
-    const GCarve g = gcarve(workspace, B, Lmax, P);
+    float *kscr = lay.k.kscr, *kscale0 = lay.k.kscale;                           // forward_device_impl's scratch and factors
     if (n_shift_failed) SD_HIP(hipMemsetAsync(n_shift_failed, 0, sizeof(int), s));
     sd::ShiftArgs sa{B, Lmax, P, wave, w.mdl, w.nl, per, w.ct, w.ut, w.nsolved, dlnT_frac, g.pers, g.cs,
                      wave == SURFDISP_KIND_RAYLEIGH ? g.ratio : nullptr, g.fail, kn.ell_ambig, kn.ell_gmax, w.ovf};
@@ -594,27 +659,21 @@ int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const i
                                           float *dedb, float *deda, float *dedr, int *n_nonfinite,
                                           void *workspace, size_t workspace_bytes)
 {
-    if (!ratio || !dedb || !dcdb) { set_err("surfdisp_forward_ellip_kernels_device: ratio, dedb or dcdb is NULL"); return SURFDISP_ERR_INVALID; }
-    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD | SURFDISP_STRICT)) {
-        set_err("surfdisp_forward_ellip_kernels_device: no PHASE_ONLY, no KERN_REFCOORD, no STRICT");
-        return SURFDISP_ERR_INVALID;
-    }
-    if ((kind & ~SD_KIND_FLAGS) != SURFDISP_KIND_RAYLEIGH) {
-        set_err("surfdisp_forward_ellip_kernels_device: Rayleigh only (Love waves have no ellipticity)");
-        return SURFDISP_ERR_INVALID;
-    }
-    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    int rc = entry_preamble("surfdisp_forward_ellip_kernels_device", ratio && dedb && dcdb, "ratio, dedb or dcdb",
+                            SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD | SURFDISP_STRICT, "no PHASE_ONLY, no KERN_REFCOORD, no STRICT",
+                            (kind & ~SD_KIND_FLAGS) == SURFDISP_KIND_RAYLEIGH ? nullptr : "Rayleigh only (Love waves have no ellipticity)",
+                            B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_ELLIP,
+                            "surfdisp_ellip_kernels_workspace_bytes", SURFDISP_ERR_INVALID);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < surfdisp_ellip_kernels_workspace_bytes(B, Lmax, P)) {
-        set_err("workspace too small (surfdisp_ellip_kernels_workspace_bytes)");
-        return SURFDISP_ERR_INVALID;
-    }
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, ratio, true);
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    o.ratio = ratio; o.record_history = true;
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Carve w = carve(workspace, B, Lmax, P);
-    const ECarve e = ecarve(workspace, B, Lmax, P);
+    const Layout lay = layout(workspace, B, Lmax, P, WS_ELLIP);
+    const Carve &w = lay.w;
+    const ECarve &e = lay.e;
     if (n_nonfinite) SD_HIP(hipMemsetAsync(n_nonfinite, 0, sizeof(int), s));
     sd::EllipKernArgs ea{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.hist, w.nsolved, e.kpk, e.wscr, e.xscr, e.fscr, e.gam, e.khs,
                          n_nonfinite};
@@ -625,8 +684,6 @@ int surfdisp_forward_ellip_kernels_device(void *stream, int B, int Lmax, const i
 
 // The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit), then the apparent attenuation of the
 // mode from the layer-major scratch those launches leave (K2c in surfdisp_kernels.hip).  Workspace: the kernels entry's.
-size_t surfdisp_atten_workspace_bytes(int B, int Lmax, int P) { return surfdisp_kernels_workspace_bytes(B, Lmax, P); }
-
 int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay,
                                   const float *model, int P, const float *per, int kind,
                                   float *c, float *u, int *status,
@@ -634,65 +691,49 @@ int surfdisp_forward_atten_device(void *stream, int B, int Lmax, const int *nlay
                                   float *qinv, float *gamma, float *dqdq,
                                   void *workspace, size_t workspace_bytes)
 {
-    if (!qinv || !dcdb) { set_err("surfdisp_forward_atten_device: qinv or dcdb is NULL"); return SURFDISP_ERR_INVALID; }
-    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
-        set_err("surfdisp_forward_atten_device: no PHASE_ONLY, no KERN_REFCOORD");
-        return SURFDISP_ERR_INVALID;
-    }
-    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    int rc = entry_preamble("surfdisp_forward_atten_device", qinv && dcdb, "qinv or dcdb",
+                            SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD, "no PHASE_ONLY, no KERN_REFCOORD", nullptr,
+                            B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_KERNELS,
+                            "surfdisp_atten_workspace_bytes", SURFDISP_ERR_INVALID);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < surfdisp_atten_workspace_bytes(B, Lmax, P)) {
-        set_err("workspace too small (surfdisp_atten_workspace_bytes)");
-        return SURFDISP_ERR_INVALID;
-    }
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, nullptr, false, true);
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    o.keep_vp_plane = true;
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave = kind & ~SD_KIND_FLAGS;
-    const Carve w = carve(workspace, B, Lmax, P);
-    char *q = static_cast<char *>(workspace) + align_up(w.total);               // forward_device_impl's scratch, factors, layers
-    const float *kscr = reinterpret_cast<const float *>(q);    q += align_up((size_t)3 * Lmax * P * B * sizeof(float));
-    const float *kscale = reinterpret_cast<const float *>(q);  q += align_up((size_t)P * B * sizeof(float));
-    const int *khs = reinterpret_cast<const int *>(q);
-    sd::AttenArgs aa{B, P, Lmax, wave, w.mdl, per, kscr, kscale, khs, w.ct, w.ut, qinv, gamma, dqdq};
+    const Layout lay = layout(workspace, B, Lmax, P, WS_KERNELS);
+    const Carve &w = lay.w;
+    const KCarve &k = lay.k;                                                    // forward_device_impl's scratch, factors, layers
+    sd::AttenArgs aa{B, P, Lmax, wave, w.mdl, per, k.kscr, k.kscale, k.khs, w.ct, w.ut, qinv, gamma, dqdq};
     SD_HIP(sd::launch_atten(s, aa));
     return SURFDISP_SUCCESS;
 }
 
 // The launches of surfdisp_forward_batch_device with the group-velocity kernel's EIG instantiation in place of the plain one
 // (c, u, status bit for bit), then the transposition of the layer-top eigenfunctions and the energy integrals (K2d in
-// surfdisp_kernels.hip).  Workspace: the forward solve's + the layer-major scratch and the per-unit words; no direct route.
-size_t surfdisp_eigen_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    return eigcarve(nullptr, B, Lmax, P).total;
-}
-
+// surfdisp_kernels.hip).  Workspace: the forward solve's + the eigen region; no direct route.
 int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay,
                                   const float *model, int P, const float *per, int kind,
                                   float *c, float *u, int *status,
                                   float *ur, float *uz, float *tz, float *tr, float *energy,
                                   void *workspace, size_t workspace_bytes)
 {
-    if (!c || !u || !status || !ur) { set_err("surfdisp_forward_eigen_device: c, u, status or ur is NULL"); return SURFDISP_ERR_INVALID; }
-    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
-        set_err("surfdisp_forward_eigen_device: no PHASE_ONLY, no KERN_REFCOORD");
-        return SURFDISP_ERR_INVALID;
-    }
-    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    int rc = entry_preamble("surfdisp_forward_eigen_device", c && u && status && ur, "c, u, status or ur",
+                            SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD, "no PHASE_ONLY, no KERN_REFCOORD", nullptr,
+                            B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_EIGEN,
+                            "surfdisp_eigen_workspace_bytes", SURFDISP_ERR_INVALID);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < surfdisp_eigen_workspace_bytes(B, Lmax, P)) {
-        set_err("workspace too small (surfdisp_eigen_workspace_bytes)");
-        return SURFDISP_ERR_INVALID;
-    }
-    const EigCarve e = eigcarve(workspace, B, Lmax, P);
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                             workspace, workspace_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, false, false, &e);
+    const Layout lay = layout(workspace, B, Lmax, P, WS_EIGEN);
+    const Carve &w = lay.w;
+    const EigCarve &e = lay.eig;
+    ForwardOpts o;
+    o.eigen = &e;
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave = kind & ~SD_KIND_FLAGS;
-    const Carve w = carve(workspace, B, Lmax, P);
     sd::EigenTransposeArgs ta{B, P, Lmax, wave, w.mdl, w.nl, per, e.escr, e.ediv, e.ehs, e.esum, w.ct, w.ut, ur, uz, tz, tr, energy};
     SD_HIP(sd::launch_eigen_transpose(s, ta));
     return SURFDISP_SUCCESS;
@@ -701,28 +742,7 @@ int surfdisp_forward_eigen_device(void *stream, int B, int Lmax, const int *nlay
 // The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit), then the EIG instantiation of the
 // group-velocity kernel on the roots and ellipticities those launches left (no second root search; its U goes to a scratch
 // plane), then the thickness kernel on both layer-major scratches (K2e in surfdisp_kernels.hip).  Workspace: the kernels
-// entry's, then the eigenfunction scratch and its per-unit words, then the scratch plane; no direct route.
-struct ThickCarve {
-    EigCarve e;
-    float *us;
-    size_t total;
-};
-static ThickCarve thickcarve(void *base, int B, int Lmax, int P)
-{
-    ThickCarve t;
-    t.e = eigcarve(base, B, Lmax, P, surfdisp_kernels_workspace_bytes(B, Lmax, P));
-    size_t off = t.e.total;
-    t.us = reinterpret_cast<float *>(static_cast<char *>(base) + off);  off += align_up((size_t)P * B * sizeof(float));
-    t.total = off;
-    return t;
-}
-
-size_t surfdisp_thickness_kernels_workspace_bytes(int B, int Lmax, int P)
-{
-    if (B < 1 || Lmax < 2 || P < 1) return 0;
-    return thickcarve(nullptr, B, Lmax, P).total;
-}
-
+// entry's, then the eigen region, then the scratch plane; no direct route.
 int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, const int *nlay,
                                               const float *model, int P, const float *per, int kind,
                                               float *c, float *u, int *status,
@@ -730,40 +750,31 @@ int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, con
                                               float *dcdh, float *dcdz, int *n_nonfinite,
                                               void *workspace, size_t workspace_bytes)
 {
-    if (!c || !u || !status || !dcdb || !dcdh) {
-        set_err("surfdisp_forward_thickness_kernels_device: c, u, status, dcdb or dcdh is NULL");
-        return SURFDISP_ERR_INVALID;
-    }
-    if (kind & (SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD)) {
-        set_err("surfdisp_forward_thickness_kernels_device: no PHASE_ONLY, no KERN_REFCOORD");
-        return SURFDISP_ERR_INVALID;
-    }
-    int rc = check_args(B, Lmax, P, kind, model, per, c, u);
+    int rc = entry_preamble("surfdisp_forward_thickness_kernels_device", c && u && status && dcdb && dcdh,
+                            "c, u, status, dcdb or dcdh", SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD,
+                            "no PHASE_ONLY, no KERN_REFCOORD", nullptr, B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes,
+                            WS_THICK, "surfdisp_thickness_kernels_workspace_bytes", SURFDISP_ERR_INVALID);
     if (rc) return rc;
-    if (!workspace || workspace_bytes < surfdisp_thickness_kernels_workspace_bytes(B, Lmax, P)) {
-        set_err("workspace too small (surfdisp_thickness_kernels_workspace_bytes)");
-        return SURFDISP_ERR_INVALID;
-    }
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                             workspace, workspace_bytes, nullptr, dcdb, dcda, dcdr, nullptr, false, true, nullptr, true);
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    o.keep_vp_plane = o.keep_rho_plane = true;
+    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave = kind & ~SD_KIND_FLAGS;
     const EnvKnobs &kn = knobs();
-    const Carve w = carve(workspace, B, Lmax, P);
-    const ThickCarve t = thickcarve(workspace, B, Lmax, P);
-    char *q = static_cast<char *>(workspace) + align_up(w.total);               // forward_device_impl's scratch, factors, layers
-    const float *kscr = reinterpret_cast<const float *>(q);    q += align_up((size_t)3 * Lmax * P * B * sizeof(float));
-    const float *kscale = reinterpret_cast<const float *>(q);  q += align_up((size_t)P * B * sizeof(float));
-    const int *khs = reinterpret_cast<const int *>(q);
+    const Layout lay = layout(workspace, B, Lmax, P, WS_THICK);
+    const Carve &w = lay.w;
+    const KCarve &k = lay.k;                                                    // forward_device_impl's scratch, factors, layers
+    const EigCarve &e = lay.eig;
     if (n_nonfinite) SD_HIP(hipMemsetAsync(n_nonfinite, 0, sizeof(int), s));
     // (kb = nullptr: the EIG instantiation, which writes no partials)
-    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, t.us, nullptr, nullptr, nullptr, nullptr,
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, lay.thick_us, nullptr, nullptr, nullptr, nullptr,
                      nullptr, nullptr, nullptr, 0, 0, 0, kn.group_order};
-    ga.escr = t.e.escr; ga.ediv = t.e.ediv; ga.ehs = t.e.ehs; ga.esum = t.e.esum;
+    ga.escr = e.escr; ga.ediv = e.ediv; ga.ehs = e.ehs; ga.esum = e.esum;
     ga.stash = -1;
     SD_HIP(sd::launch_group(s, wave, ga));
-    sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, per, t.e.escr, t.e.ediv, t.e.ehs, t.e.esum, kscr, kscale, khs,
+    sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, per, e.escr, e.ediv, e.ehs, e.esum, k.kscr, k.kscale, k.khs,
                      w.ct, w.ut, dcdh, dcdz, n_nonfinite};
     SD_HIP(sd::launch_thickness(s, ta));
     return SURFDISP_SUCCESS;
@@ -1271,20 +1282,30 @@ int surfdisp_lsq_resolution_device(void *stream, int B, int Lmax, const int *nla
     return SURFDISP_SUCCESS;
 }
 
-// Measurement variant that does NOT synchronise: the caller owns four events per call
+// Measurement variants that do NOT synchronise: the caller owns four events per call
 // (surfdisp_events_create) which are recorded on the launch stream before prep, between the
 // kernels and after finish; durations are read later with surfdisp_events_elapsed_ms, after the
 // caller's own synchronisation.  This is what bench.py uses inside its timed region.
+static int forward_with_events(void *stream, int B, int Lmax, const int *nlay,
+                               const float *model, int P, const float *per, int kind,
+                               float *c, float *u, float *ratio, int *status,
+                               void *workspace, size_t workspace_bytes, void *const *events4)
+{
+    if (!events4) { set_err("events4 is NULL"); return SURFDISP_ERR_INVALID; }
+    hipEvent_t ev[4];
+    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(events4[i]);
+    ForwardOpts o;
+    o.events = ev;
+    o.ratio = ratio;
+    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
+}
+
 int surfdisp_forward_batch_device_events(void *stream, int B, int Lmax, const int *nlay,
                                          const float *model, int P, const float *per, int kind,
                                          float *c, float *u, int *status,
                                          void *workspace, size_t workspace_bytes, void *const *events4)
 {
-    if (!events4) { set_err("events4 is NULL"); return SURFDISP_ERR_INVALID; }
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(events4[i]);
-    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                               workspace, workspace_bytes, ev);
+    return forward_with_events(stream, B, Lmax, nlay, model, P, per, kind, c, u, /* ratio */ nullptr, status, workspace, workspace_bytes, events4);
 }
 
 // ... of surfdisp_forward_batch_device2: the same events around the solve that also returns the ellipticity
@@ -1293,11 +1314,7 @@ int surfdisp_forward_batch_device2_events(void *stream, int B, int Lmax, const i
                                           float *c, float *u, float *ratio, int *status,
                                           void *workspace, size_t workspace_bytes, void *const *events4)
 {
-    if (!events4) { set_err("events4 is NULL"); return SURFDISP_ERR_INVALID; }
-    hipEvent_t ev[4];
-    for (int i = 0; i < 4; ++i) ev[i] = static_cast<hipEvent_t>(events4[i]);
-    return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                               workspace, workspace_bytes, ev, nullptr, nullptr, nullptr, ratio);
+    return forward_with_events(stream, B, Lmax, nlay, model, P, per, kind, c, u, ratio, status, workspace, workspace_bytes, events4);
 }
 
 int surfdisp_events_create(int n, void **events)
@@ -1346,8 +1363,9 @@ int surfdisp_forward_batch_device_timed(void *stream, int B, int Lmax, const int
     if (!kernel_ms) { set_err("kernel_ms is NULL"); return SURFDISP_ERR_INVALID; }
     hipEvent_t ev[4];
     for (int i = 0; i < 4; ++i) SD_HIP(hipEventCreate(&ev[i]));
-    int rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status,
-                                 workspace, workspace_bytes, ev);
+    ForwardOpts o;
+    o.events = ev;
+    int rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
     if (rc == SURFDISP_SUCCESS) {
         hipError_t e = hipEventSynchronize(ev[3]);
         if (e != hipSuccess) { set_err("hipEventSynchronize failed: %s", hipGetErrorString(e)); rc = SURFDISP_ERR_HIP; }
@@ -1447,11 +1465,8 @@ static int forward_batch_pipelined(int device, int nch, int B, int Lmax, const i
                                    int P, const float *per, int kind, float *c, float *u, int *status)
 {
     const int Bc = (int)((((long)B + nch - 1) / nch + 63) / 64 * 64);          // stacks per chunk (the last one may be shorter)
-    const size_t nm = (size_t)Bc * 5 * Lmax * sizeof(float), np = (size_t)P * sizeof(float);
-    const size_t ni = (size_t)Bc * sizeof(int), no = (size_t)Bc * P * sizeof(float);
-    const size_t ws = surfdisp_workspace_bytes(Bc, Lmax, P);
-    const size_t o_model = 0, o_per = o_model + align_up(nm), o_nl = o_per + align_up(np), o_c = o_nl + align_up(ni);
-    const size_t o_u = o_c + align_up(no), o_st = o_u + align_up(no), o_ws = o_st + align_up(ni), slot = align_up(o_ws + ws);
+    const HostSlot h = host_slot(Bc, Lmax, P);
+    const size_t slot = h.bytes;
     const int NS = knobs().host_slots >= 3 ? 3 : 2;
     if (!g_pipe.ensure(device, NS * slot)) { set_err("host-buffer pipeline: allocation failed"); return SURFDISP_ERR_HIP; }
     int ret = SURFDISP_SUCCESS;
@@ -1460,9 +1475,9 @@ static int forward_batch_pipelined(int device, int nch, int B, int Lmax, const i
         hipStream_t s = g_pipe.s[k % NS];
         const long b0 = (long)k * Bc;
         const size_t bc = (size_t)((B - b0) < Bc ? (B - b0) : Bc);
-        return hipMemcpyAsync(c + b0 * P, d + o_c, bc * P * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess &&
-               (!u || hipMemcpyAsync(u + b0 * P, d + o_u, bc * P * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess) &&
-               (!status || hipMemcpyAsync(status + b0, d + o_st, bc * sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess);
+        return hipMemcpyAsync(c + b0 * P, d + h.o_c, bc * P * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess &&
+               (!u || hipMemcpyAsync(u + b0 * P, d + h.o_u, bc * P * sizeof(float), hipMemcpyDeviceToHost, s) == hipSuccess) &&
+               (!status || hipMemcpyAsync(status + b0, d + h.o_st, bc * sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess);
     };
     int k = 0;
     for (; k < nch && ret == SURFDISP_SUCCESS; ++k) {
@@ -1474,15 +1489,13 @@ static int forward_batch_pipelined(int device, int nch, int B, int Lmax, const i
         // the slot's previous chunk leaves first (a copy to pageable memory holds the calling thread until that chunk is
         // done - the other slot's chunk is computing meanwhile)
         if (k >= NS && !copy_out(k - NS)) { set_err("device->host copy failed"); ret = SURFDISP_ERR_HIP; break; }
-        const bool ok = hipMemcpyAsync(d + o_model, model + (size_t)b0 * 5 * Lmax, (size_t)bc * 5 * Lmax * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
-                        (k >= NS || hipMemcpyAsync(d + o_per, per, np, hipMemcpyHostToDevice, s) == hipSuccess) &&
-                        (!nlay || hipMemcpyAsync(d + o_nl, nlay + b0, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess);
+        const bool ok = hipMemcpyAsync(d + h.o_model, model + (size_t)b0 * 5 * Lmax, (size_t)bc * 5 * Lmax * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+                        (k >= NS || hipMemcpyAsync(d + h.o_per, per, h.np, hipMemcpyHostToDevice, s) == hipSuccess) &&
+                        (!nlay || hipMemcpyAsync(d + h.o_nl, nlay + b0, (size_t)bc * sizeof(int), hipMemcpyHostToDevice, s) == hipSuccess);
         if (!ok) { set_err("host->device copy failed"); ret = SURFDISP_ERR_HIP; break; }
-        ret = surfdisp_forward_batch_device(s, bc, Lmax, nlay ? reinterpret_cast<int *>(d + o_nl) : nullptr,
-                                            reinterpret_cast<float *>(d + o_model), P, reinterpret_cast<float *>(d + o_per),
-                                            kind | SURFDISP_PIPELINED, reinterpret_cast<float *>(d + o_c),
-                                            u ? reinterpret_cast<float *>(d + o_u) : nullptr,
-                                            reinterpret_cast<int *>(d + o_st), d + o_ws, ws);
+        ret = surfdisp_forward_batch_device(s, bc, Lmax, nlay ? h.at<int>(d, h.o_nl) : nullptr, h.at<float>(d, h.o_model), P,
+                                            h.at<float>(d, h.o_per), kind | SURFDISP_PIPELINED, h.at<float>(d, h.o_c),
+                                            u ? h.at<float>(d, h.o_u) : nullptr, h.at<int>(d, h.o_st), d + h.o_ws, h.ws);
     }
     if (ret == SURFDISP_SUCCESS) {
         for (int j = (k >= NS ? k - NS : 0); j < k; ++j)
@@ -1516,20 +1529,8 @@ int surfdisp_forward_batch(int device, int B, int Lmax, const int *nlay, const f
     if (hipGetDevice(&scope.prev) != hipSuccess) scope.prev = -1;
     if (scope.prev == device) scope.prev = -1;                 // nothing to restore
     else SD_HIP(hipSetDevice(device));
-    const size_t nm = (size_t)B * 5 * Lmax * sizeof(float);
-    const size_t np = (size_t)P * sizeof(float);
-    const size_t ni = (size_t)B * sizeof(int);
-    const size_t no = (size_t)B * P * sizeof(float);
-    const size_t ws = surfdisp_workspace_bytes(B, Lmax, P);
-    // inputs [model | per | nlay] and outputs [c | u | status] are contiguous, then the workspace
-    const size_t o_model = 0;
-    const size_t o_per = o_model + align_up(nm);
-    const size_t o_nl = o_per + align_up(np);
-    const size_t o_c = o_nl + align_up(ni);
-    const size_t o_u = o_c + align_up(no);
-    const size_t o_st = o_u + align_up(no);
-    const size_t o_ws = o_st + align_up(ni);
-    const bool small = (o_ws + ws) <= ARENA_MAX;
+    const HostSlot hs = host_slot(B, Lmax, P);
+    const bool small = hs.bytes <= ARENA_MAX;
     if (!small) {
         const int nch = knobs().host_pipeline ? host_chunks(B, Lmax) : 1;
         if (nch > 1) return forward_batch_pipelined(device, nch, B, Lmax, nlay, model, P, per, kind, c, u, status);
@@ -1537,47 +1538,44 @@ int surfdisp_forward_batch(int device, int B, int Lmax, const int *nlay, const f
     char *d = nullptr, *h = nullptr;
     hipStream_t s = nullptr;
     if (small) {
-        if (!g_arena.reserve(device, o_ws + ws, o_ws)) { set_err("arena allocation failed"); return SURFDISP_ERR_HIP; }
+        if (!g_arena.reserve(device, hs.bytes, hs.o_ws)) { set_err("arena allocation failed"); return SURFDISP_ERR_HIP; }
         d = g_arena.d; h = g_arena.h;
     } else {
-        if (!g_pipe.ensure(device, o_ws + ws)) { set_err("host-buffer call: allocation failed"); return SURFDISP_ERR_HIP; }
+        if (!g_pipe.ensure(device, hs.bytes)) { set_err("host-buffer call: allocation failed"); return SURFDISP_ERR_HIP; }
         d = g_pipe.d; s = g_pipe.s[0];
     }
     int ret = SURFDISP_SUCCESS;
     do {
         bool ok;
         if (small) {
-            memcpy(h + o_model, model, nm);
-            memcpy(h + o_per, per, np);
-            if (nlay) memcpy(h + o_nl, nlay, ni);
-            ok = hipMemcpyAsync(d, h, o_c, hipMemcpyHostToDevice, s) == hipSuccess;
+            memcpy(h + hs.o_model, model, hs.nm);
+            memcpy(h + hs.o_per, per, hs.np);
+            if (nlay) memcpy(h + hs.o_nl, nlay, hs.ni);
+            ok = hipMemcpyAsync(d, h, hs.o_c, hipMemcpyHostToDevice, s) == hipSuccess;
         } else {
-            ok = hipMemcpyAsync(d + o_model, model, nm, hipMemcpyHostToDevice, s) == hipSuccess &&
-                 hipMemcpyAsync(d + o_per, per, np, hipMemcpyHostToDevice, s) == hipSuccess &&
-                 (!nlay || hipMemcpyAsync(d + o_nl, nlay, ni, hipMemcpyHostToDevice, s) == hipSuccess);
+            ok = hipMemcpyAsync(d + hs.o_model, model, hs.nm, hipMemcpyHostToDevice, s) == hipSuccess &&
+                 hipMemcpyAsync(d + hs.o_per, per, hs.np, hipMemcpyHostToDevice, s) == hipSuccess &&
+                 (!nlay || hipMemcpyAsync(d + hs.o_nl, nlay, hs.ni, hipMemcpyHostToDevice, s) == hipSuccess);
         }
         if (!ok) { set_err("host->device copy failed"); ret = SURFDISP_ERR_HIP; break; }
-        ret = surfdisp_forward_batch_device(s, B, Lmax, nlay ? reinterpret_cast<int *>(d + o_nl) : nullptr,
-                                            reinterpret_cast<float *>(d + o_model), P,
-                                            reinterpret_cast<float *>(d + o_per), kind,
-                                            reinterpret_cast<float *>(d + o_c),
-                                            reinterpret_cast<float *>(d + o_u),
-                                            reinterpret_cast<int *>(d + o_st), d + o_ws, ws);
+        ret = surfdisp_forward_batch_device(s, B, Lmax, nlay ? hs.at<int>(d, hs.o_nl) : nullptr, hs.at<float>(d, hs.o_model), P,
+                                            hs.at<float>(d, hs.o_per), kind, hs.at<float>(d, hs.o_c), hs.at<float>(d, hs.o_u),
+                                            hs.at<int>(d, hs.o_st), d + hs.o_ws, hs.ws);
         if (ret) break;
         if (small) {
-            ok = hipMemcpyAsync(h + o_c, d + o_c, o_ws - o_c, hipMemcpyDeviceToHost, s) == hipSuccess;
+            ok = hipMemcpyAsync(h + hs.o_c, d + hs.o_c, hs.o_ws - hs.o_c, hipMemcpyDeviceToHost, s) == hipSuccess;
         } else {
-            ok = hipMemcpyAsync(c, d + o_c, no, hipMemcpyDeviceToHost, s) == hipSuccess &&
-                 (!u || hipMemcpyAsync(u, d + o_u, no, hipMemcpyDeviceToHost, s) == hipSuccess) &&
-                 (!status || hipMemcpyAsync(status, d + o_st, ni, hipMemcpyDeviceToHost, s) == hipSuccess);
+            ok = hipMemcpyAsync(c, d + hs.o_c, hs.no, hipMemcpyDeviceToHost, s) == hipSuccess &&
+                 (!u || hipMemcpyAsync(u, d + hs.o_u, hs.no, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+                 (!status || hipMemcpyAsync(status, d + hs.o_st, hs.ni, hipMemcpyDeviceToHost, s) == hipSuccess);
         }
         if (!ok) { set_err("device->host copy failed"); ret = SURFDISP_ERR_HIP; break; }
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) { set_err("kernel execution failed: %s", hipGetErrorString(e)); ret = SURFDISP_ERR_HIP; break; }
         if (small) {
-            memcpy(c, h + o_c, no);
-            if (u) memcpy(u, h + o_u, no);
-            if (status) memcpy(status, h + o_st, ni);
+            memcpy(c, h + hs.o_c, hs.no);
+            if (u) memcpy(u, h + hs.o_u, hs.no);
+            if (status) memcpy(status, h + hs.o_st, hs.ni);
         }
     } while (0);
     // an error exit may leave copies / kernels queued on the thread's cached stream that still write into the caller's pageable

@@ -84,6 +84,12 @@ class BatchPlan:
     three kernels on torch's current stream without allocating or synchronising, so it
     can be captured in a HIP graph."""
 
+    # entry name -> the library function that sizes its workspace
+    _WS_BYTES = {"forward": "surfdisp_workspace_bytes", "kernels": "surfdisp_kernels_workspace_bytes",
+                 "group": "surfdisp_group_kernels_workspace_bytes", "ellip": "surfdisp_ellip_kernels_workspace_bytes",
+                 "atten": "surfdisp_atten_workspace_bytes", "eigen": "surfdisp_eigen_workspace_bytes",
+                 "thickness": "surfdisp_thickness_kernels_workspace_bytes"}
+
     def __init__(self, B, L, P, device="cuda:0"):
         import torch
         self.torch = torch
@@ -91,12 +97,60 @@ class BatchPlan:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.SurfdispError("BatchPlan needs a HIP device tensor (no CPU fallback)")
-        lib = _lib.lib()
-        self.ws_bytes = int(lib.surfdisp_workspace_bytes(self.B, self.L, self.P))
-        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device)
+        self._ws = {}                                  # entry name -> (uint8 tensor, bytes), kept for reuse
+        self._last_ws = self.workspace("forward")[0]   # (run() allocates nothing: made here)
         self.c = torch.zeros(self.B, self.P, dtype=torch.float32, device=self.device)
         self.u = torch.zeros(self.B, self.P, dtype=torch.float32, device=self.device)
         self.status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+
+    def workspace(self, entry, tensor=None):
+        """(uint8 tensor, bytes) of the workspace of ``entry`` (a key of ``_WS_BYTES``), created on first use with the size the
+        library asks for; ``tensor``: install the caller's own contiguous uint8 device tensor instead (all of it is handed over)."""
+        if tensor is not None:
+            self._ws[entry] = (tensor, int(tensor.numel()))
+        elif entry not in self._ws:
+            n = int(getattr(_lib.lib(), self._WS_BYTES[entry])(self.B, self.L, self.P))
+            self._ws[entry] = (self.torch.empty(n, dtype=self.torch.uint8, device=self.device), n)
+        return self._ws[entry]
+
+    def _check(self, model, periods, nlay):
+        torch = self.torch
+        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
+            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
+                    or t.device != self.device):
+                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
+        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
+                                 or nlay.device != self.device):
+            raise ValueError("nlay must be int32 [B] on the same device")
+
+    @staticmethod
+    def _ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+    def _out(self, *tail, want=True):
+        """An uninitialised float32 [B, P, *tail] output (``None`` unless ``want``)."""
+        return self.torch.empty((self.B, self.P) + tail, dtype=self.torch.float32, device=self.device) if want else None
+
+    def _counter(self, name):
+        """The int32 [1] device counter ``self.<name>``, kept for reuse."""
+        if getattr(self, name, None) is None:
+            setattr(self, name, self.torch.zeros(1, dtype=self.torch.int32, device=self.device))
+        return getattr(self, name)
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, fn, entry, model, periods, kind, nlay, mid, tail=()):
+        """Check the inputs and call the library's ``fn`` on torch's current stream with the workspace of ``entry``: the common
+        head (stream, B, L, nlay, model, P, periods, kind), ``mid``, (workspace, bytes), ``tail``."""
+        self._check(model, periods, nlay)
+        ws, nbytes = self.workspace(entry)
+        self._last_ws = ws
+        ptr = self._ptr
+        with self.torch.cuda.device(self.device):
+            rc = getattr(_lib.lib(), fn)(self._stream(), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
+                                         *mid, ptr(ws), nbytes, *tail)
+        _lib.check(rc)
 
     def run_timed(self, model, periods, kind=2, nlay=None, independent=False):
         """As run(), but blocks and also returns the (prep, phase, group) kernel durations in ms,
@@ -109,7 +163,6 @@ class BatchPlan:
         ``EventRing`` slot (4 HIP events recorded on the launch stream around the kernels).
         ``pipelined``: the caller keeps a second batch in flight on another stream
         (``SURFDISP_PIPELINED``: a launch hint, same results)."""
-        torch = self.torch
         if independent:
             kind = int(kind) | _lib.INDEPENDENT
         if pipelined:
@@ -118,64 +171,41 @@ class BatchPlan:
             kind = int(kind) | _lib.FASTSCAN
         if strict:                                     # verification mode (SURFDISP_STRICT): the exact kernel for every stack
             kind = int(kind) | _lib.STRICT
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.workspace
-        args = [ctypes.c_void_p(stream), self.B, self.L,
-                ctypes.c_void_p(nlay.data_ptr() if nlay is not None else 0),
-                ctypes.c_void_p(model.data_ptr()), self.P, ctypes.c_void_p(periods.data_ptr()),
-                int(kind), ctypes.c_void_p(self.c.data_ptr()), ctypes.c_void_p(self.u.data_ptr()),
-                ctypes.c_void_p(self.status.data_ptr()), ctypes.c_void_p(self.workspace.data_ptr()),
-                self.ws_bytes]
-        with torch.cuda.device(self.device):
-            if _timed:
-                ms = (ctypes.c_float * 3)()
-                rc = _lib.lib().surfdisp_forward_batch_device_timed(*args, ms)
-                _lib.check(rc)
-                return self.c, self.u, self.status, tuple(float(x) for x in ms)
-            if want_ratio:
-                # ABI 3: also the Rayleigh ellipticity (the reference's COMMON /o/ ratio, calcul.f:195) -> self.ratio [B, P]
-                if getattr(self, "ratio", None) is None:
-                    self.ratio = torch.zeros(self.B, self.P, dtype=torch.float32, device=self.device)
-                a2 = args[:10] + [ctypes.c_void_p(self.ratio.data_ptr())] + args[10:]
-                if events is not None:
-                    rc = _lib.lib().surfdisp_forward_batch_device2_events(*a2, events)
-                else:
-                    rc = _lib.lib().surfdisp_forward_batch_device2(*a2)
-            elif events is not None:
-                rc = _lib.lib().surfdisp_forward_batch_device_events(*args, events)
-            else:
-                rc = _lib.lib().surfdisp_forward_batch_device(*args)
-        _lib.check(rc)
+        ptr = self._ptr
+        out = (ptr(self.c), ptr(self.u), ptr(self.status))
+        if _timed:
+            ms = (ctypes.c_float * 3)()
+            self._call("surfdisp_forward_batch_device_timed", "forward", model, periods, kind, nlay, out, (ms,))
+            return self.c, self.u, self.status, tuple(float(x) for x in ms)
+        fn, tail = "surfdisp_forward_batch_device", ()
+        if want_ratio:
+            # ABI 3: also the Rayleigh ellipticity (the reference's COMMON /o/ ratio, calcul.f:195) -> self.ratio [B, P]
+            if getattr(self, "ratio", None) is None:
+                self.ratio = self.torch.zeros(self.B, self.P, dtype=self.torch.float32, device=self.device)
+            fn, out = fn + "2", (out[0], out[1], ptr(self.ratio), out[2])
+        if events is not None:
+            fn, tail = fn + "_events", (events,)
+        self._call(fn, "forward", model, periods, kind, nlay, out, tail)
         if want_ratio:
             return self.c, self.u, self.status, self.ratio
         return self.c, self.u, self.status
 
+    def _read_counters(self, fn, out):
+        with self.torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.lib(), fn)(self._stream(), self._ptr(self._last_ws), self.B, self.L, self.P, out))
 
     def fallback_count(self):
         """Stacks of the last ``run`` that the production root search handed to the exact fallback kernel
         (``surfdisp_workspace_fallback_count``; synchronises the current stream)."""
         n = ctypes.c_int(0)
-        stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        with self.torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_workspace_fallback_count(ctypes.c_void_p(stream), ctypes.c_void_p(getattr(self, '_last_ws', self.workspace).data_ptr()),
-                                                                    self.B, self.L, self.P, ctypes.byref(n)))
+        self._read_counters("surfdisp_workspace_fallback_count", ctypes.byref(n))
         return int(n.value)
 
     def counters(self):
         """(stacks through the exact fallback kernel, brackets refined with NEVILL by the phase test, ellipticities evaluated
         again with the reference's arithmetic) of the last solve (``surfdisp_workspace_counters``; synchronises the stream)."""
         n = (ctypes.c_int * 3)()
-        stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        with self.torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_workspace_counters(ctypes.c_void_p(stream), ctypes.c_void_p(getattr(self, '_last_ws', self.workspace).data_ptr()),
-                                                              self.B, self.L, self.P, n))
+        self._read_counters("surfdisp_workspace_counters", n)
         return tuple(int(x) for x in n)
 
     def run_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, small_workspace=False):
@@ -184,34 +214,13 @@ class BatchPlan:
         partials float32 [B, P, L] = d c(period) / d (Vs | Vp | rho) of input layer i (``None`` where
         not requested; Love has no dcda).  Same launch as ``run`` plus per-layer sums in the
         group-velocity kernel - what ``SensKernelPert`` obtains from 2L+1 perturbed solves."""
-        torch = self.torch
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
-        dcdb = mk()
-        dcda = mk() if (want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH) else None
-        dcdr = mk() if want_rho else None
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        if small_workspace:                            # the direct route into the rows (tests compare the two)
-            ws, ws_bytes = self.workspace, self.ws_bytes
-        else:
-            if getattr(self, "kworkspace", None) is None:      # + the layer-major scratch of the partials, kept for reuse
-                self.kws_bytes = int(_lib.lib().surfdisp_kernels_workspace_bytes(self.B, self.L, self.P))
-                self.kworkspace = torch.empty(self.kws_bytes, dtype=torch.uint8, device=self.device)
-            ws, ws_bytes = self.kworkspace, self.kws_bytes
-        self._last_ws = ws
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_kernels_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
-                ptr(ws), ws_bytes)
-        _lib.check(rc)
+        ptr, L = self._ptr, self.L
+        dcdb = self._out(L)
+        dcda = self._out(L, want=want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH)
+        dcdr = self._out(L, want=want_rho)
+        # small_workspace: the direct route into the rows (tests compare the two); else + the partials' layer-major scratch
+        self._call("surfdisp_forward_kernels_device", "forward" if small_workspace else "kernels", model, periods, kind, nlay,
+                   (ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr)))
         return self.c, self.u, self.status, dcdb, dcda, dcdr
 
     def run_group_kernels(self, model, periods, kind=2, nlay=None, dlnT_frac=0.01, want_vp=True, want_rho=True, count=True):
@@ -221,33 +230,16 @@ class BatchPlan:
         requested; Love has no duda), from the phase partials at T (1 -+ dlnT_frac).  Rows of unsolved periods are zeros,
         rows of units whose shifted root failed are NaN; ``n_failed`` (int, synchronises the stream) counts the latter
         (``count=False``: the device tensor itself, no synchronisation)."""
-        torch = self.torch
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
+        ptr, L = self._ptr, self.L
         rayleigh = (int(kind) & 3) == _lib.KIND_RAYLEIGH
-        dcdb, dudb = mk(), mk()
-        dcda, duda = (mk(), mk()) if (want_vp and rayleigh) else (None, None)
-        dcdr, dudr = (mk(), mk()) if want_rho else (None, None)
-        if getattr(self, "gworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
-            self.gws_bytes = int(_lib.lib().surfdisp_group_kernels_workspace_bytes(self.B, self.L, self.P))
-            self.gworkspace = torch.empty(self.gws_bytes, dtype=torch.uint8, device=self.device)
-            self.nfail = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.gworkspace
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_group_kernels_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                float(dlnT_frac), ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
-                ptr(dudb), ptr(duda), ptr(dudr), ptr(self.nfail), ptr(self.gworkspace), self.gws_bytes)
-        _lib.check(rc)
-        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(self.nfail.item()) if count else self.nfail
+        dcdb, dudb = self._out(L), self._out(L)
+        dcda, duda = self._out(L, want=want_vp and rayleigh), self._out(L, want=want_vp and rayleigh)
+        dcdr, dudr = self._out(L, want=want_rho), self._out(L, want=want_rho)
+        nfail = self._counter("nfail")
+        self._call("surfdisp_forward_group_kernels_device", "group", model, periods, kind, nlay,
+                   (float(dlnT_frac), ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                    ptr(dudb), ptr(duda), ptr(dudr), ptr(nfail)))
+        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, int(nfail.item()) if count else nfail
 
     def run_ellip_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, count=True):
         """``run_kernels`` plus the Rayleigh ellipticity and its analytic partials (``surfdisp_forward_ellip_kernels_device``):
@@ -256,35 +248,18 @@ class BatchPlan:
         rho) of input layer i (``None`` where not requested).  Rows of unsolved periods, water layers and layers below the half
         space are zeros, rows of units whose result is not finite are NaN; ``n_nonfinite`` (int, synchronises the stream)
         counts the latter (``count=False``: the device tensor itself, no synchronisation).  Rayleigh only."""
-        torch = self.torch
         if (int(kind) & 3) != _lib.KIND_RAYLEIGH:
             raise ValueError("run_ellip_kernels: Rayleigh only (kind=2); Love waves have no ellipticity")
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
-        dcdb, dedb = mk(), mk()
-        dcda, deda = (mk(), mk()) if want_vp else (None, None)
-        dcdr, dedr = (mk(), mk()) if want_rho else (None, None)
-        ratio = torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
-        if getattr(self, "eworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
-            self.ews_bytes = int(_lib.lib().surfdisp_ellip_kernels_workspace_bytes(self.B, self.L, self.P))
-            self.eworkspace = torch.empty(self.ews_bytes, dtype=torch.uint8, device=self.device)
-            self.nnonfin = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.eworkspace
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_ellip_kernels_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                ptr(self.c), ptr(self.u), ptr(ratio), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
-                ptr(dedb), ptr(deda), ptr(dedr), ptr(self.nnonfin), ptr(self.eworkspace), self.ews_bytes)
-        _lib.check(rc)
-        return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(self.nnonfin.item()) if count else self.nnonfin)
+        ptr, L = self._ptr, self.L
+        dcdb, dedb = self._out(L), self._out(L)
+        dcda, deda = self._out(L, want=want_vp), self._out(L, want=want_vp)
+        dcdr, dedr = self._out(L, want=want_rho), self._out(L, want=want_rho)
+        ratio = self._out()
+        nnonfin = self._counter("nnonfin")
+        self._call("surfdisp_forward_ellip_kernels_device", "ellip", model, periods, kind, nlay,
+                   (ptr(self.c), ptr(self.u), ptr(ratio), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                    ptr(dedb), ptr(deda), ptr(dedr), ptr(nnonfin)))
+        return (self.c, self.u, self.status, ratio, dcdb, dcda, dcdr, dedb, deda, dedr, int(nnonfin.item()) if count else nnonfin)
 
     def run_atten(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, want_kernel=True, want_gamma=True):
         """``run_kernels`` plus the apparent attenuation of the mode (``surfdisp_forward_atten_device``): returns (c, u, status,
@@ -293,34 +268,15 @@ class BatchPlan:
         gamma [B, P] the attenuation coefficient in 1/km, dqdq float32 [B, P, L] = d qinv / d (1/Qs of layer i) at fixed
         eigenfunction (``None`` with ``want_kernel=False``; gamma ``None`` with ``want_gamma=False``).  Unsolved periods and
         bad stacks are zeros, as are water layers and layers below the half space in dqdq.  Rayleigh and Love."""
-        torch = self.torch
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
-        mk2 = lambda: torch.empty((self.B, self.P), dtype=torch.float32, device=self.device)
-        dcdb = mk()
-        dcda = mk() if (want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH) else None
-        dcdr = mk() if want_rho else None
-        qinv = mk2()
-        gamma = mk2() if want_gamma else None
-        dqdq = mk() if want_kernel else None
-        if getattr(self, "aworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
-            self.aws_bytes = int(_lib.lib().surfdisp_atten_workspace_bytes(self.B, self.L, self.P))
-            self.aworkspace = torch.empty(self.aws_bytes, dtype=torch.uint8, device=self.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.aworkspace
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_atten_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
-                ptr(qinv), ptr(gamma), ptr(dqdq), ptr(self.aworkspace), self.aws_bytes)
-        _lib.check(rc)
+        ptr, L = self._ptr, self.L
+        dcdb = self._out(L)
+        dcda = self._out(L, want=want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH)
+        dcdr = self._out(L, want=want_rho)
+        qinv = self._out()
+        gamma = self._out(want=want_gamma)
+        dqdq = self._out(L, want=want_kernel)
+        self._call("surfdisp_forward_atten_device", "atten", model, periods, kind, nlay,
+                   (ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr), ptr(qinv), ptr(gamma), ptr(dqdq)))
         return self.c, self.u, self.status, dcdb, dcda, dcdr, qinv, gamma, dqdq
 
     def run_eigen(self, model, periods, kind=2, nlay=None, want_uz=True, want_tz=True, want_tr=True, want_energy=True):
@@ -332,32 +288,14 @@ class BatchPlan:
         uz = 1 (Love ut = 1) at the top of the first solid layer; energy [B, P, 4] = (I0, I1, I2, 1 / (2 c U I0)).  Zeros below
         the unit's effective half space, beyond nlay, for unsolved periods and bad stacks.  ``None`` where not requested.
         The conventions are those of include/surfdisp.h section (5f)."""
-        torch = self.torch
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
-        ur = mk()
-        uz = mk() if want_uz else None
-        tz = mk() if want_tz else None
-        tr = mk() if want_tr else None
-        energy = torch.empty((self.B, self.P, 4), dtype=torch.float32, device=self.device) if want_energy else None
-        if getattr(self, "eigworkspace", None) is None:        # kept for reuse, as run_kernels' workspace
-            self.eigws_bytes = int(_lib.lib().surfdisp_eigen_workspace_bytes(self.B, self.L, self.P))
-            self.eigworkspace = torch.empty(self.eigws_bytes, dtype=torch.uint8, device=self.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.eigworkspace
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_eigen_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                ptr(self.c), ptr(self.u), ptr(self.status), ptr(ur), ptr(uz), ptr(tz), ptr(tr), ptr(energy),
-                ptr(self.eigworkspace), self.eigws_bytes)
-        _lib.check(rc)
+        ptr, L = self._ptr, self.L
+        ur = self._out(L)
+        uz = self._out(L, want=want_uz)
+        tz = self._out(L, want=want_tz)
+        tr = self._out(L, want=want_tr)
+        energy = self._out(4, want=want_energy)
+        self._call("surfdisp_forward_eigen_device", "eigen", model, periods, kind, nlay,
+                   (ptr(self.c), ptr(self.u), ptr(self.status), ptr(ur), ptr(uz), ptr(tz), ptr(tr), ptr(energy)))
         return self.c, self.u, self.status, ur, uz, tz, tr, energy
 
     def run_thickness_kernels(self, model, periods, kind=2, nlay=None, want_vp=True, want_rho=True, want_dcdz=True, count=True):
@@ -370,40 +308,22 @@ class BatchPlan:
         dcdh[nlay - 1] and dcdz[0]; rows of a unit with a value that is not finite are NaN and ``n_nonfinite`` (int,
         synchronises the stream; ``count=False``: the device tensor itself) counts them.  Rayleigh and Love; the
         conventions are those of include/surfdisp.h section (5g)."""
-        torch = self.torch
-        for t, shape in ((model, (self.B, 5, self.L)), (periods, (self.P,))):
-            if (t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape
-                    or t.device != self.device):
-                raise ValueError(f"expected contiguous float32 {shape} on {self.device}")
-        if nlay is not None and (nlay.dtype != torch.int32 or nlay.numel() != self.B
-                                 or nlay.device != self.device):
-            raise ValueError("nlay must be int32 [B] on the same device")
-        mk = lambda: torch.empty((self.B, self.P, self.L), dtype=torch.float32, device=self.device)
-        dcdb, dcdh = mk(), mk()
-        dcda = mk() if (want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH) else None
-        dcdr = mk() if want_rho else None
-        dcdz = mk() if want_dcdz else None
-        if getattr(self, "tworkspace", None) is None:          # kept for reuse, as run_kernels' workspace
-            self.tws_bytes = int(_lib.lib().surfdisp_thickness_kernels_workspace_bytes(self.B, self.L, self.P))
-            self.tworkspace = torch.empty(self.tws_bytes, dtype=torch.uint8, device=self.device)
-            self.tnonfin = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        self._last_ws = self.tworkspace
-        with torch.cuda.device(self.device):
-            rc = _lib.lib().surfdisp_forward_thickness_kernels_device(
-                ctypes.c_void_p(stream), self.B, self.L, ptr(nlay), ptr(model), self.P, ptr(periods), int(kind),
-                ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
-                ptr(dcdh), ptr(dcdz), ptr(self.tnonfin), ptr(self.tworkspace), self.tws_bytes)
-        _lib.check(rc)
-        return (self.c, self.u, self.status, dcdb, dcda, dcdr, dcdh, dcdz, int(self.tnonfin.item()) if count else self.tnonfin)
+        ptr, L = self._ptr, self.L
+        dcdb, dcdh = self._out(L), self._out(L)
+        dcda = self._out(L, want=want_vp and (int(kind) & 3) == _lib.KIND_RAYLEIGH)
+        dcdr = self._out(L, want=want_rho)
+        dcdz = self._out(L, want=want_dcdz)
+        tnonfin = self._counter("tnonfin")
+        self._call("surfdisp_forward_thickness_kernels_device", "thickness", model, periods, kind, nlay,
+                   (ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr), ptr(dcdh), ptr(dcdz), ptr(tnonfin)))
+        return (self.c, self.u, self.status, dcdb, dcda, dcdr, dcdh, dcdz, int(tnonfin.item()) if count else tnonfin)
 
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's
         own c where it is unsolved or its shifted root failed) - a read-out of the workspace for tests."""
         off = int(_lib.lib().surfdisp_group_kernels_shift_offset(self.B, self.L, self.P))
         n = 2 * self.P * self.B * 4
-        return self.gworkspace[off:off + n].view(self.torch.float32).view(2, self.P, self.B).transpose(1, 2).clone()
+        return self.workspace("group")[0][off:off + n].view(self.torch.float32).view(2, self.P, self.B).transpose(1, 2).clone()
 
 
 class EventRing:

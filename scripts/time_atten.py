@@ -56,7 +56,7 @@ for kind, name in ((2, "Rayleigh"), (1, "Love")):
     lines.append(f"{name:8s} common outputs bit-identical to run_kernels: {same};  solved units {int(solved.sum())}, "
                  f"1/Q in [{float(qinv[solved].min()):.3e}, {float(qinv[solved].max()):.3e}]")
     print("\n".join(lines[-4:]), flush=True)
-lines.append(f"workspace: run_atten {plan.aws_bytes / 2**20:.0f} MiB = run_kernels {plan.kws_bytes / 2**20:.0f} MiB")
+lines.append(f"workspace: run_atten {plan.workspace('atten')[1] / 2**20:.0f} MiB = run_kernels {plan.workspace('kernels')[1] / 2**20:.0f} MiB")
 print(lines[-1], flush=True)
 if len(sys.argv) > 1:
     with open(sys.argv[1], "w") as f:

@@ -61,7 +61,7 @@ for kind, name in ((2, "Rayleigh"), (1, "Love")):
                  f"{float(deep):.1f} of {L};  transposition floor: {planes} planes written + read at most ({2 * planes * unit:.0f} MB) "
                  f"+ 4 row arrays written ({4 * unit:.0f} MB)")
     print("\n".join(lines[-4:]), flush=True)
-lines.append(f"workspace: run_eigen {plan.eigws_bytes / 2**20:.0f} MiB, run {plan.ws_bytes / 2**20:.0f} MiB, "
+lines.append(f"workspace: run_eigen {plan.workspace('eigen')[1] / 2**20:.0f} MiB, run {plan.workspace('forward')[1] / 2**20:.0f} MiB, "
              f"run_kernels {_lib.lib().surfdisp_kernels_workspace_bytes(B, L, P) / 2**20:.0f} MiB")
 print(lines[-1], flush=True)
 if len(sys.argv) > 1:

@@ -40,7 +40,7 @@ out = plan.run_ellip_kernels(m, per, kind=2)
 solved = int((out[0] > 0).sum().item())
 lines.append(f"run_kernels {t_k:.3f} ms  run_group_kernels {t_g:.3f} ms (+{t_g - t_k:.3f})  "
              f"run_ellip_kernels {t_e:.3f} ms (+{t_e - t_k:.3f})  n_nonfinite {out[10]} of {solved} solved units")
-lines.append(f"workspace: run_ellip_kernels {plan.ews_bytes / 2**20:.0f} MiB, run_group_kernels {plan.gws_bytes / 2**20:.0f} MiB")
+lines.append(f"workspace: run_ellip_kernels {plan.workspace('ellip')[1] / 2**20:.0f} MiB, run_group_kernels {plan.workspace('group')[1] / 2**20:.0f} MiB")
 print("\n".join(lines[1:]), flush=True)
 if len(sys.argv) > 1:
     with open(sys.argv[1], "w") as f:

@@ -69,8 +69,8 @@ for kind, name in ((2, "Rayleigh"), (1, "Love")):
                  f"n_nonfinite {out[8]}, all finite {finite}, mean non-zero dcdh entries per unit {float(deep):.1f} of {L};  thickness kernel's "
                  f"floor: {eplanes} + {kplanes} planes read once ({(eplanes + kplanes) * unit:.0f} MB) + 2 row arrays written ({2 * unit:.0f} MB)")
     print("\n".join(lines[-5:]), flush=True)
-lines.append(f"workspace: run_thickness_kernels {plan.tws_bytes / 2**20:.0f} MiB, run_kernels {plan.kws_bytes / 2**20:.0f} MiB, "
-             f"run_eigen {plan.eigws_bytes / 2**20:.0f} MiB, run {plan.ws_bytes / 2**20:.0f} MiB")
+lines.append(f"workspace: run_thickness_kernels {plan.workspace('thickness')[1] / 2**20:.0f} MiB, run_kernels {plan.workspace('kernels')[1] / 2**20:.0f} MiB, "
+             f"run_eigen {plan.workspace('eigen')[1] / 2**20:.0f} MiB, run {plan.workspace('forward')[1] / 2**20:.0f} MiB")
 print(lines[-1], flush=True)
 if len(sys.argv) > 1:
     with open(sys.argv[1], "w") as f:

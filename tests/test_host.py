@@ -133,3 +133,28 @@ def test_committed_counter_profiles_are_of_these_sources():
     for leg in ("latest", "grid", "c5", "mcmc"):
         tj = json.load(open(os.path.join(root, "profiles", f"traffic_{leg}.json")))
         assert tj.get("src_sha256_16") == here, (leg, tj.get("src_sha256_16"), here)
+
+
+def test_workspace_sizes_keep_the_relations_the_header_documents():
+    """The seven workspace sizes come from one layout (csrc/surfdisp_capi.hip: forward region, partials' scratch, the entry's
+    own region), every array padded to 256 bytes: the relations between them that include/surfdisp.h states."""
+    from pysurfinv_amd import _lib
+    L = _lib.lib()
+    al = lambda n: (n + 255) // 256 * 256
+    for B, Lmax, P in ((1, 2, 1), (1, 10, 20), (3, 6, 4), (100, 200, 19), (4096, 24, 200), (65536, 10, 20), (7, 200, 3)):
+        fwd, kern = L.surfdisp_workspace_bytes(B, Lmax, P), L.surfdisp_kernels_workspace_bytes(B, Lmax, P)
+        group, ellip = L.surfdisp_group_kernels_workspace_bytes(B, Lmax, P), L.surfdisp_ellip_kernels_workspace_bytes(B, Lmax, P)
+        atten, eigen = L.surfdisp_atten_workspace_bytes(B, Lmax, P), L.surfdisp_eigen_workspace_bytes(B, Lmax, P)
+        thick = L.surfdisp_thickness_kernels_workspace_bytes(B, Lmax, P)
+        for n in (fwd, kern, group, ellip, atten, eigen, thick):
+            assert n > 0 and n % 256 == 0, (B, Lmax, P, n)
+        assert kern > fwd and atten == kern and eigen > fwd, (B, Lmax, P)
+        assert group > kern and ellip > kern and thick > kern, (B, Lmax, P)
+        assert thick - kern == eigen - fwd + al(P * B * 4), (B, Lmax, P)
+        off = L.surfdisp_group_kernels_shift_offset(B, Lmax, P)
+        assert off >= kern and off + 2 * P * B * 4 <= group, (B, Lmax, P, off)
+    names = [f for f in _lib.EXPORTS if f.endswith("workspace_bytes") and "posterior" not in f] + ["surfdisp_group_kernels_shift_offset"]
+    assert len(names) == 8, names
+    for f in names:
+        for B, Lmax, P in ((0, 10, 20), (100, 1, 20), (100, 10, 0)):
+            assert getattr(L, f)(B, Lmax, P) == 0, (f, B, Lmax, P)
