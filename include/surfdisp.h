@@ -677,6 +677,62 @@ int surfdisp_posterior_predictive_device(void *stream, int npoints, int total, i
                                          int *hist, int *below, int *above,
                                          void *workspace, size_t workspace_bytes);
 
+/* ---- (6h) INTERFACE DEPTHS as unknowns of (6d) and (6e), added within ABI 4 (csrc/surfdisp_lsq.hip): the consumer of dcdh of (5g).
+ *          Behind the n Vs unknowns of a stack come K THICKNESS MODES, 0 <= K <= 8: mode k has a shape T_k [Lmax] (fp64) and an
+ *          amplitude y_k in km, and the thickness of input layer i changes by sum_k T_k[i] y_k.  modes = T: [K][Lmax], or
+ *          [B][K][Lmax] with modes_per_stack; entries at layers i >= nlay - 1 are not read (the half space has no thickness).
+ *          T[i] = h_i / sum(h[group]) on a layer group thickens the group by y and shifts everything below rigidly;
+ *          + h_i / sum(h[above]) on one group and - h_i / sum(h[below]) on the next moves the interface between them down by y
+ *          and leaves the total depth alone: a Moho, a sediment base, a sea floor (pysurfinv_amd.linearized.thickness_mode,
+ *          interface_mode).  The two entries take the arguments of (6d) / (6e) up to and including `lam`, then:
+ *   in:    K, modes, modes_per_stack.  part_h[5]: the [B][nper][Lmax] fp32 thickness kernels of the sources {cR, uR, cL, uL, chi} -
+ *          today part_h[0] and part_h[2] can be filled, with the dcdh arrays exactly as (5g) writes them; the other slots wait
+ *          for dU/dh and dchi/dh.  mode_scale [K] ([B][K] with modes_per_stack; > 0): mode k takes lam_s mode_scale_k on its
+ *          diagonal - it turns the Vs damping, in (km/s)^-2, into km^-2.  mode_prior [K] ([B][K] with modes_per_stack; beta >= 0;
+ *          NULL: 0) and mode_y [B][K] (the amplitude accumulated since the starting model; NULL: 0; read by the step only): the
+ *          Gaussian pull beta_k (y_k + delta_k)^2 back to the starting depth.  mode_scale and mode_prior are device memory and
+ *          are not checked.
+ *   rows:  unknown order: the n free layers' Vs, then the K modes.  The column of mode k in row r (source src, period idx):
+ *              G[r, n + k] = sg_r * sum_{i < nlay - 1} part_h[src][s, idx, i] * T_k[i]        (an fp64 sum of fp32 x fp64),
+ *          sg_r the sign of a source-5 row.  The row rules of (6d), and with K > 0 a row is also DROPPED when part_h of its
+ *          source is NULL (it names a missing array) or when one of its mode columns is not finite (the NaN rows of (5g)).
+ *   solve: with nu = n + K, E = diag(lam_s, .., lam_s, lam_s ms_0 + beta_0, ..) and D acting on the Vs unknowns only,
+ *              (G^T W G + alpha D^T Q D + E) (delta, delta_y) = G^T W res - alpha D^T Q D x0 - (0, beta_k y_k).
+ *   out:   surfdisp_lsq_step_modes_device: delta [B][Lmax] as (6d) and delta_y [B][K]; stats and info as (6d) - misfit and
+ *          roughness unchanged, the predicted objective with the prior term sum_k beta_k (y_k + delta_y_k)^2 (flag != 0: the
+ *          objective at x0, with sum_k beta_k y_k^2); flags as (6d), 3 still "more than nfree_max free layers"; for a flag other
+ *          than 0 delta_y is zeros, never NaN.
+ *          surfdisp_lsq_resolution_modes_device: cov, res [B][nfree_max + K][nfree_max + K], the modes behind the stack's n Vs
+ *          unknowns, rows and columns >= n + K zeros; sigma_post, sigma_data, rdiag [B][Lmax] as (6e) and sigma_post_y,
+ *          sigma_data_y, rdiag_y [B][K] of the modes; stats = dof and log det A over all nu unknowns; R = I - C (alpha D^T Q D + E).
+ *          With K = 0 both entries launch the kernels of (6d) / (6e) themselves and return their bits (the mode arguments are
+ *          then not read, the mode outputs not written).  With K > 0 the same kernels compiled with the mode columns: one
+ *          workgroup per stack, the packed triangle for nu + 1 (step) or nu (resolution) unknowns and T in dynamic LDS - 93 KB +
+ *          8 K Lmax bytes at nfree_max + K = 136; the dynamic-LDS limit is raised as in (6d): first call outside a graph capture.
+ *          SURFDISP_ERR_INVALID, before anything is launched: the conditions of (6d) / (6e), K outside 0..8, nfree_max + K > 136,
+ *          and with K > 0 a NULL modes, part_h, mode_scale, delta_y (step) or sigma_post_y, sigma_data_y, rdiag_y (resolution). */
+int surfdisp_lsq_step_modes_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                   const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                   const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                   int N, const int *cols, const double *weights,
+                                   const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                   const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                   double alpha, const double *Q, int q_per_stack, const double *lam,
+                                   int K, const double *modes, int modes_per_stack, const float *const part_h[5],
+                                   const double *mode_scale, const double *mode_prior, const double *mode_y,
+                                   double *delta, double *delta_y, double *stats, int *info);
+int surfdisp_lsq_resolution_modes_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                         const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                         const float *const part[15], const float *const pred[5], const long pred_stride[5],
+                                         const int nper[2], int N, const int *cols, const double *weights,
+                                         const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                         const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                         double alpha, const double *Q, int q_per_stack, const double *lam,
+                                         int K, const double *modes, int modes_per_stack, const float *const part_h[5],
+                                         const double *mode_scale, const double *mode_prior, const double *mode_y,
+                                         double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
+                                         double *sigma_post_y, double *sigma_data_y, double *rdiag_y, double *stats, int *info);
+
 /* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular
  *          function that leaves the fp32 range (the reference's overflow points depend on how it forms its matrix

@@ -40,6 +40,7 @@ EXPORTS = (
     "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_forward_eigen_device", "surfdisp_eigen_workspace_bytes",
     "surfdisp_forward_thickness_kernels_device", "surfdisp_thickness_kernels_workspace_bytes",
     "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device",
+    "surfdisp_lsq_step_modes_device", "surfdisp_lsq_resolution_modes_device",
     "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes",
     "surfdisp_posterior_sources_device", "surfdisp_posterior_sources_workspace_bytes",
     "surfdisp_posterior_predictive_device", "surfdisp_posterior_predictive_workspace_bytes", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
@@ -193,6 +194,14 @@ def lib() -> ctypes.CDLL:
     if hasattr(L, "surfdisp_lsq_resolution_device"):          # (absent from an older build loaded through SURFDISP_LIB_PATH)
         L.surfdisp_lsq_resolution_device.restype = ctypes.c_int
         L.surfdisp_lsq_resolution_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + [vp] * 7
+    # the same up to lam, then (K, modes, modes_per_stack, part_h[5], mode_scale, mode_prior, mode_y) and the outputs
+    # (delta, delta_y, stats, info) / (cov, res, sigma_post, sigma_data, rdiag, sigma_post_y, sigma_data_y, rdiag_y, stats, info)
+    if hasattr(L, "surfdisp_lsq_step_modes_device"):          # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        mode_in = [ctypes.c_int, vp, ctypes.c_int, vpp, vp, vp, vp]
+        L.surfdisp_lsq_step_modes_device.restype = ctypes.c_int
+        L.surfdisp_lsq_step_modes_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + mode_in + [vp] * 4
+        L.surfdisp_lsq_resolution_modes_device.restype = ctypes.c_int
+        L.surfdisp_lsq_resolution_modes_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + mode_in + [vp] * 10
     # (stream, npoints, R, N, track, row_stride, idesc (host), idesc_len, fdesc, aux, K, rows, D, zdeps (host), true_markov_chain, chainL,
     #  prefix, nbins, vlo, vhi, min_misfit, thres, imin, n_final, pmean, pstd, count, vs_mean, vs_std, vs_min, vs_max, hist, below, above,
     #  workspace, workspace_bytes)

@@ -1282,6 +1282,78 @@ int surfdisp_lsq_resolution_device(void *stream, int B, int Lmax, const int *nla
     return SURFDISP_SUCCESS;
 }
 
+// The thickness-mode arguments of section (6h), checked and copied into `a` behind lsq_args; `outputs`: the mode outputs the
+// entry requires with K > 0 are all given.
+static bool lsq_mode_args(const char *name, sd::LsqArgs &a, int nfree_max, int K, const double *modes, int modes_per_stack,
+                          const float *const part_h[5], const double *mode_scale, const double *mode_prior, const double *mode_y,
+                          bool outputs)
+{
+    if (K < 0 || K > sd::SD_LSQ_MAX_MODES || nfree_max + K > sd::SD_LSQ_MAX_FREE + sd::SD_LSQ_MAX_MODES ||
+        (K > 0 && !(modes && part_h && mode_scale && outputs))) {
+        set_err("%s: bad thickness-mode argument (0 <= K <= 8, nfree_max + K <= 136, with K > 0: modes, part_h, mode_scale and "
+                "the mode outputs)", name);
+        return false;
+    }
+    a.K = K;
+    if (K > 0) {
+        a.modes = modes; a.modes_per_stack = modes_per_stack ? 1 : 0;
+        for (int k = 0; k < 5; ++k) a.part_h[k] = part_h[k];
+        a.mode_scale = mode_scale; a.mode_prior = mode_prior; a.mode_y = mode_y;
+    }
+    return true;
+}
+
+// The step with K thickness modes behind the Vs unknowns (section (6h)); K = 0 launches the kernel of (6d) itself.
+int surfdisp_lsq_step_modes_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                   const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                   const float *const part[15], const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                   int N, const int *cols, const double *weights,
+                                   const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                   const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                   double alpha, const double *Q, int q_per_stack, const double *lam,
+                                   int K, const double *modes, int modes_per_stack, const float *const part_h[5],
+                                   const double *mode_scale, const double *mode_prior, const double *mode_y,
+                                   double *delta, double *delta_y, double *stats, int *info)
+{
+    const char *name = "surfdisp_lsq_step_modes_device";
+    sd::LsqArgs a{};
+    if (!lsq_args(name, a, B, Lmax, nlay, model, free_mask, free_per_stack, nfree_max, part, pred, pred_stride, nper, N, cols, weights,
+                  obs, uncer, mask, obs_per_stack, vp_slope, rho_slope, slope_per_stack, alpha, Q, q_per_stack, lam,
+                  delta && stats && info) ||
+        !lsq_mode_args(name, a, nfree_max, K, modes, modes_per_stack, part_h, mode_scale, mode_prior, mode_y, delta_y != nullptr))
+        return SURFDISP_ERR_INVALID;
+    a.delta = delta; a.delta_y = delta_y; a.stats = stats; a.info = info;
+    SD_HIP(sd::launch_lsq_step(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
+// ... and its covariance and resolution; K = 0 launches the kernel of (6e) itself.
+int surfdisp_lsq_resolution_modes_device(void *stream, int B, int Lmax, const int *nlay, const float *model,
+                                         const unsigned char *free_mask, int free_per_stack, int nfree_max,
+                                         const float *const part[15], const float *const pred[5], const long pred_stride[5],
+                                         const int nper[2], int N, const int *cols, const double *weights,
+                                         const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                         const double *vp_slope, const double *rho_slope, int slope_per_stack,
+                                         double alpha, const double *Q, int q_per_stack, const double *lam,
+                                         int K, const double *modes, int modes_per_stack, const float *const part_h[5],
+                                         const double *mode_scale, const double *mode_prior, const double *mode_y,
+                                         double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
+                                         double *sigma_post_y, double *sigma_data_y, double *rdiag_y, double *stats, int *info)
+{
+    const char *name = "surfdisp_lsq_resolution_modes_device";
+    sd::LsqArgs a{};
+    if (!lsq_args(name, a, B, Lmax, nlay, model, free_mask, free_per_stack, nfree_max, part, pred, pred_stride, nper, N, cols, weights,
+                  obs, uncer, mask, obs_per_stack, vp_slope, rho_slope, slope_per_stack, alpha, Q, q_per_stack, lam,
+                  sigma_post && sigma_data && rdiag && stats && info) ||
+        !lsq_mode_args(name, a, nfree_max, K, modes, modes_per_stack, part_h, mode_scale, mode_prior, mode_y,
+                       sigma_post_y && sigma_data_y && rdiag_y))
+        return SURFDISP_ERR_INVALID;
+    a.cov = cov; a.res = res; a.sigma_post = sigma_post; a.sigma_data = sigma_data; a.rdiag = rdiag;
+    a.sigma_post_y = sigma_post_y; a.sigma_data_y = sigma_data_y; a.rdiag_y = rdiag_y; a.stats = stats; a.info = info;
+    SD_HIP(sd::launch_lsq_resolution(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Measurement variants that do NOT synchronise: the caller owns four events per call
 // (surfdisp_events_create) which are recorded on the launch stream before prep, between the
 // kernels and after finish; durations are read later with surfdisp_events_elapsed_ms, after the

@@ -288,6 +288,7 @@ struct McmcJointArgs {
 };
 // damped least-squares step of the free layers' Vs (csrc/surfdisp_lsq.hip; include/surfdisp.h section (6d))
 constexpr int SD_LSQ_MAX_FREE = 128;    // unknowns per stack: the packed triangle of 129 x 129 doubles is 66 KB of LDS
+constexpr int SD_LSQ_MAX_MODES = 8;     // thickness modes per stack behind the Vs unknowns (section (6h)): 137 x 137 doubles, 93 KB
 constexpr int SD_LSQ_TILE_ROWS = 16;    // data rows staged in LDS at a time
 struct LsqArgs {
     int B, Lmax, N, nmax;   // stacks, layers per row, data rows, upper bound of the free layers of any stack (sizes the LDS)
@@ -316,6 +317,16 @@ struct LsqArgs {
     // the resolution kernel only (section (6e)); there stats is [B][2]: dof, log det A, and delta is not used
     double *cov, *res;      // [B][nmax][nmax] or nullptr
     double *sigma_post, *sigma_data, *rdiag;   // [B][Lmax]
+    // thickness modes (section (6h)); K = 0: none of these is read, the kernels are those of (6d) / (6e).  With K > 0 cov and res
+    // are [B][nmax + K][nmax + K]
+    int K;                  // 0..SD_LSQ_MAX_MODES
+    const double *modes;    // [K][Lmax], or [B][K][Lmax] when modes_per_stack
+    int modes_per_stack;
+    const float *part_h[5]; // dcdh of the five sources: [B][nper of the source's solve][Lmax] or nullptr
+    const double *mode_scale, *mode_prior;     // [K] or [B][K] (modes_per_stack); mode_prior nullptr: 0
+    const double *mode_y;   // [B][K] or nullptr: 0 (the step kernel only)
+    double *delta_y;        // [B][K] (the step kernel)
+    double *sigma_post_y, *sigma_data_y, *rdiag_y;   // [B][K] (the resolution kernel)
 };
 // posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; include/surfdisp.h section (6f)).  The descriptor's
 // integer part and the depths travel in the kernel arguments: the entry has checked them on the host.

@@ -3,7 +3,8 @@
 An iterated, damped, smoothed least-squares fit (Gauss-Newton with Levenberg-Marquardt damping, as in the surf96 family) of
 the Vs of the FREE layers of every stack of a batch, fed by the analytic sensitivity kernels of the library (dc/dm, dU/dm,
 dchi/dm for Rayleigh, dc/dm, dU/dm for Love) and solved on the device, one workgroup per stack
-(``surfdisp_lsq_step_device``, csrc/surfdisp_lsq.hip).  Fundamental mode, fixed thicknesses.
+(``surfdisp_lsq_step_device``, csrc/surfdisp_lsq.hip).  Fundamental mode; the thicknesses are fixed unless THICKNESS MODES are
+given (below).
 
 One step, per stack, with x the Vs of the n free layers and x0 the current model:
 
@@ -17,6 +18,14 @@ stack.  ``lsq_step_reference`` states the step in numpy float64; the kernel is t
 What the result is reported with (``surfdisp_lsq_resolution_device``, the same file): with H = G^T W G and A the matrix above, the
 posterior covariance C = A^-1, the resolution matrix R = C H, the layers' standard errors sqrt(C_jj) and their data share
 sqrt((C H C)_jj), dof = trace R and log det A.  ``lsq_resolution_reference`` states them in numpy float64.
+
+Thickness modes (``surfdisp_lsq_step_modes_device`` / ``surfdisp_lsq_resolution_modes_device``, include/surfdisp.h section (6h)):
+K <= 8 more unknowns per stack behind the Vs - mode k has a shape T_k [L] and an amplitude y_k in km, the thickness of layer i
+changes by sum_k T_k[i] y_k (``thickness_mode``: a layer group thickens, everything below shifts; ``interface_mode``: the
+interface between two groups moves, the total depth stays).  Its column is G[r, n + k] = sum_i dcdh[r, i] T_k[i] from the
+thickness kernels of the phase velocity (``BatchPlan.run_thickness_kernels``), its damping lam mode_scale_k, its prior
+mode_prior_k (y_k + delta_k)^2.  Phase-velocity data only: the library has no dU/dh or dchi/dh yet.
+``lsq_modes_step_reference`` and ``lsq_modes_resolution_reference`` state the two entries in numpy float64.
 
 * ``LsqPlan``: the kernels + step (``step``) or covariance and resolution (``resolution``) of one batch as device tensors.
 * ``LinearizedBatch``: the iteration - kernels and step at x, ONE forward solve of the trials, accept where the objective
@@ -32,6 +41,8 @@ from . import _lib
 from .obsdata import JointData
 
 MAX_FREE = 128          # unknowns per stack the step and resolution kernels take (SD_LSQ_MAX_FREE)
+MAX_MODES = 8           # thickness modes per stack behind them (SD_LSQ_MAX_MODES)
+MODES_NEED_PHASE = "thickness modes need phase-velocity data only: the library has no dU/dh or dchi/dh yet"
 FAIL = 88888.0          # the misfit of a failed solve (point.py:20-21)
 
 # d(Vp, rho) / dVs of the layer groups of senskernel.GROUP_RULES (sensModel._convert)
@@ -150,6 +161,178 @@ def lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam):
     return out
 
 
+def _group(name, h, layers):
+    """The layer indices of one group of a mode shape, checked: not empty, inside the stack, without the last layer (the half
+    space has no thickness), of positive total thickness."""
+    idx = np.unique(np.asarray(layers, np.int64).ravel())
+    if idx.size == 0:
+        raise ValueError(f"{name}: an empty layer group")
+    if idx[0] < 0 or idx[-1] >= h.size - 1:
+        raise ValueError(f"{name}: layers {idx.tolist()} - a group lies in 0..{h.size - 2}, the last layer has no thickness")
+    tot = float(h[idx].sum())
+    if not (np.isfinite(tot) and tot > 0.0):
+        raise ValueError(f"{name}: group thickness {tot}, a positive value expected")
+    return idx, tot
+
+
+def thickness_mode(h, layers):
+    """Shape T [L] float64 of the mode "the group ``layers`` thickens by y km, everything below shifts rigidly": T[i] =
+    h_i / sum(h[layers]) on the group, 0 elsewhere (the layers of the group keep their proportions; sum of T over the group 1).
+    ``h`` [L]: the thicknesses of the stack, the last layer being the half space.  ValueError for an empty group, a group
+    thickness that is not positive, a group that contains the last layer."""
+    h = np.asarray(h, np.float64).ravel()
+    idx, tot = _group("thickness_mode", h, layers)
+    T = np.zeros(h.size)
+    T[idx] = h[idx] / tot
+    return T
+
+
+def interface_mode(h, above, below):
+    """Shape T [L] float64 of the mode "the interface between the groups ``above`` and ``below`` moves down by y km": +h_i /
+    sum(h[above]) on ``above``, -h_i / sum(h[below]) on ``below`` - the upper group thickens by y, the lower one thins by y, the
+    total depth does not change (a Moho, a sediment base, a sea floor).  ValueError as ``thickness_mode``, and for groups that
+    share a layer."""
+    h = np.asarray(h, np.float64).ravel()
+    ia, ta = _group("interface_mode (above)", h, above)
+    ib, tb = _group("interface_mode (below)", h, below)
+    if np.intersect1d(ia, ib).size:
+        raise ValueError("interface_mode: the two groups share a layer")
+    T = np.zeros(h.size)
+    T[ia] = h[ia] / ta
+    T[ib] = -h[ib] / tb
+    return T
+
+
+def mode_columns(kh, T, nlay=None):
+    """Gy [N, K] float64: the mode columns of N data rows - ``kh`` [N, L] their thickness kernels dcdh (float32 as the library
+    returns them), ``T`` [K, L] the shapes; only the layers i < nlay - 1 are read (nlay None: L)."""
+    kh = np.atleast_2d(np.asarray(kh)).astype(np.float64)
+    T = np.atleast_2d(np.asarray(T, np.float64))
+    m = max((kh.shape[1] if nlay is None else int(nlay)) - 1, 0)
+    return kh[:, :m] @ T[:, :m].T
+
+
+def _nmodes(Gy):
+    """K of a mode-column argument: None -> 0, else the second dimension of the [N, K] array."""
+    if Gy is None:
+        return 0
+    if np.ndim(Gy) != 2:
+        raise ValueError("Gy: a [N, K] array expected")
+    return np.shape(Gy)[1]
+
+
+def _mode_vectors(K, mode_scale, mode_prior, mode_y):
+    ms = np.ones(K) if mode_scale is None else np.broadcast_to(np.asarray(mode_scale, np.float64), (K,)).copy()
+    beta = np.zeros(K) if mode_prior is None else np.broadcast_to(np.asarray(mode_prior, np.float64), (K,)).copy()
+    y = np.zeros(K) if mode_y is None else np.broadcast_to(np.asarray(mode_y, np.float64), (K,)).copy()
+    return ms, beta, y
+
+
+def modes_normal_equations(G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale=None, mode_prior=None, mode_y=None):
+    """(A, g) of the step with K thickness modes behind the n Vs unknowns, numpy float64: ``normal_equations`` of [G | Gy] with
+    D acting on the Vs unknowns only, lam ms_k + beta_k on the diagonal of mode k and -beta_k y_k on its right-hand side."""
+    x0 = np.asarray(x0, np.float64).ravel()
+    n = x0.size
+    Gy = np.asarray(Gy, np.float64)
+    K = Gy.shape[1]
+    ms, beta, y = _mode_vectors(K, mode_scale, mode_prior, mode_y)
+    Ga = np.concatenate([np.asarray(G, np.float64).reshape(-1, n), Gy.reshape(-1, K)], axis=1)
+    r = np.asarray(r, np.float64).ravel()
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    Av, gv = normal_equations(np.zeros((0, n)), np.zeros(0), np.zeros(0), x0, alpha, Q, lam)     # the regularisation alone
+    A = Ga.T @ (w[:, None] * Ga)
+    g = Ga.T @ (w * r)
+    A[:n, :n] += Av
+    g[:n] += gv
+    A[n:, n:] += np.diag(float(lam) * ms + beta)
+    g[n:] -= beta * y
+    return A, g
+
+
+def lsq_modes_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam, Gy=None, mode_scale=None, mode_prior=None, mode_y=None):
+    """``lsq_step_reference`` with K thickness modes - the statement ``surfdisp_lsq_step_modes_device`` is tested against.  ``Gy``
+    [N, K]: the mode columns of the used rows (``mode_columns``; None or K = 0: the result of ``lsq_step_reference`` with an
+    empty delta_y); mode_scale, mode_prior, mode_y: scalars or [K] (None: 1, 0, 0).  Returns dict(delta [n], delta_y [K], misfit,
+    roughness, predicted = sum W (r - G delta - Gy delta_y)^2 + alpha roughness(x0 + delta) + sum beta (y + delta_y)^2, flag);
+    with a flag the deltas are zeros and predicted = misfit + alpha roughness + sum beta y^2."""
+    K = _nmodes(Gy)
+    if K == 0:
+        out = lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam)
+        out["delta_y"] = np.zeros(0)
+        return out
+    x0 = np.asarray(x0, np.float64).ravel()
+    n = x0.size
+    G = np.asarray(G, np.float64).reshape(-1, n)
+    Gy = np.asarray(Gy, np.float64).reshape(-1, K)
+    r = np.asarray(r, np.float64).ravel()
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    Qv = np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]
+    ms, beta, y = _mode_vectors(K, mode_scale, mode_prior, mode_y)
+    rough = lambda x: float((Qv * np.diff(x) ** 2).sum())
+    prior = lambda v: float((beta * v * v).sum())
+    misfit = float((w * r * r).sum())
+    out = dict(delta=np.zeros(n), delta_y=np.zeros(K), misfit=misfit, roughness=rough(x0),
+               predicted=misfit + float(alpha) * rough(x0) + prior(y), flag=0)
+    if G.shape[0] == 0:
+        out["flag"] = 1
+        return out
+    A, g = modes_normal_equations(G, Gy, r, w, x0, alpha, Qv, lam, ms, beta, y)
+    try:
+        if not np.isfinite(A).all():
+            raise np.linalg.LinAlgError
+        Lc = np.linalg.cholesky(A)
+    except np.linalg.LinAlgError:
+        out["flag"] = 2
+        return out
+    d = np.linalg.solve(Lc.T, np.linalg.solve(Lc, g))
+    t = r - G @ d[:n] - Gy @ d[n:]
+    out["delta"], out["delta_y"] = d[:n], d[n:]
+    out["predicted"] = float((w * t * t).sum()) + float(alpha) * rough(x0 + d[:n]) + prior(y + d[n:])
+    return out
+
+
+def lsq_modes_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam, Gy=None, mode_scale=None, mode_prior=None):
+    """``lsq_resolution_reference`` with K thickness modes - the statement ``surfdisp_lsq_resolution_modes_device`` is tested
+    against (``Gy``, mode_scale, mode_prior as ``lsq_modes_step_reference``; None or K = 0: the result of
+    ``lsq_resolution_reference``).  Every array is over the n + K unknowns, the modes last: cov, res [n + K, n + K], sigma_post,
+    sigma_data, rdiag [n + K], dof, logdet, flag."""
+    K = _nmodes(Gy)
+    if K == 0:
+        return lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam)
+    n = int(x0_or_n) if np.ndim(x0_or_n) == 0 else np.size(x0_or_n)
+    nu = n + K
+    G = np.asarray(G, np.float64).reshape(-1, n)
+    Gy = np.asarray(Gy, np.float64).reshape(-1, K)
+    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    z = np.zeros(nu)
+    out = dict(cov=np.zeros((nu, nu)), res=np.zeros((nu, nu)), sigma_post=z.copy(), sigma_data=z.copy(), rdiag=z.copy(), dof=0.0,
+               logdet=0.0, flag=0)
+    if G.shape[0] == 0:
+        out["flag"] = 1
+        return out
+    A, _ = modes_normal_equations(G, Gy, np.zeros(G.shape[0]), w, np.zeros(n), alpha, np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)],
+                                  lam, mode_scale, mode_prior, None)
+    Ga = np.concatenate([G, Gy], axis=1)
+    H = Ga.T @ (w[:, None] * Ga)
+    try:
+        if not np.isfinite(A).all():
+            raise np.linalg.LinAlgError
+        Lc = np.linalg.cholesky(A)
+        T = np.linalg.solve(Lc, np.eye(nu))
+        cov = T.T @ T
+        cov = 0.5 * (cov + cov.T)
+        res = cov @ H
+        cd = np.einsum("ij,ji->i", res, cov)
+        if not (np.isfinite(cov).all() and np.isfinite(res).all() and np.isfinite(cd).all()):
+            raise np.linalg.LinAlgError
+    except np.linalg.LinAlgError:
+        out["flag"] = 2
+        return out
+    out.update(cov=cov, res=res, sigma_post=np.sqrt(np.diag(cov)), sigma_data=np.sqrt(np.maximum(cd, 0.0)), rdiag=np.diag(res).copy(),
+               dof=float(np.trace(res)), logdet=float(2.0 * np.log(np.diag(Lc)).sum()))
+    return out
+
+
 def _per_layer(name, v, M, L, cols=None):
     """A scalar, [cols] or [M, cols] argument as float64 (cols = L unless given); ValueError otherwise."""
     cols = L if cols is None else cols
@@ -203,14 +386,33 @@ class LsqPlan:
         self.info = torch.zeros(self.B, 3, dtype=torch.int32, device=dev)
         self._sets = {w: {d.quantity for d in jd.datasets if d.wave == w} for w in jd.waves}
 
-    def kernels(self, model, nlay=None, want_vp=True, want_rho=True):
+    def check_modes(self):
+        """ValueError when the data hold a group-velocity or ellipticity set: thickness modes need dcdh of every row."""
+        if any(q - {"c"} for q in self._sets.values()):
+            raise ValueError(MODES_NEED_PHASE)
+
+    def kernels(self, model, nlay=None, want_vp=True, want_rho=True, thickness=False):
         """The kernel entries the data need, once per wave type: U data -> ``run_group_kernels``, an "E" set ->
         ``run_ellip_kernels``, both -> both calls (``senskernel.analytic_kernels``), otherwise ``run_kernels``.  Returns (pred,
         part): the forward dict of ``JointData.predictions`` (the plans' own output tensors) and the 15 partial arrays
-        [source 0..4][Vs, Vp, rho] (None where absent).  No host synchronisation."""
+        [source 0..4][Vs, Vp, rho] (None where absent).  ``thickness`` (phase-velocity data only): ``run_thickness_kernels``
+        in place of ``run_kernels`` - the same bits plus dcdh - and a third result, the five thickness arrays [source 0..4]
+        (cR and cL; None elsewhere).  No host synchronisation."""
         jd = self.joint
         pred = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
         part = [None] * 15
+        if thickness:
+            self.check_modes()
+            part_h = [None] * 5
+            for w in jd.waves:
+                kind = _lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE
+                o = 0 if w == "R" else 6
+                c, u, st, kb, ka, kr, kh, _, _ = self.plans[w].run_thickness_kernels(
+                    model, jd.periods_t[w], kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho, want_dcdz=False, count=False)
+                part[o:o + 3] = [kb, ka, kr]
+                part_h[o // 3] = kh
+                pred["c" + w], pred["status" + w] = c, st
+            return pred, part, part_h
         for w in jd.waves:
             plan, per = self.plans[w], jd.periods_t[w]
             kind = _lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE
@@ -236,11 +438,37 @@ class LsqPlan:
             pred["c" + w], pred["status" + w] = c, st
         return pred, part
 
-    def _step_args(self, model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q):
+    def _mode_args(self, modes, mode_scale, mode_prior, mode_y):
+        """The checks of the thickness-mode arguments of ``step`` / ``resolution``.  Returns (K, per_stack, modes, mode_scale,
+        mode_prior, mode_y) with mode_scale filled with ones when None."""
+        torch = self.torch
+        B, L, dev = self.B, self.L, self.device
+        self.check_modes()
+        ok = lambda t: t.dtype == torch.float64 and t.device == dev and t.is_contiguous()
+        if not ok(modes) or modes.ndim not in (2, 3) or modes.shape[-1] != L or (modes.ndim == 3 and modes.shape[0] != B) \
+                or not 1 <= modes.shape[-2] <= MAX_MODES:
+            raise ValueError(f"modes: expected contiguous float64 (K, {L}) or ({B}, K, {L}) on {dev} with 1 <= K <= {MAX_MODES}, got "
+                             f"{modes.dtype} {tuple(modes.shape)}")
+        K, per_stack = int(modes.shape[-2]), modes.ndim == 3
+        want = (B, K) if per_stack else (K,)
+        if mode_scale is None:
+            if getattr(self, "_ones", None) is None or tuple(self._ones.shape) != want:
+                self._ones = torch.ones(want, dtype=torch.float64, device=dev)
+            mode_scale = self._ones
+        for name, t, shape in (("mode_scale", mode_scale, want), ("mode_prior", mode_prior, want), ("mode_y", mode_y, (B, K))):
+            if t is not None and (not ok(t) or tuple(t.shape) != shape):
+                raise ValueError(f"{name}: expected contiguous float64 {shape} on {dev}, got {t.dtype} {tuple(t.shape)}")
+        return K, per_stack, modes, mode_scale, mode_prior, mode_y
+
+    def _step_args(self, model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes=None, mode_scale=None,
+                   mode_prior=None, mode_y=None):
         """The argument checks of ``step`` / ``resolution``, one call of ``kernels``, and the entries' shared argument list (up to
-        and including lam).  Returns (args, pred, part); args keeps its ctypes arrays alive."""
+        and including lam).  Returns (args, pred, part, mode) - mode None without ``modes``, else (K, part_h, the mode entries'
+        input arguments behind lam); args and mode keep their ctypes arrays alive."""
         torch = self.torch
         B, L = self.B, self.L
+        if modes is not None:
+            K, m_ps, modes, mode_scale, mode_prior, mode_y = self._mode_args(modes, mode_scale, mode_prior, mode_y)
         nmax = L if nfree_max is None else int(nfree_max)
         if not 1 <= nmax <= min(MAX_FREE, L):
             raise ValueError(f"nfree_max = {nmax}: the step kernel takes 1..{min(MAX_FREE, L)} free layers per stack (give nfree_max "
@@ -262,7 +490,13 @@ class LsqPlan:
         q_ps = chk("Q", Q, torch.float64, L - 1) if L > 1 else 0
         if lam.dtype != torch.float64 or tuple(lam.shape) != (B,) or lam.device != self.device or not lam.is_contiguous():
             raise ValueError(f"lam: expected contiguous float64 ({B},) on {self.device}")
-        pred, part = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None)
+        mode = None
+        if modes is None:
+            pred, part = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None)
+        else:
+            pred, part, part_h = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None, thickness=True)
+            parthp = (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in part_h])
+            mode = (K, part_h, (K, _ptr(modes), 1 if m_ps else 0, parthp, _ptr(mode_scale), _ptr(mode_prior), _ptr(mode_y)))
         jd = self.joint
         arrs = [pred["cR"], pred["uR"], pred["cL"], pred["uL"], pred["eR"]]
         predp = (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in arrs])
@@ -273,23 +507,38 @@ class LsqPlan:
         head = (stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, partp, predp, strides, nper,
                 jd.Ptot, _ptr(jd.cols), _ptr(jd.weights), _ptr(self.obs), _ptr(self.uncer), _ptr(self.mask8),
                 1 if self.obs.ndim == 2 else 0, _ptr(vp_slope), _ptr(rho_slope), sl_ps, float(alpha), _ptr(Q), q_ps, _ptr(lam))
-        return head, pred, part
+        return head, pred, part, mode
 
-    def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None):
+    def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None,
+             modes=None, mode_scale=None, mode_prior=None, mode_y=None):
         """Kernels at ``model`` (float32 [B, 5, L]) and one least-squares step.  Device tensors: ``lam`` float64 [B]; ``nlay``
         int32 [B]; ``free`` uint8 [L] or [B, L] (None: every layer); ``vp_slope`` / ``rho_slope`` float64 [L] or [B, L] (None:
         held fixed, the Vp / rho partials are not computed); ``Q`` float64 [L-1] or [B, L-1] (None: 1).  ``nfree_max``: an
         upper bound of the free layers of any stack (default L; at most 128).  Returns dict(delta [B, L] float64, misfit,
         roughness, predicted [B] float64, used, dropped, flag [B] int32, pred, part) - views of the plan's buffers, rewritten by
-        the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max."""
-        head, pred, part = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q)
+        the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max.
+        Thickness modes (``surfdisp_lsq_step_modes_device``; phase-velocity data only, ValueError otherwise): ``modes`` float64
+        [K, L] or [B, K, L], ``mode_scale`` and ``mode_prior`` float64 [K] ([B, K] with per-stack modes; None: 1 and 0),
+        ``mode_y`` float64 [B, K] (None: 0); the result then holds delta_y [B, K] float64 and part_h, the five thickness
+        arrays, as well."""
+        head, pred, part, mode = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale,
+                                                 mode_prior, mode_y)
+        out = dict(delta=self.delta, misfit=self.stats[:, 0], roughness=self.stats[:, 1], predicted=self.stats[:, 2],
+                   used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=pred, part=part)
         with self.torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_lsq_step_device(*head, _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
-        return dict(delta=self.delta, misfit=self.stats[:, 0], roughness=self.stats[:, 1], predicted=self.stats[:, 2],
-                    used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=pred, part=part)
+            if mode is None:
+                _lib.check(_lib.lib().surfdisp_lsq_step_device(*head, _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
+            else:
+                K, part_h, margs = mode
+                if getattr(self, "delta_y", None) is None or self.delta_y.shape[1] != K:
+                    self.delta_y = self.torch.zeros(self.B, K, dtype=self.torch.float64, device=self.device)
+                _lib.check(_lib.lib().surfdisp_lsq_step_modes_device(*head, *margs, _ptr(self.delta), _ptr(self.delta_y),
+                                                                     _ptr(self.stats), _ptr(self.info)))
+                out.update(delta_y=self.delta_y, part_h=part_h)
+        return out
 
     def resolution(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None,
-                   want_cov=True, want_res=True):
+                   want_cov=True, want_res=True, modes=None, mode_scale=None, mode_prior=None, mode_y=None):
         """Kernels at ``model`` and the posterior covariance and resolution of the step's problem there
         (``surfdisp_lsq_resolution_device``; arguments as ``step``): with H = G^T W G and A = H + alpha D^T Q D + lam I, cov = A^-1,
         res = cov H.  One ``kernels`` call, one launch, no host synchronisation.  Returns dict(cov, res [B, nmax, nmax] float64 in
@@ -297,22 +546,35 @@ class LsqPlan:
         sqrt(diag(cov H cov)), rdiag = diag res [B, L] float64 (0 at layers that are not free), dof = trace res, logdet = log det A
         [B] float64, used, dropped, flag [B] int32 (flags as ``step``; every output of a stack with a flag is zeros), free_index
         [B, nmax] int64 (layer of unknown j, -1 as padding), nfree [B] int64, pred, part) - the plan's buffers, allocated at
-        the first call and rewritten by the next."""
+        the first call and rewritten by the next.
+        Thickness modes (``surfdisp_lsq_resolution_modes_device``; arguments as ``step``, ``mode_y`` is not read): cov and res are
+        [B, nmax + K, nmax + K], the K modes behind a stack's n Vs unknowns (zeros beyond n + K); dof and logdet are over all
+        unknowns; the result holds sigma_post_y, sigma_data_y, rdiag_y [B, K] float64 and part_h as well."""
         torch = self.torch
-        head, pred, part = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q)
+        head, pred, part, mode = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale,
+                                                 mode_prior, mode_y)
         B, L, nmax, dev = self.B, self.L, head[7], self.device
+        K = 0 if mode is None else mode[0]
+        z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
         if getattr(self, "_res", None) is None:
-            z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
             self._res = dict(sigma_post=z(B, L), sigma_data=z(B, L), rdiag=z(B, L), stats=z(B, 2), info=z(B, 3, dtype=torch.int32))
         buf = self._res
         for name, want in (("cov", want_cov), ("res", want_res)):
-            if want and (buf.get(name) is None or buf[name].shape[1] != nmax):
-                buf[name] = torch.zeros(B, nmax, nmax, dtype=torch.float64, device=dev)
+            if want and (buf.get(name) is None or buf[name].shape[1] != nmax + K):
+                buf[name] = z(B, nmax + K, nmax + K)
         cov, res = (buf[k] if w else None for k, w in (("cov", want_cov), ("res", want_res)))
+        outs = [_ptr(cov), _ptr(res), _ptr(buf["sigma_post"]), _ptr(buf["sigma_data"]), _ptr(buf["rdiag"])]
+        extra = {}
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().surfdisp_lsq_resolution_device(*head, _ptr(cov), _ptr(res), _ptr(buf["sigma_post"]),
-                                                                _ptr(buf["sigma_data"]), _ptr(buf["rdiag"]), _ptr(buf["stats"]),
-                                                                _ptr(buf["info"])))
+            if mode is None:
+                _lib.check(_lib.lib().surfdisp_lsq_resolution_device(*head, *outs, _ptr(buf["stats"]), _ptr(buf["info"])))
+            else:
+                if buf.get("rdiag_y") is None or buf["rdiag_y"].shape[1] != K:
+                    buf.update(sigma_post_y=z(B, K), sigma_data_y=z(B, K), rdiag_y=z(B, K))
+                extra = dict(sigma_post_y=buf["sigma_post_y"], sigma_data_y=buf["sigma_data_y"], rdiag_y=buf["rdiag_y"], part_h=mode[1])
+                _lib.check(_lib.lib().surfdisp_lsq_resolution_modes_device(
+                    *head, *mode[2], *outs, _ptr(buf["sigma_post_y"]), _ptr(buf["sigma_data_y"]), _ptr(buf["rdiag_y"]),
+                    _ptr(buf["stats"]), _ptr(buf["info"])))
         lay = torch.arange(L, device=dev)
         fr = torch.ones(B, L, dtype=torch.bool, device=dev) if free is None else (free != 0).expand(B, L)
         if nlay is not None:
@@ -320,7 +582,8 @@ class LsqPlan:
         order = torch.where(fr, lay[None, :], L).sort(dim=1).values[:, :nmax]
         return dict(cov=cov, res=res, sigma_post=buf["sigma_post"], sigma_data=buf["sigma_data"], rdiag=buf["rdiag"],
                     dof=buf["stats"][:, 0], logdet=buf["stats"][:, 1], used=buf["info"][:, 0], dropped=buf["info"][:, 1],
-                    flag=buf["info"][:, 2], free_index=torch.where(order < L, order, -1), nfree=fr.sum(dim=1), pred=pred, part=part)
+                    flag=buf["info"][:, 2], free_index=torch.where(order < L, order, -1), nfree=fr.sum(dim=1), pred=pred, part=part,
+                    **extra)
 
     def forward(self, model, nlay=None):
         """ONE forward solve per wave type of ``model`` (``BatchPlan.run``, with the ratio when an "E" set is present; kind
@@ -364,10 +627,18 @@ class LinearizedBatch:
     the trials; objective = chi-square + alpha roughness of the trial, by the misfit rule of ``obsdata`` (a failed solve is a
     rejected trial: its objective is inf); per stack, where the objective fell: accept, lam <- max(lam / nu, lam_min), else keep
     x and lam <- lam nu.  A rejected stack's kernels are computed again in the next iteration although x did not move (they
-    are not cached per stack): the batch stays one launch, and a rejected step is the rare case."""
+    are not cached per stack): the batch stays one launch, and a rejected step is the rare case.
+
+    Thickness modes (phase-velocity data only): ``modes`` [K, L] or [M, K, L], the shapes (``thickness_mode``,
+    ``interface_mode``; entries at layers >= nlay - 1 are set to 0); ``mode_scale`` (> 0) and ``mode_prior`` (>= 0): a scalar,
+    [K] or [M, K]; ``mode_bounds`` = (lo, hi), scalars or arrays that broadcast to [M, K], on the amplitude ``y`` [M, K]
+    accumulated since ``model0`` (km); ``h_min`` (km).  The trial then also has h <- float32(h + T (y_new - y)) with y_new =
+    clamp(y + delta_y), it is rejected (objective inf) when a layer with a non-zero shape entry would be thinner than ``h_min``,
+    and the objective is chi-square + alpha roughness + sum_k mode_prior_k y_k^2."""
 
     def __init__(self, model0, datasets, free=None, vp_slope=0.0, rho_slope=0.0, alpha=1.0, Q=None, lam0=1.0, nu=4.0,
-                 lam_min=1e-9, vs_bounds=None, nlay=None, mask=None, device="cuda:0"):
+                 lam_min=1e-9, vs_bounds=None, nlay=None, mask=None, device="cuda:0", modes=None, mode_scale=1.0, mode_prior=0.0,
+                 mode_bounds=None, h_min=1e-3):
         m0 = model0.detach().cpu().numpy() if hasattr(model0, "detach") else np.asarray(model0)
         if m0.ndim != 3 or m0.shape[1] != 5:
             raise ValueError("model0 must be [M, 5, L]")
@@ -408,6 +679,35 @@ class LinearizedBatch:
             ia[m, :w.size], ib[m, :w.size], qw[m, :w.size] = idx[:-1], idx[1:], w
         if vs_bounds is not None:
             lo, hi = (np.broadcast_to(np.asarray(b, np.float64), (M, L)) for b in vs_bounds)
+        if modes is not None:
+            T = np.array(modes, np.float64)
+            if T.ndim not in (2, 3) or T.shape[-1] != L or (T.ndim == 3 and T.shape[0] != M) or not 1 <= T.shape[-2] <= MAX_MODES:
+                raise ValueError(f"modes: shape {T.shape}, expected (K, {L}) or ({M}, K, {L}) with 1 <= K <= {MAX_MODES}")
+            K = T.shape[-2]
+            if T.ndim == 2 and nlay is not None:
+                T = np.broadcast_to(T, (M, K, L)).copy()
+            if T.ndim == 3:
+                T[~np.broadcast_to((np.arange(L)[None, :] < nl[:, None] - 1)[:, None, :], T.shape)] = 0.0
+            else:
+                T[:, L - 1] = 0.0
+            if not np.isfinite(T).all():
+                raise ValueError("modes: entries that are not finite")
+            shape = (M, K) if T.ndim == 3 else (K,)
+
+            def per_mode(name, v):
+                a = np.asarray(v, np.float64)
+                if a.ndim > len(shape) or (a.ndim and a.shape[-1] != K) or (a.ndim == 2 and a.shape[0] != M):
+                    raise ValueError(f"{name}: shape {a.shape}, expected a scalar, ({K},) or ({M}, {K}) (per stack only with per-stack modes)")
+                return np.array(np.broadcast_to(a, shape))
+            m_scale, m_prior = per_mode("mode_scale", mode_scale), per_mode("mode_prior", mode_prior)
+            if not ((m_scale > 0).all() and np.isfinite(m_scale).all() and (m_prior >= 0).all() and np.isfinite(m_prior).all()):
+                raise ValueError("mode_scale > 0 and mode_prior >= 0, finite, expected")
+            if mode_bounds is not None:
+                ylo, yhi = (np.array(np.broadcast_to(np.asarray(b, np.float64), (M, K))) for b in mode_bounds)
+            if not (np.isfinite(h_min) and h_min >= 0):
+                raise ValueError("h_min must be finite and >= 0")
+            if any(d.quantity != "c" for d in JointData(datasets, device="cpu").datasets):
+                raise ValueError(MODES_NEED_PHASE)
         self.plan = plan = LsqPlan(M, L, datasets, device=device, mask=mask)      # (data errors: ValueError; no HIP device: SurfdispError)
         import torch
         self.torch = torch
@@ -424,6 +724,13 @@ class LinearizedBatch:
         self._ia, self._ib, self._qw = t(ia), t(ib), t(qw)
         self.bounds = None if vs_bounds is None else (t(lo), t(hi))
         self.lam = torch.full((M,), float(lam0), dtype=torch.float64, device=dev)
+        self.modes = None
+        if modes is not None:
+            self.modes, self.mode_scale, self.mode_prior = t(T), t(m_scale), t(m_prior)
+            self._touched = t((T != 0).any(axis=-2))                       # [L] or [M, L]: layers a mode moves
+            self.mode_bounds = None if mode_bounds is None else (t(ylo), t(yhi))
+            self.h_min = float(h_min)
+            self.y = torch.zeros(M, K, dtype=torch.float64, device=dev)
         chi, rms, failed = plan.chi_square(self.model, self.nlay)
         self.objective = torch.where(failed, torch.full_like(chi, float("inf")), chi + self.alpha * self.roughness(self.model))
         self.rms = rms
@@ -452,31 +759,62 @@ class LinearizedBatch:
             out[:, 2, :] = (model[:, 2, :].to(torch.float64) + self.rho_slope * dv).to(torch.float32)
         return out
 
+    def _mode_kw(self):
+        """The thickness-mode arguments of ``LsqPlan.step`` / ``resolution`` at the current state ({} without modes)."""
+        if self.modes is None:
+            return {}
+        return dict(modes=self.modes, mode_scale=self.mode_scale, mode_prior=self.mode_prior, mode_y=self.y)
+
+    def move_modes(self, model, delta_y):
+        """(h [M, L] float32, y_new [M, K], thin [M] bool) of the mode step ``delta_y`` from the current ``y``: y_new = y + delta_y
+        clamped into ``mode_bounds``, h = float32(h + sum_k T_k (y_new - y)_k) (the sum taken mode by mode, in float64), thin:
+        a layer that a mode moves would be thinner than ``h_min``."""
+        torch = self.torch
+        y_new = self.y + delta_y
+        if self.mode_bounds is not None:
+            y_new = torch.minimum(torch.maximum(y_new, self.mode_bounds[0]), self.mode_bounds[1])
+        dy = y_new - self.y
+        T = self.modes if self.modes.ndim == 3 else self.modes[None]
+        upd = T[:, 0, :] * dy[:, 0, None]
+        for k in range(1, T.shape[1]):
+            upd = upd + T[:, k, :] * dy[:, k, None]
+        h = (model[:, 3, :].to(torch.float64) + upd).to(torch.float32)
+        thin = (self._touched & (h.to(torch.float64) < self.h_min)).any(dim=-1)
+        return h, y_new, thin
+
     def run(self, n_iter, keep_models=False):
         """``n_iter`` iterations from the current state (a second call goes on).  Returns dict(model [M, 5, L] the final models;
         per iteration, [n_iter, M]: objective and rms (the data rms misfit sqrt(chi2 / N) of ``obsdata``; 88888 for a model
         whose solve fails) of the state AFTER the iteration, lam after its update, accepted (bool), flag, used, dropped (of the
-        step), predicted (the step's linear prediction of the objective); models [n_iter, M, 5, L] with ``keep_models``)."""
+        step), predicted (the step's linear prediction of the objective); models [n_iter, M, 5, L] with ``keep_models``).  With
+        thickness modes also y [n_iter, M, K], the amplitudes after each iteration (``self.y`` holds the current ones)."""
         torch = self.torch
         plan = self.plan
-        keys = ("objective", "rms", "lam", "accepted", "flag", "used", "dropped", "predicted")
+        with_modes = self.modes is not None
+        keys = ("objective", "rms", "lam", "accepted", "flag", "used", "dropped", "predicted") + (("y",) if with_modes else ())
         hist = {k: [] for k in keys}
         models = []
         inf = torch.full((self.M,), float("inf"), dtype=torch.float64, device=self.device)
         for _ in range(int(n_iter)):
             st = plan.step(self.model, self.lam, nlay=self.nlay, free=self.free8, nfree_max=self.nfree_max,
                            vp_slope=self.vp_slope if self.has_vp else None, rho_slope=self.rho_slope if self.has_rho else None,
-                           alpha=self.alpha, Q=self.Q)
+                           alpha=self.alpha, Q=self.Q, **self._mode_kw())
             flag, used, dropped, predicted = (st[k].clone() for k in ("flag", "used", "dropped", "predicted"))
             tr = self.trial(self.model, st["delta"])
+            if with_modes:
+                tr[:, 3, :], y_new, thin = self.move_modes(self.model, st["delta_y"])
             chi, rms, failed = plan.chi_square(tr, self.nlay)
             obj = torch.where(failed, inf, chi + self.alpha * self.roughness(tr))
+            if with_modes:
+                obj = torch.where(thin, inf, obj + (self.mode_prior * y_new * y_new).sum(dim=1))
             acc = obj < self.objective
             self.model = torch.where(acc[:, None, None], tr, self.model)
             self.objective = torch.where(acc, obj, self.objective)
             self.rms = torch.where(acc, rms, self.rms)
             self.lam = torch.where(acc, torch.clamp(self.lam / self.nu, min=self.lam_min), self.lam * self.nu)
-            for k, v in zip(keys, (self.objective, self.rms, self.lam, acc, flag, used, dropped, predicted)):
+            if with_modes:
+                self.y = torch.where(acc[:, None], y_new, self.y)
+            for k, v in zip(keys, (self.objective, self.rms, self.lam, acc, flag, used, dropped, predicted) + ((self.y,) if with_modes else ())):
                 hist[k].append(v)
             if keep_models:
                 models.append(self.model)
@@ -504,4 +842,4 @@ class LinearizedBatch:
         return self.plan.resolution(self.model, lam_t, nlay=self.nlay, free=self.free8, nfree_max=self.nfree_max,
                                     vp_slope=self.vp_slope if self.has_vp else None,
                                     rho_slope=self.rho_slope if self.has_rho else None, alpha=self.alpha, Q=self.Q,
-                                    want_cov=want_cov, want_res=want_res)
+                                    want_cov=want_cov, want_res=want_res, **self._mode_kw())
