@@ -13,11 +13,11 @@ One step, per stack, with x the Vs of the n free layers and x0 the current model
     (G^T W G + alpha D^T Q D + lam I) delta = G^T W res - alpha D^T Q D x0
 
 D is the first difference between consecutive free layers, Q its weights (``consecutive_weights``), lam the damping of the
-stack.  ``lsq_step_reference`` states the step in numpy float64; the kernel is tested against it.
+stack.
 
 What the result is reported with (``surfdisp_lsq_resolution_device``, the same file): with H = G^T W G and A the matrix above, the
 posterior covariance C = A^-1, the resolution matrix R = C H, the layers' standard errors sqrt(C_jj) and their data share
-sqrt((C H C)_jj), dof = trace R and log det A.  ``lsq_resolution_reference`` states them in numpy float64.
+sqrt((C H C)_jj), dof = trace R and log det A.
 
 Thickness modes (``surfdisp_lsq_step_modes_device`` / ``surfdisp_lsq_resolution_modes_device``, include/surfdisp.h section (6h)):
 K <= 8 more unknowns per stack behind the Vs - mode k has a shape T_k [L] and an amplitude y_k in km, the thickness of layer i
@@ -25,7 +25,13 @@ changes by sum_k T_k[i] y_k (``thickness_mode``: a layer group thickens, everyth
 interface between two groups moves, the total depth stays).  Its column is G[r, n + k] = sum_i dcdh[r, i] T_k[i] from the
 thickness kernels of the phase velocity (``BatchPlan.run_thickness_kernels``), its damping lam mode_scale_k, its prior
 mode_prior_k (y_k + delta_k)^2.  Phase-velocity data only: the library has no dU/dh or dchi/dh yet.
-``lsq_modes_step_reference`` and ``lsq_modes_resolution_reference`` state the two entries in numpy float64.
+
+The kernels are tested against ONE numpy float64 statement, ``_System``: (H, A, g) of n Vs unknowns followed by K >= 0 modes, K = 0
+being the problem without modes.  ``lsq_modes_step_reference`` and ``lsq_modes_resolution_reference`` are the step and the resolution
+read from it, with one solve block (A finite, Cholesky, flag 2 on failure, zeros on a flag); ``normal_equations``,
+``modes_normal_equations``, ``lsq_step_reference`` and ``lsq_resolution_reference`` are calls of those.  The same holds on the device
+side of the module: the rules of the mode arguments are ``_mode_count`` and ``_phase_only`` for ``LinearizedBatch`` and ``LsqPlan``
+alike, and a call of ``LsqPlan.step`` or ``resolution``, with or without modes, is one ``_Launch``.
 
 * ``LsqPlan``: the kernels + step (``step``) or covariance and resolution (``resolution``) of one batch as device tensors.
 * ``LinearizedBatch``: the iteration - kernels and step at x, ONE forward solve of the trials, accept where the objective
@@ -34,6 +40,7 @@ mode_prior_k (y_k + delta_k)^2.  Phase-velocity data only: the library has no dU
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 
@@ -66,99 +73,6 @@ def consecutive_weights(free, Q=None):
     Q = np.ones(max(len(free) - 1, 0)) if Q is None else np.asarray(Q, np.float64)
     w = np.array([Q[a:b].min() for a, b in zip(idx[:-1], idx[1:])], np.float64)
     return idx, w
-
-
-def normal_equations(G, r, w_over_sigma2, x0, alpha, Q, lam):
-    """(A, g) of the step, numpy float64: A = G^T W G + alpha D^T Q D + lam I, g = G^T W r - alpha D^T Q D x0.  G [N, n], r and
-    w_over_sigma2 [N], x0 [n], Q [n-1] (weights of the differences of consecutive unknowns)."""
-    G = np.asarray(G, np.float64).reshape(-1, np.size(x0))
-    r = np.asarray(r, np.float64).ravel()
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
-    x0 = np.asarray(x0, np.float64).ravel()
-    n = x0.size
-    D = np.zeros((max(n - 1, 0), n))
-    for k in range(n - 1):
-        D[k, k], D[k, k + 1] = -1.0, 1.0
-    Qd = np.diag(np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]) if n > 1 else np.zeros((0, 0))
-    S = D.T @ Qd @ D
-    A = G.T @ (w[:, None] * G) + float(alpha) * S + float(lam) * np.eye(n)
-    g = G.T @ (w * r) - float(alpha) * (S @ x0)
-    return A, g
-
-
-def lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam):
-    """One damped least-squares step of one stack in numpy float64 - the statement ``surfdisp_lsq_step_device`` is tested
-    against.  G [N, n]: the effective Jacobian rows of the USED data rows, r [N] their residuals obs - pred, w_over_sigma2 [N],
-    x0 [n] the free layers' Vs, Q [n-1] the weights of the differences of consecutive free layers, alpha, lam scalars.
-    Returns dict(delta [n], misfit = sum W r^2, roughness = x0^T D^T Q D x0, predicted = sum W (r - G delta)^2 + alpha
-    roughness(x0 + delta), flag): flag 1 without rows, 2 when the Cholesky factorisation fails - then delta = 0 and
-    predicted = misfit + alpha roughness."""
-    x0 = np.asarray(x0, np.float64).ravel()
-    n = x0.size
-    G = np.asarray(G, np.float64).reshape(-1, n)
-    r = np.asarray(r, np.float64).ravel()
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
-    Qv = np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]
-    rough = lambda x: float((Qv * np.diff(x) ** 2).sum())
-    misfit = float((w * r * r).sum())
-    out = dict(delta=np.zeros(n), misfit=misfit, roughness=rough(x0), predicted=misfit + float(alpha) * rough(x0), flag=0)
-    if G.shape[0] == 0:
-        out["flag"] = 1
-        return out
-    A, g = normal_equations(G, r, w, x0, alpha, Qv, lam)
-    try:
-        if not np.isfinite(A).all():
-            raise np.linalg.LinAlgError
-        Lc = np.linalg.cholesky(A)
-    except np.linalg.LinAlgError:
-        out["flag"] = 2
-        return out
-    delta = np.linalg.solve(Lc.T, np.linalg.solve(Lc, g))
-    t = r - G @ delta
-    out["delta"] = delta
-    out["predicted"] = float((w * t * t).sum()) + float(alpha) * rough(x0 + delta)
-    return out
-
-
-def lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam):
-    """Posterior covariance and resolution of one stack's damped, smoothed problem in numpy float64 - the statement
-    ``surfdisp_lsq_resolution_device`` is tested against.  G [N, n] and w_over_sigma2 [N] as ``lsq_step_reference``; ``x0_or_n``:
-    the unknowns' vector or just their number n (the matrices do not depend on x0); Q [n-1], alpha, lam.  With H = G^T W G and
-    A = H + alpha D^T Q D + lam I (``normal_equations``):
-
-        cov = A^-1,   res = cov H,   sigma_post = sqrt(diag cov),   sigma_data = sqrt(diag(res cov)),   rdiag = diag res,
-        dof = trace res
-
-    Returns dict(cov, res [n, n], sigma_post, sigma_data, rdiag [n], dof, logdet = log det A, flag): flag 1 without rows, 2
-    when the Cholesky factorisation fails or A is not finite - then every array is zeros, dof and logdet 0."""
-    n = int(x0_or_n) if np.ndim(x0_or_n) == 0 else np.size(x0_or_n)
-    G = np.asarray(G, np.float64).reshape(-1, n)
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
-    z = np.zeros(n)
-    out = dict(cov=np.zeros((n, n)), res=np.zeros((n, n)), sigma_post=z.copy(), sigma_data=z.copy(), rdiag=z.copy(), dof=0.0,
-               logdet=0.0, flag=0)
-    if G.shape[0] == 0:
-        out["flag"] = 1
-        return out
-    A, _ = normal_equations(G, np.zeros(G.shape[0]), w, z, alpha, np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)], lam)
-    H = G.T @ (w[:, None] * G)
-    try:
-        if not np.isfinite(A).all():
-            raise np.linalg.LinAlgError
-        Lc = np.linalg.cholesky(A)
-        T = np.linalg.solve(Lc, np.eye(n))
-        cov = T.T @ T
-        cov = 0.5 * (cov + cov.T)
-        res = cov @ H
-        cd = np.einsum("ij,ji->i", res, cov)
-        if not (np.isfinite(cov).all() and np.isfinite(res).all() and np.isfinite(cd).all()):
-            raise np.linalg.LinAlgError
-    except np.linalg.LinAlgError:
-        out["flag"] = 2
-        return out
-    out.update(cov=cov, res=res, sigma_post=np.sqrt(np.diag(cov)), sigma_data=np.sqrt(np.maximum(cd, 0.0)), rdiag=np.diag(res).copy(),
-               dof=float(np.trace(res)), logdet=float(2.0 * np.log(np.diag(Lc)).sum()))
-    return out
 
 
 def _group(name, h, layers):
@@ -212,125 +126,147 @@ def mode_columns(kh, T, nlay=None):
     return kh[:, :m] @ T[:, :m].T
 
 
-def _nmodes(Gy):
-    """K of a mode-column argument: None -> 0, else the second dimension of the [N, K] array."""
-    if Gy is None:
-        return 0
-    if np.ndim(Gy) != 2:
-        raise ValueError("Gy: a [N, K] array expected")
-    return np.shape(Gy)[1]
+class _System:
+    """The numpy float64 statement of one stack's problem, read by every reference below: n Vs unknowns x0 followed by K >= 0
+    thickness modes (``Gy`` None or [N, 0]: K = 0, the plain case of the same lines).  With Ga = [G | Gy] and S = D^T Q D, D the
+    first difference of consecutive Vs unknowns:
 
+        H = Ga^T W Ga
+        A = H,        its Vs block (H + alpha S) + lam I,    its mode diagonal + lam ms_k + beta_k
+        g = Ga^T W r, its Vs part - alpha S x0,              its mode part - beta_k y_k
 
-def _mode_vectors(K, mode_scale, mode_prior, mode_y):
-    ms = np.ones(K) if mode_scale is None else np.broadcast_to(np.asarray(mode_scale, np.float64), (K,)).copy()
-    beta = np.zeros(K) if mode_prior is None else np.broadcast_to(np.asarray(mode_prior, np.float64), (K,)).copy()
-    y = np.zeros(K) if mode_y is None else np.broadcast_to(np.asarray(mode_y, np.float64), (K,)).copy()
-    return ms, beta, y
+    G [N, n], Gy [N, K], r (None: zeros) and w_over_sigma2 [N], x0 [n], Q [n-1]; mode_scale ms, mode_prior beta, mode_y y:
+    scalars or [K] (None: 1, 0, 0)."""
+
+    def __init__(self, G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale=None, mode_prior=None, mode_y=None):
+        self.x0 = x0 = np.asarray(x0, np.float64).ravel()
+        self.n = n = x0.size
+        self.G = G = np.asarray(G, np.float64).reshape(-1, n)
+        N = G.shape[0]
+        if Gy is not None and np.ndim(Gy) != 2:
+            raise ValueError("Gy: a [N, K] array expected")
+        self.K = K = 0 if Gy is None else np.shape(Gy)[1]
+        self.Gy = Gy = np.zeros((N, 0)) if Gy is None else np.asarray(Gy, np.float64).reshape(N, K)
+        self.r = r = np.zeros(N) if r is None else np.asarray(r, np.float64).ravel()
+        self.w = w = np.asarray(w_over_sigma2, np.float64).ravel()
+        self.alpha, lam = float(alpha), float(lam)
+        self.Q = np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]
+        vec = lambda v, default: np.full(K, default) if v is None else np.broadcast_to(np.asarray(v, np.float64), (K,)).copy()
+        ms, self.beta, self.y = vec(mode_scale, 1.0), vec(mode_prior, 0.0), vec(mode_y, 0.0)
+        D = np.zeros((max(n - 1, 0), n))
+        for k in range(n - 1):
+            D[k, k], D[k, k + 1] = -1.0, 1.0
+        S = D.T @ np.diag(self.Q) @ D
+        Ga = np.concatenate([G, Gy], axis=1) if K else G
+        self.H = Ga.T @ (w[:, None] * Ga)
+        self.A = self.H.copy()
+        self.A[:n, :n] = self.H[:n, :n] + self.alpha * S + lam * np.eye(n)
+        self.A[n:, n:] += np.diag(lam * ms + self.beta)
+        self.g = Ga.T @ (w * r)
+        self.g[:n] -= self.alpha * (S @ x0)
+        self.g[n:] -= self.beta * self.y
+
+    def objective(self, misfit, x, y):
+        """misfit + alpha roughness(x) + sum beta y^2."""
+        return misfit + self.alpha * self.roughness(x) + float((self.beta * y * y).sum())
+
+    def roughness(self, x):
+        return float((self.Q * np.diff(x) ** 2).sum())
+
+    def factor(self):
+        """(flag, Lc) - the solve block of every reference: flag 1 and None without rows, flag 2 and None when A is not finite
+        or its Cholesky factorisation fails, else 0 and the lower factor of A."""
+        if self.G.shape[0] == 0:
+            return 1, None
+        try:
+            if not np.isfinite(self.A).all():
+                raise np.linalg.LinAlgError
+            return 0, np.linalg.cholesky(self.A)
+        except np.linalg.LinAlgError:
+            return 2, None
 
 
 def modes_normal_equations(G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale=None, mode_prior=None, mode_y=None):
-    """(A, g) of the step with K thickness modes behind the n Vs unknowns, numpy float64: ``normal_equations`` of [G | Gy] with
-    D acting on the Vs unknowns only, lam ms_k + beta_k on the diagonal of mode k and -beta_k y_k on its right-hand side."""
-    x0 = np.asarray(x0, np.float64).ravel()
-    n = x0.size
-    Gy = np.asarray(Gy, np.float64)
-    K = Gy.shape[1]
-    ms, beta, y = _mode_vectors(K, mode_scale, mode_prior, mode_y)
-    Ga = np.concatenate([np.asarray(G, np.float64).reshape(-1, n), Gy.reshape(-1, K)], axis=1)
-    r = np.asarray(r, np.float64).ravel()
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
-    Av, gv = normal_equations(np.zeros((0, n)), np.zeros(0), np.zeros(0), x0, alpha, Q, lam)     # the regularisation alone
-    A = Ga.T @ (w[:, None] * Ga)
-    g = Ga.T @ (w * r)
-    A[:n, :n] += Av
-    g[:n] += gv
-    A[n:, n:] += np.diag(float(lam) * ms + beta)
-    g[n:] -= beta * y
-    return A, g
+    """(A, g) of the step with K >= 0 thickness modes behind the n Vs unknowns, numpy float64 (``_System``): A = [G | Gy]^T W [G | Gy]
+    with alpha D^T Q D + lam I on the Vs block - D acts on the Vs unknowns only - and lam ms_k + beta_k on the diagonal of mode k;
+    g = [G | Gy]^T W r with - alpha D^T Q D x0 on the Vs part and - beta_k y_k on mode k."""
+    p = _System(G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale, mode_prior, mode_y)
+    return p.A, p.g
+
+
+def normal_equations(G, r, w_over_sigma2, x0, alpha, Q, lam):
+    """(A, g) of the step, numpy float64: A = G^T W G + alpha D^T Q D + lam I, g = G^T W r - alpha D^T Q D x0.  G [N, n], r and
+    w_over_sigma2 [N], x0 [n], Q [n-1] (weights of the differences of consecutive unknowns).  ``modes_normal_equations`` without
+    modes."""
+    return modes_normal_equations(G, None, r, w_over_sigma2, x0, alpha, Q, lam)
 
 
 def lsq_modes_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam, Gy=None, mode_scale=None, mode_prior=None, mode_y=None):
-    """``lsq_step_reference`` with K thickness modes - the statement ``surfdisp_lsq_step_modes_device`` is tested against.  ``Gy``
-    [N, K]: the mode columns of the used rows (``mode_columns``; None or K = 0: the result of ``lsq_step_reference`` with an
-    empty delta_y); mode_scale, mode_prior, mode_y: scalars or [K] (None: 1, 0, 0).  Returns dict(delta [n], delta_y [K], misfit,
-    roughness, predicted = sum W (r - G delta - Gy delta_y)^2 + alpha roughness(x0 + delta) + sum beta (y + delta_y)^2, flag);
-    with a flag the deltas are zeros and predicted = misfit + alpha roughness + sum beta y^2."""
-    K = _nmodes(Gy)
-    if K == 0:
-        out = lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam)
-        out["delta_y"] = np.zeros(0)
-        return out
-    x0 = np.asarray(x0, np.float64).ravel()
-    n = x0.size
-    G = np.asarray(G, np.float64).reshape(-1, n)
-    Gy = np.asarray(Gy, np.float64).reshape(-1, K)
-    r = np.asarray(r, np.float64).ravel()
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
-    Qv = np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)]
-    ms, beta, y = _mode_vectors(K, mode_scale, mode_prior, mode_y)
-    rough = lambda x: float((Qv * np.diff(x) ** 2).sum())
-    prior = lambda v: float((beta * v * v).sum())
-    misfit = float((w * r * r).sum())
-    out = dict(delta=np.zeros(n), delta_y=np.zeros(K), misfit=misfit, roughness=rough(x0),
-               predicted=misfit + float(alpha) * rough(x0) + prior(y), flag=0)
-    if G.shape[0] == 0:
-        out["flag"] = 1
-        return out
-    A, g = modes_normal_equations(G, Gy, r, w, x0, alpha, Qv, lam, ms, beta, y)
-    try:
-        if not np.isfinite(A).all():
-            raise np.linalg.LinAlgError
-        Lc = np.linalg.cholesky(A)
-    except np.linalg.LinAlgError:
-        out["flag"] = 2
-        return out
-    d = np.linalg.solve(Lc.T, np.linalg.solve(Lc, g))
-    t = r - G @ d[:n] - Gy @ d[n:]
-    out["delta"], out["delta_y"] = d[:n], d[n:]
-    out["predicted"] = float((w * t * t).sum()) + float(alpha) * rough(x0 + d[:n]) + prior(y + d[n:])
+    """One damped least-squares step of one stack in numpy float64 - the statement ``surfdisp_lsq_step_modes_device`` and, without
+    modes, ``surfdisp_lsq_step_device`` are tested against.  G [N, n]: the effective Jacobian rows of the USED data rows, r [N] their
+    residuals obs - pred, w_over_sigma2 [N], x0 [n] the free layers' Vs, Q [n-1] the weights of the differences of consecutive
+    free layers, alpha, lam scalars; ``Gy`` [N, K]: the mode columns of the used rows (``mode_columns``; None: K = 0);
+    mode_scale, mode_prior, mode_y: scalars or [K] (None: 1, 0, 0).  Returns dict(delta [n], delta_y [K], misfit = sum W r^2,
+    roughness = x0^T D^T Q D x0, predicted = sum W (r - G delta - Gy delta_y)^2 + alpha roughness(x0 + delta) + sum beta
+    (y + delta_y)^2, flag): flag 1 without rows, 2 when A is not finite or the Cholesky factorisation fails - then the deltas are
+    zeros and predicted = misfit + alpha roughness + sum beta y^2."""
+    p = _System(G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale, mode_prior, mode_y)
+    n = p.n
+    misfit = float((p.w * p.r * p.r).sum())
+    out = dict(delta=np.zeros(n), delta_y=np.zeros(p.K), misfit=misfit, roughness=p.roughness(p.x0),
+               predicted=p.objective(misfit, p.x0, p.y), flag=0)
+    out["flag"], Lc = p.factor()
+    if Lc is not None:
+        d = np.linalg.solve(Lc.T, np.linalg.solve(Lc, p.g))
+        t = p.r - p.G @ d[:n] - p.Gy @ d[n:]
+        out.update(delta=d[:n], delta_y=d[n:], predicted=p.objective(float((p.w * t * t).sum()), p.x0 + d[:n], p.y + d[n:]))
+    return out
+
+
+def lsq_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam):
+    """``lsq_modes_step_reference`` without modes - the statement ``surfdisp_lsq_step_device`` is tested against; the result has no
+    delta_y."""
+    out = lsq_modes_step_reference(G, r, w_over_sigma2, x0, alpha, Q, lam)
+    del out["delta_y"]
     return out
 
 
 def lsq_modes_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam, Gy=None, mode_scale=None, mode_prior=None):
-    """``lsq_resolution_reference`` with K thickness modes - the statement ``surfdisp_lsq_resolution_modes_device`` is tested
-    against (``Gy``, mode_scale, mode_prior as ``lsq_modes_step_reference``; None or K = 0: the result of
-    ``lsq_resolution_reference``).  Every array is over the n + K unknowns, the modes last: cov, res [n + K, n + K], sigma_post,
-    sigma_data, rdiag [n + K], dof, logdet, flag."""
-    K = _nmodes(Gy)
-    if K == 0:
-        return lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam)
+    """Posterior covariance and resolution of one stack's damped, smoothed problem in numpy float64 - the statement
+    ``surfdisp_lsq_resolution_modes_device`` and, without modes, ``surfdisp_lsq_resolution_device`` are tested against.  G, Gy,
+    w_over_sigma2, Q, alpha, lam, mode_scale, mode_prior as ``lsq_modes_step_reference``; ``x0_or_n``: the Vs unknowns' vector or
+    just their number n (the matrices do not depend on x0).  With H and A of ``_System`` over the n + K unknowns, the modes last:
+
+        cov = A^-1,   res = cov H,   sigma_post = sqrt(diag cov),   sigma_data = sqrt(diag(res cov)),   rdiag = diag res,
+        dof = trace res
+
+    Returns dict(cov, res [n + K, n + K], sigma_post, sigma_data, rdiag [n + K], dof, logdet = log det A, flag): flag 1 without
+    rows, 2 when the Cholesky factorisation fails or A, cov or res is not finite - then every array is zeros, dof and logdet 0."""
     n = int(x0_or_n) if np.ndim(x0_or_n) == 0 else np.size(x0_or_n)
-    nu = n + K
-    G = np.asarray(G, np.float64).reshape(-1, n)
-    Gy = np.asarray(Gy, np.float64).reshape(-1, K)
-    w = np.asarray(w_over_sigma2, np.float64).ravel()
+    p = _System(G, Gy, None, w_over_sigma2, np.zeros(n), alpha, Q, lam, mode_scale, mode_prior)
+    nu = n + p.K
     z = np.zeros(nu)
     out = dict(cov=np.zeros((nu, nu)), res=np.zeros((nu, nu)), sigma_post=z.copy(), sigma_data=z.copy(), rdiag=z.copy(), dof=0.0,
                logdet=0.0, flag=0)
-    if G.shape[0] == 0:
-        out["flag"] = 1
-        return out
-    A, _ = modes_normal_equations(G, Gy, np.zeros(G.shape[0]), w, np.zeros(n), alpha, np.asarray(Q, np.float64).ravel()[:max(n - 1, 0)],
-                                  lam, mode_scale, mode_prior, None)
-    Ga = np.concatenate([G, Gy], axis=1)
-    H = Ga.T @ (w[:, None] * Ga)
-    try:
-        if not np.isfinite(A).all():
-            raise np.linalg.LinAlgError
-        Lc = np.linalg.cholesky(A)
+    out["flag"], Lc = p.factor()
+    if Lc is not None:
         T = np.linalg.solve(Lc, np.eye(nu))
         cov = T.T @ T
         cov = 0.5 * (cov + cov.T)
-        res = cov @ H
+        res = cov @ p.H
         cd = np.einsum("ij,ji->i", res, cov)
         if not (np.isfinite(cov).all() and np.isfinite(res).all() and np.isfinite(cd).all()):
-            raise np.linalg.LinAlgError
-    except np.linalg.LinAlgError:
-        out["flag"] = 2
-        return out
-    out.update(cov=cov, res=res, sigma_post=np.sqrt(np.diag(cov)), sigma_data=np.sqrt(np.maximum(cd, 0.0)), rdiag=np.diag(res).copy(),
-               dof=float(np.trace(res)), logdet=float(2.0 * np.log(np.diag(Lc)).sum()))
+            out["flag"] = 2
+            return out
+        out.update(cov=cov, res=res, sigma_post=np.sqrt(np.diag(cov)), sigma_data=np.sqrt(np.maximum(cd, 0.0)), rdiag=np.diag(res).copy(),
+                   dof=float(np.trace(res)), logdet=float(2.0 * np.log(np.diag(Lc)).sum()))
     return out
+
+
+def lsq_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam):
+    """``lsq_modes_resolution_reference`` without modes - the statement ``surfdisp_lsq_resolution_device`` is tested against: every
+    array over the n Vs unknowns."""
+    return lsq_modes_resolution_reference(G, w_over_sigma2, x0_or_n, alpha, Q, lam)
 
 
 def _per_layer(name, v, M, L, cols=None):
@@ -348,17 +284,55 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
 
 
+def _ptrs(arrs):
+    return (ctypes.c_void_p * len(arrs))(*[a.data_ptr() if a is not None else None for a in arrs])
+
+
+def _mode_count(modes, B, L):
+    """(K, per_stack) of a thickness-mode array or tensor: [K, L] or [B, K, L] with 1 <= K <= MAX_MODES, ValueError otherwise."""
+    s = tuple(modes.shape)
+    if len(s) not in (2, 3) or s[-1] != L or (len(s) == 3 and s[0] != B) or not 1 <= s[-2] <= MAX_MODES:
+        raise ValueError(f"modes: shape {s}, expected (K, {L}) or ({B}, K, {L}) with 1 <= K <= {MAX_MODES}")
+    return int(s[-2]), len(s) == 3
+
+
+def _phase_only(jd):
+    """ValueError when the data hold a group-velocity or ellipticity set: thickness modes need dcdh of every row."""
+    if any(d.quantity != "c" for d in jd.datasets):
+        raise ValueError(MODES_NEED_PHASE)
+
+
+@dataclasses.dataclass
+class _Launch:
+    """The checked arguments of one ``LsqPlan.step`` / ``resolution`` call after its ``kernels`` call.  ``head``: the arguments the four
+    entries share, up to and including lam; ``mode_in``: the mode entries' inputs behind them, () when K = 0.  The two tuples
+    keep their ctypes arrays alive."""
+    nmax: int
+    K: int
+    pred: dict
+    part: list
+    part_h: list
+    head: tuple
+    mode_in: tuple
+
+    def __call__(self, name, outs, mode_outs, tail):
+        """surfdisp_lsq_<name>_device on the tensors ``outs`` + ``tail`` (None: NULL), or, with modes, surfdisp_lsq_<name>_modes_device
+        with ``mode_outs`` between the two."""
+        fn = getattr(_lib.lib(), f"surfdisp_lsq_{name}{'_modes' if self.K else ''}_device")
+        _lib.check(fn(*self.head, *self.mode_in, *map(_ptr, outs + (mode_outs if self.K else []) + tail)))
+
+
 class LsqPlan:
     """The sensitivity kernels and the least-squares step of B stacks of L layers against ``datasets`` (``obsdata``
-    ``DispersionData`` sets, or their dict form), on ``device``.  Owns the ``BatchPlan`` of each wave type with data, the
-    ``JointData`` table and the output buffers.  ``mask``: bool [Ptot] or [B, Ptot], rows to leave out on top of the data's own
-    unusable entries (columns in data-set order)."""
+    ``DispersionData`` sets, their dict form, or a ``JointData`` of them), on ``device``.  Owns the ``BatchPlan`` of each wave type
+    with data, the ``JointData`` table and the output buffers.  ``mask``: bool [Ptot] or [B, Ptot], rows to leave out on top of the
+    data's own unusable entries (columns in data-set order)."""
 
     def __init__(self, B, L, datasets, device="cuda:0", mask=None):
         import torch
         self.torch = torch
         self.B, self.L = int(B), int(L)
-        self.joint = jd = JointData(datasets, device="cpu")
+        self.joint = jd = datasets if isinstance(datasets, JointData) else JointData(datasets, device="cpu")
         if jd.C is not None and jd.C != self.B:
             raise ValueError(f"per-stack data of {jd.C} rows against {self.B} stacks")
         obs, unc = np.asarray(jd.obs_raw, np.float64), np.asarray(jd.uncer_raw, np.float64)
@@ -381,15 +355,22 @@ class LsqPlan:
         self.uncer = torch.as_tensor(np.where(ok, unc, 1.0), device=dev).contiguous()
         self.mask8 = self.mask.to(torch.uint8).contiguous()
         self.plans = {w: BatchPlan(self.B, self.L, jd.solve_periods[w].size, device=dev) for w in jd.waves}
-        self.delta = torch.zeros(self.B, self.L, dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(self.B, 3, dtype=torch.float64, device=dev)
-        self.info = torch.zeros(self.B, 3, dtype=torch.int32, device=dev)
+        self._buffers = {}
+        self.delta, self.stats = self._buffer("delta", self.B, self.L), self._buffer("stats", self.B, 3)
+        self.info = self._buffer("info", self.B, 3, dtype=torch.int32)
         self._sets = {w: {d.quantity for d in jd.datasets if d.wave == w} for w in jd.waves}
+
+    def _buffer(self, name, *shape, dtype=None, fill=0):
+        """The plan's buffer ``name``: allocated (filled with ``fill``) at its first use and again when another shape is asked for.
+        The entries rewrite an output buffer as a whole at every call."""
+        t = self._buffers.get(name)
+        if t is None or tuple(t.shape) != shape:
+            t = self._buffers[name] = self.torch.full(shape, fill, dtype=dtype or self.torch.float64, device=self.device)
+        return t
 
     def check_modes(self):
         """ValueError when the data hold a group-velocity or ellipticity set: thickness modes need dcdh of every row."""
-        if any(q - {"c"} for q in self._sets.values()):
-            raise ValueError(MODES_NEED_PHASE)
+        _phase_only(self.joint)
 
     def kernels(self, model, nlay=None, want_vp=True, want_rho=True, thickness=False):
         """The kernel entries the data need, once per wave type: U data -> ``run_group_kernels``, an "E" set ->
@@ -400,114 +381,78 @@ class LsqPlan:
         (cR and cL; None elsewhere).  No host synchronisation."""
         jd = self.joint
         pred = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
-        part = [None] * 15
+        part, part_h = [None] * 15, [None] * 5
         if thickness:
             self.check_modes()
-            part_h = [None] * 5
-            for w in jd.waves:
-                kind = _lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE
-                o = 0 if w == "R" else 6
-                c, u, st, kb, ka, kr, kh, _, _ = self.plans[w].run_thickness_kernels(
-                    model, jd.periods_t[w], kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho, want_dcdz=False, count=False)
-                part[o:o + 3] = [kb, ka, kr]
-                part_h[o // 3] = kh
-                pred["c" + w], pred["status" + w] = c, st
-            return pred, part, part_h
         for w in jd.waves:
-            plan, per = self.plans[w], jd.periods_t[w]
-            kind = _lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE
+            plan, per, q = self.plans[w], jd.periods_t[w], self._sets[w]
+            kw = dict(kind=_lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
             o = 0 if w == "R" else 6
-            q = self._sets[w]
-            done = False
+            if thickness:
+                c, u, st, kb, ka, kr, kh, _, _ = plan.run_thickness_kernels(model, per, want_dcdz=False, count=False, **kw)
+                part_h[o // 3] = kh
+            elif not q & {"U", "E"}:
+                c, u, st, kb, ka, kr = plan.run_kernels(model, per, **kw)
             if "U" in q:
-                c, u, st, kb, ka, kr, ub, ua, ur, _ = plan.run_group_kernels(model, per, kind=kind, nlay=nlay, want_vp=want_vp,
-                                                                             want_rho=want_rho, count=False)
-                part[o:o + 6] = [kb, ka, kr, ub, ua, ur]
+                c, u, st, kb, ka, kr, ub, ua, ur, _ = plan.run_group_kernels(model, per, count=False, **kw)
+                part[o + 3:o + 6] = [ub, ua, ur]
                 pred["u" + w] = u
-                done = True
             if "E" in q:
-                c, u, st, ratio, kb, ka, kr, eb, ea, er, _ = plan.run_ellip_kernels(model, per, kind=kind, nlay=nlay,
-                                                                                  want_vp=want_vp, want_rho=want_rho, count=False)
-                part[0:3] = [kb, ka, kr]
+                c, u, st, ratio, kb, ka, kr, eb, ea, er, _ = plan.run_ellip_kernels(model, per, count=False, **kw)
                 part[12:15] = [eb, ea, er]
                 pred["eR"] = ratio
-                done = True
-            if not done:
-                c, u, st, kb, ka, kr = plan.run_kernels(model, per, kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
-                part[o:o + 3] = [kb, ka, kr]
+            part[o:o + 3] = [kb, ka, kr]
             pred["c" + w], pred["status" + w] = c, st
-        return pred, part
+        return (pred, part, part_h) if thickness else (pred, part)
 
-    def _mode_args(self, modes, mode_scale, mode_prior, mode_y):
-        """The checks of the thickness-mode arguments of ``step`` / ``resolution``.  Returns (K, per_stack, modes, mode_scale,
-        mode_prior, mode_y) with mode_scale filled with ones when None."""
+    def _prepare(self, model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale, mode_prior, mode_y):
+        """The argument checks of ``step`` / ``resolution`` and one call of ``kernels`` -> the ``_Launch`` of the call."""
         torch = self.torch
         B, L, dev = self.B, self.L, self.device
-        self.check_modes()
-        ok = lambda t: t.dtype == torch.float64 and t.device == dev and t.is_contiguous()
-        if not ok(modes) or modes.ndim not in (2, 3) or modes.shape[-1] != L or (modes.ndim == 3 and modes.shape[0] != B) \
-                or not 1 <= modes.shape[-2] <= MAX_MODES:
-            raise ValueError(f"modes: expected contiguous float64 (K, {L}) or ({B}, K, {L}) on {dev} with 1 <= K <= {MAX_MODES}, got "
-                             f"{modes.dtype} {tuple(modes.shape)}")
-        K, per_stack = int(modes.shape[-2]), modes.ndim == 3
-        want = (B, K) if per_stack else (K,)
-        if mode_scale is None:
-            if getattr(self, "_ones", None) is None or tuple(self._ones.shape) != want:
-                self._ones = torch.ones(want, dtype=torch.float64, device=dev)
-            mode_scale = self._ones
-        for name, t, shape in (("mode_scale", mode_scale, want), ("mode_prior", mode_prior, want), ("mode_y", mode_y, (B, K))):
-            if t is not None and (not ok(t) or tuple(t.shape) != shape):
-                raise ValueError(f"{name}: expected contiguous float64 {shape} on {dev}, got {t.dtype} {tuple(t.shape)}")
-        return K, per_stack, modes, mode_scale, mode_prior, mode_y
 
-    def _step_args(self, model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes=None, mode_scale=None,
-                   mode_prior=None, mode_y=None):
-        """The argument checks of ``step`` / ``resolution``, one call of ``kernels``, and the entries' shared argument list (up to
-        and including lam).  Returns (args, pred, part, mode) - mode None without ``modes``, else (K, part_h, the mode entries'
-        input arguments behind lam); args and mode keep their ctypes arrays alive."""
-        torch = self.torch
-        B, L = self.B, self.L
+        def chk(name, t, dtype, *shapes):
+            """0 for None or the first of ``shapes``, 1 for the second; ValueError for another shape, dtype, device or layout."""
+            if t is None:
+                return 0
+            if t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) not in shapes:
+                raise ValueError(f"{name}: expected contiguous {dtype} {' or '.join(map(str, shapes))} on {dev}, got {t.dtype} "
+                                 f"{tuple(t.shape)}")
+            return shapes.index(tuple(t.shape))
+
+        K, m_ps = 0, 0
         if modes is not None:
-            K, m_ps, modes, mode_scale, mode_prior, mode_y = self._mode_args(modes, mode_scale, mode_prior, mode_y)
+            self.check_modes()
+            K, m_ps = _mode_count(modes, B, L)
+            chk("modes", modes, torch.float64, tuple(modes.shape))
+            per_mode = (B, K) if m_ps else (K,)
+            if mode_scale is None:
+                mode_scale = self._buffer("mode_scale", *per_mode, fill=1.0)
+            chk("mode_scale", mode_scale, torch.float64, per_mode)
+            chk("mode_prior", mode_prior, torch.float64, per_mode)
+            chk("mode_y", mode_y, torch.float64, (B, K))
         nmax = L if nfree_max is None else int(nfree_max)
         if not 1 <= nmax <= min(MAX_FREE, L):
             raise ValueError(f"nfree_max = {nmax}: the step kernel takes 1..{min(MAX_FREE, L)} free layers per stack (give nfree_max "
                              "when L > 128)")
-
-        def chk(name, t, dtype, cols):
-            if t is None:
-                return 0
-            if t.dtype != dtype or t.device != self.device or not t.is_contiguous() or tuple(t.shape) not in ((cols,), (B, cols)):
-                raise ValueError(f"{name}: expected contiguous {dtype} ({cols},) or ({B}, {cols}) on {self.device}, got "
-                                 f"{t.dtype} {tuple(t.shape)}")
-            return 1 if t.ndim == 2 else 0
-
-        free_ps = chk("free", free, torch.uint8, L)
-        sl_ps = chk("vp_slope", vp_slope, torch.float64, L)
+        free_ps = chk("free", free, torch.uint8, (L,), (B, L))
+        sl_ps = chk("vp_slope", vp_slope, torch.float64, (L,), (B, L))
         if rho_slope is not None and vp_slope is not None and rho_slope.ndim != vp_slope.ndim:
             raise ValueError("vp_slope and rho_slope: both [L] or both [B, L]")
-        sl_ps = max(sl_ps, chk("rho_slope", rho_slope, torch.float64, L))
-        q_ps = chk("Q", Q, torch.float64, L - 1) if L > 1 else 0
-        if lam.dtype != torch.float64 or tuple(lam.shape) != (B,) or lam.device != self.device or not lam.is_contiguous():
-            raise ValueError(f"lam: expected contiguous float64 ({B},) on {self.device}")
-        mode = None
-        if modes is None:
-            pred, part = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None)
-        else:
-            pred, part, part_h = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None, thickness=True)
-            parthp = (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in part_h])
-            mode = (K, part_h, (K, _ptr(modes), 1 if m_ps else 0, parthp, _ptr(mode_scale), _ptr(mode_prior), _ptr(mode_y)))
+        sl_ps = max(sl_ps, chk("rho_slope", rho_slope, torch.float64, (L,), (B, L)))
+        q_ps = chk("Q", Q, torch.float64, (L - 1,), (B, L - 1)) if L > 1 else 0
+        chk("lam", lam, torch.float64, (B,))
+        kern = self.kernels(model, nlay, want_vp=vp_slope is not None, want_rho=rho_slope is not None, thickness=K > 0)
+        pred, part, part_h = kern if K else (*kern, None)
         jd = self.joint
         arrs = [pred["cR"], pred["uR"], pred["cL"], pred["uL"], pred["eR"]]
-        predp = (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in arrs])
         strides = (ctypes.c_long * 5)(*[a.stride(0) if a is not None else 0 for a in arrs])
-        partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
         nper = (ctypes.c_int * 2)(*[int(jd.solve_periods[w].size) if w in jd.solve_periods else 0 for w in ("R", "L")])
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        head = (stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, partp, predp, strides, nper,
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        head = (stream, B, L, _ptr(nlay), _ptr(model), _ptr(free), free_ps, nmax, _ptrs(part), _ptrs(arrs), strides, nper,
                 jd.Ptot, _ptr(jd.cols), _ptr(jd.weights), _ptr(self.obs), _ptr(self.uncer), _ptr(self.mask8),
                 1 if self.obs.ndim == 2 else 0, _ptr(vp_slope), _ptr(rho_slope), sl_ps, float(alpha), _ptr(Q), q_ps, _ptr(lam))
-        return head, pred, part, mode
+        mode_in = (K, _ptr(modes), int(m_ps), _ptrs(part_h), _ptr(mode_scale), _ptr(mode_prior), _ptr(mode_y)) if K else ()
+        return _Launch(nmax, K, pred, part, part_h, head, mode_in)
 
     def step(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None,
              modes=None, mode_scale=None, mode_prior=None, mode_y=None):
@@ -520,21 +465,14 @@ class LsqPlan:
         Thickness modes (``surfdisp_lsq_step_modes_device``; phase-velocity data only, ValueError otherwise): ``modes`` float64
         [K, L] or [B, K, L], ``mode_scale`` and ``mode_prior`` float64 [K] ([B, K] with per-stack modes; None: 1 and 0),
         ``mode_y`` float64 [B, K] (None: 0); the result then holds delta_y [B, K] float64 and part_h, the five thickness
-        arrays, as well."""
-        head, pred, part, mode = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale,
-                                                 mode_prior, mode_y)
+        arrays, as well.  Without ``modes`` the entry without modes is launched."""
+        call = self._prepare(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale, mode_prior, mode_y)
         out = dict(delta=self.delta, misfit=self.stats[:, 0], roughness=self.stats[:, 1], predicted=self.stats[:, 2],
-                   used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=pred, part=part)
+                   used=self.info[:, 0], dropped=self.info[:, 1], flag=self.info[:, 2], pred=call.pred, part=call.part)
+        if call.K:
+            out.update(delta_y=self._buffer("delta_y", self.B, call.K), part_h=call.part_h)
         with self.torch.cuda.device(self.device):
-            if mode is None:
-                _lib.check(_lib.lib().surfdisp_lsq_step_device(*head, _ptr(self.delta), _ptr(self.stats), _ptr(self.info)))
-            else:
-                K, part_h, margs = mode
-                if getattr(self, "delta_y", None) is None or self.delta_y.shape[1] != K:
-                    self.delta_y = self.torch.zeros(self.B, K, dtype=self.torch.float64, device=self.device)
-                _lib.check(_lib.lib().surfdisp_lsq_step_modes_device(*head, *margs, _ptr(self.delta), _ptr(self.delta_y),
-                                                                     _ptr(self.stats), _ptr(self.info)))
-                out.update(delta_y=self.delta_y, part_h=part_h)
+            call("step", [self.delta], [out.get("delta_y")], [self.stats, self.info])
         return out
 
     def resolution(self, model, lam, nlay=None, free=None, nfree_max=None, vp_slope=None, rho_slope=None, alpha=0.0, Q=None,
@@ -551,38 +489,22 @@ class LsqPlan:
         [B, nmax + K, nmax + K], the K modes behind a stack's n Vs unknowns (zeros beyond n + K); dof and logdet are over all
         unknowns; the result holds sigma_post_y, sigma_data_y, rdiag_y [B, K] float64 and part_h as well."""
         torch = self.torch
-        head, pred, part, mode = self._step_args(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale,
-                                                 mode_prior, mode_y)
-        B, L, nmax, dev = self.B, self.L, head[7], self.device
-        K = 0 if mode is None else mode[0]
-        z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)
-        if getattr(self, "_res", None) is None:
-            self._res = dict(sigma_post=z(B, L), sigma_data=z(B, L), rdiag=z(B, L), stats=z(B, 2), info=z(B, 3, dtype=torch.int32))
-        buf = self._res
-        for name, want in (("cov", want_cov), ("res", want_res)):
-            if want and (buf.get(name) is None or buf[name].shape[1] != nmax + K):
-                buf[name] = z(B, nmax + K, nmax + K)
-        cov, res = (buf[k] if w else None for k, w in (("cov", want_cov), ("res", want_res)))
-        outs = [_ptr(cov), _ptr(res), _ptr(buf["sigma_post"]), _ptr(buf["sigma_data"]), _ptr(buf["rdiag"])]
-        extra = {}
+        call = self._prepare(model, lam, nlay, free, nfree_max, vp_slope, rho_slope, alpha, Q, modes, mode_scale, mode_prior, mode_y)
+        B, L, nmax, K, dev = self.B, self.L, call.nmax, call.K, self.device
+        cov, res = (self._buffer(k, B, nmax + K, nmax + K) if want else None for k, want in (("cov", want_cov), ("res", want_res)))
+        per_layer = {k: self._buffer("res_" + k, B, L) for k in ("sigma_post", "sigma_data", "rdiag")}
+        per_mode = {k + "_y": self._buffer("res_" + k + "_y", B, K) for k in per_layer} if K else {}
+        stats, info = self._buffer("res_stats", B, 2), self._buffer("res_info", B, 3, dtype=torch.int32)
         with torch.cuda.device(dev):
-            if mode is None:
-                _lib.check(_lib.lib().surfdisp_lsq_resolution_device(*head, *outs, _ptr(buf["stats"]), _ptr(buf["info"])))
-            else:
-                if buf.get("rdiag_y") is None or buf["rdiag_y"].shape[1] != K:
-                    buf.update(sigma_post_y=z(B, K), sigma_data_y=z(B, K), rdiag_y=z(B, K))
-                extra = dict(sigma_post_y=buf["sigma_post_y"], sigma_data_y=buf["sigma_data_y"], rdiag_y=buf["rdiag_y"], part_h=mode[1])
-                _lib.check(_lib.lib().surfdisp_lsq_resolution_modes_device(
-                    *head, *mode[2], *outs, _ptr(buf["sigma_post_y"]), _ptr(buf["sigma_data_y"]), _ptr(buf["rdiag_y"]),
-                    _ptr(buf["stats"]), _ptr(buf["info"])))
+            call("resolution", [cov, res, *per_layer.values()], [*per_mode.values()], [stats, info])
         lay = torch.arange(L, device=dev)
         fr = torch.ones(B, L, dtype=torch.bool, device=dev) if free is None else (free != 0).expand(B, L)
         if nlay is not None:
             fr = fr & (lay[None, :] < nlay[:, None])
         order = torch.where(fr, lay[None, :], L).sort(dim=1).values[:, :nmax]
-        return dict(cov=cov, res=res, sigma_post=buf["sigma_post"], sigma_data=buf["sigma_data"], rdiag=buf["rdiag"],
-                    dof=buf["stats"][:, 0], logdet=buf["stats"][:, 1], used=buf["info"][:, 0], dropped=buf["info"][:, 1],
-                    flag=buf["info"][:, 2], free_index=torch.where(order < L, order, -1), nfree=fr.sum(dim=1), pred=pred, part=part,
+        extra = dict(per_mode, part_h=call.part_h) if K else {}
+        return dict(cov=cov, res=res, **per_layer, dof=stats[:, 0], logdet=stats[:, 1], used=info[:, 0], dropped=info[:, 1],
+                    flag=info[:, 2], free_index=torch.where(order < L, order, -1), nfree=fr.sum(dim=1), pred=call.pred, part=call.part,
                     **extra)
 
     def forward(self, model, nlay=None):
@@ -681,22 +603,20 @@ class LinearizedBatch:
             lo, hi = (np.broadcast_to(np.asarray(b, np.float64), (M, L)) for b in vs_bounds)
         if modes is not None:
             T = np.array(modes, np.float64)
-            if T.ndim not in (2, 3) or T.shape[-1] != L or (T.ndim == 3 and T.shape[0] != M) or not 1 <= T.shape[-2] <= MAX_MODES:
-                raise ValueError(f"modes: shape {T.shape}, expected (K, {L}) or ({M}, K, {L}) with 1 <= K <= {MAX_MODES}")
-            K = T.shape[-2]
-            if T.ndim == 2 and nlay is not None:
-                T = np.broadcast_to(T, (M, K, L)).copy()
-            if T.ndim == 3:
+            K, per_stack = _mode_count(T, M, L)
+            if not per_stack and nlay is not None:
+                T, per_stack = np.broadcast_to(T, (M, K, L)).copy(), True
+            if per_stack:
                 T[~np.broadcast_to((np.arange(L)[None, :] < nl[:, None] - 1)[:, None, :], T.shape)] = 0.0
             else:
                 T[:, L - 1] = 0.0
             if not np.isfinite(T).all():
                 raise ValueError("modes: entries that are not finite")
-            shape = (M, K) if T.ndim == 3 else (K,)
+            shape = (M, K) if per_stack else (K,)
 
             def per_mode(name, v):
                 a = np.asarray(v, np.float64)
-                if a.ndim > len(shape) or (a.ndim and a.shape[-1] != K) or (a.ndim == 2 and a.shape[0] != M):
+                if a.shape not in ((), (K,), shape):
                     raise ValueError(f"{name}: shape {a.shape}, expected a scalar, ({K},) or ({M}, {K}) (per stack only with per-stack modes)")
                 return np.array(np.broadcast_to(a, shape))
             m_scale, m_prior = per_mode("mode_scale", mode_scale), per_mode("mode_prior", mode_prior)
@@ -706,9 +626,10 @@ class LinearizedBatch:
                 ylo, yhi = (np.array(np.broadcast_to(np.asarray(b, np.float64), (M, K))) for b in mode_bounds)
             if not (np.isfinite(h_min) and h_min >= 0):
                 raise ValueError("h_min must be finite and >= 0")
-            if any(d.quantity != "c" for d in JointData(datasets, device="cpu").datasets):
-                raise ValueError(MODES_NEED_PHASE)
-        self.plan = plan = LsqPlan(M, L, datasets, device=device, mask=mask)      # (data errors: ValueError; no HIP device: SurfdispError)
+        jd = JointData(datasets, device="cpu")                                    # (data errors: ValueError)
+        if modes is not None:
+            _phase_only(jd)
+        self.plan = plan = LsqPlan(M, L, jd, device=device, mask=mask)            # (no HIP device: SurfdispError)
         import torch
         self.torch = torch
         dev = self.device = plan.device

@@ -4,125 +4,20 @@ Bars.  Backward error of the solve: ||A delta - g||inf <= 1e-11 (||A||inf ||delt
 numpy float64 from the same fp32 inputs: the fp64 Cholesky bound gamma_{3n+1} plus the N-term accumulation is
 (3 * 128 + 1 + 256) * 1.1e-16 ~ 7e-14 (Higham, Accuracy and Stability of Numerical Algorithms); the bar is ~100 x that and does
 not depend on the conditioning.  Misfit, roughness and predicted objective: relative 1e-12; counts exact."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from lsq_cases import (ALPHA, CASES, LAM0, LAM_MIN, N_ITER, NU, SETS3, _case, _chi_rms, _datasets, _forward_all, _rows_of,
+                       _true_and_start, cpu_route, launch)
 from pysurfinv_amd import _lib, linearized, synth
-from pysurfinv_amd.obsdata import DispersionData, JointData
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(1, 2, 1), (5, 3, 7), (3, 17, 40), (2, 64, 100), (2, 96, 100), (1, 128, 256), (300, 9, 12)]
 
-
-def _case(B, Lmax, N, seed):
-    """Random inputs of one launch, numpy.  Mixed in: ragged nlay, a water top layer that is not free, a free mask with gaps,
-    Q with a zero, slopes per stack, sources 0-5 with negative chi, a masked row, a NaN kernel row, an unsolved period,
-    per-stack or shared observations (alternating with the case), a stack with every row masked (per-stack cases)."""
-    rng = np.random.default_rng(seed)
-    P = N // 6 + 2
-    per_stack = (B > 1) and (Lmax % 2 == 1)
-    c = dict(B=B, Lmax=Lmax, N=N, P=P, alpha=0.8)
-    c["nlay"] = np.array([max(2, Lmax - (b % 3)) for b in range(B)], np.int32)
-    model = rng.uniform(2.0, 4.5, (B, 5, Lmax)).astype(np.float32)
-    free = np.ones((B, Lmax), np.uint8)
-    if Lmax >= 9:
-        free[:, 4::5] = 0                                      # gaps
-    if Lmax >= 3:
-        free[::2, 0] = 0; model[::2, 1, 0] = 0.0               # a water top layer
-    c["model"], c["free"] = model, (free if per_stack else free[0].copy())
-    c["part"] = [rng.normal(0, 0.3, (B, P, Lmax)).astype(np.float32) for _ in range(15)]
-    c["part"][7] = c["part"][10] = None                        # Love has no d/dVp
-    pred = [rng.uniform(2.5, 4.5, (B, P)).astype(np.float32) for _ in range(4)]
-    pred.append((rng.uniform(0.5, 1.0, (B, P)) * rng.choice([-1.0, 1.0], (B, P))).astype(np.float32))
-    cols = np.stack([np.arange(N) % 6, np.arange(N) // 6], axis=1).astype(np.int32)
-    if N > 12:
-        for a in c["part"][3:6]:
-            a[0, 1, :] = np.nan                                # a failed unit of the group entry: source 1, period 1, stack 0
-        pred[0][B - 1, 2] = 0.0                                # an unsolved Rayleigh period of the last stack (c and chi rows)
-    c["pred"], c["cols"] = pred, cols
-    c["weights"] = rng.uniform(0.5, 2.0, N)
-    shape = (B, N) if per_stack else (N,)
-    c["obs"] = rng.uniform(2.5, 4.5, shape)
-    c["uncer"] = rng.uniform(0.02, 0.05, shape)
-    mask = np.ones(shape, np.uint8)
-    if N > 1:
-        mask[..., N // 2] = 0
-    if N > 2:
-        c["obs"][..., 0] = np.nan                              # unusable by the rule of DispersionData
-        c["uncer"][..., 1] = -1.0
-    if per_stack and B >= 3:
-        mask[2] = 0                                            # flag 1, between two good neighbours
-    c["mask"] = mask
-    slope = lambda: rng.uniform(0.0, 2.0, (B, Lmax)) * (rng.random((B, Lmax)) > 0.2)
-    c["vp_slope"], c["rho_slope"] = slope(), slope()
-    Q = rng.uniform(0.5, 1.5, (B, max(Lmax - 1, 1)))
-    if Lmax >= 3:
-        Q[:, (Lmax - 1) // 2] = 0.0
-    c["Q"] = Q if per_stack else Q[0].copy()
-    c["lam"] = rng.uniform(5.0, 20.0, B)
-    return c
-
-
-def _launch(c, nfree_max=None, **null):
-    """surfdisp_lsq_step_device on the arrays of ``c``; ``null``: names passed as NULL.  Returns (rc, delta, stats, info)."""
-    import torch
-    dev = torch.device("cuda:0")
-    t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    B, Lmax, N = c["B"], c["Lmax"], c["N"]
-    keep = {k: t(None if null.get(k) else c[k]) for k in ("nlay", "model", "free", "cols", "weights", "obs", "uncer", "mask",
-                                                          "vp_slope", "rho_slope", "Q", "lam")}
-    part, pred = [t(a) for a in c["part"]], [t(a) for a in c["pred"]]
-    out = dict(delta=torch.full((B, Lmax), 7.0, dtype=torch.float64, device=dev),
-               stats=torch.full((B, 3), 7.0, dtype=torch.float64, device=dev),
-               info=torch.full((B, 3), 7, dtype=torch.int32, device=dev))
-    p = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)
-    partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
-    predp = (ctypes.c_void_p * 5)(*[a.data_ptr() for a in pred])
-    strides = (ctypes.c_long * 5)(*[c["P"]] * 5)
-    nper = (ctypes.c_int * 2)(c["P"], c["P"])
-    rc = _lib.lib().surfdisp_lsq_step_device(
-        None, B, Lmax, p(keep["nlay"]), p(keep["model"]), p(keep["free"]), int(c["free"].ndim == 2),
-        Lmax if nfree_max is None else nfree_max, partp, predp, strides, nper, N, p(keep["cols"]), p(keep["weights"]),
-        p(keep["obs"]), p(keep["uncer"]), p(keep["mask"]), int(c["obs"].ndim == 2), p(keep["vp_slope"]), p(keep["rho_slope"]), 1,
-        float(c["alpha"]), p(keep["Q"]), int(c["Q"].ndim == 2), p(keep["lam"]), p(out["delta"]), p(out["stats"]), p(out["info"]))
-    torch.cuda.synchronize()
-    return rc, out["delta"].cpu().numpy(), out["stats"].cpu().numpy(), out["info"].cpu().numpy()
-
-
-def _rows_of(c, b):
-    """(idx, Qw, G, res, w) of stack b in numpy float64, by the rules of include/surfdisp.h section (6d)."""
-    pick = lambda a, nd: a[b] if a.ndim == nd else a
-    fr = pick(c["free"], 2).astype(bool) & (np.arange(c["Lmax"]) < c["nlay"][b])
-    idx, Qw = linearized.consecutive_weights(fr, pick(c["Q"], 2))
-    obs, unc, mask = pick(c["obs"], 2), pick(c["uncer"], 2), pick(c["mask"], 2)
-    ps, qs = c["vp_slope"][b, idx], c["rho_slope"][b, idx]
-    G, res, w = [], [], []
-    for r, (src, k) in enumerate(c["cols"]):
-        sa = 4 if src == 5 else int(src)
-        o, sg = obs[r], unc[r]
-        if not (mask[r] and np.isfinite(o) and np.isfinite(sg) and sg > 0):
-            continue
-        v, sign = float(c["pred"][sa][b, k]), 1.0
-        if sa == 4:
-            if not (np.isfinite(v) and c["pred"][0][b, k] >= 0.01):
-                continue
-            if src == 5 and v < 0:
-                sign, v = -1.0, -v
-        elif not v >= 0.01:
-            continue
-        kb, ka, kr = (None if a is None else a[b, k, idx].astype(np.float64) for a in c["part"][3 * sa:3 * sa + 3])
-        g = kb.copy()
-        if ka is not None:
-            g += np.where(ps != 0, ps * ka, 0.0)
-        g += np.where(qs != 0, qs * kr, 0.0)
-        g *= sign
-        if not np.isfinite(g).all():
-            continue
-        G.append(g); res.append(o - v); w.append(c["weights"][r] / (sg * sg))
-    return idx, Qw, np.array(G).reshape(len(G), idx.size), np.array(res), np.array(w)
+def _launch(c, **kw):
+    """surfdisp_lsq_step_device on the arrays of ``c`` (``lsq_cases.launch``).  Returns (rc, delta, stats, info)."""
+    rc, o = launch("step", c, **kw)
+    return rc, o["delta"], o["stats"], o["info"]
 
 
 def _check_stack(tag, idx, Qw, G, res, w, x0, alpha, lam, delta_row, stats, info, N):
@@ -198,30 +93,6 @@ def test_step_entry_refuses_bad_arguments_before_launching():
 
 
 # ------------------------------------------------------------------------------------------------- on real kernels
-def _datasets(per, values, sets, frac, C=None):
-    """DispersionData of ``sets`` ((wave, quantity), ...) from the forward dict ``values`` (numpy), uncer = frac |value|."""
-    key = {("R", "c"): "cR", ("R", "U"): "uR", ("L", "c"): "cL", ("R", "E"): "eR"}
-    out = []
-    for w, q in sets:
-        v = np.asarray(values[key[w, q]], np.float64)
-        out.append(DispersionData(w, q, per, v, frac * np.abs(v)))
-    return out
-
-
-def _forward_all(model, per, ratio=True):
-    """dict(cR, uR, cL, eR) float64 numpy [B, P] of the GPU forward solve; every solve must succeed."""
-    import torch
-    from pysurfinv_amd.forward import BatchPlan
-    B, _, L = model.shape
-    dm, dp = torch.from_numpy(model).cuda(), torch.from_numpy(per).cuda()
-    plan = BatchPlan(B, L, per.size)
-    cR, uR, st, eR = (x.cpu().numpy().astype(np.float64) for x in plan.run(dm, dp, kind=2, want_ratio=True))
-    assert (st == 0).all()
-    cL, _, stL = (x.cpu().numpy().astype(np.float64) for x in plan.run(dm, dp, kind=1))
-    assert (stL == 0).all()
-    return dict(cR=cR, uR=uR, cL=cL, eR=eR)
-
-
 @pytest.mark.parametrize("name", ["synth_L8", "water_L9"])
 def test_step_on_real_kernels(name):
     """LsqPlan.step against G, r re-formed on the host from analytic_kernels of the same model; its data misfit against the
@@ -263,34 +134,6 @@ def test_step_on_real_kernels(name):
 
 
 # ------------------------------------------------------------------------------------------------- the iteration
-NU, LAM0, LAM_MIN, ALPHA, N_ITER = 4.0, 1.0, 1e-9, 0.05, 8
-SETS3 = (("R", "c"), ("R", "U"), ("L", "c"))
-
-
-def _true_and_start(seed=31):
-    """16 stacks of 8 layers and their starts: Vs times a smooth +-5 % perturbation (half a cosine over depth, sign and
-    phase per stack)."""
-    true = synth.synth_models(16, 8, seed=seed)
-    rng = np.random.default_rng(seed + 1)
-    z = np.linspace(0.0, 1.0, 8)
-    pert = 0.05 * rng.choice([-1.0, 1.0], (16, 1)) * np.cos(np.pi * (z[None, :] + rng.uniform(0, 1, (16, 1))))
-    start = true.copy()
-    start[:, 1, :] = (true[:, 1, :] * (1.0 + pert)).astype(np.float32)
-    return true, start
-
-
-def _chi_rms(pred, data, mask=None):
-    """chi2 and rms [B] of the forward dict ``pred`` (numpy float64) by the definition of obsdata (weights 1)."""
-    key = {("R", "c"): "cR", ("R", "U"): "uR", ("L", "c"): "cL", ("R", "E"): "eR"}
-    r = np.concatenate([(d.values - pred[key[d.wave, d.quantity]]) / d.uncer for d in data], axis=1)
-    if mask is not None:
-        r = np.where(mask, r, 0.0)
-    n = r.shape[1] if mask is None else mask.sum(axis=1)
-    chi = (r * r).sum(axis=1)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        return chi, np.sqrt(chi / n)
-
-
 @pytest.fixture(scope="module")
 def loop_problem():
     true, start = _true_and_start()
@@ -332,50 +175,8 @@ def test_loop_invariants(loop_problem):
 
 
 def _cpu_route(start, per, data, n_iter):
-    """The same iteration in numpy float64 on the CPU checker: forward solves by oracle.cport.forward_batch, Jacobians by its
-    central differences (1 % of Vs, as tests/test_group_kernels.py), steps by lsq_step_reference, the same accept rule."""
-    from oracle import cport
-    M, _, L = start.shape
-    eps = 0.01
-
-    def fwd(m):
-        cR, uR, sR = cport.forward_batch(m, per, 2, nthreads=8)
-        cL, _, sL = cport.forward_batch(m, per, 1, nthreads=8)
-        return dict(cR=cR.astype(np.float64), uR=uR.astype(np.float64), cL=cL.astype(np.float64)), (sR != 0) | (sL != 0)
-
-    def objective(m):
-        p, bad = fwd(m)
-        chi, rms = _chi_rms(p, data)
-        rough = (np.diff(m[:, 1, :].astype(np.float64), axis=1) ** 2).sum(axis=1)
-        return np.where(bad, np.inf, chi + ALPHA * rough), rms, p
-
-    model = start.copy()
-    obj, rms, p0 = objective(model)
-    assert np.isfinite(obj).all()
-    lam = np.full(M, LAM0)
-    sig = np.concatenate([d.uncer for d in data], axis=1 if data[0].uncer.ndim == 2 else 0)
-    obsv = np.concatenate([d.values for d in data], axis=1 if data[0].values.ndim == 2 else 0)
-    for _ in range(n_iter):
-        big = np.repeat(model, 2 * L, axis=0).reshape(M, 2 * L, 5, L)
-        for i in range(L):
-            big[:, i, 1, i] *= (1 - eps); big[:, L + i, 1, i] *= (1 + eps)
-        pb, bad = fwd(big.reshape(M * 2 * L, 5, L))
-        assert not bad.any()
-        pc, _ = fwd(model)
-        trial = model.copy()
-        for m in range(M):
-            y = np.concatenate([pb[k].reshape(M, 2 * L, per.size)[m] for k in ("cR", "uR", "cL")], axis=1)      # [2L, N]
-            f0 = np.concatenate([pc[k][m] for k in ("cR", "uR", "cL")])
-            G = ((y[L:] - y[:L]) / (2 * eps * model[m, 1, :].astype(np.float64))[:, None]).T
-            o, s = (obsv[m], sig[m]) if obsv.ndim == 2 else (obsv, sig)
-            st = linearized.lsq_step_reference(G, o - f0, 1.0 / s ** 2, model[m, 1].astype(np.float64), ALPHA, np.ones(L - 1), lam[m])
-            trial[m, 1] = (model[m, 1].astype(np.float64) + st["delta"]).astype(np.float32)
-        tobj, trms, _ = objective(trial)
-        acc = tobj < obj
-        model = np.where(acc[:, None, None], trial, model)
-        obj, rms = np.where(acc, tobj, obj), np.where(acc, trms, rms)
-        lam = np.where(acc, np.maximum(lam / NU, LAM_MIN), lam * NU)
-    return model, rms
+    """The same iteration in numpy float64 on the CPU checker (``lsq_cases.cpu_route`` without a mode).  Returns (model, rms)."""
+    return cpu_route(start, per, data, n_iter)[:2]
 
 
 def test_recovery_against_the_cpu_route(loop_problem):

@@ -3,21 +3,9 @@ least-squares problem, and the argument errors of the linearised inversion.  CPU
 import numpy as np
 import pytest
 
+from lsq_cases import _problem
 from pysurfinv_amd import _lib, linearized, synth
 from pysurfinv_amd.obsdata import DispersionData
-
-
-def _problem(N, n, seed):
-    """Random G with orthonormal-ish columns times a modest spectrum, so that cond(A) <= 1e4 whatever (N, n)."""
-    rng = np.random.default_rng(seed)
-    G = rng.standard_normal((N, n))
-    r = rng.standard_normal(N)
-    w = rng.uniform(0.5, 2.0, N)
-    x0 = rng.uniform(2.0, 4.5, n)
-    Q = rng.uniform(0.5, 1.5, max(n - 1, 0))
-    if n > 2:
-        Q[n // 2] = 0.0                                   # a cut interface
-    return G, r, w, x0, 0.7, Q, 0.3
 
 
 @pytest.mark.parametrize("N,n", [(1, 1), (7, 3), (40, 17), (100, 64)])

@@ -1,107 +1,36 @@
 """Thickness modes as unknowns of the least-squares step and of the resolution kernel (surfdisp_lsq_step_modes_device,
 surfdisp_lsq_resolution_modes_device, include/surfdisp.h section (6h)) and the Python layers on them, on the GPU.
 
-The random inputs are those of tests/test_lsq_gpu.py (``_case``) plus the mode arguments; the rows of a stack come from its
-``_rows_of`` with the two extra drop rules applied through the mask.  Bars: those of tests/test_lsq_gpu.py for the step (backward
+The random inputs are those of tests/test_lsq_gpu.py (``_case`` of tests/lsq_cases.py) plus the mode arguments; the rows of a stack come
+from ``_rows_of`` with the two extra drop rules applied through the mask.  Bars: those of tests/test_lsq_gpu.py for the step (backward
 error 1e-11 (||A||inf ||delta||inf + ||g||inf): the fp64 Cholesky bound plus the N-term accumulation is (3 x 136 + 1 + 256) x 1.1e-16
 ~ 7e-14 at the largest size, a hundred times under; objectives relative 1e-12; counts and flags exact) and those of
 tests/test_lsq_resolution_gpu.py for the resolution."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from lsq_cases import (ALPHA, LAM0, LAM_MIN, LAM_FACTOR, N_ITER, NU, _chi_rms, _datasets, _forward_all, _mode_case, _nan_row, _rows_of,
+                       _true_and_start, cpu_route, launch)
 from pysurfinv_amd import _lib, linearized, synth
-from test_lsq_gpu import (ALPHA, LAM0, LAM_MIN, N_ITER, NU, _case, _chi_rms, _datasets, _forward_all, _rows_of, _true_and_start)
-from test_lsq_gpu import _launch as _launch_step_old
-from test_lsq_resolution_gpu import _launch as _launch_res_old
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(1, 2, 1, 1), (5, 3, 7, 2), (3, 17, 40, 3), (2, 64, 100, 8), (1, 128, 256, 8), (300, 9, 12, 1)]
-STEP_OUT = ("delta", "delta_y", "stats", "info")
-RES_OUT = ("cov", "res", "sigma_post", "sigma_data", "rdiag", "sigma_post_y", "sigma_data_y", "rdiag_y", "stats", "info")
-LAM_FACTOR = 30.0      # the damping of a mode case over that of ``_case`` (see _mode_case)
 
 
-def _nan_row(N):
-    """The data row whose thickness kernel gets a NaN in stack 0: period 1 of source 0 (row 6), or of source 2 (row 8) where
-    ``_case`` masks row 6 out; None when the case has no such row."""
-    r = 8 if N // 2 == 6 else 6
-    return r if N > r else None
+def _launch(c, entry, **kw):
+    """surfdisp_lsq_step_modes_device (entry "step") or surfdisp_lsq_resolution_modes_device ("res") on the arrays of ``c``
+    (``lsq_cases.launch``).  Returns (rc, dict of numpy outputs)."""
+    return launch(entry + "_modes", c, **kw)
 
 
-def _mode_case(B, Lmax, N, K, seed=None):
-    """``_case`` of tests/test_lsq_gpu.py plus K modes.  Mixed in: T per stack or shared (as the case's observations), a mode
-    that touches the top (water) layer, T entries at and beyond nlay - 1, part_h of the sources 1, 3, 4 absent, one part_h row
-    with a NaN (``_nan_row``), mode_scale and mode_prior per stack or shared, a prior of 0, a non-zero mode_y.  Lmax = 128:
-    every layer of the stack free, n = 128 - with 8 modes the largest triangle and LDS request."""
-    c = _case(B, Lmax, N, seed=1000 + Lmax if seed is None else seed)
-    if Lmax == 128:
-        c["free"] = np.ones_like(c["free"])
-        c["nlay"][:] = Lmax
-    rng = np.random.default_rng(77 + Lmax + K)
-    per_stack = c["obs"].ndim == 2
-    lead = (B,) if per_stack else ()
-    T = rng.normal(0.0, 1.0, lead + (K, Lmax)) * (rng.random(lead + (K, Lmax)) > 0.3)
-    T[..., 0, 0] = 0.7                                           # the top layer: water in every other stack
-    T[..., Lmax - 1] = 1.5                                       # beyond nlay - 1 in every stack: not read
-    part_h = [rng.normal(0, 0.3, (B, c["P"], Lmax)).astype(np.float32) if k in (0, 2) else None for k in range(5)]
-    if _nan_row(N) is not None:
-        part_h[_nan_row(N) % 6][0, 1, 0] = np.nan
-    c.update(K=K, modes=T, part_h=part_h, mode_scale=rng.uniform(0.5, 30.0, lead + (K,)),
-             mode_prior=rng.uniform(0.0, 2.0, lead + (K,)), mode_y=rng.normal(0.0, 1.0, (B, K)))
-    c["mode_prior"][..., K - 1] = 0.0
-    # two rows in three are dropped here (no part_h of their source), which leaves fewer rows than unknowns at the larger shapes and
-    # the damping alone to bound cond(A); 30 x the damping of _case keeps it below the 1e4 that the relative bars of
-    # tests/test_lsq_resolution_gpu.py are derived for (asserted in _check_resolution)
-    c["lam"] = c["lam"] * LAM_FACTOR
-    return c
+def _launch_step_old(c):
+    rc, o = launch("step", c)
+    return rc, o["delta"], o["stats"], o["info"]
 
 
-def _head(c, keep, part, pred, nfree_max):
-    """The argument list the four least-squares entries share, up to and including lam."""
-    p = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)
-    partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
-    predp = (ctypes.c_void_p * 5)(*[a.data_ptr() for a in pred])
-    strides = (ctypes.c_long * 5)(*[c["P"]] * 5)
-    nper = (ctypes.c_int * 2)(c["P"], c["P"])
-    return (None, c["B"], c["Lmax"], p(keep["nlay"]), p(keep["model"]), p(keep["free"]), int(c["free"].ndim == 2),
-            c["Lmax"] if nfree_max is None else nfree_max, partp, predp, strides, nper, c["N"], p(keep["cols"]), p(keep["weights"]),
-            p(keep["obs"]), p(keep["uncer"]), p(keep["mask"]), int(c["obs"].ndim == 2), p(keep["vp_slope"]), p(keep["rho_slope"]), 1,
-            float(c["alpha"]), p(keep["Q"]), int(c["Q"].ndim == 2), p(keep["lam"]))
-
-
-def _launch(c, entry, K=None, nfree_max=None, lam_scale=1.0, no_part_h=False, **null):
-    """surfdisp_lsq_step_modes_device (entry "step") or surfdisp_lsq_resolution_modes_device ("res") on the arrays of ``c``; K:
-    the number of modes passed (default c["K"]); ``null``: names passed as NULL.  Every output is pre-filled with 7.  Returns
-    (rc, dict of numpy outputs)."""
-    import torch
-    dev = torch.device("cuda:0")
-    t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    B, Lmax = c["B"], c["Lmax"]
-    K = c["K"] if K is None else K
-    keep = {k: t(None if null.get(k) else c[k]) for k in ("nlay", "model", "free", "cols", "weights", "obs", "uncer", "mask",
-                                                          "vp_slope", "rho_slope", "Q", "modes", "mode_scale", "mode_prior", "mode_y")}
-    keep["lam"] = t(c["lam"] * lam_scale)
-    part, pred, part_h = [t(a) for a in c["part"]], [t(a) for a in c["pred"]], [t(a) for a in c["part_h"]]
-    p = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)
-    parthp = None if no_part_h else (ctypes.c_void_p * 5)(*[a.data_ptr() if a is not None else None for a in part_h])
-    mode_in = (K, p(keep["modes"]), int(c["modes"].ndim == 3), parthp, p(keep["mode_scale"]), p(keep["mode_prior"]), p(keep["mode_y"]))
-    f7 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float64, device=dev)
-    Ko = max(min(K, 8), 0)
-    no = min(Lmax if nfree_max is None else nfree_max, 128) + Ko          # (a refused launch writes nothing)
-    info = torch.full((B, 3), 7, dtype=torch.int32, device=dev)
-    if entry == "step":
-        out = dict(delta=f7(B, Lmax), delta_y=f7(B, max(Ko, 1)), stats=f7(B, 3), info=info)
-        names, fn = STEP_OUT, _lib.lib().surfdisp_lsq_step_modes_device
-    else:
-        out = dict(cov=f7(B, no, no), res=f7(B, no, no), sigma_post=f7(B, Lmax), sigma_data=f7(B, Lmax), rdiag=f7(B, Lmax),
-                   sigma_post_y=f7(B, max(Ko, 1)), sigma_data_y=f7(B, max(Ko, 1)), rdiag_y=f7(B, max(Ko, 1)), stats=f7(B, 2), info=info)
-        names, fn = RES_OUT, _lib.lib().surfdisp_lsq_resolution_modes_device
-    rc = fn(*_head(c, keep, part, pred, nfree_max), *mode_in, *[p(None if null.get(k) else out[k]) for k in names])
-    torch.cuda.synchronize()
-    return rc, {k: v.cpu().numpy() for k, v in out.items()}
+def _launch_res_old(c):
+    return launch("res", c)
 
 
 def _kept_rows(c, b):
@@ -362,6 +291,47 @@ def test_step_with_modes_on_real_kernels(name):
         linearized.LinearizedBatch(model, _datasets(per, values, (("R", "c"), ("R", "E")), 0.01, C=B), modes=T)
 
 
+def test_one_plan_with_and_without_modes_in_turn_is_a_fresh_plan_each_time_bit_for_bit():
+    """The buffers a plan keeps between calls (allocated at first use, reallocated when K changes, rewritten by the next call): six
+    calls on ONE LsqPlan - step and resolution, K = 0, 1, 2 in turn - each against the same call on a plan built for it.  The
+    kernels use no device atomics, so the bar is equality of every tensor of the result; cov and res are [B, nmax + K, nmax + K]."""
+    import torch
+    model = synth.synth_models(3, 8, seed=1)
+    B, _, L = model.shape
+    per = synth.default_periods(6)
+    truth = model.copy(); truth[:, 1, :] *= 1.03
+    data = _datasets(per, _forward_all(truth, per), (("R", "c"),), 0.01, C=B)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a)).cuda()
+    dm, lam = t(model), t(np.full(B, 3.0))
+    h = model[0, 3]
+    T = t(np.stack([linearized.interface_mode(h, [0, 1, 2], [3, 4]), linearized.thickness_mode(h, [0])]))
+    with_K = lambda K: dict(modes=T[:K].contiguous(), mode_scale=t(np.full(K, 1e-3)), mode_y=t(np.full((B, K), 0.5))) if K else {}
+
+    def flat(out):
+        """Every tensor of a result, cloned, by name: pred, part and part_h entry by entry."""
+        items = {}
+        for k, v in out.items():
+            if isinstance(v, (dict, list)):
+                items.update({f"{k}[{i}]": x for i, x in (v.items() if isinstance(v, dict) else enumerate(v))})
+            else:
+                items[k] = v
+        return {k: v.clone() for k, v in items.items() if v is not None}
+
+    calls = [("step", 0), ("step", 1), ("resolution", 2), ("resolution", 0), ("step", 2), ("step", 0)]
+    plan = linearized.LsqPlan(B, L, data)
+    for which, K in calls:
+        got = flat(getattr(plan, which)(dm, lam, alpha=0.5, **with_K(K)))
+        want = flat(getattr(linearized.LsqPlan(B, L, data), which)(dm, lam, alpha=0.5, **with_K(K)))
+        tag = f"{which}, K = {K}"
+        assert set(got) == set(want) and ("delta_y" in got or "rdiag_y" in got) == (K > 0), tag
+        assert not got["flag"].any(), tag
+        if which == "resolution":
+            assert tuple(got["cov"].shape) == (B, L + K, L + K) and tuple(got["res"].shape) == (B, L + K, L + K), tag
+        for k in want:
+            assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (tag, k)
+            assert got[k].cpu().numpy().tobytes() == want[k].cpu().numpy().tobytes(), (tag, k)
+
+
 # ------------------------------------------------------------------------------------------------- 6., 7. the iteration
 SETS_C = (("R", "c"), ("L", "c"))
 ABOVE, BELOW = [0, 1, 2, 3], [4, 5, 6]
@@ -440,59 +410,9 @@ def test_loop_invariants_with_modes(moho_problem):
 
 
 def _cpu_route_modes(start, per, data, n_iter, T, mode_scale):
-    """_cpu_route of tests/test_lsq_gpu.py (numpy float64, forward solves of the CPU checker, central differences of 1 % of Vs)
-    with one more column: the central difference of the mode amplitude, +-1 % of the upper group's thickness, and the step of
-    lsq_modes_step_reference.  Returns (model, rms, y)."""
-    from oracle import cport
-    M, _, L = start.shape
-    eps = 0.01
-
-    def fwd(m):
-        cR, _, sR = cport.forward_batch(m, per, 2, nthreads=8)
-        cL, _, sL = cport.forward_batch(m, per, 1, nthreads=8)
-        return dict(cR=cR.astype(np.float64), cL=cL.astype(np.float64)), (sR != 0) | (sL != 0)
-
-    def objective(m):
-        p, bad = fwd(m)
-        chi, rms = _chi_rms(p, data)
-        rough = (np.diff(m[:, 1, :].astype(np.float64), axis=1) ** 2).sum(axis=1)
-        return np.where(bad, np.inf, chi + ALPHA * rough), rms
-
-    model, y = start.copy(), np.zeros(M)
-    obj, rms = objective(model)
-    assert np.isfinite(obj).all()
-    lam = np.full(M, LAM0)
-    sig = np.concatenate([d.uncer for d in data], axis=1)                                   # [M, N]: the data are per stack
-    obsv = np.concatenate([d.values for d in data], axis=1)
-    keys = ("cR", "cL")
-    for _ in range(n_iter):
-        ey = 0.01 * model[:, 3, ABOVE].astype(np.float64).sum(axis=1)                       # [M] km
-        big = np.repeat(model, 2 * L + 2, axis=0).reshape(M, 2 * L + 2, 5, L)
-        for i in range(L):
-            big[:, i, 1, i] *= (1 - eps); big[:, L + i, 1, i] *= (1 + eps)
-        big[:, 2 * L, 3, :] = (model[:, 3, :].astype(np.float64) - T[None, :] * ey[:, None]).astype(np.float32)
-        big[:, 2 * L + 1, 3, :] = (model[:, 3, :].astype(np.float64) + T[None, :] * ey[:, None]).astype(np.float32)
-        pb, bad = fwd(big.reshape(M * (2 * L + 2), 5, L))
-        assert not bad.any()
-        pc, _ = fwd(model)
-        trial, ty = model.copy(), y.copy()
-        for m in range(M):
-            v = np.concatenate([pb[k].reshape(M, 2 * L + 2, per.size)[m] for k in keys], axis=1)    # [2L + 2, N]
-            f0 = np.concatenate([pc[k][m] for k in keys])
-            G = ((v[L:2 * L] - v[:L]) / (2 * eps * model[m, 1, :].astype(np.float64))[:, None]).T
-            Gy = ((v[2 * L + 1] - v[2 * L]) / (2 * ey[m]))[:, None]
-            st = linearized.lsq_modes_step_reference(G, obsv[m] - f0, 1.0 / sig[m] ** 2, model[m, 1].astype(np.float64), ALPHA,
-                                                     np.ones(L - 1), lam[m], Gy, mode_scale, 0.0, y[m])
-            trial[m, 1] = (model[m, 1].astype(np.float64) + st["delta"]).astype(np.float32)
-            trial[m, 3] = (model[m, 3].astype(np.float64) + T * st["delta_y"][0]).astype(np.float32)
-            ty[m] = y[m] + st["delta_y"][0]
-        tobj, trms = objective(trial)
-        acc = tobj < obj
-        model = np.where(acc[:, None, None], trial, model)
-        y = np.where(acc, ty, y)
-        obj, rms = np.where(acc, tobj, obj), np.where(acc, trms, rms)
-        lam = np.where(acc, np.maximum(lam / NU, LAM_MIN), lam * NU)
-    return model, rms, y
+    """``lsq_cases.cpu_route`` with the mode T as one more unknown, its finite-difference step 1 % of the upper group's thickness.
+    Returns (model, rms, y)."""
+    return cpu_route(start, per, data, n_iter, T, mode_scale, ABOVE)
 
 
 def test_recovery_of_a_displaced_interface(moho_problem):

@@ -4,9 +4,9 @@ argument errors.  CPU only."""
 import numpy as np
 import pytest
 
+from lsq_cases import _problem
 from pysurfinv_amd import linearized, synth
 from pysurfinv_amd.obsdata import DispersionData
-from test_lsq_host import _problem
 
 H = np.array([0.5, 1.5, 2.0, 6.0, 10.0, 12.0, 8.0, 0.0])                    # the last layer is the half space
 

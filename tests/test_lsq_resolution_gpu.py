@@ -9,49 +9,19 @@ most 2e-5 of the first bar and 2e-4 of the second on these cases; a float32 fact
 residual, above its bar.  Diagonals (rdiag, sigma_post^2, sigma_data^2) against the reference: relative 1e-9 plus 1e-12 of the
 largest; dof to 1e-9 n; log det A to 1e-10 (|log det A| + n).  The conditioning of A on these cases is below 1e4, so cond(A) eps
 ~ 1e-12 stands three digits below the relative bar.  Counts, flags, zeros and the symmetry of cov are exact."""
-import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+from lsq_cases import (ALPHA, CASES, ENTRIES, LAM0, LAM_MIN, NU, SETS3, _case, _datasets, _forward_all, _rows_of, _true_and_start,
+                       launch)
 from pysurfinv_amd import _lib, linearized, synth
-from test_lsq_gpu import (ALPHA, CASES, LAM0, LAM_MIN, NU, SETS3, _case, _datasets, _forward_all, _rows_of,
-                          _true_and_start)
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("cov", "res", "sigma_post", "sigma_data", "rdiag", "stats", "info")
-
-
-def _launch(c, nfree_max=None, lam_scale=1.0, no_cov=False, no_res=False, **null):
-    """surfdisp_lsq_resolution_device on the arrays of ``c``; ``null``: inputs passed as NULL; ``no_cov`` / ``no_res``: that
-    output passed as NULL.  Every output buffer is pre-filled with 7.  Returns (rc, dict of numpy outputs)."""
-    import torch
-    dev = torch.device("cuda:0")
-    t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    B, Lmax, N = c["B"], c["Lmax"], c["N"]
-    nmax = Lmax if nfree_max is None else nfree_max
-    keep = {k: t(None if null.get(k) else c[k]) for k in ("nlay", "model", "free", "cols", "weights", "obs", "uncer", "mask",
-                                                          "vp_slope", "rho_slope", "Q")}
-    keep["lam"] = None if null.get("lam") else t(c["lam"] * lam_scale)
-    part, pred = [t(a) for a in c["part"]], [t(a) for a in c["pred"]]
-    f7 = lambda *shape: torch.full(shape, 7.0, dtype=torch.float64, device=dev)
-    nm = min(nmax, 128)                                                     # (a refused launch writes nothing)
-    out = dict(cov=f7(B, nm, nm), res=f7(B, nm, nm), sigma_post=f7(B, Lmax), sigma_data=f7(B, Lmax), rdiag=f7(B, Lmax),
-               stats=f7(B, 2), info=torch.full((B, 3), 7, dtype=torch.int32, device=dev))
-    p = lambda x: ctypes.c_void_p(x.data_ptr() if x is not None else 0)
-    po = lambda k: p(None if null.get(k) or (k == "cov" and no_cov) or (k == "res" and no_res) else out[k])
-    partp = (ctypes.c_void_p * 15)(*[a.data_ptr() if a is not None else None for a in part])
-    predp = (ctypes.c_void_p * 5)(*[a.data_ptr() for a in pred])
-    strides = (ctypes.c_long * 5)(*[c["P"]] * 5)
-    nper = (ctypes.c_int * 2)(c["P"], c["P"])
-    rc = _lib.lib().surfdisp_lsq_resolution_device(
-        None, B, Lmax, p(keep["nlay"]), p(keep["model"]), p(keep["free"]), int(c["free"].ndim == 2), nmax, partp, predp, strides,
-        nper, N, p(keep["cols"]), p(keep["weights"]), p(keep["obs"]), p(keep["uncer"]), p(keep["mask"]), int(c["obs"].ndim == 2),
-        p(keep["vp_slope"]), p(keep["rho_slope"]), 1, float(c["alpha"]), p(keep["Q"]), int(c["Q"].ndim == 2), p(keep["lam"]),
-        *[po(k) for k in NAMES])
-    torch.cuda.synchronize()
-    return rc, {k: v.cpu().numpy() for k, v in out.items()}
+NAMES = ENTRIES["res"][1]
+_launch = functools.partial(launch, "res")          # surfdisp_lsq_resolution_device on the arrays of a case: (rc, dict of numpy outputs)
 
 
 def _check_stack(tag, idx, Qw, G, w, alpha, lam, o, b, N):
