@@ -870,6 +870,44 @@ size_t surfdisp_posterior_workspace_bytes(int npoints, int R, int N, int D)
     return units * ((size_t)(D + N) * 5 * sizeof(double) + sizeof(double) + 4 * sizeof(int));
 }
 
+// What the two entries on a track ((6f) profiles, (6g) sources) share: the sizes both refuse (each with its own text), ...
+static bool post_track_sizes_ok(int npoints, int R, long row_stride, long min_stride)
+{
+    return npoints >= 1 && R >= 1 && R <= (1 << 30) && row_stride >= min_stride && (long)npoints * post_slabs(R) <= 0x7fffffffL;
+}
+// ... the prefix rule, ...
+static int post_check_prefix(const char *name, int R, int chainL, int prefix)
+{
+    if (chainL > 0 && (prefix < 1 || prefix > chainL || R % chainL != 0)) {
+        set_err("%s: invalid prefix: 1 <= prefix <= chainL and R a multiple of chainL", name); return SURFDISP_ERR_INVALID;
+    }
+    return SURFDISP_SUCCESS;
+}
+
+// ... and the selection part of a PostArgs (what launch_post_selection reads and writes): sizes, rule, track, the four selection
+// outputs and the [npoints][nslab] tail of the workspace from `tail` on - doubles first, then the four int arrays.
+static void post_fill_selection(sd::PostArgs &a, int npoints, int R, const double *track, long row_stride, int true_markov_chain,
+                                int chainL, int prefix, double *min_misfit, double *thres, int *imin, int *n_final, void *tail)
+{
+    a.npoints = npoints; a.R = R; a.nslab = (int)post_slabs(R);
+    a.tmc = true_markov_chain ? 1 : 0; a.chainL = chainL > 0 ? chainL : 0; a.prefix = prefix;
+    a.row_stride = row_stride; a.track = track;
+    a.min_misfit = min_misfit; a.thres = thres; a.imin = imin; a.n_final = n_final;
+    const size_t units = (size_t)npoints * a.nslab;
+    a.ws_mis = static_cast<double *>(tail);
+    a.ws_row = reinterpret_cast<int *>(a.ws_mis + units);
+    a.ws_last = a.ws_row + units; a.ws_carry = a.ws_last + units; a.ws_nfin = a.ws_carry + units;
+}
+
+// hist [cols][nbins], below [cols], above [cols] zeroed on the stream: the kernels add into them
+static int post_zero_hist(hipStream_t s, int *hist, int *below, int *above, size_t cols, int nbins)
+{
+    SD_HIP(hipMemsetAsync(hist, 0, cols * nbins * sizeof(int), s));
+    SD_HIP(hipMemsetAsync(below, 0, cols * sizeof(int), s));
+    SD_HIP(hipMemsetAsync(above, 0, cols * sizeof(int), s));
+    return SURFDISP_SUCCESS;
+}
+
 // the integer part of the params->stack descriptor (layout: csrc/surfdisp_layers.hip), as the profile kernel walks it
 static const char *post_check_desc(const int *idesc, int len, int width, bool has_aux, int N)
 {
@@ -906,8 +944,8 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
                                       void *workspace, size_t workspace_bytes)
 {
     const char *name = "surfdisp_posterior_profile_device";
-    if (npoints < 1 || R < 1 || R > (1 << 30) || N < 1 || N > sd::SD_POST_MAX_PARAMS || row_stride < 3 + (long)N || K < 0 ||
-        D < 1 || D > SURFDISP_POST_DEPTHS_MAX || (long)npoints * post_slabs(R) > 0x7fffffffL) {
+    if (!post_track_sizes_ok(npoints, R, row_stride, 3 + (long)N) || N < 1 || N > sd::SD_POST_MAX_PARAMS || K < 0 || D < 1 ||
+        D > SURFDISP_POST_DEPTHS_MAX) {
         set_err("%s: invalid size (npoints, R, N >= 1; N <= 128; R <= 2^30; row_stride >= 3 + N; K >= 0; 1 <= D <= 256)", name);
         return SURFDISP_ERR_INVALID;
     }
@@ -922,9 +960,7 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
     if (hist && (nbins < 1 || !std::isfinite(vlo) || !std::isfinite(vhi) || !(vhi > vlo))) {
         set_err("%s: invalid histogram: nbins >= 1, finite vlo < vhi", name); return SURFDISP_ERR_INVALID;
     }
-    if (chainL > 0 && (prefix < 1 || prefix > chainL || R % chainL != 0)) {
-        set_err("%s: invalid prefix: 1 <= prefix <= chainL and R a multiple of chainL", name); return SURFDISP_ERR_INVALID;
-    }
+    if (int rc = post_check_prefix(name, R, chainL, prefix)) return rc;
     if (const char *why = post_check_desc(idesc, idesc_len, N + K, aux != nullptr, N)) {
         set_err("%s: invalid descriptor: %s", name, why); return SURFDISP_ERR_INVALID;
     }
@@ -932,16 +968,11 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
         set_err("%s: invalid workspace: smaller than surfdisp_posterior_workspace_bytes", name); return SURFDISP_ERR_INVALID;
     }
     sd::PostArgs a{};
-    a.npoints = npoints; a.R = R; a.N = N; a.K = K; a.D = D; a.nslab = (int)post_slabs(R);
-    a.tmc = true_markov_chain ? 1 : 0; a.chainL = chainL > 0 ? chainL : 0; a.prefix = prefix;
-    a.row_stride = row_stride; a.track = track; a.fdesc = fdesc; a.aux = aux; a.rows = aux ? rows : nullptr;
-    a.min_misfit = min_misfit; a.thres = thres; a.imin = imin; a.n_final = n_final; a.pmean = pmean; a.pstd = pstd;
-    a.count = count; a.vs_mean = vs_mean; a.vs_std = vs_std; a.vs_min = vs_min; a.vs_max = vs_max;
-    const size_t units = (size_t)npoints * a.nslab;
     a.ws_part = static_cast<double *>(workspace);
-    a.ws_mis = a.ws_part + units * (size_t)(D + N) * 5;
-    a.ws_row = reinterpret_cast<int *>(a.ws_mis + units);
-    a.ws_last = a.ws_row + units; a.ws_carry = a.ws_last + units; a.ws_nfin = a.ws_carry + units;
+    post_fill_selection(a, npoints, R, track, row_stride, true_markov_chain, chainL, prefix, min_misfit, thres, imin, n_final,
+                        a.ws_part + (size_t)npoints * (size_t)post_slabs(R) * (size_t)(D + N) * 5);
+    a.N = N; a.K = K; a.D = D; a.fdesc = fdesc; a.aux = aux; a.rows = aux ? rows : nullptr; a.pmean = pmean; a.pstd = pstd;
+    a.count = count; a.vs_mean = vs_mean; a.vs_std = vs_std; a.vs_min = vs_min; a.vs_max = vs_max;
     const int nin = idesc[0];
     for (int i = 0; i < 4 + 16 * nin; ++i) a.idesc[i] = idesc[i];
     for (int d = 0; d < D; ++d) a.zdeps[d] = zdeps[d];
@@ -949,9 +980,7 @@ int surfdisp_posterior_profile_device(void *stream, int npoints, int R, int N, c
     if (hist) {
         a.hist = hist; a.below = below; a.above = above; a.nbins = nbins; a.vlo = vlo; a.vhi = vhi;
         a.bin_w = (vhi - vlo) / nbins; a.inv_w = nbins / (vhi - vlo);
-        SD_HIP(hipMemsetAsync(hist, 0, (size_t)npoints * D * nbins * sizeof(int), s));
-        SD_HIP(hipMemsetAsync(below, 0, (size_t)npoints * D * sizeof(int), s));
-        SD_HIP(hipMemsetAsync(above, 0, (size_t)npoints * D * sizeof(int), s));
+        if (int rc = post_zero_hist(s, hist, below, above, (size_t)npoints * D, nbins)) return rc;
     }
     SD_HIP(sd::launch_posterior(s, a));
     return SURFDISP_SUCCESS;
@@ -972,29 +1001,20 @@ int surfdisp_posterior_sources_device(void *stream, int npoints, int R, const do
                                       void *workspace, size_t workspace_bytes)
 {
     const char *name = "surfdisp_posterior_sources_device";
-    if (npoints < 1 || R < 1 || R > (1 << 30) || row_stride < 3 || (long)npoints * post_slabs(R) > 0x7fffffffL) {
+    if (!post_track_sizes_ok(npoints, R, row_stride, 3)) {
         set_err("%s: invalid size (npoints, R >= 1; R <= 2^30; row_stride >= 3; npoints x slabs <= 2^31 - 1)", name);
         return SURFDISP_ERR_INVALID;
     }
     if (!track || !min_misfit || !thres || !imin || !n_final || !weight || !n_sources || !imin_source || !workspace) {
         set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
     }
-    if (chainL > 0 && (prefix < 1 || prefix > chainL || R % chainL != 0)) {
-        set_err("%s: invalid prefix: 1 <= prefix <= chainL and R a multiple of chainL", name); return SURFDISP_ERR_INVALID;
-    }
+    if (int rc = post_check_prefix(name, R, chainL, prefix)) return rc;
     if (workspace_bytes < surfdisp_posterior_sources_workspace_bytes(npoints, R)) {
         set_err("%s: invalid workspace: smaller than surfdisp_posterior_sources_workspace_bytes", name); return SURFDISP_ERR_INVALID;
     }
     sd::PostSourcesArgs S{};
-    sd::PostArgs &a = S.sel;
-    a.npoints = npoints; a.R = R; a.nslab = (int)post_slabs(R);
-    a.tmc = true_markov_chain ? 1 : 0; a.chainL = chainL > 0 ? chainL : 0; a.prefix = prefix;
-    a.row_stride = row_stride; a.track = track;
-    a.min_misfit = min_misfit; a.thres = thres; a.imin = imin; a.n_final = n_final;
-    const size_t units = (size_t)npoints * a.nslab;
-    a.ws_mis = static_cast<double *>(workspace);
-    a.ws_row = reinterpret_cast<int *>(a.ws_mis + units);
-    a.ws_last = a.ws_row + units; a.ws_carry = a.ws_last + units; a.ws_nfin = a.ws_carry + units;
+    post_fill_selection(S.sel, npoints, R, track, row_stride, true_markov_chain, chainL, prefix, min_misfit, thres, imin, n_final,
+                        workspace);
     S.weight = weight; S.n_sources = n_sources; S.imin_source = imin_source;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SD_HIP(hipMemsetAsync(weight, 0, (size_t)npoints * R * sizeof(int), s));
@@ -1052,9 +1072,7 @@ int surfdisp_posterior_predictive_device(void *stream, int npoints, int total, i
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (hist) {
         a.hist = hist; a.below = below; a.above = above; a.nbins = nbins;
-        SD_HIP(hipMemsetAsync(hist, 0, (size_t)npoints * P * nbins * sizeof(int), s));
-        SD_HIP(hipMemsetAsync(below, 0, (size_t)npoints * P * sizeof(int), s));
-        SD_HIP(hipMemsetAsync(above, 0, (size_t)npoints * P * sizeof(int), s));
+        if (int rc = post_zero_hist(s, hist, below, above, (size_t)npoints * P, nbins)) return rc;
     }
     SD_HIP(sd::launch_pred_stats(s, a, vlo, vhi));
     return SURFDISP_SUCCESS;

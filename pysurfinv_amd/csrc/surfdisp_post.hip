@@ -6,13 +6,15 @@
 //   K1 post_select_kernel   one workgroup per (slab of SD_POST_SLAB rows, point): smallest misfit with its first row, last accepted row
 //   K2 post_threshold_kernel one thread per point: slabs merged in order -> min_misfit, imin, thres; the accepted row every slab starts from
 //   K3 post_profile_kernel  one workgroup per (slab, point, chunk of 64 depths): 256 rows at a time -
-//        phase 1 (a thread per row): final test, the row whose parameters count (max-scan of the accepted rows, carried across
-//        the tiles and slabs), the final rows compacted in row order into LDS with their layer tops;
+//        phase 1 (a thread per row): tile_scan - final test, the row whose parameters count (carried across the tiles and
+//        slabs) -, the final rows compacted in row order into LDS with their layer tops;
 //        phase 2 (a lane per depth, a wavefront per final row): Vs at the lane's depth from the layer tops, the two bracketing grid
-//        points' t and basis rows, and the parameters read from the track IN PLACE; every lane keeps (n, pivot, sum, sum of
-//        squares, min, max) of its depth in registers - in chunk 0 also of parameter `lane` and `lane + 64`;
-//        per slab the four wavefronts' figures are merged in wavefront order and stored as (n, mean, M2, min, max).
-//   K4 post_finish_kernel   one thread per (point, depth or parameter): the slabs' partials merged in slab order (Chan's pairwise update).
+//        points' t and basis rows, and the parameters read from the track IN PLACE; every lane keeps an Acc of its depth in
+//        registers (weight 1.0; hist_add for the histogram) - in chunk 0 also of parameter `lane` and `lane + 64`;
+//        per slab waves_merge_store.
+//   K4 post_finish_kernel   one thread per (point, depth or parameter): slabs_merge, the results written.
+// tile_scan, Acc, hist_add, waves_merge_store and slabs_merge are stated in csrc/surfdisp_post_common.h, for this file and
+// csrc/surfdisp_pred.hip alike.
 // Every sum is fp64 and runs in an order the input alone fixes: two calls give the same bits.  Only the histogram counts are
 // integer atomics.  No per-thread array (see surfdisp_mcmc.hip, propose kernel), no scratch, 24 KB of static LDS.
 // The arithmetic follows numpy's statement by statement (np.interp: slope * (x - x0) + y0), without contraction to fma.
@@ -27,27 +29,6 @@ namespace sd {
 
 constexpr int POST_TOPS = SD_POST_MAX_LAYERS + 1;
 
-// running figures of one column (a depth, or a parameter) over the final rows, in row order
-struct Acc { double n, piv, s1, s2, mn, mx; };
-__device__ __forceinline__ void acc_clear(Acc &a) { a.n = 0.0; a.piv = 0.0; a.s1 = 0.0; a.s2 = 0.0; a.mn = 0.0; a.mx = 0.0; }
-__device__ __forceinline__ void acc_add(Acc &a, double v)
-{
-    if (!isfinite(v)) return;
-    if (a.n == 0.0) { a.piv = v; a.mn = v; a.mx = v; }
-    const double d = v - a.piv;                        // sums about the first value: no cancellation at Vs ~ 4 +- 0.3
-    a.s1 += d; a.s2 += d * d; a.n += 1.0;
-    a.mn = fmin(a.mn, v); a.mx = fmax(a.mx, v);
-}
-__device__ __forceinline__ Part acc_part(const Acc &a)
-{
-    Part p{a.n, 0.0, 0.0, a.mn, a.mx};
-    if (a.n > 0.0) {
-        p.mean = a.piv + a.s1 / a.n;
-        const double m2 = a.s2 - a.s1 * a.s1 / a.n;
-        p.m2 = m2 > 0.0 ? m2 : 0.0;
-    }
-    return p;
-}
 // value `sl` of the [params | aux] row of track row `prow`
 __device__ __forceinline__ double slot_value(const PostArgs &A, const double *prow, const double *arow, int sl)
 {
@@ -174,30 +155,11 @@ __global__ __launch_bounds__(POST_BLOCK) void post_profile_kernel(PostArgs A)
     int carry = A.ws_carry[(size_t)pt * A.nslab + slab];
     int nfin = 0;
     for (int t0 = r0; t0 < r1; t0 += POST_BLOCK) {
-        // ---- phase 1: a thread per row
-        const int r = t0 + tid;
-        bool fin = false;
-        int cand = -1;
-        if (r < r1) {
-            const double *p = trk + (size_t)r * A.row_stride;
-            fin = row_misfit(A, p, r) < thres;
-            cand = (!A.tmc || p[2] > 0.5) ? r : -1;
-        }
-        for (int o = 1; o < 64; o <<= 1) {             // inclusive max-scan: the last accepted row at or before this one
-            const int v = __shfl_up(cand, o);
-            if (lane >= o) cand = max(cand, v);
-        }
-        const unsigned long long bal = __ballot(fin);
-        if (lane == 63) s_wmax[w] = cand;
-        if (lane == 0) s_wcnt[w] = __popcll(bal);
-        __syncthreads();
-        int pre = carry, off = 0, total = 0, next = carry;
-        for (int q = 0; q < POST_WAVES; ++q) {
-            if (q < w) { pre = max(pre, s_wmax[q]); off += s_wcnt[q]; }
-            next = max(next, s_wmax[q]); total += s_wcnt[q];
-        }
-        if (fin) s_src[off + __popcll(bal & ((1ull << lane) - 1ull))] = max(cand, pre);
-        carry = next;
+        // ---- phase 1: a thread per row (tile_scan, csrc/surfdisp_post_common.h); the final rows' sources compacted in row order
+        const TileScan ts = tile_scan(A, trk, t0 + tid, r1, thres, carry, s_wmax, s_wcnt);
+        const int total = ts.total;
+        if (ts.fin) s_src[ts.pos] = ts.src;
+        carry = ts.carry;
         nfin += total;
         __syncthreads();
         if (tid < total) {                             // layer tops of final row `tid` of the list: z0, then + H layer by layer
@@ -219,21 +181,11 @@ __global__ __launch_bounds__(POST_BLOCK) void post_profile_kernel(PostArgs A)
             const double *p = trk + (size_t)src * A.row_stride;
             if (has_d) {
                 const double v = vs_at_depth(A, s_buf + j, p, arow, zd);
-                acc_add(ad, v);
-                if (A.hist && isfinite(v)) {
-                    if (v < A.vlo) atomicAdd(&A.below[(size_t)pt * A.D + d], 1);
-                    else if (!(v < A.vhi)) atomicAdd(&A.above[(size_t)pt * A.D + d], 1);
-                    else {                             // the bin of edges vlo + i w (np.linspace): a guess, then the edges themselves
-                        int b = (int)((v - A.vlo) * A.inv_w);
-                        b = b < 0 ? 0 : (b > A.nbins - 1 ? A.nbins - 1 : b);
-                        if (b > 0 && v < (double)b * A.bin_w + A.vlo) --b;
-                        else if (b < A.nbins - 1 && v >= (double)(b + 1) * A.bin_w + A.vlo) ++b;
-                        atomicAdd(&A.hist[((size_t)pt * A.D + d) * A.nbins + b], 1);
-                    }
-                }
+                if (acc_add(ad, v, 1.0) && A.hist)
+                    hist_add(A.hist, A.below, A.above, (size_t)pt * A.D + d, A.nbins, v, A.vlo, A.vhi, A.bin_w, A.inv_w, 1);
             }
-            if (has_p0) acc_add(ap0, p[3 + lane]);
-            if (has_p1) acc_add(ap1, p[3 + lane + 64]);
+            if (has_p0) acc_add(ap0, p[3 + lane], 1.0);
+            if (has_p1) acc_add(ap1, p[3 + lane + 64], 1.0);
         }
         __syncthreads();
     }
@@ -247,12 +199,7 @@ __global__ __launch_bounds__(POST_BLOCK) void post_profile_kernel(PostArgs A)
         __syncthreads();
         const int col = which == 0 ? d : A.D + lane + 64 * (which - 1);
         const bool live = which == 0 ? has_d : (which == 1 ? has_p0 : has_p1);
-        if (w == 0 && live) {
-            Part m = sp[lane];
-            for (int q = 1; q < POST_WAVES; ++q) part_merge(m, sp[q * 64 + lane]);
-            double *o = out + (size_t)col * 5;
-            o[0] = m.n; o[1] = m.mean; o[2] = m.m2; o[3] = m.mn; o[4] = m.mx;
-        }
+        if (w == 0 && live) waves_merge_store(sp, lane, out + (size_t)col * 5);
         __syncthreads();
     }
     if (par && tid == 0) A.ws_nfin[(size_t)pt * A.nslab + slab] = nfin;
@@ -264,15 +211,12 @@ __global__ __launch_bounds__(POST_BLOCK) void post_finish_kernel(PostArgs A)
     const long idx = (long)blockIdx.x * POST_BLOCK + threadIdx.x;
     if (idx >= (long)A.npoints * ncol) return;
     const int pt = (int)(idx / ncol), col = (int)(idx % ncol);
-    Part m{0.0, 0.0, 0.0, 0.0, 0.0};
-    int nfin = 0;
-    for (int s = 0; s < A.nslab; ++s) {
-        const size_t k = (size_t)pt * A.nslab + s;
-        const double *o = A.ws_part + (k * ncol + col) * 5;
-        part_merge(m, Part{o[0], o[1], o[2], o[3], o[4]});
-        if (col == 0) nfin += A.ws_nfin[k];
+    const Part m = slabs_merge(A.ws_part + ((size_t)pt * A.nslab * ncol + col) * 5, (size_t)ncol * 5, A.nslab);
+    if (col == 0) {
+        int nfin = 0;
+        for (int s = 0; s < A.nslab; ++s) nfin += A.ws_nfin[(size_t)pt * A.nslab + s];
+        A.n_final[pt] = nfin;
     }
-    if (col == 0) A.n_final[pt] = nfin;
     const bool any = m.n > 0.0;
     const double mean = any ? m.mean : NAN, sd = any ? sqrt(m.m2 / m.n) : NAN;
     if (col < A.D) {
@@ -297,8 +241,8 @@ hipError_t launch_post_selection(hipStream_t s, const PostArgs &a)
 hipError_t launch_posterior(hipStream_t s, const PostArgs &a)
 {
     const int nchunk = (a.D + 63) / 64;
-    hipLaunchKernelGGL(post_select_kernel, dim3(a.npoints * a.nslab), dim3(POST_BLOCK), 0, s, a);
-    hipLaunchKernelGGL(post_threshold_kernel, dim3((a.npoints + 63) / 64), dim3(64), 0, s, a);
+    const hipError_t e = launch_post_selection(s, a);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(post_profile_kernel, dim3(a.npoints * a.nslab, nchunk), dim3(POST_BLOCK), 0, s, a);
     const long total = (long)a.npoints * (a.D + a.N);
     hipLaunchKernelGGL(post_finish_kernel, dim3((unsigned)((total + POST_BLOCK - 1) / POST_BLOCK)), dim3(POST_BLOCK), 0, s, a);

@@ -6,21 +6,21 @@
 //     models among the final rows are far fewer than the final rows.  Four launches on the caller's stream:
 //       K1, K2 post_select_kernel / post_threshold_kernel of csrc/surfdisp_post.hip (launch_post_selection): min_misfit, imin, thres
 //              and the accepted row every slab of SD_POST_SLAB rows starts from (ws_carry)
-//       K3 post_sources_kernel  one workgroup per (slab, point), 256 rows at a time, a thread per row - phase 1 of
-//              post_profile_kernel: the final test and the row whose parameters count (inclusive max-scan of the accepted rows,
-//              carried across the tiles and slabs); every final row adds 1 to weight[source row] (integer atomics: no order),
+//       K3 post_sources_kernel  one workgroup per (slab, point), 256 rows at a time, a thread per row - tile_scan
+//              (csrc/surfdisp_post_common.h), as phase 1 of post_profile_kernel: the final test and the row whose parameters count,
+//              carried across the tiles and slabs; every final row adds 1 to weight[source row] (integer atomics: no order),
 //              the thread of row imin writes imin_source, the slab's final rows go to ws_nfin
 //       K4 post_sources_count_kernel  one workgroup per point: n_sources = rows with weight > 0, n_final = the slabs' sum
 // (2) surfdisp_posterior_predictive_device: weighted column statistics of a list of predictions [total][ld] (float32, P columns
 //     used), segmented by point through offsets [npoints + 1].  Two launches (with a histogram K5 is launched once per chunk of 64
 //     columns: the per-column ranges travel in the kernel arguments):
 //       K5 pred_stats_kernel   one workgroup per (slab, point, chunk of 64 columns): a lane is a column, so the rows of pred are read
-//              coalesced; the four wavefronts stride over the rows of the slab.  Every lane keeps (n, pivot, sum w d, sum w d^2,
-//              min, max) of its column in registers, in fp64, about the first value it counted; the wavefronts are merged in
-//              wavefront order (weighted Chan update) into (n, mean, M2, min, max) per slab.  The point's list is cut into slabs of
+//              coalesced; the four wavefronts stride over the rows of the slab.  Every lane keeps the Acc of its column in
+//              registers (the profile kernel's, here with the row's integer weight; hist_add for the histogram), then
+//              waves_merge_store per slab.  The point's list is cut into slabs of
 //              SD_PRED_SLAB rows; workgroup s of the nslab of a point walks slabs s, s + nslab, ... (nslab is fixed by `total`
 //              alone), so a list of any length is covered.
-//       K6 pred_finish_kernel  one thread per (point, column): the slabs merged in slab order, the results written.
+//       K6 pred_finish_kernel  one thread per (point, column): slabs_merge, the results written.
 // Every sum runs in an order the input alone fixes: two calls give the same bits.  Only the histogram counts are integer atomics
 // (adding the row's weight).  No per-thread array, no scratch, LDS only for the merge (10 KB).
 // The row loops of K5 hold no barrier: the wavefronts of a workgroup walk different numbers of rows, and every __syncthreads()
@@ -38,9 +38,7 @@ __global__ __launch_bounds__(POST_BLOCK) void post_sources_kernel(PostSourcesArg
 {
     __shared__ int s_wmax[POST_WAVES], s_wcnt[POST_WAVES];
     const PostArgs &A = S.sel;
-    const int slab = blockIdx.x % A.nslab, pt = blockIdx.x / A.nslab;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slab = blockIdx.x % A.nslab, pt = blockIdx.x / A.nslab, tid = threadIdx.x;
     const int r0 = slab * SD_POST_SLAB, r1 = min(A.R, r0 + SD_POST_SLAB);
     const double *trk = A.track + (size_t)pt * A.R * A.row_stride;
     int *wgt = S.weight + (size_t)pt * A.R;
@@ -50,31 +48,11 @@ __global__ __launch_bounds__(POST_BLOCK) void post_sources_kernel(PostSourcesArg
     int nfin = 0;
     for (int t0 = r0; t0 < r1; t0 += POST_BLOCK) {         // the same bound for every thread of the workgroup
         const int r = t0 + tid;
-        bool fin = false;
-        int cand = -1;
-        if (r < r1) {
-            const double *p = trk + (size_t)r * A.row_stride;
-            fin = row_misfit(A, p, r) < thres;
-            cand = (!A.tmc || p[2] > 0.5) ? r : -1;
-        }
-        for (int o = 1; o < 64; o <<= 1) {                 // inclusive max-scan: the last accepted row at or before this one
-            const int v = __shfl_up(cand, o);
-            if (lane >= o) cand = max(cand, v);
-        }
-        const unsigned long long bal = __ballot(fin);
-        if (lane == 63) s_wmax[w] = cand;
-        if (lane == 0) s_wcnt[w] = __popcll(bal);
-        __syncthreads();
-        int pre = carry, next = carry;
-        for (int q = 0; q < POST_WAVES; ++q) {
-            if (q < w) pre = max(pre, s_wmax[q]);
-            next = max(next, s_wmax[q]);
-            nfin += s_wcnt[q];
-        }
-        const int src = max(cand, pre);                    // 0 <= src <= r
-        if (fin) atomicAdd(&wgt[src], 1);
-        if (r < r1 && r == imin) S.imin_source[pt] = src;
-        carry = next;
+        const TileScan ts = tile_scan(A, trk, r, r1, thres, carry, s_wmax, s_wcnt);
+        if (ts.fin) atomicAdd(&wgt[ts.src], 1);            // 0 <= src <= r
+        if (r < r1 && r == imin) S.imin_source[pt] = ts.src;
+        carry = ts.carry;
+        nfin += ts.total;
         __syncthreads();
     }
     if (tid == 0) A.ws_nfin[(size_t)pt * A.nslab + slab] = nfin;
@@ -109,26 +87,6 @@ hipError_t launch_post_sources(hipStream_t s, const PostSourcesArgs &a)
     return hipGetLastError();
 }
 
-// running figures of one column over the rows that count, each with its integer weight, in row order
-struct WAcc { double n, piv, s1, s2, mn, mx; };
-__device__ __forceinline__ void wacc_add(WAcc &a, double v, double wt)
-{
-    if (a.n == 0.0) { a.piv = v; a.mn = v; a.mx = v; }
-    const double d = v - a.piv;                            // sums about the first value: no cancellation at c ~ 3.5 +- 0.1
-    a.s1 += wt * d; a.s2 += wt * (d * d); a.n += wt;
-    a.mn = fmin(a.mn, v); a.mx = fmax(a.mx, v);
-}
-__device__ __forceinline__ Part wacc_part(const WAcc &a)
-{
-    Part p{a.n, 0.0, 0.0, a.mn, a.mx};
-    if (a.n > 0.0) {
-        p.mean = a.piv + a.s1 / a.n;
-        const double m2 = a.s2 - a.s1 * a.s1 / a.n;
-        p.m2 = m2 > 0.0 ? m2 : 0.0;
-    }
-    return p;
-}
-
 __global__ __launch_bounds__(POST_BLOCK) void pred_stats_kernel(PredArgs A)
 {
     __shared__ Part s_part[POST_WAVES * 64];               // [wavefront][lane]
@@ -143,7 +101,8 @@ __global__ __launch_bounds__(POST_BLOCK) void pred_stats_kernel(PredArgs A)
     const double vlo = hist ? A.vlo[lane] : 0.0, vhi = hist ? A.vhi[lane] : 1.0;
     const double bin_w = (vhi - vlo) / A.nbins, inv_w = A.nbins / (vhi - vlo);
     const size_t ocol = (size_t)pt * A.P + col;
-    WAcc a{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    Acc a;
+    acc_clear(a);
     int nfail = 0;
     for (long s0 = lo + (long)slab * SD_PRED_SLAB; s0 < hi; s0 += (long)A.nslab * SD_PRED_SLAB) {
         const long s1 = min(hi, s0 + SD_PRED_SLAB);
@@ -153,32 +112,16 @@ __global__ __launch_bounds__(POST_BLOCK) void pred_stats_kernel(PredArgs A)
             if (A.failed && A.failed[j]) { nfail += wj; continue; }
             if (!has) continue;
             const double v = (double)A.pred[(size_t)j * A.ld + col];
-            if (!isfinite(v)) continue;
-            wacc_add(a, v, (double)wj);
-            if (hist) {
-                if (v < vlo) atomicAdd(&A.below[ocol], wj);
-                else if (!(v < vhi)) atomicAdd(&A.above[ocol], wj);
-                else {                                     // the bin of edges vlo + i w (np.linspace): a guess, then the edges themselves
-                    int b = (int)((v - vlo) * inv_w);
-                    b = b < 0 ? 0 : (b > A.nbins - 1 ? A.nbins - 1 : b);
-                    if (b > 0 && v < (double)b * bin_w + vlo) --b;
-                    else if (b < A.nbins - 1 && v >= (double)(b + 1) * bin_w + vlo) ++b;
-                    atomicAdd(&A.hist[ocol * A.nbins + b], wj);
-                }
-            }
+            if (acc_add(a, v, (double)wj) && hist)
+                hist_add(A.hist, A.below, A.above, ocol, A.nbins, v, vlo, vhi, bin_w, inv_w, wj);
         }
     }
     // ---- the workgroup's partials: the four wavefronts merged in wavefront order
-    s_part[w * 64 + lane] = wacc_part(a);
+    s_part[w * 64 + lane] = acc_part(a);
     if (lane == 0) s_fail[w] = nfail;
     __syncthreads();
     const size_t unit = (size_t)pt * A.nslab + slab;
-    if (w == 0 && has) {
-        Part m = s_part[lane];
-        for (int q = 1; q < POST_WAVES; ++q) part_merge(m, s_part[q * 64 + lane]);
-        double *o = A.ws_part + (unit * A.P + col) * 5;
-        o[0] = m.n; o[1] = m.mean; o[2] = m.m2; o[3] = m.mn; o[4] = m.mx;
-    }
+    if (w == 0 && has) waves_merge_store(s_part, lane, A.ws_part + (unit * A.P + col) * 5);
     if (chunk == 0 && tid == 0) {
         for (int q = 1; q < POST_WAVES; ++q) nfail += s_fail[q];
         A.ws_nfail[unit] = nfail;
@@ -190,15 +133,12 @@ __global__ __launch_bounds__(POST_BLOCK) void pred_finish_kernel(PredArgs A)
     const long idx = (long)blockIdx.x * POST_BLOCK + threadIdx.x;
     if (idx >= (long)A.npoints * A.P) return;
     const int pt = (int)(idx / A.P), col = (int)(idx % A.P);
-    Part m{0.0, 0.0, 0.0, 0.0, 0.0};
-    int nfail = 0;
-    for (int s = 0; s < A.nslab; ++s) {
-        const size_t k = (size_t)pt * A.nslab + s;
-        const double *o = A.ws_part + (k * A.P + col) * 5;
-        part_merge(m, Part{o[0], o[1], o[2], o[3], o[4]});
-        if (col == 0) nfail += A.ws_nfail[k];
+    const Part m = slabs_merge(A.ws_part + ((size_t)pt * A.nslab * A.P + col) * 5, (size_t)A.P * 5, A.nslab);
+    if (col == 0) {
+        int nfail = 0;
+        for (int s = 0; s < A.nslab; ++s) nfail += A.ws_nfail[(size_t)pt * A.nslab + s];
+        A.n_failed[pt] = nfail;
     }
-    if (col == 0) A.n_failed[pt] = nfail;
     const bool any = m.n > 0.0;
     A.count[idx] = (int)m.n;
     A.mean[idx] = any ? m.mean : NAN;

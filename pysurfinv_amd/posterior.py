@@ -38,12 +38,15 @@ DEPTHS_MAX = 256          # SURFDISP_POST_DEPTHS_MAX
 
 def quantiles_from_hist(hist, vlo, vhi, quantiles):
     """Quantiles ``[..., Q]`` of histograms ``[..., nbins]`` over the equal bins of ``[vlo, vhi)`` (torch, on the histogram's
-    device).  With n the in-range count, cum the running sum and w the bin width, b is the first bin with cum[b] >= q n
-    (and cum[b] > 0), and the value is ``vlo + w (b + (q n - cum[b - 1]) / hist[b])`` - linear inside the bin; NaN where n = 0."""
+    device); ``vlo``, ``vhi`` scalars, or ``[P]`` arrays with ``hist`` ``[..., P, nbins]``: one range per column.  With n the
+    in-range count, cum the running sum and w the bin width, b is the first bin with cum[b] >= q n (and cum[b] > 0), and the
+    value is ``vlo + w (b + (q n - cum[b - 1]) / hist[b])`` - linear inside the bin; NaN where n = 0."""
     import torch
     h = hist.to(torch.float64)
     nb = h.shape[-1]
-    w = (float(vhi) - float(vlo)) / nb
+    # a scalar range stays a Python float: no host-to-device copy, so no wait for the stream the histogram was just launched on
+    lo, hi = (float(a) if np.ndim(a) == 0 else torch.as_tensor(np.asarray(a, np.float64), device=h.device)[:, None] for a in (vlo, vhi))
+    w = (hi - lo) / nb
     cum = h.cumsum(dim=-1)
     n = cum[..., -1:]
     out = []
@@ -52,18 +55,60 @@ def quantiles_from_hist(hist, vlo, vhi, quantiles):
         b = ((cum >= target) & (cum > 0)).to(torch.int8).argmax(dim=-1, keepdim=True)
         hb = h.gather(-1, b)
         before = cum.gather(-1, b) - hb
-        v = float(vlo) + w * (b.to(torch.float64) + (target - before) / hb)
+        v = lo + w * (b.to(torch.float64) + (target - before) / hb)
         out.append(torch.where(n > 0, v, torch.full_like(v, float("nan"))))
     return torch.cat(out, dim=-1) if out else h.new_zeros(h.shape[:-1] + (0,))
 
 
-def _hist_args(hist):
+quantiles_from_hist_cols = quantiles_from_hist            # the name the per-column form had
+
+
+def _hist_args(hist, P=None):
+    """None, or ``(vlo, vhi, nbins)`` of ``hist = (vlo, vhi, nbins)``, checked: floats (``P`` None: one range), or float64 arrays
+    ``[P]`` from scalars or ``[P]`` arrays (one range per column)."""
     if hist is None:
         return None
-    vlo, vhi, nbins = float(hist[0]), float(hist[1]), int(hist[2])
-    if not (np.isfinite(vlo) and np.isfinite(vhi) and vhi > vlo and nbins >= 1):
-        raise ValueError("hist = (vlo, vhi, nbins) with finite vlo < vhi and nbins >= 1")
+    if P is None:
+        vlo, vhi, each = float(hist[0]), float(hist[1]), ""
+    else:
+        try:
+            vlo = np.array(np.broadcast_to(np.asarray(hist[0], np.float64), (P,)))
+            vhi = np.array(np.broadcast_to(np.asarray(hist[1], np.float64), (P,)))
+        except ValueError:
+            raise ValueError(f"hist = (vlo, vhi, nbins): vlo and vhi scalars or arrays of the {P} data columns") from None
+        each = " in every column"
+    nbins = int(hist[2])
+    if not (np.all(np.isfinite(vlo)) and np.all(np.isfinite(vhi)) and np.all(vhi > vlo) and nbins >= 1):
+        raise ValueError(f"hist = (vlo, vhi, nbins) with finite vlo < vhi{each} and nbins >= 1")
     return vlo, vhi, nbins
+
+
+_pred_hist_args = _hist_args                              # the name the per-column form had: callers pass (hist, P)
+
+
+def _column_statistics(vals, name, hist=None):
+    """THE per-column statement of both reference functions, numpy float64: ``vals`` ``[n, C]``, a value counts when it is
+    finite.  dict ``count`` ``[C]`` and, with n > 0, ``<name>mean, <name>std`` (population), ``<name>min, <name>max`` (NaN where
+    count is 0); with ``hist = (vlo, vhi, nbins)`` (scalars or ``[C]``) also ``below`` (v < vlo), ``above`` (v >= vhi) and
+    ``hist`` ``[C, nbins]``: ``np.histogram`` on the fixed edges ``vlo + i w``.  All-NaN columns warn: the caller silences
+    RuntimeWarning."""
+    vals = np.where(np.isfinite(vals), vals, np.nan)
+    n, C = vals.shape
+    st = dict(count=np.isfinite(vals).sum(axis=0))
+    if n == 0:
+        return st
+    st.update({name + "mean": np.nanmean(vals, axis=0), name + "std": np.nanstd(vals, axis=0),
+               name + "min": np.nanmin(vals, axis=0), name + "max": np.nanmax(vals, axis=0)})
+    if hist is not None:
+        vlo, vhi, nbins = np.broadcast_to(hist[0], (C,)), np.broadcast_to(hist[1], (C,)), hist[2]
+        st.update(hist=np.zeros((C, nbins), np.int32), below=np.zeros(C, np.int32), above=np.zeros(C, np.int32))
+        for c in range(C):
+            edges = np.arange(nbins + 1) * ((vhi[c] - vlo[c]) / nbins) + vlo[c]
+            v = vals[:, c][np.isfinite(vals[:, c])]
+            st["below"][c], st["above"][c] = (v < vlo[c]).sum(), (v >= vhi[c]).sum()
+            v = v[(v >= vlo[c]) & (v < vhi[c])]
+            st["hist"][c] = np.histogram(v, edges)[0] if v.size else 0
+    return st
 
 
 def _prefix_args(R, chainL, prefix):
@@ -118,7 +163,6 @@ def posterior_reference(model_batch, track, zdeps, rows=None, true_markov_chain=
                vs_min=np.full((npnt, D), np.nan), vs_max=np.full((npnt, D), np.nan))
     if hist is not None:
         vlo, vhi, nbins = hist
-        edges = np.arange(nbins + 1) * ((vhi - vlo) / nbins) + vlo
         out.update(hist=np.zeros((npnt, D, nbins), np.int32), below=np.zeros((npnt, D), np.int32),
                    above=np.zeros((npnt, D), np.int32))
     rows = None if rows is None else np.asarray(torch.as_tensor(rows).cpu().numpy(), dtype=np.int64)
@@ -132,20 +176,12 @@ def posterior_reference(model_batch, track, zdeps, rows=None, true_markov_chain=
             par = tr[p, src[p][final[p]], 3:]
             if par.shape[0] == 0:
                 continue
-            fin_p = np.where(np.isfinite(par), par, np.nan)
-            out["pmean"][p], out["pstd"][p] = np.nanmean(fin_p, axis=0), np.nanstd(fin_p, axis=0)
+            st = _column_statistics(par, "p")
+            out["pmean"][p], out["pstd"][p] = st["pmean"], st["pstd"]
             vals = model_batch.value(torch.as_tensor(par, dtype=torch.float64, device=model_batch.device), zd,
-                                     rows=None if rows is None else np.full(par.shape[0], rows[p]))
-            vals = np.where(np.isfinite(vals), vals, np.nan)               # [n_final, D]
-            out["count"][p] = np.isfinite(vals).sum(axis=0)
-            out["vs_mean"][p], out["vs_std"][p] = np.nanmean(vals, axis=0), np.nanstd(vals, axis=0)
-            out["vs_min"][p], out["vs_max"][p] = np.nanmin(vals, axis=0), np.nanmax(vals, axis=0)
-            if hist is not None:
-                for d in range(D):
-                    v = vals[:, d][np.isfinite(vals[:, d])]
-                    out["below"][p, d], out["above"][p, d] = (v < vlo).sum(), (v >= vhi).sum()
-                    v = v[(v >= vlo) & (v < vhi)]
-                    out["hist"][p, d] = np.histogram(v, edges)[0] if v.size else 0
+                                     rows=None if rows is None else np.full(par.shape[0], rows[p]))     # [n_final, D]
+            for k, v in _column_statistics(vals, "vs_", hist).items():
+                out[k][p] = v
     out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items()}
     if hist is not None:
         out["quantiles"] = quantiles_from_hist(out["hist"], vlo, vhi, quantiles)
@@ -165,6 +201,33 @@ def _host_descriptor(model_batch):
         cached = (desc[0], np.ascontiguousarray(desc[0].cpu().numpy(), dtype=np.int32))
         model_batch._post_idesc = cached
     return cached[1], desc[1]
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _hist_outputs(hist, npnt, C):
+    """The three histogram outputs of an entry over ``[npnt, C]`` columns, as ``_entry_call`` takes them: None without ``hist``."""
+    import torch
+    shapes = dict(hist=(npnt, C, hist[2] if hist else 0), below=(npnt, C), above=(npnt, C))
+    return {k: (v, torch.int32) if hist is not None else None for k, v in shapes.items()}
+
+
+def _entry_call(entry, dev, ws_bytes, args, outputs):
+    """One call of the C entry ``entry`` on the current stream of ``dev``.  ``outputs``: name -> (shape, dtype), in the order of
+    the entry's output arguments, or None for an output that is not asked for (passed as NULL, absent from the result); they
+    and the workspace of ``ws_bytes`` (the entry's ``*_workspace_bytes`` and its arguments) are allocated on ``dev``, the entry is
+    called as ``entry(stream, *args, *outputs, workspace, its bytes)`` and its return code checked.  Returns the dict of device
+    tensors."""
+    import torch
+    L = _lib.lib()
+    o = {k: torch.empty(v[0], dtype=v[1], device=dev) for k, v in outputs.items() if v is not None}
+    ws = torch.empty(max(int(getattr(L, ws_bytes[0])(*ws_bytes[1:])), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(getattr(L, entry)(ctypes.c_void_p(stream), *args, *[_ptr(o.get(k)) for k in outputs], _ptr(ws), ws.numel()))
+    return o
 
 
 def posterior_profiles(model_batch, track, zdeps, rows=None, true_markov_chain=True, chainL=None, prefix=None, hist=None,
@@ -204,28 +267,15 @@ def posterior_profiles(model_batch, track, zdeps, rows=None, true_markov_chain=T
                 raise ValueError("rows must be [points]")
         elif aux.shape[0] != npnt:
             raise ValueError(f"{npnt} points against {aux.shape[0]} rows of local info: pass rows=")
-    L = _lib.lib()
-    f64 = dict(dtype=torch.float64, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    o = dict(min_misfit=torch.empty(npnt, **f64), thres=torch.empty(npnt, **f64), imin=torch.empty(npnt, **i32),
-             n_final=torch.empty(npnt, **i32), pmean=torch.empty((npnt, N), **f64), pstd=torch.empty((npnt, N), **f64),
-             count=torch.empty((npnt, D), **i32), vs_mean=torch.empty((npnt, D), **f64), vs_std=torch.empty((npnt, D), **f64),
-             vs_min=torch.empty((npnt, D), **f64), vs_max=torch.empty((npnt, D), **f64))
+    f64, i32 = torch.float64, torch.int32
     vlo, vhi, nbins = hist if hist is not None else (0.0, 0.0, 0)
-    if hist is not None:
-        o.update(hist=torch.empty((npnt, D, nbins), **i32), below=torch.empty((npnt, D), **i32), above=torch.empty((npnt, D), **i32))
-    ws = torch.empty(max(int(L.surfdisp_posterior_workspace_bytes(npnt, R, N, max(D, 1))), 8), dtype=torch.uint8, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = L.surfdisp_posterior_profile_device(
-            ctypes.c_void_p(stream), npnt, R, N, ptr(track), W,
-            idesc.ctypes.data_as(ctypes.c_void_p), int(idesc.size), ptr(fdesc), ptr(aux), K, ptr(rows_t),
-            D, zd.ctypes.data_as(ctypes.c_void_p), 1 if true_markov_chain else 0, chainL, prefix, nbins, vlo, vhi,
-            ptr(o["min_misfit"]), ptr(o["thres"]), ptr(o["imin"]), ptr(o["n_final"]), ptr(o["pmean"]), ptr(o["pstd"]),
-            ptr(o["count"]), ptr(o["vs_mean"]), ptr(o["vs_std"]), ptr(o["vs_min"]), ptr(o["vs_max"]),
-            ptr(o.get("hist")), ptr(o.get("below")), ptr(o.get("above")), ptr(ws), ws.numel())
-    _lib.check(rc)
+    o = _entry_call(
+        "surfdisp_posterior_profile_device", dev, ("surfdisp_posterior_workspace_bytes", npnt, R, N, max(D, 1)),
+        (npnt, R, N, _ptr(track), W, idesc.ctypes.data_as(ctypes.c_void_p), int(idesc.size), _ptr(fdesc), _ptr(aux), K, _ptr(rows_t),
+         D, zd.ctypes.data_as(ctypes.c_void_p), 1 if true_markov_chain else 0, chainL, prefix, nbins, vlo, vhi),
+        dict(min_misfit=(npnt, f64), thres=(npnt, f64), imin=(npnt, i32), n_final=(npnt, i32), pmean=((npnt, N), f64),
+             pstd=((npnt, N), f64), count=((npnt, D), i32), vs_mean=((npnt, D), f64), vs_std=((npnt, D), f64),
+             vs_min=((npnt, D), f64), vs_max=((npnt, D), f64), **_hist_outputs(hist, npnt, D)))
     o["imin"], o["n_final"] = o["imin"].to(torch.int64), o["n_final"].to(torch.int64)
     if hist is not None:
         o["quantiles"] = quantiles_from_hist(o["hist"], vlo, vhi, quantiles)
@@ -247,41 +297,6 @@ def convergence(model_batch, track, zdeps, chainL, rows=None, true_markov_chain=
 PRED_SLAB_ROWS = 4096     # SURFDISP_PRED_SLAB_ROWS: list rows a workgroup of the statistics kernel walks at a time
 PRED_SLABS_MAX = 16       # SURFDISP_PRED_SLABS_MAX
 PRED_COLS_MAX = 1024      # SURFDISP_PRED_COLS_MAX
-
-
-def quantiles_from_hist_cols(hist, vlo, vhi, quantiles):
-    """``quantiles_from_hist`` with one range per column: ``hist`` ``[..., P, nbins]``, ``vlo``, ``vhi`` ``[P]`` -> ``[..., P, Q]``."""
-    import torch
-    h = hist.to(torch.float64)
-    nb = h.shape[-1]
-    lo = torch.as_tensor(np.asarray(vlo, np.float64), device=h.device)[:, None]
-    w = (torch.as_tensor(np.asarray(vhi, np.float64), device=h.device)[:, None] - lo) / nb
-    cum = h.cumsum(dim=-1)
-    n = cum[..., -1:]
-    out = []
-    for q in quantiles:
-        target = float(q) * n
-        b = ((cum >= target) & (cum > 0)).to(torch.int8).argmax(dim=-1, keepdim=True)
-        hb = h.gather(-1, b)
-        before = cum.gather(-1, b) - hb
-        v = lo + w * (b.to(torch.float64) + (target - before) / hb)
-        out.append(torch.where(n > 0, v, torch.full_like(v, float("nan"))))
-    return torch.cat(out, dim=-1) if out else h.new_zeros(h.shape[:-1] + (0,))
-
-
-def _pred_hist_args(hist, P):
-    """None, or (vlo [P], vhi [P] float64 arrays, nbins) of ``hist = (vlo, vhi, nbins)`` with scalars or [P] arrays."""
-    if hist is None:
-        return None
-    try:
-        vlo = np.array(np.broadcast_to(np.asarray(hist[0], np.float64), (P,)))
-        vhi = np.array(np.broadcast_to(np.asarray(hist[1], np.float64), (P,)))
-    except ValueError:
-        raise ValueError(f"hist = (vlo, vhi, nbins): vlo and vhi scalars or arrays of the {P} data columns") from None
-    nbins = int(hist[2])
-    if not (np.isfinite(vlo).all() and np.isfinite(vhi).all() and (vhi > vlo).all() and nbins >= 1):
-        raise ValueError("hist = (vlo, vhi, nbins) with finite vlo < vhi in every column and nbins >= 1")
-    return vlo, vhi, nbins
 
 
 def _predictive_args(sampler, shape, obs_rows, chainL, prefix, hist, max_batch):
@@ -310,7 +325,7 @@ def _predictive_args(sampler, shape, obs_rows, chainL, prefix, hist, max_batch):
             raise ValueError(f"{npnt} points against {nrows} rows of observations: pass obs_rows=")
         obs_rows = np.arange(npnt, dtype=np.int64)
     chainL, prefix = _prefix_args(R, chainL, prefix)
-    return P, obs_rows, chainL, prefix, _pred_hist_args(hist, P)
+    return P, obs_rows, chainL, prefix, _hist_args(hist, P)
 
 
 def _predict(sampler, params, rows, max_batch):
@@ -381,24 +396,12 @@ def predictive_reference(sampler, track, obs_rows=None, true_markov_chain=True, 
             at = np.nonzero(fin_rows[sel] == imin[p])[0]
             if at.size:
                 out["min_pred"][p] = pred[sel][at[0]]
-            vals = pred[sel][~failed[sel]]
-            vals = np.where(np.isfinite(vals), vals, np.nan)
-            out["count"][p] = np.isfinite(vals).sum(axis=0)
-            if vals.shape[0] == 0:
-                continue
-            out["pred_mean"][p], out["pred_std"][p] = np.nanmean(vals, axis=0), np.nanstd(vals, axis=0)
-            out["pred_min"][p], out["pred_max"][p] = np.nanmin(vals, axis=0), np.nanmax(vals, axis=0)
-            if hist is not None:
-                for c in range(P):
-                    edges = np.arange(nbins + 1) * ((vhi[c] - vlo[c]) / nbins) + vlo[c]
-                    v = vals[:, c][np.isfinite(vals[:, c])]
-                    out["below"][p, c], out["above"][p, c] = (v < vlo[c]).sum(), (v >= vhi[c]).sum()
-                    v = v[(v >= vlo[c]) & (v < vhi[c])]
-                    out["hist"][p, c] = np.histogram(v, edges)[0] if v.size else 0
+            for k, v in _column_statistics(pred[sel][~failed[sel]], "pred_", hist).items():
+                out[k][p] = v
     out = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items()}
     out["fit"] = _fit(torch, sampler, out["pred_mean"], None if obs_rows is None else torch.as_tensor(obs_rows))
     if hist is not None:
-        out["quantiles"] = quantiles_from_hist_cols(out["hist"], vlo, vhi, quantiles)
+        out["quantiles"] = quantiles_from_hist(out["hist"], vlo, vhi, quantiles)
     return out
 
 
@@ -409,52 +412,32 @@ def posterior_sources(track, true_markov_chain=True, chainL=None, prefix=None):
     import torch
     npnt, R, W = track.shape
     chainL, prefix = _prefix_args(R, chainL, prefix)
-    dev = track.device
-    L = _lib.lib()
-    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
-    o = dict(min_misfit=torch.empty(npnt, **f64), thres=torch.empty(npnt, **f64), imin=torch.empty(npnt, **i32),
-             n_final=torch.empty(npnt, **i32), weight=torch.empty((npnt, R), **i32), n_sources=torch.empty(npnt, **i32),
-             imin_source=torch.empty(npnt, **i32))
-    ws = torch.empty(max(int(L.surfdisp_posterior_sources_workspace_bytes(npnt, R)), 8), dtype=torch.uint8, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.surfdisp_posterior_sources_device(
-            ctypes.c_void_p(stream), npnt, R, ptr(track), W, 1 if true_markov_chain else 0, chainL, prefix,
-            ptr(o["min_misfit"]), ptr(o["thres"]), ptr(o["imin"]), ptr(o["n_final"]), ptr(o["weight"]), ptr(o["n_sources"]),
-            ptr(o["imin_source"]), ptr(ws), ws.numel()))
-    return o
+    f64, i32 = torch.float64, torch.int32
+    return _entry_call("surfdisp_posterior_sources_device", track.device, ("surfdisp_posterior_sources_workspace_bytes", npnt, R),
+                       (npnt, R, _ptr(track), W, 1 if true_markov_chain else 0, chainL, prefix),
+                       dict(min_misfit=(npnt, f64), thres=(npnt, f64), imin=(npnt, i32), n_final=(npnt, i32), weight=((npnt, R), i32),
+                            n_sources=(npnt, i32), imin_source=(npnt, i32)))
 
 
 def predictive_statistics(pred, failed, w, offsets, hist=None):
     """One call of ``surfdisp_posterior_predictive_device``: ``pred`` float32 ``[total, P]`` (rows ``pred.stride(0)`` apart),
     ``failed`` uint8 ``[total]`` or None, ``w`` int32 ``[total]``, ``offsets`` int32 ``[points + 1]``, all on one device;
-    ``hist`` None or ``(vlo [P], vhi [P], nbins)`` as ``_pred_hist_args`` returns it.  Dict of device tensors ``count`` int32 and
+    ``hist`` None or ``(vlo [P], vhi [P], nbins)`` as ``_hist_args(hist, P)`` returns it.  Dict of device tensors ``count`` int32 and
     ``pred_mean, pred_std, pred_min, pred_max`` float64 ``[points, P]``, ``n_failed`` int32 ``[points]``, and with ``hist``
     ``hist [points, P, nbins]``, ``below``, ``above``."""
     import torch
     total, P = pred.shape
     npnt = offsets.numel() - 1
-    dev = pred.device
-    L = _lib.lib()
-    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
-    o = dict(count=torch.empty((npnt, P), **i32), n_failed=torch.empty(npnt, **i32))
-    for k in ("pred_mean", "pred_std", "pred_min", "pred_max"):
-        o[k] = torch.empty((npnt, P), **f64)
+    f64, i32 = torch.float64, torch.int32
     vlo, vhi, nbins = hist if hist is not None else (None, None, 0)
     if hist is not None:
         vlo, vhi = np.ascontiguousarray(vlo, np.float64), np.ascontiguousarray(vhi, np.float64)
-        o.update(hist=torch.empty((npnt, P, nbins), **i32), below=torch.empty((npnt, P), **i32), above=torch.empty((npnt, P), **i32))
-    ws = torch.empty(max(int(L.surfdisp_posterior_predictive_workspace_bytes(npnt, total, P)), 8), dtype=torch.uint8, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)
     host = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(L.surfdisp_posterior_predictive_device(
-            ctypes.c_void_p(stream), npnt, total, P, ptr(pred), pred.stride(0) if total else P, ptr(failed), ptr(w), ptr(offsets),
-            nbins, host(vlo), host(vhi), ptr(o["count"]), ptr(o["pred_mean"]), ptr(o["pred_std"]), ptr(o["pred_min"]),
-            ptr(o["pred_max"]), ptr(o["n_failed"]), ptr(o.get("hist")), ptr(o.get("below")), ptr(o.get("above")), ptr(ws), ws.numel()))
-    return o
+    return _entry_call(
+        "surfdisp_posterior_predictive_device", pred.device, ("surfdisp_posterior_predictive_workspace_bytes", npnt, total, P),
+        (npnt, total, P, _ptr(pred), pred.stride(0) if total else P, _ptr(failed), _ptr(w), _ptr(offsets), nbins, host(vlo), host(vhi)),
+        dict(count=((npnt, P), i32), pred_mean=((npnt, P), f64), pred_std=((npnt, P), f64), pred_min=((npnt, P), f64),
+             pred_max=((npnt, P), f64), n_failed=(npnt, i32), **_hist_outputs(hist, npnt, P)))
 
 
 def posterior_predictive(sampler, track, obs_rows=None, true_markov_chain=True, chainL=None, prefix=None, hist=None,
@@ -527,5 +510,5 @@ def posterior_predictive(sampler, track, obs_rows=None, true_markov_chain=True, 
         o[k] = src[k].to(torch.int64)
     o["n_failed"] = o["n_failed"].to(torch.int64)
     if hist is not None:
-        o["quantiles"] = quantiles_from_hist_cols(o["hist"], hist[0], hist[1], quantiles)
+        o["quantiles"] = quantiles_from_hist(o["hist"], hist[0], hist[1], quantiles)
     return o

@@ -12,31 +12,19 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
+sys.path[:0] = [HERE, os.path.join(HERE, "golden")]
 from settings import CONT, OCEAN                     # noqa: E402
 from settings_therm import HYBRID_STATIC             # noqa: E402
+from posterior_cases import (CHUNK_DEPTHS, DEPTHS, DEV, _carry_track, _close, _edges, _fixture_track, _local_case, _random_track,   # noqa: E402
+                             _same, _slab_plus_one_track)
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd import posterior, _lib            # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GP = np.load(os.path.join(HERE, "golden", "ref_post.npz"), allow_pickle=True)
-POST_NPZ = os.path.join(HERE, "golden", "post_trace.npz")
 G = np.load(os.path.join(HERE, "golden", "ref_driver.npz"))
 HIST = (1.0, 5.0, 400)
-DEPTHS = [0.0, 0.3, 1.7, 5.0, 20.3, 33.3, 47.0, 100.0, 180.0, 197.7, 260.0]
-DEV = "cuda:0"
-# a static ocean structure (water, constant sediment, two-point crust, BottomDepth mantle): the layer kinds CONT lacks
-OCEAN_STATIC = {"OceanWater": {"H": 2.5}, "OceanSediment": {"H": [0.4, "abs", 0.2, 0.05], "Vs": [1.0, 0.5, 1.6, 0.05]},
-                "OceanCrust": {"H": [6.0, "abs", 0.9, 0.2], "Vs": [[3.25, "abs", 0.3, 0.02], [3.94, "abs", 0.3, 0.02]]},
-                "OceanMantle": {"BottomDepth": [200.0, "abs", 30.0, 2.0],
-                                "Vs": [[4.4, "abs", 0.4, 0.02], [4.2, "abs", 0.4, 0.02], [4.3, "abs", 0.4, 0.02], [4.5, "abs", 0.4, 0.02]]},
-                "Info": {"modelType": "MCInv", "refLayer": False}}
-
-
-def _edges(hist):
-    vlo, vhi, nb = hist
-    return np.arange(nb + 1) * ((vhi - vlo) / nb) + vlo
 
 
 def _final_values(mb, track, zdeps, rows=None, **sel):
@@ -50,15 +38,6 @@ def _final_values(mb, track, zdeps, rows=None, **sel):
         out.append(mb.value(torch.as_tensor(par), zdeps, rows=None if rows is None else np.full(par.shape[0], rows[p]))
                    if par.shape[0] else np.zeros((0, len(zdeps))))
     return out
-
-
-def _close(name, a, b, tol):
-    a, b = a.detach().cpu().numpy().astype(float), b.detach().cpu().numpy().astype(float)
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    assert np.array_equal(np.isnan(a), np.isnan(b)), name
-    err = float(np.nanmax(np.abs(a - b))) if np.isfinite(a).any() else 0.0
-    print(f"PARITY {name}: max |device - reference| = {err:.3e} (bar {tol:g})")
-    assert err < tol, (name, err)
 
 
 def _check(label, mb_dev, mb_cpu, track, zdeps, hist=HIST, rows=None, **sel):
@@ -83,25 +62,6 @@ def _check(label, mb_dev, mb_cpu, track, zdeps, hist=HIST, rows=None, **sel):
             assert torch.equal(dev[k].cpu(), ref[k]), (label, k)
         _close(f"{label} quantiles", dev["quantiles"], ref["quantiles"], 1e-9)
     return dev
-
-
-def _fixture_track():
-    return np.array(np.load(POST_NPZ, allow_pickle=True)["mcTrack"], float)
-
-
-def _random_track(mb, npnt, R, seed, chainL=None):
-    """Parameters uniform in the prior box, misfits in 0.5..3 (about a fifth of the rows final), a random accept column."""
-    rng = np.random.default_rng(seed)
-    N = mb.spec.n
-    lo, hi = np.asarray(mb.spec.vmin, float), np.asarray(mb.spec.vmax, float)
-    tr = np.zeros((npnt, R, 3 + N))
-    tr[:, :, 0] = rng.uniform(0.5, 3.0, (npnt, R))
-    tr[:, :, 1] = np.exp(-tr[:, :, 0])
-    tr[:, :, 2] = rng.random((npnt, R)) < 0.4
-    tr[:, :, 3:] = lo + (hi - lo) * rng.random((npnt, R, N))
-    if chainL:
-        tr[:, ::chainL, 2] = 1.0
-    return tr
 
 
 # ------------------------------------------------------------------ 1. the reference PostPoint's fixture
@@ -129,16 +89,6 @@ def test_fixture_parity_from_the_device_entry():
 
 
 # ------------------------------------------------------------------ 2. the carry across tile and slab boundaries
-def _carry_track(mb):
-    tr = _random_track(mb, 2, 2 * 263, seed=11, chainL=263)
-    tr[:, 200:301, 2] = 0.0                       # chain 0: a rejected run across the 256-row tile boundary
-    tr[:, 264:, 2] = 0.0                          # chain 1: nothing accepted but its first row
-    tr[0, [5, 250, 300], 0] = np.nan
-    tr[1, [0, 17, 400], 0] = 88888.0
-    tr[0, 255, 0] = 0.45; tr[0, 256, 0] = 0.46    # final rows on either side of the boundary, both inside the rejected run
-    return tr
-
-
 @pytest.mark.parametrize("sel", [dict(), dict(true_markov_chain=False), dict(chainL=263, prefix=100)], ids=["tmc", "raw", "prefix"])
 def test_boundary_carry(sel):
     mb, mbc = Model1DBatch(CONT, device=DEV), Model1DBatch(CONT)
@@ -150,22 +100,14 @@ def test_one_row_past_a_slab():
     R = posterior.SLAB_ROWS + 1
     hdr = open(os.path.join(os.path.dirname(HERE), "include", "surfdisp.h")).read()
     assert f"#define SURFDISP_POST_SLAB_ROWS {posterior.SLAB_ROWS}\n" in hdr
-    tr = _random_track(mbc, 1, R, seed=12)
-    tr[0, R - 60:, 2] = 0.0                       # the last row of the first slab and the lone row of the second: rejected
-    tr[0, R - 1, 0] = 0.4                         # ... and that lone row is final, and holds the minimum
+    tr = _slab_plus_one_track(mbc)
     dev = _check("slab + 1", mb, mbc, tr, DEPTHS)
     assert int(dev["imin"][0]) == R - 1
     two = _check("slab + 1, two depth chunks", mb, mbc, tr, CHUNK_DEPTHS[65])     # two slabs x two chunks of partials
     assert int(two["n_final"][0]) == int(dev["n_final"][0]) and torch.equal(two["pmean"], dev["pmean"])
 
 
-# ------------------------------------------------------------------ 2b. more than one chunk of 64 depths
-# D > 64 launches a second grid dimension of the profile kernel (a workgroup per slab, point and chunk of 64 depths); only chunk 0
-# keeps the parameters' figures and the count of final rows.  65: a one-lane tail in chunk 1.  200: the reference's own use
-# (plotVsProfileShaded: 200 depths), here from above the surface to below every model's bottom, a partly filled last chunk.
-CHUNK_DEPTHS = {65: np.linspace(0.0, 186.0, 65), 200: np.linspace(-4.0, 261.0, 200), 256: np.linspace(0.05, 199.0, 256)}
-
-
+# ------------------------------------------------------------------ 2b. more than one chunk of 64 depths (CHUNK_DEPTHS)
 @pytest.mark.parametrize("D", [65, 200, 256])
 def test_more_than_one_depth_chunk(D):
     mb, mbc = Model1DBatch(CONT, device=DEV), Model1DBatch(CONT)
@@ -225,10 +167,9 @@ def test_two_calls_give_the_same_bits(depths):
     torch.cuda.synchronize()
     c = posterior.posterior_profiles(mb, tr.flip(0).contiguous(), depths, hist=HIST)
     torch.cuda.synchronize()
-    same = lambda x, y: torch.equal(torch.nan_to_num(x.double(), nan=-7.0), torch.nan_to_num(y.double(), nan=-7.0))
     for k in a:
-        assert same(a[k], b[k]), k
-        assert same(a[k], c[k].flip(0)), k
+        assert _same(a[k], b[k]), k
+        assert _same(a[k], c[k].flip(0)), k
 
 
 # ------------------------------------------------------------------ 5. per-point constants
@@ -237,14 +178,11 @@ def test_per_point_constants(name):
     """The settings of tests/test_local_info.py are thermal, non-static or carry the Gaussian crust term - none has a native
     descriptor the entry supports -, so: CONT with a per-point topography and mantle thickness, and a static ocean structure
     (water layer, BottomDepth mantle) with a per-point topography."""
-    setting, keys, table = ((CONT, ["topo", "Mantle.H"], [[-1.0, 152.0], [0.7, 160.0], [2.2, 171.5]]) if name == "cont" else
-                            (OCEAN_STATIC, ["topo"], [[-3.0], [0.0], [1.5]]))
+    setting, keys, table, rows, zd = _local_case(name)
     mb = Model1DBatch(setting, device=DEV, local_keys=keys).set_local_info(table)
     mbc = Model1DBatch(setting, local_keys=keys).set_local_info(table)
     assert mb.native_descriptor() is not None and not mb._native_thermal
     tr = _random_track(mbc, 3, 300, seed=14)
-    rows = np.array([2, 0, 1])
-    zd = [-2.0, -1.4, 0.0, 0.8, 2.6, 3.4, 9.0, 12.0, 60.0, 155.0, 172.0, 199.0, 228.0]
     dev = _check(f"local {name}", mb, mbc, tr, zd, rows=rows)
     assert not torch.equal(dev["count"][0], dev["count"][1])             # the points' tops differ, and it shows
     _check(f"local {name}, rows = None", mb, mbc, tr, zd)                        # point p reads table row p

@@ -12,24 +12,15 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
+sys.path[:0] = [HERE, os.path.join(HERE, "golden")]
 from settings import CONT, PERIODS                   # noqa: E402
+from posterior_cases import POST_NPZ, _edges, _oracle_forward, _track   # noqa: E402
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd import posterior                  # noqa: E402
 
 GP = np.load(os.path.join(HERE, "golden", "ref_post.npz"), allow_pickle=True)
-POST_NPZ = os.path.join(HERE, "golden", "post_trace.npz")
 G = np.load(os.path.join(HERE, "golden", "ref_driver.npz"))
 HIST = (1.0, 5.0, 400)
-
-
-def _track():
-    return np.array(np.load(POST_NPZ, allow_pickle=True)["mcTrack"], float)[None]
-
-
-def _edges():
-    vlo, vhi, nb = HIST
-    return np.arange(nb + 1) * ((vhi - vlo) / nb) + vlo
 
 
 @pytest.mark.parametrize("tmc,key", [(True, "tmc"), (False, "raw")])
@@ -48,7 +39,7 @@ def test_reference_statement_matches_reference_postpoint(tmc, key):
     assert np.abs(r["vs_min"][0].numpy() - vz.min(axis=1)).max() < 1e-9
     assert np.abs(r["vs_max"][0].numpy() - vz.max(axis=1)).max() < 1e-9
     # histogram: exact, which is fair while no value sits on an edge
-    edges = _edges()
+    edges = _edges(HIST)
     assert np.abs(vz[:, :, None] - edges[None, None, :]).min() > 1e-9
     for d in range(37):
         assert np.array_equal(r["hist"][0, d].numpy(), np.histogram(vz[d], edges)[0])
@@ -127,16 +118,6 @@ def _obs():
     c = np.tile(G["trace/c_obs"], (NPTS, 1)) * (1 + 0.002 * np.arange(NPTS)[:, None])
     c[3, 5] = np.nan
     return c, np.tile(G["trace/uncer"], (NPTS, 1))
-
-
-def _oracle_forward(periods):
-    from oracle import cport
-
-    def fwd(model, nlay):
-        c, u, st = cport.forward_batch(model.cpu().numpy(), periods, 2,
-                                       nlay=None if nlay is None else nlay.cpu().numpy(), nthreads=2)
-        return torch.from_numpy(c.astype(np.float64)), torch.from_numpy(st)
-    return fwd
 
 
 def _worker(rank, world, port, q):

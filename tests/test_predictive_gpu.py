@@ -20,10 +20,11 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
+sys.path[:0] = [HERE, os.path.join(HERE, "golden")]
 from settings import CONT                            # noqa: E402
 from settings_therm import HYBRID_STATIC, PERIODS as PERIODS_THERM   # noqa: E402
-from test_posterior_gpu import _carry_track, _random_track           # noqa: E402
+from posterior_cases import (DEV, P_A, SLAB_BOUNDARY_SELECTIONS, _carry_track, _close, _empty_list_inputs, _random_track, _same,   # noqa: E402
+                             _slab_boundary_track, _stats_inputs)
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd.mcmc import MetropolisBatch       # noqa: E402
 from pysurfinv_amd import posterior, _lib            # noqa: E402
@@ -32,24 +33,7 @@ pytestmark = pytest.mark.gpu
 
 G = np.load(os.path.join(HERE, "golden", "ref_driver.npz"))
 GT = np.load(os.path.join(HERE, "golden", "ref_therm.npz"))
-DEV = "cuda:0"
 TEAM = 4
-SLAB = posterior.PRED_SLAB_ROWS
-
-
-def _same(a, b):
-    return torch.equal(torch.nan_to_num(a.double(), nan=-7.0), torch.nan_to_num(b.double(), nan=-7.0))
-
-
-def _close(name, a, b, tol):
-    a, b = a.detach().cpu().numpy().astype(float), b.detach().cpu().numpy().astype(float)
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    assert np.array_equal(np.isnan(a), np.isnan(b)), name
-    both = np.isfinite(a) & np.isfinite(b)
-    assert np.array_equal(a[~both & ~np.isnan(a)], b[~both & ~np.isnan(b)]), name          # (infinities: the same ones)
-    err = float(np.abs(a[both] - b[both]).max()) if both.any() else 0.0
-    print(f"PARITY {name}: max |device - reference| = {err:.3e} (bar {tol:g})")
-    assert err < tol, (name, err)
 
 
 def test_header_constants():
@@ -60,28 +44,7 @@ def test_header_constants():
 
 
 # ------------------------------------------------------------------ (a) the statistics entry alone
-P_A, NBINS_A = 70, 37                 # two chunks of 64 columns, the second ragged
-LENS_A = [0, 5, SLAB + 300]           # an empty point, one wavefront's worth, a slab boundary (two workgroups per point and chunk)
-
-
-def _stats_inputs(seed=3):
-    rng = np.random.default_rng(seed)
-    total = sum(LENS_A)
-    centre = np.linspace(0.5, 4.5, P_A)                                  # the columns live on different scales
-    pred = (centre[None, :] + 0.2 * rng.standard_normal((total, P_A))).astype(np.float32)
-    w = rng.integers(0, 6, total).astype(np.int32)
-    failed = (rng.random(total) < 0.1).astype(np.uint8)
-    bad = rng.random((total, P_A))
-    pred[bad < 0.01] = np.nan
-    pred[(bad >= 0.01) & (bad < 0.015)] = np.inf
-    pred[(bad >= 0.015) & (bad < 0.02)] = -np.inf
-    pred[:, P_A - 1] = np.nan                                            # a column in which no row counts
-    w[:5] = [2, 0, 1, 5, 3]; failed[:5] = [0, 0, 1, 0, 0]                # the five rows of point 1
-    pred[3, 6] = np.nan
-    offsets = np.concatenate([[0], np.cumsum(LENS_A)]).astype(np.int32)
-    return pred, failed, w, offsets, (centre - 0.3, centre + 0.35, NBINS_A)
-
-
+# P_A columns, lists of 0, 5 and a slab + 300 rows: posterior_cases._stats_inputs
 def _stats_numpy(pred, failed, w, offsets, hist):
     """numpy on the list with row i repeated w[i] times."""
     npnt, P = offsets.size - 1, pred.shape[1]
@@ -139,9 +102,8 @@ def test_statistics_entry_against_numpy_on_the_repeated_rows():
 
 
 def test_statistics_entry_with_an_empty_list():
-    off = torch.zeros(3, dtype=torch.int32, device=DEV)
-    r = posterior.predictive_statistics(torch.empty((0, 4), dtype=torch.float32, device=DEV), None,
-                                        torch.empty(0, dtype=torch.int32, device=DEV), off, hist=(np.zeros(4), np.ones(4), 3))
+    pred, failed, w, offsets, hist = _empty_list_inputs()
+    r = posterior.predictive_statistics(pred, failed, w, offsets, hist=hist)
     torch.cuda.synchronize()
     assert int(r["count"].sum()) == 0 and int(r["hist"].sum()) == 0 and bool(torch.isnan(r["pred_mean"]).all())
 
@@ -180,14 +142,10 @@ def test_sources_across_the_tile_boundary(sel):
         assert int(got["weight"][:, 264:].sum()) == 0                    # chain 1: everything sits on its first row
 
 
-@pytest.mark.parametrize("sel", [dict(), dict(true_markov_chain=False), dict(chainL=posterior.SLAB_ROWS + 300, prefix=posterior.SLAB_ROWS + 200)],
-                         ids=["tmc", "raw", "prefix"])
+@pytest.mark.parametrize("sel", SLAB_BOUNDARY_SELECTIONS, ids=["tmc", "raw", "prefix"])
 def test_sources_across_the_slab_boundary(sel):
     S = posterior.SLAB_ROWS
-    tr = _random_track(Model1DBatch(CONT), 1, S + 300, seed=21)
-    tr[0, 0, 2] = 1.0
-    tr[0, S - 40:S + 50, 2] = 0.0                                        # a rejected run across the slab boundary
-    tr[0, S - 1, 0] = 0.45; tr[0, S, 0] = 0.46; tr[0, S + 7, 0] = 0.4    # final rows on either side, the minimum behind it
+    tr = _slab_boundary_track(Model1DBatch(CONT))
     got = _check_sources(tr, **sel)
     if sel.get("true_markov_chain", True):
         assert int(got["imin"][0]) == S + 7 and int(got["imin_source"][0]) == S - 41 and int(got["weight"][0, S - 41]) >= 3
@@ -352,7 +310,7 @@ def _check(label, mc, track, hist, **sel):
         assert torch.equal(dev[k].cpu(), ref[k]), (label, k)
     P = cP.shape[1]
     failed = mis == 88888.0
-    vlo, vhi, nb = posterior._pred_hist_args(hist, P)
+    vlo, vhi, nb = posterior._hist_args(hist, P)
     for c in range(P):                                                   # exactness of the histograms is a fair demand
         v = cP[~failed, c]
         v = v[np.isfinite(v)]

@@ -10,32 +10,18 @@ import pytest
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
+sys.path[:0] = [HERE, os.path.join(HERE, "golden")]
 from settings import CONT                            # noqa: E402
+from posterior_cases import POST_NPZ, _oracle_forward, _track   # noqa: E402
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd.mcmc import MetropolisBatch       # noqa: E402
 from pysurfinv_amd import posterior, _lib            # noqa: E402
 
 GP = np.load(os.path.join(HERE, "golden", "ref_post.npz"), allow_pickle=True)
-POST_NPZ = os.path.join(HERE, "golden", "post_trace.npz")
 SRC = np.load(POST_NPZ, allow_pickle=True)
 OBS = SRC["obs"][()]
 PERIODS = np.asarray(OBS["T"], np.float32)
 HIST = (2.5, 4.5, 200)
-
-
-def _track():
-    return np.array(SRC["mcTrack"], float)[None]
-
-
-def _oracle_forward(periods):
-    from oracle import cport
-
-    def fwd(model, nlay):
-        c, u, st = cport.forward_batch(model.cpu().numpy(), periods, 2,
-                                       nlay=None if nlay is None else nlay.cpu().numpy(), nthreads=2)
-        return torch.from_numpy(c.astype(np.float64)), torch.from_numpy(st)
-    return fwd
 
 
 def _sampler(c_obs=None, uncer=None):
