@@ -64,7 +64,7 @@ struct PhaseArgs {
     float ell_gmax;       // ... and so does g = 2 b^2 / c^2 of the stack's fastest layer beyond this
     int scan_general;     // 1: pure scan passes also run the general pass body (SURFDISP_LEANSCAN=0, for A/B and the tests)
 #ifdef SD_WAVECLOCK
-    unsigned long long *wclk;   // developer build: [waves][2] s_memrealtime at wavefront start / end
+    unsigned long long *wclk;   // developer build: [waves][24], s_memrealtime at wavefront start / end and the counters of scripts/waveclock.py
 #endif
 };
 

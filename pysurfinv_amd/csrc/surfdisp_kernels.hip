@@ -639,12 +639,22 @@ __device__ __forceinline__ float ray_close(const RState &s, const RTrial &t, con
     return (start == 1) ? -bb1 : bb1;
 }
 
+// *bhs (if given) receives the half space's b - A.sv of layer mmax - 1, the LDS word the scan's upper guard compares the
+// trial with (see LEAN_BHS in phase_body)
 template <bool PIPE2 = true, bool CERT = false, bool SKIP = true>
 __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, const int S,
                                                 const int mmax, const float c, const float T,
                                                 const int start, float &phi, float *mag = nullptr, const bool want_mag = true,
-                                                int *kcp = nullptr, bool *kuncp = nullptr, const bool count = false)
+                                                int *kcp = nullptr, bool *kuncp = nullptr, const bool count = false,
+                                                float *bhs = nullptr
+#ifdef SD_WAVECLOCK
+                                                , unsigned long long *wsec = nullptr   // cycles: [0] head, [1] layer loop, [2] closure
+#endif
+                                                )
 {
+#ifdef SD_WAVECLOCK
+    const unsigned long long ws0 = __builtin_readcyclecounter();
+#endif
     int kc_ = 0; bool kunc_ = !count;
     int *const kc = &kc_; bool *const kunc = &kunc_;
     // phi: vertical phase sum_i k d_i sqrt(c^2/v_i^2 - 1) over the layers (and wave types) that are oscillatory
@@ -659,6 +669,9 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
     const int last = mmax - 1;                                       // the half space
     RLyr A = load(0);
     int m = 0;
+#ifdef SD_WAVECLOCK
+    const unsigned long long ws1 = __builtin_readcyclecounter();   // (head: trial constants, start vector, first loads issued)
+#endif
     if (last >= 1) {                                                 // layer 0: the one that may be water
         const RLyr Bq = load(1);
         if (CERT && count) ray_step<true, true, SKIP>(s, t, A, start, phi, kc, kunc); else ray_step<true, false, SKIP>(s, t, A, start, phi);
@@ -700,9 +713,16 @@ __device__ __forceinline__ float delta_rayleigh(const float *wq, const int LS, c
         A = Bq;
     }
     // A holds layer mmax-1 here; the state is in the scale of the last layer stepped through
+#ifdef SD_WAVECLOCK
+    const unsigned long long ws2 = __builtin_readcyclecounter();
+#endif
     const float v = ray_close(s, t, A, W_R(last), last >= 1 ? W_R(last - 1) : 0.0f, start, mag, want_mag,
                               (CERT && count) ? kc : nullptr, kunc);
+    if (bhs) *bhs = A.sv;
     if (CERT) { *kcp = kc_; *kuncp = kunc_ || (last < 1); }
+#ifdef SD_WAVECLOCK
+    if (wsec) { wsec[0] += ws1 - ws0; wsec[1] += ws2 - ws1; wsec[2] += __builtin_readcyclecounter() - ws2; }
+#endif
     return v;
 }
 
@@ -997,6 +1017,8 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     // shader cycles (s_memtime) of this wavefront: whole loop, evaluations of the secular function, stack rebuilds
     const unsigned long long wcyc0 = __builtin_readcyclecounter();
     unsigned long long wcyc_eval = 0, wcyc_build = 0, wcyc_pre = 0, wpasses = 0;
+    // ... and inside the Rayleigh evaluation (head, layer loop, closure), the lean scan pass's decision block, lean passes
+    unsigned long long wsec[3] = {0, 0, 0}, wcyc_lean = 0, wn_lean = 0;
     // team-passes by state, layers stepped per pass (the wavefront's trip count = max over lanes) and summed over lanes
     unsigned long long wn_scan = 0, wn_refine = 0, wn_nevill = 0, wn_ellip = 0, wn_idle = 0, wtrip = 0, wlanelayers = 0, wlanes = 0;
 #endif
@@ -1239,6 +1261,17 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
 #else
     constexpr bool LEAN = !FAST && !EXACT && !INDEP && (G == 2);
 #endif
+    // LEAN_BHS (the Rayleigh instantiation, the headline's root search): the lean body's upper guard compares the trial with
+    // the half-space b the evaluation hands back - a register it held a few instructions earlier - instead of reading
+    // W_B(mmj - 1), the same LDS word, again: that read, its address and its wait stood alone between the evaluation and
+    // the team's decision.  Root search of one bench batch with two-lane teams 1.848 -> 1.809 ms (-2.1 %, spread 7 us); the
+    // three-batch headline gains 1-2 %, which is close to its run-to-run spread (profiles/r11a, where the moves that gained
+    // nothing or lost are recorded too).  -DSD_NO_GUARD_HANDBACK builds the parent's code for the A/B.
+#ifdef SD_NO_GUARD_HANDBACK
+    constexpr bool LEAN_BHS = false;
+#else
+    constexpr bool LEAN_BHS = LEAN && (KIND == 2);
+#endif
     // NEVILL's prologue, surfa.f:12-16, from the scan's bracket (del1 is the scan's value, whatever layer dropping it was computed
     // with - as in the reference)
     auto nevill_start = [&]() {
@@ -1337,10 +1370,16 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         }
 #endif
         float vmag = 0.0f;                                     // magnitude of the terms the value is the sum of (production recursion)
+        [[maybe_unused]] float bhsj = 0.0f;                    // b of this lane's effective half space (LEAN_BHS)
         if (eval) {
             const bool want_mag = want_ratio && st == ST_ELLIP;   // (the in-kernel ellipticity passes' cancellation test)
             if (KIND == 2) val = EXACT ? delta_rayleigh_ref(wq, LS, S, mmj, cj, T, start)
-                                       : delta_rayleigh<(G != 2) && !FAST, CERT, (G <= 16)>(wq, LS, S, mmj, cj, T, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse);
+                                       : delta_rayleigh<(G != 2) && !FAST, CERT, (G <= 16)>(wq, LS, S, mmj, cj, T, start, phj, &vmag, want_mag, &kcj, &kuncj, coarse,
+                                                                                                            LEAN_BHS ? &bhsj : nullptr
+#ifdef SD_WAVECLOCK
+                                                                                                            , wsec
+#endif
+                                                                                                            );
             // Love, NEVILL passes of the production kernel: DLTAR1 statement by statement on the production working stack (it holds
             // b, rho, d as the exact kernel's does).  A bracket goes to NEVILL because it may hold several roots, and which of them
             // NEVILL lands on depends on the VALUES it sees (its 10 x rule, its interpolation) - with e^{kd} of hundreds of km of
@@ -1358,7 +1397,8 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                              (A.ell_ambig < 0.0f || fabsf(val) < A.ell_ambig * vmag ||
                               cj * cj < ell_c2min);                                       // see surfdisp_ellip_kernel
 #ifdef SD_WAVECLOCK
-        wcyc_eval += __builtin_readcyclecounter() - we0;
+        const unsigned long long wl0 = __builtin_readcyclecounter();
+        wcyc_eval += wl0 - we0;
 #endif
         if (lean) {
             // ------------------------------------------------------------ lean scan pass (see LEAN)
@@ -1382,8 +1422,10 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             const bool has_prev = !(first && j == 0);
             const bool cross = has_prev && (negnan(val) != negnan(pd));
             bool guard = false;
-            if (scan && has_prev && !cross)                    // calcul.f:165-166
-                guard = (cj < 0.8f * b1top) || !(cj < W_B(mmj - 1) + 0.3f);
+            if (scan && has_prev && !cross) {                  // calcul.f:165-166
+                if constexpr (LEAN_BHS) guard = (cj < 0.8f * b1top) || !(cj < bhsj + 0.3f);
+                else                    guard = (cj < 0.8f * b1top) || !(cj < W_B(mmj - 1) + 0.3f);
+            }
             const unsigned long long em = __ballot(scan && (cross || guard)) & tmask;
             const int fl = em ? (__ffsll((long long)em) - 1) : -1;
             const int q = (fl < 0) ? tbase + G - 1 : fl;
@@ -1431,6 +1473,9 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 st = ST_REFINE;
                 if (bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
             }
+#ifdef SD_WAVECLOCK
+            wcyc_lean += __builtin_readcyclecounter() - wl0; ++wn_lean;
+#endif
             continue;
         }
         // ---------------------------------------------------------------- team-level decisions
@@ -1818,12 +1863,13 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
 #ifdef SD_WAVECLOCK
     if (!EXACT && A.wclk && (threadIdx.x & 63) == 0) {
         const size_t w = (size_t)blockIdx.x * (SD_PHASE_BLOCK / 64) + (threadIdx.x >> 6);
-        unsigned long long *o = A.wclk + 16 * w;
+        unsigned long long *o = A.wclk + 24 * w;
         o[0] = wclk0; o[1] = __builtin_amdgcn_s_memrealtime();
         o[2] = __builtin_readcyclecounter() - wcyc0; o[3] = wcyc_eval;
         o[4] = wcyc_build; o[5] = wpasses; o[6] = wcyc_pre;
         o[7] = wn_scan; o[8] = wn_refine; o[9] = wn_nevill; o[10] = wn_ellip; o[11] = wn_idle;
-        o[12] = wtrip; o[13] = wlanelayers; o[14] = wlanes; o[15] = 0;
+        o[12] = wtrip; o[13] = wlanelayers; o[14] = wlanes; o[15] = wsec[0];
+        o[16] = wsec[1]; o[17] = wsec[2]; o[18] = wcyc_lean; o[19] = wn_lean;
     }
 #endif
     if (INDEP) {

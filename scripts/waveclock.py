@@ -31,14 +31,14 @@ else:
     per = torch.as_tensor(np.asarray(settings.MCMC_PERIODS, np.float32) if which == "mcmc" else synth.default_periods(20), device="cuda:0")
 Lm, P = int(model.shape[2]), int(per.numel())
 plan = forward.BatchPlan(B, Lm, P)
-buf = torch.zeros(16 * (B + 64) + 1024, dtype=torch.int64, device="cuda")
+buf = torch.zeros(24 * (B + 64) + 1024, dtype=torch.int64, device="cuda")
 for kind, name in ((wave, "c+U"), (wave | 0x10, "phase only")):
     plan.run(model, per, kind=kind, nlay=nlay); torch.cuda.synchronize()
     buf.zero_()
     L.surfdisp_debug_buffer(ctypes.c_void_p(buf.data_ptr()))
     plan.run(model, per, kind=kind, nlay=nlay); torch.cuda.synchronize()
     L.surfdisp_debug_buffer(ctypes.c_void_p(0))
-    raw = buf[:16 * B].cpu().numpy().reshape(B, 16)
+    raw = buf[:24 * B].cpu().numpy().reshape(B, 24)
     raw = raw[raw[:, 1] > 0].astype(np.float64)               # the wavefronts that ran
     nw = raw.shape[0]
     G = B * 64 // nw if nw else 0
@@ -64,3 +64,10 @@ for kind, name in ((wave, "c+U"), (wave | 0x10, "phase only")):
     trip, ll, lanes = raw[:, 12].sum(), raw[:, 13].sum(), raw[:, 14].sum()
     print(f"   evaluations: {lanes / stacks:.0f} lane-evaluations per stack ({lanes / stacks / P:.1f} per root search), mean layers per evaluation "
           f"{ll / lanes:.1f}, mean trip count of a pass {trip / npass.sum():.1f}; lane x layer slots doing work {ll / (64 * trip):.3f}")
+    if wave == 2:
+        hd, lp, cl, ln, nln = (raw[:, i].sum() for i in (15, 16, 17, 18, 19))
+        tot = cyc.sum()
+        print(f"   sections of a pass (shares of the main loop's cycles): trial choice up to the evaluation {pre.sum() / tot:.4f}, evaluation head "
+              f"(trial constants, start vector, first loads) {hd / tot:.4f}, layer loop {lp / tot:.4f}, half-space closure {cl / tot:.4f}, "
+              f"rest of the evaluation block {(ev.sum() - hd - lp - cl) / tot:.4f}, lean decision block {ln / tot:.4f} "
+              f"({nln / max(npass.sum(), 1):.3f} of the passes are lean, {ln / max(nln, 1):.0f} cycles each)")
