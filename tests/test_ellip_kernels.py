@@ -77,7 +77,8 @@ def test_ellip_kernels_match_oracle_finite_differences_of_chi(name):
     2L solves per column); bar 2e-2 of each period's largest |FD| entry.  Measured on MI355X: 3.5e-4 .. 2.1e-3 (synth_L12),
     1.5e-3 .. 4.9e-3 (eus_L68), 4.6e-4 (water_L9, dchi/dVs) - the fp32 differences of chi under 1 % perturbations.  Water rows
     are exactly zero (a liquid layer gets no partials, as in (5b); its Vp and rho do move chi through the root, so the water
-    column is left out of the comparison)."""
+    column is left out of the comparison).  This ties the rows to the reference's own fp32 chi; the sharp comparison, 3e-4 of
+    the peak against float64 differences, is tests/test_ellip_fd.py::test_fresh_stack_rows_against_float64_differences."""
     import torch
     from pysurfinv_amd import senskernel
     m = _kernel_cases()[name]
