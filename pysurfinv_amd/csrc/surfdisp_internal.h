@@ -1,5 +1,7 @@
 // surfdisp_internal.h -- kernel argument blocks and launch prototypes shared by
 // surfdisp_kernels.hip and surfdisp_capi.hip.  Not part of the public ABI (include/surfdisp.h).
+// surfdisp_kernels.hip is one translation unit; its first stages are headers it includes: surfdisp_k_common.h,
+// surfdisp_k_prep.h (K0), surfdisp_k_secular.h.  The root search (K1) and what follows it stand in the .hip itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -2,15 +2,14 @@
 group_rayleigh / group_love of surfdisp_kernels.hip compiled for the host with hipcc).  Skipped if hipcc is absent."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 class EigenHost:
@@ -55,13 +54,4 @@ def finish(vals, div, hs, kind):
 
 @pytest.fixture(scope="module")
 def eigenlib():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    so = os.path.join(HC, "libeigencheck.so")
-    src = [os.path.join(HC, "eigencheck.hip"), os.path.join(HERE, "..", "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in src):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
-                               "-I" + os.path.join(HERE, "..", "include"),
-                               "-I" + os.path.join(HERE, "..", "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, src[0]], stderr=subprocess.DEVNULL)
-    return EigenHost(so)
+    return EigenHost(hostbuild.build(os.path.join(HC, "eigencheck.hip"), os.path.join(HC, "libeigencheck.so")))

@@ -14,30 +14,22 @@ through the stand-alone host program tests/hostcheck/trimscheck.hip:
 No GPU needed; skipped if hipcc is absent."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-ROOT = os.path.dirname(HERE)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-KSRC = os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")
 SRC = os.path.join(HC, "trimscheck.hip")
 EXE = os.path.join(HC, "trimscheck")
 
 
 @pytest.fixture(scope="module")
 def exe():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    if not os.path.exists(EXE) or os.path.getmtime(EXE) < max(os.path.getmtime(s) for s in (SRC, KSRC)):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pysurfinv_amd", "csrc"),
-                               "-o", EXE, SRC], stderr=subprocess.DEVNULL)
-    return EXE
+    return hostbuild.build(SRC, EXE, shared=False)
 
 
 def _oracle(model, nlay, per):

@@ -5,33 +5,20 @@ host-compiled group_rayleigh against the oracle on random stacks, fed with the o
 No GPU needed; skipped if hipcc is absent."""
 import ctypes
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-ROOT = os.path.dirname(HERE)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-KSRC = os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")
-
-
-def _host_lib(src, so):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in (src, KSRC)):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, src], stderr=subprocess.DEVNULL)
-    return ctypes.CDLL(so)
 
 
 @pytest.fixture(scope="module")
 def powlib():
-    return _host_lib(os.path.join(HC, "powcheck.hip"), os.path.join(HC, "libpowcheck.so"))
+    return ctypes.CDLL(hostbuild.build(os.path.join(HC, "powcheck.hip"), os.path.join(HC, "libpowcheck.so")))
 
 
 def _layers(rng, n):
@@ -103,7 +90,7 @@ def test_closed_form_powers(powlib):
 @pytest.fixture(scope="module")
 def hostlib():
     """tests/hostcheck/run_hostcheck.py on the group-velocity host build (the library test_hostcheck.py builds)."""
-    _host_lib(os.path.join(HC, "hostcheck.hip"), os.path.join(HC, "libhostcheck.so"))
+    hostbuild.build(os.path.join(HC, "hostcheck.hip"), os.path.join(HC, "libhostcheck.so"))
     sys.path.insert(0, HC)
     import run_hostcheck
     return run_hostcheck

@@ -12,18 +12,14 @@ sweep must step the same split, and above SD_GROUP_OWN_CANCEL both step the refe
 No GPU needed; skipped if hipcc is absent."""
 import ctypes
 import os
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-ROOT = os.path.dirname(HERE)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-KSRC = os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")
 SRC = os.path.join(HC, "splitcheck.hip")
 
 U_SPLIT_BAR = {"rock": 1e-6, "sediment": 4e-6}   # U, new split vs the reference's split (8 fp32 ulps; sediment: below
@@ -31,20 +27,10 @@ U_SPLIT_BAR = {"rock": 1e-6, "sediment": 4e-6}   # U, new split vs the reference
 U_ORACLE_BAR = 5e-6      # U vs the oracle on rock stacks (tests/test_group_powers.py)
 
 
-def _build(so, extra):
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in (SRC, KSRC)):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-fPIC", *extra,
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, SRC], stderr=subprocess.DEVNULL)
-    return ctypes.CDLL(so)
-
-
 @pytest.fixture(scope="module")
 def libs():
-    return {"new": _build(os.path.join(HC, "libsplitcheck.so"), []),
-            "ref": _build(os.path.join(HC, "libsplitcheck_ref.so"), ["-DSD_GROUP_LAMH=0.0f"])}
+    return {"new": ctypes.CDLL(hostbuild.build(SRC, os.path.join(HC, "libsplitcheck.so"))),
+            "ref": ctypes.CDLL(hostbuild.build(SRC, os.path.join(HC, "libsplitcheck_ref.so"), extra=["-DSD_GROUP_LAMH=0.0f"]))}
 
 
 @pytest.fixture(scope="module")

@@ -5,32 +5,22 @@ tests/hostcheck/lcoefcheck.hip, the old one as a copy in that file.  NaN compare
 No GPU needed; skipped if hipcc is absent."""
 import ctypes
 import os
-import shutil
-import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
 
+import hostbuild
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-ROOT = os.path.dirname(HERE)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-KSRC = os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")
 FIELDS = ("r", "rsin", "sinr", "cs", "x", "ph")
 f32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    src, so = os.path.join(HC, "lcoefcheck.hip"), os.path.join(HC, "liblcoefcheck.so")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in (src, KSRC)):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, src], stderr=subprocess.DEVNULL)
-    L = ctypes.CDLL(so)
+    L = ctypes.CDLL(hostbuild.build(os.path.join(HC, "lcoefcheck.hip"), os.path.join(HC, "liblcoefcheck.so")))
     L.lc_pairs.restype = ctypes.c_int
     L.lc_pairs.argtypes = [ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p]
     L.lc_random.restype = ctypes.c_long

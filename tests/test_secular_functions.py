@@ -9,20 +9,17 @@ source and runs its functions one thread per case.  Bounds marked "measured" wer
 to each gives the figure the build before the small-argument sinh fix produced on the same cases."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import secular64 as s64
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PROBE = os.path.join(HERE, "probe")
-ROOT = os.path.dirname(HERE)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ULP = 2.0 ** -24
 fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
@@ -30,14 +27,8 @@ ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
 
 @pytest.fixture(scope="module")
 def probe():
-    so = os.path.join(PROBE, "libsecular_probe.so")
-    src = [os.path.join(PROBE, "secular_probe.hip"), os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_kernels.hip"),
-           os.path.join(ROOT, "pysurfinv_amd", "csrc", "surfdisp_internal.h")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in src):
-        subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fno-slp-vectorize",
-                               "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, src[0]])
-    return ctypes.CDLL(so)
+    return ctypes.CDLL(hostbuild.build(os.path.join(PROBE, "secular_probe.hip"), os.path.join(PROBE, "libsecular_probe.so"),
+                                       extra=["-fno-slp-vectorize"], opt="-O3", quiet=False))
 
 
 def _f32(a):

@@ -4,19 +4,17 @@ hipcc is absent) - the fp32 layer values the kernels integrate with the last lay
 statement fed with a unit's returned rows, and the float64 finite differences of tests/golden/thickness_fd.npz."""
 import ctypes
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import eigen_ref as E
+import hostbuild
 from kernel_rows_ref import prep_factors32
 from pysurfinv_amd import senskernel
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HC = os.path.join(HERE, "hostcheck")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # worst figure of the host-compiled unit function against the numpy statement fed with the same fp32 rows
 # (tests/test_thickness_host.py, fraction of the unit's largest |reference| entry; profiles/thickness/parity.txt) and the
 # committed bar: 8 x that (the device's logf against numpy's in the attenuation factor, amplified by the jump's
@@ -101,13 +99,4 @@ class ThickHost:
 
 @pytest.fixture(scope="module")
 def thicklib():
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    so = os.path.join(HC, "libthickcheck.so")
-    src = [os.path.join(HC, "thickcheck.hip"), os.path.join(HERE, "..", "pysurfinv_amd", "csrc", "surfdisp_kernels.hip")]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in src):
-        subprocess.check_call([HIPCC, "-O2", "-std=c++17", "--offload-arch=gfx950", "-fPIC",
-                               "-I" + os.path.join(HERE, "..", "include"),
-                               "-I" + os.path.join(HERE, "..", "pysurfinv_amd", "csrc"),
-                               "-shared", "-o", so, src[0]], stderr=subprocess.DEVNULL)
-    return ThickHost(so)
+    return ThickHost(hostbuild.build(os.path.join(HC, "thickcheck.hip"), os.path.join(HC, "libthickcheck.so")))
