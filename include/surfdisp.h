@@ -381,6 +381,40 @@ int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, con
                                               int *n_nonfinite,
                                               void *workspace, size_t workspace_bytes);
 
+/* ---- (5h) ... and the same derivatives of the GROUP velocity, added within ABI 4.  Rodi's rule of (5c) holds for any model
+ *          parameter; with d = dlnT_frac and dcdh-, dcdh+ the rows of (5g) at the periods T (1 - d) and T (1 + d),
+ *              dudh = (U/c) (2 - U/c) (dcdh- + dcdh+) / 2  -  (U/c)^2 (dcdh+ - dcdh-) / ln((1 + d) / (1 - d)),
+ *          and dudz from dcdz-, dcdz+ in the same way; c and U are the unit's own values at T.  The rows at the shifted periods are
+ *          evaluated on what (5c) finds or rebuilds there: its shifted roots and ellipticities, a fresh stack per shifted period,
+ *          attenuation correction and chain factors at the shifted period, the phase partials and the structural U of its shifted
+ *          launches; the eigenfunction instantiation of the group-velocity kernel runs once more per shifted period (no further
+ *          root search).  dudh [B][P][Lmax]: d U(period) / d (thickness of input layer i), everything below shifted rigidly - what a
+ *          change of model[:, 3, i] does; dudz [B][P][Lmax]: d U(period) / d (depth of the top of input layer j) alone.  fp32
+ *          combination of fp32 rows; pysurfinv_amd.senskernel.group_thickness_reference is the same statement in float64.
+ *          One entry, the launches of (5b), (5c) and (5g) on one stream: c, u, status, dcdb, dcda, dcdr are bit-identical to
+ *          surfdisp_forward_kernels_device, dudb, duda, dudr to surfdisp_forward_group_kernels_device at the same dlnT_frac, dcdh,
+ *          dcdz to surfdisp_forward_thickness_kernels_device, also with SURFDISP_INDEPENDENT.
+ *          Rows: an entry of dudh is zero where that entry of dcdh is (below the effective half space at T, beyond nlay, unsolved
+ *          periods, bad stacks, dudh[nlay - 1]); dudz[j] is zero where dcdh[j - 1] is - the same interfaces as dcdz - and
+ *          dudz[0] = 0.  Every entry of dudh and dudz is NaN for a solved unit whose shifted root failed - the units of dudb's NaN
+ *          rows, counted once in *n_shift_failed - and for a unit whose thickness rows are not finite at T or, its shifted roots
+ *          found, at a shifted period: *n_nonfinite counts those (at T: the units (5g) counts).  dcda, dcdr, duda, dudr, dcdz,
+ *          dudz and both counters may be NULL; dudh has the same bits whichever of them are.  Rayleigh and Love.
+ *          SURFDISP_ERR_INVALID, before anything is launched: SURFDISP_PHASE_ONLY, SURFDISP_KERN_REFCOORD, a NULL c, u, status,
+ *          dcdb, dudb, dcdh or dudh, dlnT_frac outside [1e-3, 0.05], and a workspace smaller than
+ *          surfdisp_group_thickness_kernels_workspace_size (that of (5c) plus the eigenfunction scratch of (5f), one word per unit
+ *          and four [B][P][Lmax] row planes: there is no direct route).  The size function ends in _size, not in _workspace_bytes: the
+ *          *_workspace_bytes functions are the seven of (5) - (5g), whose count and mutual relations tests/test_host.py pins. */
+size_t surfdisp_group_thickness_kernels_workspace_size(int B, int Lmax, int P);
+int surfdisp_forward_group_thickness_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                                    const float *model, int P, const float *per, int kind, float dlnT_frac,
+                                                    float *c, float *u, int *status,
+                                                    float *dcdb, float *dcda, float *dcdr,
+                                                    float *dudb, float *duda, float *dudr,
+                                                    float *dcdh, float *dcdz, float *dudh, float *dudz,   /* [B][P][Lmax] */
+                                                    int *n_shift_failed, int *n_nonfinite,
+                                                    void *workspace, size_t workspace_bytes);
+
 /* ---- (6) parameters -> layer stacks on the device (the row next to the hot path, SURVEY.md 8f-2:
  *          Model1D.seisPropLayers, models.py:72-102 + layers.py:139-284) for models with a static
  *          layer structure.  params [C][N] fp64, model [C][5][L] fp32 (rows vp, vs, rho, h, 1/Qs);
@@ -686,8 +720,8 @@ int surfdisp_posterior_predictive_device(void *stream, int npoints, int total, i
  *          and leaves the total depth alone: a Moho, a sediment base, a sea floor (pysurfinv_amd.linearized.thickness_mode,
  *          interface_mode).  The two entries take the arguments of (6d) / (6e) up to and including `lam`, then:
  *   in:    K, modes, modes_per_stack.  part_h[5]: the [B][nper][Lmax] fp32 thickness kernels of the sources {cR, uR, cL, uL, chi} -
- *          today part_h[0] and part_h[2] can be filled, with the dcdh arrays exactly as (5g) writes them; the other slots wait
- *          for dU/dh and dchi/dh.  mode_scale [K] ([B][K] with modes_per_stack; > 0): mode k takes lam_s mode_scale_k on its
+ *          part_h[0] and part_h[2] take the dcdh arrays exactly as (5g) writes them, part_h[1] and part_h[3] the dudh arrays of
+ *          (5h); part_h[4] waits for dchi/dh.  mode_scale [K] ([B][K] with modes_per_stack; > 0): mode k takes lam_s mode_scale_k on its
  *          diagonal - it turns the Vs damping, in (km/s)^-2, into km^-2.  mode_prior [K] ([B][K] with modes_per_stack; beta >= 0;
  *          NULL: 0) and mode_y [B][K] (the amplitude accumulated since the starting model; NULL: 0; read by the step only): the
  *          Gaussian pull beta_k (y_k + delta_k)^2 back to the starting depth.  mode_scale and mode_prior are device memory and

@@ -39,6 +39,7 @@ EXPORTS = (
     "surfdisp_forward_ellip_kernels_device", "surfdisp_ellip_kernels_workspace_bytes",
     "surfdisp_forward_atten_device", "surfdisp_atten_workspace_bytes", "surfdisp_forward_eigen_device", "surfdisp_eigen_workspace_bytes",
     "surfdisp_forward_thickness_kernels_device", "surfdisp_thickness_kernels_workspace_bytes",
+    "surfdisp_forward_group_thickness_kernels_device", "surfdisp_group_thickness_kernels_workspace_size",
     "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device",
     "surfdisp_lsq_step_modes_device", "surfdisp_lsq_resolution_modes_device",
     "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes",
@@ -149,6 +150,14 @@ def lib() -> ctypes.CDLL:
         L.surfdisp_forward_thickness_kernels_device.restype = ctypes.c_int
         L.surfdisp_forward_thickness_kernels_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
                                                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t]
+    if hasattr(L, "surfdisp_forward_group_thickness_kernels_device"):   # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        L.surfdisp_group_thickness_kernels_workspace_size.restype = ctypes.c_size_t
+        L.surfdisp_group_thickness_kernels_workspace_size.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        # (stream, B, Lmax, nlay, model, P, per, kind, dlnT_frac, c, u, status, dcdb, dcda, dcdr, dudb, duda, dudr, dcdh, dcdz, dudh, dudz,
+        #  n_shift_failed, n_nonfinite, workspace, workspace_bytes)
+        L.surfdisp_forward_group_thickness_kernels_device.restype = ctypes.c_int
+        L.surfdisp_forward_group_thickness_kernels_device.argtypes = ([vp, ctypes.c_int, ctypes.c_int, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                                       ctypes.c_float] + [vp] * 16 + [ctypes.c_size_t])
     L.surfdisp_group_kernels_shift_offset.restype = ctypes.c_size_t     # test read-out (not in include/surfdisp.h)
     L.surfdisp_group_kernels_shift_offset.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.surfdisp_thermal_scratch_bytes.restype = ctypes.c_size_t

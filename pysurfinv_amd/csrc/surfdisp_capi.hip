@@ -210,14 +210,15 @@ EigCarve eigcarve(Carver &cv, int B, int Lmax, int P)
 
 // The entries' workspaces: the forward region, then (all but WS_FORWARD and WS_EIGEN) the partials' scratch, then the entry's
 // own region(s).  Regions an entry does not have stay null.  The attenuation entry's workspace is WS_KERNELS.
-enum WsEntry { WS_FORWARD, WS_KERNELS, WS_GROUP, WS_ELLIP, WS_EIGEN, WS_THICK };
+enum WsEntry { WS_FORWARD, WS_KERNELS, WS_GROUP, WS_ELLIP, WS_EIGEN, WS_THICK, WS_GROUP_THICK };
 struct Layout {
     Carve w;
     KCarve k;
     GCarve g;
     ECarve e;
     EigCarve eig;
-    float *thick_us;      // the thickness entry's plane [P][B]: the U of its second group-velocity launch
+    float *thick_us;      // the thickness entries' plane [P][B]: the U of their EIG group-velocity launches
+    float *thick_rows;    // the group-thickness entry's row planes [2 shifts][dcdh, dcdz][B][P][Lmax]: K2e's rows at T (1 -+ dfrac)
     size_t total;
 };
 Layout layout(void *base, int B, int Lmax, int P, WsEntry entry)
@@ -226,10 +227,11 @@ Layout layout(void *base, int B, int Lmax, int P, WsEntry entry)
     Layout l{};
     l.w = carve(cv, B, Lmax, P);
     if (entry != WS_FORWARD && entry != WS_EIGEN) l.k = kcarve(cv, B, Lmax, P);
-    if (entry == WS_GROUP) l.g = gcarve(cv, B, Lmax, P);
+    if (entry == WS_GROUP || entry == WS_GROUP_THICK) l.g = gcarve(cv, B, Lmax, P);
     if (entry == WS_ELLIP) l.e = ecarve(cv, B, Lmax, P);
-    if (entry == WS_EIGEN || entry == WS_THICK) l.eig = eigcarve(cv, B, Lmax, P);
-    if (entry == WS_THICK) l.thick_us = cv.take<float>((size_t)P * B);
+    if (entry == WS_EIGEN || entry == WS_THICK || entry == WS_GROUP_THICK) l.eig = eigcarve(cv, B, Lmax, P);
+    if (entry == WS_THICK || entry == WS_GROUP_THICK) l.thick_us = cv.take<float>((size_t)P * B);
+    if (entry == WS_GROUP_THICK) l.thick_rows = cv.take<float>((size_t)4 * B * P * Lmax);
     l.total = cv.off;
     return l;
 }
@@ -391,6 +393,7 @@ size_t surfdisp_group_kernels_workspace_bytes(int B, int Lmax, int P) { return l
 size_t surfdisp_atten_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_KERNELS); }
 size_t surfdisp_eigen_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_EIGEN); }
 size_t surfdisp_thickness_kernels_workspace_bytes(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_THICK); }
+size_t surfdisp_group_thickness_kernels_workspace_size(int B, int Lmax, int P) { return layout_bytes(B, Lmax, P, WS_GROUP_THICK); }
 
 // developer / test read-out (not in include/surfdisp.h): byte offset, inside that workspace, of the shifted roots
 // [2][P][B] (float; T (1 - dfrac) first) of the last surfdisp_forward_group_kernels_device call on it
@@ -604,6 +607,88 @@ int surfdisp_forward_kernels_device(void *stream, int B, int Lmax, const int *nl
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
 }
 
+// What surfdisp_forward_group_thickness_kernels_device asks of group_launches beyond the group entry's outputs.
+struct GroupThickOuts {
+    float *dcdh, *dcdz, *dudh, *dudz;     // the caller's [B][P][Lmax] rows (dcdz, dudz may be nullptr)
+    int *n_nonfinite;
+};
+
+// The launches of the two group entries behind their preambles.  `ws`: the entry's workspace composition; `t`: null for the
+// group entry.  With `t` the thickness passes run where their inputs are still (or already) in the scratches: K2e at T before
+// the shifted KERN launch of shift 0 overwrites the phase partials' scratch, K2e at a shifted period right behind that shift's
+// KERN launch (its scratch, factor, deepest layer and U) and an EIG launch on the same root into the one eigen region.  They
+// read what the group entry's launches write and write only the eigen region, the U plane, the row planes and the caller's
+// thickness rows, so c .. dudr are the group entry's; the shifted KERN launches keep the dc/dVp and dc/drho planes whether or
+// not the caller wants duda / dudr rows (K2e reads them), which changes no value of a plane.
+static int group_launches(void *stream, int B, int Lmax, const int *nlay, const float *model, int P, const float *per, int kind,
+                          float dlnT_frac, float *c, float *u, int *status, float *dcdb, float *dcda, float *dcdr,
+                          float *dudb, float *duda, float *dudr, int *n_shift_failed, void *workspace, size_t workspace_bytes,
+                          WsEntry ws, const GroupThickOuts *t)
+{
+    ForwardOpts o;
+    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
+    if (t) o.keep_vp_plane = o.keep_rho_plane = true;
+    int rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int wave = kind & ~SD_KIND_FLAGS;
+    const EnvKnobs &kn = knobs();
+    const Layout lay = layout(workspace, B, Lmax, P, ws);
+    const Carve &w = lay.w;
+    const GCarve &g = lay.g;
+    const EigCarve &e = lay.eig;
+    const size_t PB = (size_t)P * B, rows = PB * Lmax;
+    float *kscr = lay.k.kscr, *kscale0 = lay.k.kscale;                           // forward_device_impl's scratch and factors
+    // the EIG instantiation (kb = nullptr: it writes no partials) on the roots at `tper`, then K2e on its region and the given
+    // KERN scratch -> rows; a NaN row marks a unit that is not finite, the combination counts them
+    auto thickness_pass = [&](const float *tper, const float *tc, const float *tratio, const float *tu, const float *tkscr,
+                              const float *tksc, const int *tkhs, float *dh, float *dz) -> int {
+        sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, tper, tc, tratio, w.nsolved, lay.thick_us, nullptr, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, 0, 0, 0, kn.group_order};
+        ga.escr = e.escr; ga.ediv = e.ediv; ga.ehs = e.ehs; ga.esum = e.esum;
+        ga.stash = -1;
+        SD_HIP(sd::launch_group(s, wave, ga));
+        sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, tper, e.escr, e.ediv, e.ehs, e.esum, tkscr, tksc, tkhs,
+                         tc, tu, dh, dz, nullptr};
+        SD_HIP(sd::launch_thickness(s, ta));
+        return SURFDISP_SUCCESS;
+    };
+    if (t) {
+        if (t->n_nonfinite) SD_HIP(hipMemsetAsync(t->n_nonfinite, 0, sizeof(int), s));
+        rc = thickness_pass(per, w.ct, w.ratio, w.ut, kscr, kscale0, lay.k.khs, t->dcdh, t->dcdz);
+        if (rc) return rc;
+    }
+    if (n_shift_failed) SD_HIP(hipMemsetAsync(n_shift_failed, 0, sizeof(int), s));
+    sd::ShiftArgs sa{B, Lmax, P, wave, w.mdl, w.nl, per, w.ct, w.ut, w.nsolved, dlnT_frac, g.pers, g.cs,
+                     wave == SURFDISP_KIND_RAYLEIGH ? g.ratio : nullptr, g.fail, kn.ell_ambig, kn.ell_gmax, w.ovf};
+    SD_HIP(sd::launch_shift(s, sa));
+    // the row planes: [shift][dcdh, dcdz][B][P][Lmax]
+    auto plane = [&](int sg, int z) { return lay.thick_rows + (size_t)(2 * sg + z) * rows; };
+    for (int sg = 0; sg < 2; ++sg) {
+        // (kb / ka / kr only say which partials are wanted: on the scratch route the kernel writes the scratch alone)
+        float *const ka = wave == SURFDISP_KIND_RAYLEIGH ? (t ? dudb : duda) : nullptr, *const kr = t ? dudb : dudr;
+        sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB, w.nsolved,
+                         g.us + sg * PB, nullptr, dudb, ka, kr,
+                         sg ? g.kscr_p : kscr, g.ksc + sg * PB, g.khs + sg * PB, 0, 0, 0, kn.group_order};
+        SD_HIP(sd::launch_group(s, wave, ga));
+        if (t) {
+            rc = thickness_pass(g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB, g.us + sg * PB, sg ? g.kscr_p : kscr,
+                                g.ksc + sg * PB, g.khs + sg * PB, plane(sg, 0), t->dudz ? plane(sg, 1) : nullptr);
+            if (rc) return rc;
+        }
+    }
+    const float inv_dlnT = (float)(1.0 / log((1.0 + (double)dlnT_frac) / (1.0 - (double)dlnT_frac)));
+    sd::GroupCombineArgs ca{B, P, Lmax, wave, kscr, g.kscr_p, g.ksc, g.ksc + PB, g.khs, g.khs + PB, kscale0, g.fail,
+                            w.ct, w.ut, inv_dlnT, dudb, duda, dudr, n_shift_failed};
+    SD_HIP(sd::launch_group_combine(s, ca));
+    if (t) {
+        sd::GroupThickCombineArgs ta{B, P, Lmax, plane(0, 0), plane(1, 0), plane(0, 1), plane(1, 1), t->dcdh, g.ksc, g.ksc + PB,
+                                     kscale0, g.fail, w.ct, w.ut, inv_dlnT, t->dudh, t->dudz, t->n_nonfinite};
+        SD_HIP(sd::launch_group_thick_combine(s, ta));
+    }
+    return SURFDISP_SUCCESS;
+}
+
 // The same launches, then the analytic partials of the GROUP velocity (K4 in surfdisp_kernels.hip): the roots at
 // T (1 -+ dlnT_frac), the phase partials there, and their combination.  c, u, status, dc* are those of
 // surfdisp_forward_kernels_device, bit for bit.
@@ -620,34 +705,8 @@ int surfdisp_forward_group_kernels_device(void *stream, int B, int Lmax, const i
                             B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_GROUP,
                             "surfdisp_group_kernels_workspace_bytes", SURFDISP_ERR_WORKSPACE);
     if (rc) return rc;
-    ForwardOpts o;
-    o.dcdb = dcdb; o.dcda = dcda; o.dcdr = dcdr;
-    rc = forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int wave = kind & ~SD_KIND_FLAGS;
-    const EnvKnobs &kn = knobs();
-    const Layout lay = layout(workspace, B, Lmax, P, WS_GROUP);
-    const Carve &w = lay.w;
-    const GCarve &g = lay.g;
-    const size_t PB = (size_t)P * B;
-    float *kscr = lay.k.kscr, *kscale0 = lay.k.kscale;                           // forward_device_impl's scratch and factors
-    if (n_shift_failed) SD_HIP(hipMemsetAsync(n_shift_failed, 0, sizeof(int), s));
-    sd::ShiftArgs sa{B, Lmax, P, wave, w.mdl, w.nl, per, w.ct, w.ut, w.nsolved, dlnT_frac, g.pers, g.cs,
-                     wave == SURFDISP_KIND_RAYLEIGH ? g.ratio : nullptr, g.fail, kn.ell_ambig, kn.ell_gmax, w.ovf};
-    SD_HIP(sd::launch_shift(s, sa));
-    for (int sg = 0; sg < 2; ++sg) {
-        // (kb / ka / kr only say which partials are wanted: on the scratch route the kernel writes the scratch alone)
-        sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB, w.nsolved,
-                         g.us + sg * PB, nullptr, dudb, wave == SURFDISP_KIND_RAYLEIGH ? duda : nullptr, dudr,
-                         sg ? g.kscr_p : kscr, g.ksc + sg * PB, g.khs + sg * PB, 0, 0, 0, kn.group_order};
-        SD_HIP(sd::launch_group(s, wave, ga));
-    }
-    const float inv_dlnT = (float)(1.0 / log((1.0 + (double)dlnT_frac) / (1.0 - (double)dlnT_frac)));
-    sd::GroupCombineArgs ca{B, P, Lmax, wave, kscr, g.kscr_p, g.ksc, g.ksc + PB, g.khs, g.khs + PB, kscale0, g.fail,
-                            w.ct, w.ut, inv_dlnT, dudb, duda, dudr, n_shift_failed};
-    SD_HIP(sd::launch_group_combine(s, ca));
-    return SURFDISP_SUCCESS;
+    return group_launches(stream, B, Lmax, nlay, model, P, per, kind, dlnT_frac, c, u, status, dcdb, dcda, dcdr, dudb, duda, dudr,
+                          n_shift_failed, workspace, workspace_bytes, WS_GROUP, nullptr);
 }
 
 // The same launches as surfdisp_forward_kernels_device (c, u, status, dc* bit for bit; `ratio` as
@@ -778,6 +837,31 @@ int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, con
                      w.ct, w.ut, dcdh, dcdz, n_nonfinite};
     SD_HIP(sd::launch_thickness(s, ta));
     return SURFDISP_SUCCESS;
+}
+
+// The launches of surfdisp_forward_group_kernels_device and of surfdisp_forward_thickness_kernels_device in one pass (c .. dcdr,
+// dudb .. dudr, dcdh, dcdz bit for bit), and the thickness kernel again at the two shifted periods: dU/d(layer thickness, interface
+// depth) by the rule of K4 (K4d in surfdisp_group_thick.hip).  Workspace: the group entry's, then the eigen region, the U plane and
+// the four row planes; no direct route.
+int surfdisp_forward_group_thickness_kernels_device(void *stream, int B, int Lmax, const int *nlay,
+                                                    const float *model, int P, const float *per, int kind, float dlnT_frac,
+                                                    float *c, float *u, int *status,
+                                                    float *dcdb, float *dcda, float *dcdr,
+                                                    float *dudb, float *duda, float *dudr,
+                                                    float *dcdh, float *dcdz, float *dudh, float *dudz,
+                                                    int *n_shift_failed, int *n_nonfinite,
+                                                    void *workspace, size_t workspace_bytes)
+{
+    int rc = entry_preamble("surfdisp_forward_group_thickness_kernels_device", c && u && status && dcdb && dudb && dcdh && dudh,
+                            "c, u, status, dcdb, dudb, dcdh or dudh", SURFDISP_PHASE_ONLY | SURFDISP_KERN_REFCOORD,
+                            "no PHASE_ONLY, no KERN_REFCOORD",
+                            (dlnT_frac >= 1.0e-3f && dlnT_frac <= 0.05f) ? nullptr : "dlnT_frac outside [1e-3, 0.05]",
+                            B, Lmax, P, kind, model, per, c, u, workspace, workspace_bytes, WS_GROUP_THICK,
+                            "surfdisp_group_thickness_kernels_workspace_size", SURFDISP_ERR_INVALID);
+    if (rc) return rc;
+    const GroupThickOuts t{dcdh, dcdz, dudh, dudz, n_nonfinite};
+    return group_launches(stream, B, Lmax, nlay, model, P, per, kind, dlnT_frac, c, u, status, dcdb, dcda, dcdr, dudb, duda, dudr,
+                          n_shift_failed, workspace, workspace_bytes, WS_GROUP_THICK, &t);
 }
 
 // Parameters -> layer stacks on the device for a static-structure model; the

@@ -182,6 +182,21 @@ struct GroupCombineArgs {
     int *n_failed;                      // nullptr, or [1]: solved units whose shifted pass failed (NaN rows)
 };
 hipError_t launch_group_combine(hipStream_t s, const GroupCombineArgs &a);
+// dU/d(layer thickness, interface depth) (surfdisp_forward_group_thickness_kernels_device) from the rows of K2e at the two shifted
+// periods, see K4d in surfdisp_group_thick.hip
+struct GroupThickCombineArgs {
+    int B, P, Lmax;
+    const float *hm, *hp;               // [B][P][Lmax] dcdh at T (1 - dfrac) and T (1 + dfrac), as K2e writes them
+    const float *zm, *zp;               // ... and dcdz there (read with dudz only)
+    const float *h0;                    // [B][P][Lmax] dcdh at T (the caller's rows): where it is zero the results are
+    const float *ksc_m, *ksc_p, *ksc0;  // [P][B] as GroupCombineArgs: the units the shifted pass failed for are the same
+    const unsigned char *fail;          // [2][P][B] see ShiftArgs
+    const float *c, *u;                 // [P][B] c and U at T
+    float inv_dlnT;                     // 1 / ln((1 + dfrac) / (1 - dfrac))
+    float *dudh, *dudz;                 // the caller's [B][P][Lmax] rows (dudz may be nullptr)
+    int *n_nonfinite;                   // nullptr, or [1]: units with a NaN thickness row at T or at a shifted period
+};
+hipError_t launch_group_thick_combine(hipStream_t s, const GroupThickCombineArgs &a);
 
 struct EllipArgs {
     int B, Lmax, P;

@@ -88,7 +88,8 @@ class BatchPlan:
     _WS_BYTES = {"forward": "surfdisp_workspace_bytes", "kernels": "surfdisp_kernels_workspace_bytes",
                  "group": "surfdisp_group_kernels_workspace_bytes", "ellip": "surfdisp_ellip_kernels_workspace_bytes",
                  "atten": "surfdisp_atten_workspace_bytes", "eigen": "surfdisp_eigen_workspace_bytes",
-                 "thickness": "surfdisp_thickness_kernels_workspace_bytes"}
+                 "thickness": "surfdisp_thickness_kernels_workspace_bytes",
+                 "group_thickness": "surfdisp_group_thickness_kernels_workspace_size"}
 
     def __init__(self, B, L, P, device="cuda:0"):
         import torch
@@ -317,6 +318,32 @@ class BatchPlan:
         self._call("surfdisp_forward_thickness_kernels_device", "thickness", model, periods, kind, nlay,
                    (ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr), ptr(dcdh), ptr(dcdz), ptr(tnonfin)))
         return (self.c, self.u, self.status, dcdb, dcda, dcdr, dcdh, dcdz, int(tnonfin.item()) if count else tnonfin)
+
+    def run_group_thickness_kernels(self, model, periods, kind=2, nlay=None, dlnT_frac=0.01, want_vp=True, want_rho=True,
+                                    want_dcdz=True, want_dudz=True, count=True):
+        """``run_group_kernels`` and ``run_thickness_kernels`` in one pass plus the derivatives of the GROUP velocity with respect
+        to the layer thicknesses and the interface depths (``surfdisp_forward_group_thickness_kernels_device``): returns (c, u,
+        status, dcdb, dcda, dcdr, dudb, duda, dudr, dcdh, dcdz, dudh, dudz, n_failed, n_nonfinite).  c .. dudr equal
+        ``run_group_kernels``' at the same ``dlnT_frac`` and dcdh, dcdz ``run_thickness_kernels``' bit for bit; dudh float32
+        [B, P, L] = d U(period) / d (thickness of input layer i), everything below shifted rigidly - what a change of
+        ``model[:, 3, i]`` does; dudz [B, P, L] = d U(period) / d (depth of the top of layer j) alone (``None`` with
+        ``want_dudz=False``), from the thickness rows at T (1 -+ dlnT_frac) by the rule of ``senskernel.group_thickness_reference``.
+        Zeros where dcdh is zero; rows of units whose shifted root failed are NaN (``n_failed``, the units of dudb's NaN rows), as
+        are rows of units whose thickness rows are not finite (``n_nonfinite``); both counts are ints and synchronise the stream
+        (``count=False``: the device tensors).  Rayleigh and Love; include/surfdisp.h section (5h)."""
+        ptr, L = self._ptr, self.L
+        rayleigh = (int(kind) & 3) == _lib.KIND_RAYLEIGH
+        dcdb, dudb, dcdh, dudh = self._out(L), self._out(L), self._out(L), self._out(L)
+        dcda, duda = self._out(L, want=want_vp and rayleigh), self._out(L, want=want_vp and rayleigh)
+        dcdr, dudr = self._out(L, want=want_rho), self._out(L, want=want_rho)
+        dcdz, dudz = self._out(L, want=want_dcdz), self._out(L, want=want_dudz)
+        nfail, nnonfin = self._counter("nfail"), self._counter("gtnonfin")
+        self._call("surfdisp_forward_group_thickness_kernels_device", "group_thickness", model, periods, kind, nlay,
+                   (float(dlnT_frac), ptr(self.c), ptr(self.u), ptr(self.status), ptr(dcdb), ptr(dcda), ptr(dcdr),
+                    ptr(dudb), ptr(duda), ptr(dudr), ptr(dcdh), ptr(dcdz), ptr(dudh), ptr(dudz), ptr(nfail), ptr(nnonfin)))
+        if count:
+            nfail, nnonfin = int(nfail.item()), int(nnonfin.item())
+        return self.c, self.u, self.status, dcdb, dcda, dcdr, dudb, duda, dudr, dcdh, dcdz, dudh, dudz, nfail, nnonfin
 
     def shifted_roots(self):
         """[2, B, P] float32: the roots at T (1 - dlnT_frac) and T (1 + dlnT_frac) the last ``run_group_kernels`` used (a unit's

@@ -24,13 +24,15 @@ K <= 8 more unknowns per stack behind the Vs - mode k has a shape T_k [L] and an
 changes by sum_k T_k[i] y_k (``thickness_mode``: a layer group thickens, everything below shifts; ``interface_mode``: the
 interface between two groups moves, the total depth stays).  Its column is G[r, n + k] = sum_i dcdh[r, i] T_k[i] from the
 thickness kernels of the phase velocity (``BatchPlan.run_thickness_kernels``), its damping lam mode_scale_k, its prior
-mode_prior_k (y_k + delta_k)^2.  Phase-velocity data only: the library has no dU/dh or dchi/dh yet.
+mode_prior_k (y_k + delta_k)^2.  By default phase-velocity data only; with ``group_modes=True`` group-velocity sets are taken
+next to modes, their columns from dudh (``BatchPlan.run_group_thickness_kernels``).  An ellipticity set is refused with modes
+either way: the library has no dchi/dh.
 
 The kernels are tested against ONE numpy float64 statement, ``_System``: (H, A, g) of n Vs unknowns followed by K >= 0 modes, K = 0
 being the problem without modes.  ``lsq_modes_step_reference`` and ``lsq_modes_resolution_reference`` are the step and the resolution
 read from it, with one solve block (A finite, Cholesky, flag 2 on failure, zeros on a flag); ``normal_equations``,
 ``modes_normal_equations``, ``lsq_step_reference`` and ``lsq_resolution_reference`` are calls of those.  The same holds on the device
-side of the module: the rules of the mode arguments are ``_mode_count`` and ``_phase_only`` for ``LinearizedBatch`` and ``LsqPlan``
+side of the module: the rules of the mode arguments are ``_mode_count`` and ``_mode_data`` for ``LinearizedBatch`` and ``LsqPlan``
 alike, and a call of ``LsqPlan.step`` or ``resolution``, with or without modes, is one ``_Launch``.
 
 * ``LsqPlan``: the kernels + step (``step``) or covariance and resolution (``resolution``) of one batch as device tensors.
@@ -50,6 +52,7 @@ from .obsdata import JointData
 MAX_FREE = 128          # unknowns per stack the step and resolution kernels take (SD_LSQ_MAX_FREE)
 MAX_MODES = 8           # thickness modes per stack behind them (SD_LSQ_MAX_MODES)
 MODES_NEED_PHASE = "thickness modes need phase-velocity data only: the library has no dU/dh or dchi/dh yet"
+MODES_NEED_NO_ELLIPTICITY = "thickness modes take phase- and group-velocity data (group_modes=True): the library has no dchi/dh"
 FAIL = 88888.0          # the misfit of a failed solve (point.py:20-21)
 
 # d(Vp, rho) / dVs of the layer groups of senskernel.GROUP_RULES (sensModel._convert)
@@ -296,9 +299,13 @@ def _mode_count(modes, B, L):
     return int(s[-2]), len(s) == 3
 
 
-def _phase_only(jd):
-    """ValueError when the data hold a group-velocity or ellipticity set: thickness modes need dcdh of every row."""
-    if any(d.quantity != "c" for d in jd.datasets):
+def _mode_data(jd, group_modes=False):
+    """ValueError when the data hold a set thickness modes have no column for: they need dcdh (dudh) of every row.  Without
+    ``group_modes`` that is a group-velocity or ellipticity set, with it an ellipticity set."""
+    if group_modes:
+        if any(d.quantity not in ("c", "U") for d in jd.datasets):
+            raise ValueError(MODES_NEED_NO_ELLIPTICITY)
+    elif any(d.quantity != "c" for d in jd.datasets):
         raise ValueError(MODES_NEED_PHASE)
 
 
@@ -326,12 +333,14 @@ class LsqPlan:
     """The sensitivity kernels and the least-squares step of B stacks of L layers against ``datasets`` (``obsdata``
     ``DispersionData`` sets, their dict form, or a ``JointData`` of them), on ``device``.  Owns the ``BatchPlan`` of each wave type
     with data, the ``JointData`` table and the output buffers.  ``mask``: bool [Ptot] or [B, Ptot], rows to leave out on top of the
-    data's own unusable entries (columns in data-set order)."""
+    data's own unusable entries (columns in data-set order).  ``group_modes``: thickness modes are taken next to
+    group-velocity sets (see ``kernels``); False keeps them to phase-velocity data."""
 
-    def __init__(self, B, L, datasets, device="cuda:0", mask=None):
+    def __init__(self, B, L, datasets, device="cuda:0", mask=None, group_modes=False):
         import torch
         self.torch = torch
         self.B, self.L = int(B), int(L)
+        self.group_modes = bool(group_modes)
         self.joint = jd = datasets if isinstance(datasets, JointData) else JointData(datasets, device="cpu")
         if jd.C is not None and jd.C != self.B:
             raise ValueError(f"per-stack data of {jd.C} rows against {self.B} stacks")
@@ -369,16 +378,17 @@ class LsqPlan:
         return t
 
     def check_modes(self):
-        """ValueError when the data hold a group-velocity or ellipticity set: thickness modes need dcdh of every row."""
-        _phase_only(self.joint)
+        """ValueError when the data hold a set thickness modes have no column for (``_mode_data``)."""
+        _mode_data(self.joint, self.group_modes)
 
     def kernels(self, model, nlay=None, want_vp=True, want_rho=True, thickness=False):
         """The kernel entries the data need, once per wave type: U data -> ``run_group_kernels``, an "E" set ->
         ``run_ellip_kernels``, both -> both calls (``senskernel.analytic_kernels``), otherwise ``run_kernels``.  Returns (pred,
         part): the forward dict of ``JointData.predictions`` (the plans' own output tensors) and the 15 partial arrays
-        [source 0..4][Vs, Vp, rho] (None where absent).  ``thickness`` (phase-velocity data only): ``run_thickness_kernels``
-        in place of ``run_kernels`` - the same bits plus dcdh - and a third result, the five thickness arrays [source 0..4]
-        (cR and cL; None elsewhere).  No host synchronisation."""
+        [source 0..4][Vs, Vp, rho] (None where absent).  ``thickness`` (no "E" set; U sets with ``group_modes`` only):
+        ``run_thickness_kernels`` in place of ``run_kernels`` - the same bits plus dcdh - or, for a wave type with U data,
+        ``run_group_thickness_kernels`` in place of ``run_group_kernels`` - the same bits plus dcdh and dudh - and a third
+        result, the five thickness arrays [source 0..4] (cR, uR, cL, uL; None where absent).  No host synchronisation."""
         jd = self.joint
         pred = dict(cR=None, uR=None, cL=None, uL=None, statusR=None, statusL=None, eR=None)
         part, part_h = [None] * 15, [None] * 5
@@ -388,12 +398,18 @@ class LsqPlan:
             plan, per, q = self.plans[w], jd.periods_t[w], self._sets[w]
             kw = dict(kind=_lib.KIND_RAYLEIGH if w == "R" else _lib.KIND_LOVE, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
             o = 0 if w == "R" else 6
-            if thickness:
+            if thickness and "U" in q:
+                c, u, st, kb, ka, kr, ub, ua, ur, kh, _, uh, _, _, _ = plan.run_group_thickness_kernels(
+                    model, per, want_dcdz=False, want_dudz=False, count=False, **kw)
+                part[o + 3:o + 6] = [ub, ua, ur]
+                part_h[o // 3], part_h[o // 3 + 1] = kh, uh
+                pred["u" + w] = u
+            elif thickness:
                 c, u, st, kb, ka, kr, kh, _, _ = plan.run_thickness_kernels(model, per, want_dcdz=False, count=False, **kw)
                 part_h[o // 3] = kh
             elif not q & {"U", "E"}:
                 c, u, st, kb, ka, kr = plan.run_kernels(model, per, **kw)
-            if "U" in q:
+            if "U" in q and not thickness:
                 c, u, st, kb, ka, kr, ub, ua, ur, _ = plan.run_group_kernels(model, per, count=False, **kw)
                 part[o + 3:o + 6] = [ub, ua, ur]
                 pred["u" + w] = u
@@ -462,7 +478,8 @@ class LsqPlan:
         upper bound of the free layers of any stack (default L; at most 128).  Returns dict(delta [B, L] float64, misfit,
         roughness, predicted [B] float64, used, dropped, flag [B] int32, pred, part) - views of the plan's buffers, rewritten by
         the next call.  Flags: 0 solved, 1 no usable row, 2 pivot <= 0 or not finite, 3 more free layers than nfree_max.
-        Thickness modes (``surfdisp_lsq_step_modes_device``; phase-velocity data only, ValueError otherwise): ``modes`` float64
+        Thickness modes (``surfdisp_lsq_step_modes_device``; phase-velocity data, group-velocity data too on a plan with
+        ``group_modes``, ValueError otherwise): ``modes`` float64
         [K, L] or [B, K, L], ``mode_scale`` and ``mode_prior`` float64 [K] ([B, K] with per-stack modes; None: 1 and 0),
         ``mode_y`` float64 [B, K] (None: 0); the result then holds delta_y [B, K] float64 and part_h, the five thickness
         arrays, as well.  Without ``modes`` the entry without modes is launched."""
@@ -551,7 +568,8 @@ class LinearizedBatch:
     x and lam <- lam nu.  A rejected stack's kernels are computed again in the next iteration although x did not move (they
     are not cached per stack): the batch stays one launch, and a rejected step is the rare case.
 
-    Thickness modes (phase-velocity data only): ``modes`` [K, L] or [M, K, L], the shapes (``thickness_mode``,
+    Thickness modes (phase-velocity data only; with ``group_modes=True`` group-velocity data as well, never an ellipticity
+    set): ``modes`` [K, L] or [M, K, L], the shapes (``thickness_mode``,
     ``interface_mode``; entries at layers >= nlay - 1 are set to 0); ``mode_scale`` (> 0) and ``mode_prior`` (>= 0): a scalar,
     [K] or [M, K]; ``mode_bounds`` = (lo, hi), scalars or arrays that broadcast to [M, K], on the amplitude ``y`` [M, K]
     accumulated since ``model0`` (km); ``h_min`` (km).  The trial then also has h <- float32(h + T (y_new - y)) with y_new =
@@ -560,7 +578,7 @@ class LinearizedBatch:
 
     def __init__(self, model0, datasets, free=None, vp_slope=0.0, rho_slope=0.0, alpha=1.0, Q=None, lam0=1.0, nu=4.0,
                  lam_min=1e-9, vs_bounds=None, nlay=None, mask=None, device="cuda:0", modes=None, mode_scale=1.0, mode_prior=0.0,
-                 mode_bounds=None, h_min=1e-3):
+                 mode_bounds=None, h_min=1e-3, group_modes=False):
         m0 = model0.detach().cpu().numpy() if hasattr(model0, "detach") else np.asarray(model0)
         if m0.ndim != 3 or m0.shape[1] != 5:
             raise ValueError("model0 must be [M, 5, L]")
@@ -628,8 +646,8 @@ class LinearizedBatch:
                 raise ValueError("h_min must be finite and >= 0")
         jd = JointData(datasets, device="cpu")                                    # (data errors: ValueError)
         if modes is not None:
-            _phase_only(jd)
-        self.plan = plan = LsqPlan(M, L, jd, device=device, mask=mask)            # (no HIP device: SurfdispError)
+            _mode_data(jd, group_modes)
+        self.plan = plan = LsqPlan(M, L, jd, device=device, mask=mask, group_modes=group_modes)            # (no HIP device: SurfdispError)
         import torch
         self.torch = torch
         dev = self.device = plan.device

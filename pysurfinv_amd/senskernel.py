@@ -163,6 +163,15 @@ def group_from_phase_partials(c, u, k_minus, k_plus, dlnT):
     return r * (2.0 - r) * 0.5 * (km + kp) - r * r * (kp - km) / float(dlnT)
 
 
+def group_thickness_reference(c, u, h_minus, h_plus, dlnT):
+    """dU/dh (or dU/dz) in float64 from the thickness rows ``h_minus`` / ``h_plus`` of the phase velocity (dcdh or dcdz of
+    ``thickness_kernels_reference`` / ``run_thickness_kernels``) at T (1 - d) and T (1 + d): Rodi's rule holds for any model
+    parameter, so this is ``group_from_phase_partials`` on those rows - the host statement of what
+    ``surfdisp_forward_group_thickness_kernels_device`` combines (include/surfdisp.h section (5h)).  c, u: the unit's own values
+    at T, broadcast against the rows; ``dlnT`` = ln((1 + d) / (1 - d))."""
+    return group_from_phase_partials(c, u, h_minus, h_plus, dlnT)
+
+
 def attenuation_from_kernels(model, periods, c, u, kb, ka=None):
     """Apparent attenuation of the mode from its phase-velocity kernels, in float64 (the host statement of what the HIP
     attenuation kernel computes; the reference forms the same numbers after REIGEN / LEIGEN, calcul.f:256-265, 341-349,
@@ -441,6 +450,33 @@ def _eigen_dict(model, kind, c, u, st, ur, uz, tz, tr, en):
     return out
 
 
+def _per_km(model, k):
+    """A row of partials in the reference's ``SensKernelPert`` units: k * Vs / 100 / h (zeros where a layer has no thickness)."""
+    import torch
+    h = model[:, 3, :][:, None, :]
+    vs = model[:, 1, :][:, None, :]
+    return torch.where(h > 0, k * vs / 100.0 / torch.where(h > 0, h, torch.ones_like(h)), torch.zeros_like(k))
+
+
+def group_thickness_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, dlnT_frac=0.01):
+    """``analytic_kernels(group=True)`` and ``analytic_kernels(thickness=True)`` from ONE forward solve, and the derivatives of
+    the GROUP velocity with respect to the layer thicknesses and the interface depths on top of them
+    (``surfdisp_forward_group_thickness_kernels_device``, both wave types).  Returns the keys of both calls with the same
+    numbers - dcdb, dcda, dcdr, c0, u0, status, phv, dudb, duda, dudr, grv, dcdh, dcdz - plus dudh [M, P, L] = d U / d (thickness
+    of layer i), everything below shifted rigidly, dudz [M, P, L] = d U / d (depth of the top of layer j) alone, n_failed
+    (units whose shifted root failed: NaN rows in dudb .. dudz) and n_nonfinite (units whose thickness rows are not finite:
+    NaN rows in dudh, dudz); see ``group_thickness_reference``.  A function of its own: ``analytic_kernels`` refuses
+    ``thickness=True`` together with ``group=True`` (each of its flags names one entry of the library;
+    tests/test_thickness_host.py pins the refusal)."""
+    kind = {"R": 2, "L": 1}[wtype]
+    M, _, L = model.shape
+    plan = _forward.BatchPlan(M, L, periods.numel(), device=model.device)
+    c, u, st, kb, ka, kr, ub, ua, ur, kh, kz, uh, uz, nf, nnf = plan.run_group_thickness_kernels(
+        model, periods, kind=kind, nlay=nlay, dlnT_frac=dlnT_frac, want_vp=want_vp, want_rho=want_rho)
+    return dict(dcdb=kb, dcda=ka, dcdr=kr, c0=c, u0=u, status=st, phv=_per_km(model, kb), dudb=ub, duda=ua, dudr=ur,
+                grv=_per_km(model, ub), dcdh=kh, dcdz=kz, dudh=uh, dudz=uz, n_failed=nf, n_nonfinite=nnf)
+
+
 def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rho=True, group=False, dlnT_frac=0.01,
                      ellipticity=False, attenuation=False, eigen=False, thickness=False):
     """Sensitivity kernels of a whole batch from ONE forward solve (``surfdisp_forward_kernels_device``):
@@ -467,7 +503,7 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
     of layer i), everything below shifted rigidly (what a change of ``model[:, 3, i]`` does), dcdz [M, P, L] = d c / d (depth of
     the top of layer j) with the other interfaces fixed, and n_nonfinite (units whose rows are NaN); see
     ``thickness_kernels_reference``.  One entry of its own as well: refused together with ``group=True``, ``ellipticity=True``
-    or ``attenuation=True``.
+    or ``attenuation=True``; ``group_thickness_kernels`` is the call that returns the rows of group and thickness and dU/dh.
     ``eigen=True`` (``surfdisp_forward_eigen_device``, one more solve on the same plan): also the keys of
     ``eigenfunctions`` - ur, uz, tz, tr (Love ut, tt), I0, I1, I2, amp, ztop."""
     import torch
@@ -496,9 +532,7 @@ def analytic_kernels(model, periods, wtype="R", nlay=None, want_vp=True, want_rh
                                                                       want_vp=want_vp, want_rho=want_rho)
     else:
         c, u, st, kb, ka, kr = plan.run_kernels(model, periods, kind=kind, nlay=nlay, want_vp=want_vp, want_rho=want_rho)
-    h = model[:, 3, :][:, None, :]
-    vs = model[:, 1, :][:, None, :]
-    per_km = lambda k: torch.where(h > 0, k * vs / 100.0 / torch.where(h > 0, h, torch.ones_like(h)), torch.zeros_like(k))
+    per_km = lambda k: _per_km(model, k)
     out = dict(dcdb=kb, dcda=ka, dcdr=kr, c0=c, u0=u, status=st, phv=per_km(kb))
     if group:
         out.update(dudb=ub, duda=ua, dudr=ur, grv=per_km(ub), n_failed=nf)
