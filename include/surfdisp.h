@@ -470,6 +470,35 @@ int surfdisp_prior_device(void *stream, int C, int N, int L, const double *param
 int surfdisp_mcmc_propose_masked_device(void *stream, int C, int N, const double *p, const double *vmin, const double *vmax,
                                         const double *step, unsigned long long seed, unsigned long long counter, int attempt, int mode,
                                         const unsigned char *tags, int tag, double *out, long chain0);
+/* The same loop INSIDE one kernel (csrc/surfdisp_mcmc_prior.hip; added within ABI 4), with the reference's caps and for every node
+ * of the speculative tree below: surfdisp_mcmc_propose_prior_device draws out [C][2^depth - 1][N] (depth 1..4; depth 1: the plain
+ * proposal) so that every row satisfies the rules.  One wavefront per chain.  Node k = 0, 1, ..., 2^depth - 2 draws from the state
+ * of its branch (node 0: p[c]; child 2k+1: the final proposal of k; child 2k+2: the state of k).  Retry r = 0 .. gauss_tries - 1
+ * redraws ALL N scalars with the bounded Gaussian step of (6b), retry r = gauss_tries .. gauss_tries + uniform_tries - 1 with its
+ * uniform branch (reset); the candidate row [N scalars | aux[c][0..K)] is tested with surfdisp_prior_device's rules (flags [L],
+ * eps; vs_max < 0: no cap); the first good candidate is out[c][k][:], tries[c][k] = r.  No good candidate: out[c][k][:] is the
+ * state the node drew from, tries[c][k] = gauss_tries + uniform_tries, and *exhausted (one device int the caller zeroes once; it
+ * is only ever incremented) grows by one - the reference raises there (models.py:219), a caller reads the count when it
+ * synchronises anyway.  gauss_tries >= 0, uniform_tries >= 0, 1 <= gauss_tries + uniform_tries <= SURFDISP_MCMC_PRIOR_TRIES_MAX;
+ * N + K <= SURFDISP_MCMC_PRIOR_ROW_MAX (the row lives in LDS, with the candidate's Vs at the grid points: (N + K + L + 11) doubles
+ * per chain); aux may be NULL when K == 0; tries may be NULL; L = the descriptor's output layers.  Static-structure models without
+ * a thermal layer, as surfdisp_prior_device (a descriptor with one, or with more grid points than L layers can have: every node is
+ * reported exhausted).
+ * Random numbers: Philox4x32-10 with the word layout of the other entries - word 0 the counter's low half; word 1 its high half
+ * XOR (node << 20) XOR (try t << 8) for the Gaussian tries t = 0..499 of one scalar, XOR (node << 20) XOR 0x00ffff00 for its
+ * uniform draw; words 2, 3 the stream index gidx + (r << 48), gidx = (chain0 + c) * N + n: the whole-proposal retry r sits in
+ * bits 16..29 of word 3, hence (chain0 + C) * N < 2^48 is required.  With r = 0 every draw is the draw of
+ * surfdisp_mcmc_propose_device / surfdisp_mcmc_propose_tree_device: with rules that accept everything the three entries write the
+ * same bits.  A sampler split into chain groups (chain0) draws what one call draws.  Bad arguments: SURFDISP_ERR_INVALID before
+ * any device call.  Stream-ordered, no host synchronisation, graph-capturable. */
+#define SURFDISP_MCMC_PRIOR_ROW_MAX 256
+#define SURFDISP_MCMC_PRIOR_TRIES_MAX 16384
+int surfdisp_mcmc_propose_prior_device(void *stream, int C, int N, int K, int L, int depth,
+                                       const double *p, const double *aux, const double *vmin, const double *vmax, const double *step,
+                                       const int *idesc, const double *fdesc, const int *flags, double vs_max,
+                                       int gauss_tries, int uniform_tries,
+                                       unsigned long long seed, unsigned long long counter, long chain0,
+                                       double *out, unsigned short *tries, int *exhausted);
 /* The SPECULATIVE lock step for few chains (a lock step of 100 chains leaves the chip idle, so it costs no more to solve
  * several proposals per chain): propose_tree draws the binary tree of the next `depth` (1..4) accept / reject outcomes -
  * node k's proposal from the state its branch would be in (node 0: the chain's state; child 2k+1 "accepted": proposal k;

@@ -943,6 +943,43 @@ int surfdisp_mcmc_propose_tree_device(void *stream, int C, int N, int depth, con
                         false, nullptr, 0, 0);
 }
 
+// The proposal tree of a sampler with a prior, redrawn inside the kernel until the rules hold (csrc/surfdisp_mcmc_prior.hip; header
+// section (6c)).  Every argument is judged on the host before anything touches the device.
+int surfdisp_mcmc_propose_prior_device(void *stream, int C, int N, int K, int L, int depth,
+                                       const double *p, const double *aux, const double *vmin, const double *vmax, const double *step,
+                                       const int *idesc, const double *fdesc, const int *flags, double vs_max,
+                                       int gauss_tries, int uniform_tries,
+                                       unsigned long long seed, unsigned long long counter, long chain0,
+                                       double *out, unsigned short *tries, int *exhausted)
+{
+    const char *name = "surfdisp_mcmc_propose_prior_device";
+    if (C < 1 || N < 1 || K < 0 || L < 1 || L > SURFDISP_NLAY_MAX || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH) {
+        set_err("%s: invalid size (C >= 1; N >= 1; K >= 0; 1 <= L <= SURFDISP_NLAY_MAX; 1 <= depth <= 4)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if ((long)N + (long)K > sd::SD_MCMC_PRIOR_ROW) {
+        set_err("%s: invalid size: N + K beyond the SURFDISP_MCMC_PRIOR_ROW_MAX = 256 doubles of the row in LDS", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (gauss_tries < 0 || uniform_tries < 0 || (long)gauss_tries + uniform_tries < 1 ||
+        (long)gauss_tries + uniform_tries > sd::SD_MCMC_PRIOR_TRIES) {
+        set_err("%s: invalid caps: gauss_tries >= 0, uniform_tries >= 0, 1 <= their sum <= 16384", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    // (chain0 + C) * N < 2^48: the retry index sits above bit 48 of the stream index
+    const long lim = 1L << 48;
+    if (chain0 < 0 || chain0 >= lim || chain0 + (long)C > (lim - 1) / N) {
+        set_err("%s: invalid chain0: (chain0 + C) * N must stay below 2^48", name); return SURFDISP_ERR_INVALID;
+    }
+    if (!p || !vmin || !vmax || !step || !idesc || !fdesc || !flags || !out || !exhausted || (K > 0 && !aux)) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::McmcPriorArgs a{C, N, K, L, depth, p, aux, vmin, vmax, step, idesc, fdesc, flags, vs_max, gauss_tries, uniform_tries,
+                        seed, counter, chain0, out, tries, exhausted};
+    SD_HIP(sd::launch_mcmc_propose_prior(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; header section (6f)).  Workspace: the per-slab partials
 // [npoints][nslab][D + N][5] doubles, the slabs' smallest misfits [npoints][nslab] doubles, then four int arrays [npoints][nslab].
 static long post_slabs(int R) { return ((long)R + SURFDISP_POST_SLAB_ROWS - 1) / SURFDISP_POST_SLAB_ROWS; }

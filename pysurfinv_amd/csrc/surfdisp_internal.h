@@ -292,6 +292,28 @@ struct McmcAcceptArgs {
     int depth, nsteps;      // speculative tree: walk nsteps <= depth steps (depth <= 1: the plain single test)
     long step_stride;       // doubles between the mcTrack rows of consecutive steps of one chain
 };
+// the proposal tree of a sampler with a prior, redrawn inside the kernel until the rules hold (csrc/surfdisp_mcmc_prior.hip;
+// include/surfdisp.h section (6c))
+constexpr int SD_MCMC_PRIOR_ROW = SURFDISP_MCMC_PRIOR_ROW_MAX;   // doubles of the candidate row in LDS: N + K
+constexpr int SD_MCMC_PRIOR_TRIES = SURFDISP_MCMC_PRIOR_TRIES_MAX;
+constexpr int SD_MCMC_PRIOR_GRID_EXTRA = 11;   // grid points whose Vs it keeps in LDS, beyond L: L output layers of <= 10 input layers have <= L + 10 (with the ReferenceMantle's 21 points: <= L + 11)
+struct McmcPriorArgs {
+    int C, N, K, L, depth;
+    const double *p;        // [C][N] chain states
+    const double *aux;      // [C][K] per-chain local constants (slots N .. N + K - 1 of a row), nullptr when K == 0
+    const double *vmin, *vmax, *step;   // [N]
+    const int *idesc;       // the params -> stack descriptor, see surfdisp_layers.hip
+    const double *fdesc;
+    const int *flags;       // [L] the rules per output layer, see surfdisp_prior_kernel
+    double vs_max;          // < 0: no cap
+    int gauss_tries, uniform_tries;
+    unsigned long long seed, counter;
+    long chain0;
+    double *out;            // [C][2^depth - 1][N]
+    unsigned short *tries;  // [C][2^depth - 1] or nullptr
+    int *exhausted;         // [1], incremented per node without a good candidate
+};
+hipError_t launch_mcmc_propose_prior(hipStream_t s, const McmcPriorArgs &a);
 // joint data (Rayleigh / Love, phase / group, Rayleigh ellipticity): the accept kernel's arguments plus the solves' predictions and
 // the column table.  In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
 struct McmcJointArgs {

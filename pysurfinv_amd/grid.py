@@ -53,7 +53,9 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
                   min, max)``, [n_points, D] each, on every rank.
     Returns dict(points=(lo, hi), mcTrack=[n_local, chains*chainL, 3+N] or None, summaries=[n_points, 6+2N+P]
     (every rank holds all rows, point order), columns, elapsed (sampling + summaries + gather, this rank),
-    elapsed_write, report).  ``report`` carries the MAX over ranks of ``elapsed`` and the summed counters."""
+    elapsed_write, report).  ``report`` carries the MAX over ranks of ``elapsed`` and the summed counters; among them
+    ``prior_exhausted`` (and ``prior_exhausted_rank``, this rank's share): ``MetropolisBatch.prior_exhausted()``, 0 unless
+    ``isgood`` is a ``PriorRules(redraw="kernel")`` whose caps ran out - reported here, never raised."""
     import torch
     lons, lats = np.asarray(lons), np.asarray(lats)
     c_obs, uncer = np.asarray(c_obs, float), np.asarray(uncer, float)
@@ -66,6 +68,7 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     cdev = dev if dev.type != "cpu" else None
     t0 = time.perf_counter()
     n_forward = 0
+    mc = None
     tracks_dev = torch.zeros((n_local, chains_per_point * chainL, 3 + N), dtype=torch.float64, device=dev)
     summ = torch.zeros((n_local, 6 + 2 * N + P), dtype=torch.float64, device=dev)
     if model_batch.n_aux and local_info is None:
@@ -107,6 +110,9 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    # PriorRules(redraw="kernel"): proposals that found no good model within the caps.  Reported, not raised: a rank that raised
+    # here would leave the others waiting in the collectives below.
+    prior_exhausted = mc.prior_exhausted() if mc is not None else 0
     # ---- outside the timed path: tracks to the host and {lon}_{lat}.npz files from writer threads
     t1 = time.perf_counter()
     tracks = tracks_dev.cpu().numpy() if (keep_tracks or outdir is not None) else None
@@ -121,11 +127,12 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
         with ThreadPoolExecutor(max_workers=max(1, int(writer_threads))) as ex:
             list(ex.map(write, range(n_local)))
     elapsed_write = time.perf_counter() - t1
-    max_elapsed, (tot_forward, tot_points) = shard.reduce_report(elapsed, [n_forward, n_local], device=cdev)
+    max_elapsed, (tot_forward, tot_points, tot_exhausted) = shard.reduce_report(elapsed, [n_forward, n_local, prior_exhausted], device=cdev)
     steps = tot_points * chains_per_point * chainL
     res = dict(points=(lo, hi), mcTrack=tracks if keep_tracks else None, summaries=summaries,
                columns=summary_columns(N, P), elapsed=elapsed, elapsed_write=elapsed_write,
                report=dict(elapsed_max=max_elapsed, forward_solves=tot_forward, points=tot_points,
+                           prior_exhausted=tot_exhausted, prior_exhausted_rank=prior_exhausted,
                            metropolis_steps=steps,
                            steps_per_s=steps / max_elapsed if max_elapsed > 0 else 0.0,
                            solves_per_s=tot_forward / max_elapsed if max_elapsed > 0 else 0.0))

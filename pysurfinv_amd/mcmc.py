@@ -76,14 +76,26 @@ class PriorRules:
     ``rounds`` Gaussian rounds (only the chains whose proposal broke a rule draw again), then ``reset_rounds`` rounds of uniform
     prior draws, and a chain that is still without a good proposal proposes its own state (a wasted step: with a prior that
     accepts half of the Gaussian draws, 1 chain in 60 reaches the uniform rounds and fewer than 1 in 1e3 the wasted step).  Called with a parameter tensor it evaluates
-    the same rules in torch on ``Model1DBatch.seis_prop_grids`` (the torch lock step; the tests compare the two)."""
+    the same rules in torch on ``Model1DBatch.seis_prop_grids`` (the torch lock step; the tests compare the two).
+    ``redraw="kernel"`` runs the reference's own loop instead, inside one kernel per lock step (``surfdisp_mcmc_propose_prior_device``):
+    ``gauss_tries`` whole-proposal Gaussian redraws, then ``uniform_tries`` uniform ones, at every node of the speculative tree too;
+    a chain that exhausts both proposes its own state and is counted (``MetropolisBatch.prior_exhausted``)."""
 
-    def __init__(self, model, monotone_groups=("sediment", "crust"), positive_jumps=True, vs_max=None, rounds=5, reset_rounds=2):
+    MAX_TRIES = 16384               # gauss_tries + uniform_tries: the retry index has 14 bits of the random streams' index
+
+    def __init__(self, model, monotone_groups=("sediment", "crust"), positive_jumps=True, vs_max=None, rounds=5, reset_rounds=2,
+                 redraw="rounds", gauss_tries=1000, uniform_tries=10000):
         self.model = model
         self.monotone_groups = tuple(monotone_groups)
         self.positive_jumps = bool(positive_jumps)
         self.vs_max = None if vs_max is None else float(vs_max)
         self.rounds, self.reset_rounds = int(rounds), int(reset_rounds)
+        if redraw not in ("rounds", "kernel"):
+            raise ValueError("PriorRules: redraw must be 'rounds' or 'kernel'")
+        self.redraw = redraw
+        self.gauss_tries, self.uniform_tries = int(gauss_tries), int(uniform_tries)
+        if self.gauss_tries < 0 or self.uniform_tries < 0 or not 1 <= self.gauss_tries + self.uniform_tries <= self.MAX_TRIES:
+            raise ValueError(f"PriorRules: gauss_tries >= 0, uniform_tries >= 0 and 1 <= their sum <= {self.MAX_TRIES}")
         self._flags = None
 
     def __call__(self, params, rows=None):
@@ -132,6 +144,7 @@ class ChainGroups:
             ch.independent, ch.fast_scan, ch.isgood = mc.independent, mc.fast_scan, mc.isgood
             ch.joint, ch.periods = mc.joint, mc.periods
             ch._chain0 = mc._chain0 + lo
+            ch._exh = mc._exhausted_counter() if mc._kernel_rules() is not None else None   # one counter for all groups
             if ch._fz is not None and (ch._fz["c_obs"].data_ptr() != ch.c_obs.contiguous().data_ptr()):
                 ch._fz = None                                   # (the fused buffers hold contiguous copies of the observations)
 
@@ -226,6 +239,8 @@ class MetropolisBatch:
         self._counter = 0                                       # calls of the fused kernels so far: the Philox counter of the next one
         self._pipelined = False                                 # a chain group: another group's solve is in flight beside this one
         self._chain0 = 0                                        # index of this object's chain 0 in the whole sampler (chain groups)
+        self._exh = None                                        # PriorRules(redraw="kernel"): one device int, shared with the chain groups
+        self._last_groups = None                                # the ChainGroups of the last run (last_prior_tries)
 
     def _fresh_state(self):
         """What a sampler owns and a chain group's child (a shallow copy of its parent) must not share with it."""
@@ -322,7 +337,7 @@ class MetropolisBatch:
     def fused_available(self):
         """The lock step can run as propose kernel -> stacks -> solver -> accept kernel (no torch glue, no host
         synchronisation): device proposer, the HIP forward path, and no ``isgood`` callback - or a ``PriorRules`` one, whose
-        redraw loop runs on the device too (``_propose_with_rules``)."""
+        redraw loop runs on the device too (``_redraw_with_rules``, or ``_propose_prior`` with ``redraw="kernel"``)."""
         dev_prior = self.isgood is None or (isinstance(self.isgood, PriorRules) and self.device.type == "cuda"
                                             and self.local_rows is None and self.isgood.device_flags() is not None)
         return (dev_prior and isinstance(self.proposer, TorchProposer) and self.device.type == "cuda"
@@ -336,8 +351,57 @@ class MetropolisBatch:
             st = dict(C=C, data=self.joint, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
                       chi=torch.zeros(C, dtype=torch.float64, device=self.device),
                       mask8=self.mask.to(torch.uint8).contiguous(), c_obs=self.c_obs.contiguous(), uncer=self.uncer.contiguous())
+            if self._kernel_rules() is not None:
+                self._exhausted_counter()                         # (made and zeroed here, once: no memset per step)
             self._fz = st
         return st
+
+    # ------------------------------------------------------------------ prior redraw inside the propose kernel
+    def _kernel_rules(self):
+        """The ``PriorRules`` of this sampler when its redraw loop runs inside the propose kernel (``redraw="kernel"``), else None."""
+        rules = self.isgood
+        return rules if isinstance(rules, PriorRules) and rules.redraw == "kernel" else None
+
+    def _exhausted_counter(self):
+        """The device int the prior-redraw kernel counts exhausted nodes in: one per sampler, shared by its chain groups."""
+        if self._exh is None:
+            self._exh = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
+        return self._exh
+
+    def prior_exhausted(self):
+        """How many proposals of this sampler (tree nodes of all fused lock steps so far) found no model the prior accepts within
+        ``gauss_tries + uniform_tries`` redraws and proposed the state they drew from - where the reference raises
+        ``RuntimeError`` (models.py:219).  0 for every other redraw mode.  Synchronises once; ``run()`` itself never does."""
+        return 0 if self._exh is None else int(self._exh.item())
+
+    def last_prior_tries(self):
+        """uint16 [C, M]: the retry index every proposal of the last fused lock step was accepted at by the prior (M = 2^depth - 1
+        tree nodes, 1 for a plain step; ``gauss_tries + uniform_tries``: exhausted), or None before the first such step."""
+        torch = self.torch
+        owners = self._last_groups.children if self._last_groups is not None else [self]
+        ts = [o._fz.get("tries") if o._fz is not None else None for o in owners]
+        if any(t is None for t in ts):
+            return None
+        return ts[0] if len(ts) == 1 else torch.cat([t.view(torch.int16) for t in ts], dim=0).view(torch.uint16)
+
+    def _propose_prior(self, stream, p, out, depth, counter, st):
+        """The proposal tree ``out`` [C, 2^depth - 1, N] (depth 1: [C, N]) of the states ``p``, every row redrawn inside the kernel
+        until the ``PriorRules`` hold (``surfdisp_mcmc_propose_prior_device``: one launch)."""
+        torch = self.torch
+        rules = self._kernel_rules()
+        C, N = p.shape
+        M = (1 << int(depth)) - 1
+        mb = rules.model
+        idesc, fdesc, Lout = mb.native_descriptor()
+        tries = st.get("tries")
+        if tries is None or tries.shape != (C, M):
+            tries = st["tries"] = torch.zeros((C, M), dtype=torch.int16, device=self.device).view(torch.uint16)
+        aux = mb._full(p)[:, N:].contiguous() if mb.n_aux else None
+        pr = self.proposer
+        _lib.check(_lib.lib().surfdisp_mcmc_propose_prior_device(
+            stream, C, N, int(mb.n_aux), int(Lout), int(depth), _ptr(p), _ptr(aux), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
+            _ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()), ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max),
+            rules.gauss_tries, rules.uniform_tries, pr.seed_int, counter, self._chain0, _ptr(out), _ptr(tries), _ptr(self._exhausted_counter())))
 
     def _solve_raw(self, params, rows=None):
         """The solver's own fp32 output tensors (no copies) for the stacks of ``params``: (c[C, P], status[C]), or with joint
@@ -483,10 +547,13 @@ class MetropolisBatch:
                 p1 = p
             else:
                 p1 = st["p1"]
-                _lib.check(_lib.lib().surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
-                                                                   pr.seed_int, counter, 0, _ptr(p1), self._chain0))
-                if self.isgood is not None:
-                    self._redraw_with_rules(p, p1, counter, stream)
+                if self._kernel_rules() is not None:           # proposal and the prior's redraw loop in one kernel
+                    self._propose_prior(stream, p, p1, 1, counter, st)
+                else:
+                    _lib.check(_lib.lib().surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
+                                                                       pr.seed_int, counter, 0, _ptr(p1), self._chain0))
+                    if self.isgood is not None:
+                        self._redraw_with_rules(p, p1, counter, stream)
             self._accept(stream, self._solve_raw(p1), st, p1, p, rowp, row_stride, counter, False, first=first)
         return p
 
@@ -529,10 +596,12 @@ class MetropolisBatch:
         its periods one after the other on a mostly idle chip, and costs the same 0.9-1.0 ms for 100 stacks as for 700
         (100 chains x 96 layers: 0.96 ms per step plain, 0.345 with d = 3, 0.31 with d = 4 at 4.1 forward solves per step;
         scripts/time_speculative.py): 4 up to 136 chains, 3 up to 292, 2 up to 682, 1 from 683 chains on, and 1 where the (stack, period) decomposition fills the chip
-        instead (``independent``: 0.24 ms per step plain, 0.29 with d = 3)."""
+        instead (``independent``: 0.24 ms per step plain, 0.29 with d = 3).  A ``PriorRules`` in its default ``redraw="rounds"`` mode
+        keeps depth 1 (the rounds know no tree); with ``redraw="kernel"`` every node is redrawn until the rules hold and the depth
+        is the one above."""
         if self._indep(C):
             return 1
-        if self.isgood is not None:
+        if self.isgood is not None and self._kernel_rules() is None:
             return 1                                               # (prior rules: the redraw rounds belong to the plain lock step)
         for d in (4, 3, 2):
             if C * ((1 << d) - 1) <= self.SPEC_MAX_STACKS:
@@ -556,8 +625,11 @@ class MetropolisBatch:
             st["qrows"] = torch.arange(C, device=self.device).repeat_interleave(M) if self.local_rows is not None else None
         pr = self.proposer
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax),
-                                                                    _ptr(pr.step), pr.seed_int, counter, _ptr(st["q"]), self._chain0))
+            if self._kernel_rules() is not None:                   # every node redrawn until the prior's rules hold
+                self._propose_prior(stream, p, st["q"], depth, counter, st)
+            else:
+                _lib.check(_lib.lib().surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax),
+                                                                        _ptr(pr.step), pr.seed_int, counter, _ptr(st["q"]), self._chain0))
             self._accept(stream, self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"]), st, st["q"], p, rowp, row_stride, counter,
                          True, depth=depth, nsteps=nsteps, step_stride=step_stride)
         return p
@@ -669,6 +741,7 @@ class MetropolisBatch:
             p = self._start(C, init_first, _init_mask).contiguous().clone()
             stride = chainL * (3 + N)
             cg = self.chain_groups(C, groups) if spec_depth <= 1 else None
+            self._last_groups = cg
             base = self._counter
             if cg is None and spec_depth > 1:
                 # speculative lock steps: the first row is the start model itself, then spec_depth steps per batched solve

@@ -89,6 +89,9 @@ class Point:
         track = mc.run(max(int(runN) // int(chainL), 1), int(chainL), init_first=True, priori=priori,
                        spec_depth=spec_depth)
         arr = track.cpu().numpy().reshape(-1, track.shape[-1])
+        n_exhausted = mc.prior_exhausted()                         # PriorRules(redraw="kernel"); the track is on the host already
+        if n_exhausted:
+            raise RuntimeError(f"Error: Cound not find a good model through reset ({n_exhausted} proposals).")   # models.py:219
         MetropolisBatch.save_npz(outdir, pid, arr, self.setting, self.obs, chainL)
         return arr
 
