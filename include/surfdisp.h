@@ -796,7 +796,61 @@ int surfdisp_lsq_resolution_modes_device(void *stream, int B, int Lmax, const in
                                          double *cov, double *res, double *sigma_post, double *sigma_data, double *rdiag,
                                          double *sigma_post_y, double *sigma_data_y, double *rdiag_y, double *stats, int *info);
 
-/* ---- (7) introspection of the two-tier root search.  The production kernel hands the stacks it cannot treat
+/* ---- (6i) LINEARISED INVERSION IN THE SAMPLER'S PARAMETERS, added within ABI 4 (csrc/surfdisp_lsq_params.hip): the least-squares fit of
+ *          a `setting` itself - B-spline coefficients, group thicknesses, BottomDepth - where (6d)/(6h) fit layer Vs and hand-made modes.
+ *          surfdisp_params_jacobian_device: the exact derivative of the map of (6) for a static-structure model WITHOUT a thermal
+ *          layer.  params [C][N] and idesc / fdesc exactly as surfdisp_params_to_model_device takes them; the leading Nu columns of
+ *          params are the unknowns (1 <= Nu <= min(N, 64); the random-walk parameters come first in a row, the per-point local
+ *          constants behind them are never unknowns).
+ *   out:   layer [C][4][L] fp64 (may be NULL): vp, vs, rho, h of the output layers - the row order of `model` - before the rounding
+ *          to fp32; jac [C][4][L][Nu] fp64: their partial derivatives with respect to unknown j.  Covered: coefficient slots and
+ *          constants, H slots, the BottomDepth rule (H = p - z: a thickness above enters with the opposite sign), the Vs(H) of
+ *          OceanSedimentCascadia, the closed forms Vp(Vs), rho(Vs) of every layer class, the 21 points of the ReferenceMantle (z, and
+ *          Vs of the last grid point), the midpoint averaging and h = z_b - z_a.  -max(topo, 0) is a local constant.  A descriptor
+ *          with a thermal layer (kind 6): NaN everywhere, nothing is read from a scratch array.
+ *          One thread per (chain, layer, unknown), each a dual number for its one unknown.  No workspace; graph-capturable.
+ *          SURFDISP_ERR_INVALID, before anything is launched: C < 1, N < 1, Nu outside 1..min(N, 64), L outside 2..200, a NULL params,
+ *          idesc, fdesc or jac.
+ *          surfdisp_lsq_step_params_device: one damped least-squares step of the parameters, one stack per chain (B = C, Lmax = L).
+ *   rows:  the row table of (6d) - cols, weights, obs, uncer, mask, obs_per_stack, pred[5], pred_stride[5], nper[2], part[15] - and
+ *          part_h[5] of (6h) (part_h[4] waits for dchi/dh).  free [Nu] uint8, or [B][Nu] with free_per_stack (NULL: every unknown is
+ *          free): the n unknowns that move.  scale [Nu] (> 0), prior_w [Nu] (beta >= 0; NULL: 0), prior_ref [Nu] (required with prior_w),
+ *          params [B][Np] (Np >= Nu doubles per row; the current point, read for the prior term only), lam [B]; device memory, the
+ *          values are not checked.  With sg_r the sign of a source-5 row and src the row's source,
+ *              G[r,j] = sg_r * ( sum_{i<nlay}   part[src][Vs][i] jac[vs][i][j] + part[src][Vp][i] jac[vp][i][j] + part[src][rho][i] jac[rho][i][j]
+ *                              + sum_{i<nlay-1} part_h[src][i] jac[h][i][j] )
+ *          in fp64, layers ascending; a term whose jac entry is exactly 0 is skipped, not multiplied (a water layer's NaN d/dVs does not
+ *          poison a row), and so is a term of an absent part array.  Residual, weight and every row-drop rule are those of (6d) / (6h):
+ *          a row is also dropped when part_h of its source is NULL or when one of its columns is not finite.
+ *   solve: in fp64 by Cholesky factorisation over the n free unknowns,
+ *              A = G^T W G + lam_s diag(1 / scale_j^2) + diag(beta_j),    rhs = G^T W res - beta_j (p_j - ref_j),    delta = A^-1 rhs.
+ *          The step is not clamped.
+ *   out:   delta [B][Nu] (0 at fixed unknowns); stats [B][3] fp64 = data misfit sum W res^2, prior term sum beta (p - ref)^2 at p, and the
+ *          objective the linear model predicts at p + delta, sum W (res - G delta)^2 + sum beta (p + delta - ref)^2; info [B][3] int = rows
+ *          used, rows dropped, flag: 0 solved; 1 no usable row; 2 a pivot <= 0 or not finite (or a step or an inverse that is not
+ *          finite).  For a flag other than 0 delta, cov, sigma and logdet of that stack are zeros, never NaN, and the predicted
+ *          objective is the one at p.  Optional, each may be NULL and is then not computed: cov [B][Nu][Nu] = A^-1 in unknown order,
+ *          exactly symmetric, zeros in the rows and columns of fixed unknowns; sigma [B][Nu] = sqrt(diag cov); logdet [B] = log det A.
+ *          One workgroup of 256 lanes per stack, normal equations accumulated 16 rows at a time in LDS, G never stored, jac read from
+ *          global memory.  LDS: 48 112 bytes, static, at every Nu <= 64 (the triangle of 65 x 65 doubles 17 KB, the staged rows 8 KB, a 64-layer
+ *          chunk of their kernels 16 KB): no limit to raise, graph-capturable from the first call.  No workspace.
+ *          SURFDISP_ERR_INVALID, before anything is launched: B < 1, Lmax outside 1..200, N outside 1..800, Nu outside 1..64, Np < Nu,
+ *          a NULL required pointer (jac, part, part_h, pred, pred_stride, nper, cols, weights, obs, uncer, mask, scale, params, lam,
+ *          delta, stats, info), prior_w without prior_ref, and the conditions of (6d) on the prediction and partial arrays (part_h
+ *          of a source without predictions included). */
+int surfdisp_params_jacobian_device(void *stream, int C, int N, int Nu, int L, const double *params,
+                                    const int *idesc, const double *fdesc, double *layer, double *jac);
+int surfdisp_lsq_step_params_device(void *stream, int B, int Lmax, const int *nlay, int Nu, const double *jac,
+                                    const float *const part[15], const float *const part_h[5],
+                                    const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                    int N, const int *cols, const double *weights,
+                                    const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                    const unsigned char *free_mask, int free_per_stack,
+                                    const double *scale, const double *prior_w, const double *prior_ref,
+                                    const double *params, int Np, const double *lam,
+                                    double *delta, double *stats, int *info, double *cov, double *sigma, double *logdet);
+
+/* ---- (7) introspection of the two-tier root search. The production kernel hands the stacks it cannot treat
  *          faithfully to an exact fallback kernel that runs right behind it inside the same call: a secular
  *          function that leaves the fp32 range (the reference's overflow points depend on how it forms its matrix
  *          entries, surfa.f:289-330) and brackets with more than one visible sign change (which root NEVILL,

@@ -42,6 +42,7 @@ EXPORTS = (
     "surfdisp_forward_group_thickness_kernels_device", "surfdisp_group_thickness_kernels_workspace_size",
     "surfdisp_lsq_step_device", "surfdisp_lsq_resolution_device",
     "surfdisp_lsq_step_modes_device", "surfdisp_lsq_resolution_modes_device",
+    "surfdisp_params_jacobian_device", "surfdisp_lsq_step_params_device",
     "surfdisp_posterior_profile_device", "surfdisp_posterior_workspace_bytes",
     "surfdisp_posterior_sources_device", "surfdisp_posterior_sources_workspace_bytes",
     "surfdisp_posterior_predictive_device", "surfdisp_posterior_predictive_workspace_bytes", "surfdisp_workspace_fallback_count", "surfdisp_workspace_counters", "surfdisp_set_team", "surfdisp_get_team", "surfdisp_get_team2",
@@ -217,6 +218,16 @@ def lib() -> ctypes.CDLL:
         L.surfdisp_lsq_step_modes_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + mode_in + [vp] * 4
         L.surfdisp_lsq_resolution_modes_device.restype = ctypes.c_int
         L.surfdisp_lsq_resolution_modes_device.argtypes = L.surfdisp_lsq_step_device.argtypes[:-3] + mode_in + [vp] * 10
+    if hasattr(L, "surfdisp_params_jacobian_device"):         # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        # (stream, C, N, Nu, L, params, idesc, fdesc, layer, jac)
+        L.surfdisp_params_jacobian_device.restype = ctypes.c_int
+        L.surfdisp_params_jacobian_device.argtypes = [vp] + [ctypes.c_int] * 4 + [vp] * 5
+        # (stream, B, Lmax, nlay, Nu, jac, part[15], part_h[5], pred[5], pred_stride[5], nper[2], N, cols, weights, obs, uncer, mask,
+        #  obs_per_stack, free, free_per_stack, scale, prior_w, prior_ref, params, Np, lam, delta, stats, info, cov, sigma, logdet)
+        L.surfdisp_lsq_step_params_device.restype = ctypes.c_int
+        L.surfdisp_lsq_step_params_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, vp, vpp, vpp, vpp, lp, ipp,
+                                                      ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp, ctypes.c_int,
+                                                      vp, vp, vp, vp, ctypes.c_int, vp] + [vp] * 6
     # (stream, npoints, R, N, track, row_stride, idesc (host), idesc_len, fdesc, aux, K, rows, D, zdeps (host), true_markov_chain, chainL,
     #  prefix, nbins, vlo, vhi, min_misfit, thres, imin, n_final, pmean, pstd, count, vs_mean, vs_std, vs_min, vs_max, hist, below, above,
     #  workspace, workspace_bytes)

@@ -1493,6 +1493,74 @@ int surfdisp_lsq_resolution_modes_device(void *stream, int B, int Lmax, const in
     return SURFDISP_SUCCESS;
 }
 
+// Jacobian of the params -> stack map for a static-structure model without a thermal layer (section (6i);
+// csrc/surfdisp_lsq_params.hip): the leading Nu columns of params are the unknowns.
+int surfdisp_params_jacobian_device(void *stream, int C, int N, int Nu, int L, const double *params,
+                                    const int *idesc, const double *fdesc, double *layer, double *jac)
+{
+    if (C < 1 || N < 1 || Nu < 1 || Nu > N || Nu > sd::SD_PLSQ_MAX_UNKNOWNS || L < 2 || L > SURFDISP_NLAY_MAX ||
+        !params || !idesc || !fdesc || !jac) {
+        set_err("surfdisp_params_jacobian_device: bad argument (C >= 1, 1 <= Nu <= min(N, 64), 2 <= L <= 200, params, idesc, fdesc, jac)");
+        return SURFDISP_ERR_INVALID;
+    }
+    sd::ParamsJacArgs a{C, N, Nu, L, params, idesc, fdesc, layer, jac};
+    SD_HIP(sd::launch_params_jacobian(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
+// One damped least-squares step of the model parameters of every stack (section (6i)): the row table of (6d), the thickness
+// arrays of (6h), and jac of surfdisp_params_jacobian_device.
+int surfdisp_lsq_step_params_device(void *stream, int B, int Lmax, const int *nlay, int Nu, const double *jac,
+                                    const float *const part[15], const float *const part_h[5],
+                                    const float *const pred[5], const long pred_stride[5], const int nper[2],
+                                    int N, const int *cols, const double *weights,
+                                    const double *obs, const double *uncer, const unsigned char *mask, int obs_per_stack,
+                                    const unsigned char *free_mask, int free_per_stack,
+                                    const double *scale, const double *prior_w, const double *prior_ref,
+                                    const double *params, int Np, const double *lam,
+                                    double *delta, double *stats, int *info, double *cov, double *sigma, double *logdet)
+{
+    sd::ParamLsqArgs a{};
+    bool ok = B >= 1 && Lmax >= 1 && Lmax <= SURFDISP_NLAY_MAX && N >= 1 && N <= sd::SD_MCMC_JOINT_MAX_COLS &&
+              Nu >= 1 && Nu <= sd::SD_PLSQ_MAX_UNKNOWNS && Np >= Nu && jac && part && part_h && pred && pred_stride && nper &&
+              cols && weights && obs && uncer && mask && scale && params && lam && delta && stats && info && (!prior_w || prior_ref);
+    for (int w = 0; ok && w < 2; ++w) {
+        a.nper[w] = nper[w];
+        if (!pred[2 * w] && pred[2 * w + 1]) ok = false;                  // a group array without the phase array of its solve
+        for (int k = 2 * w; ok && k < 2 * w + 2; ++k) {
+            a.pred[k] = pred[k];
+            a.pstride[k] = pred_stride[k];
+            if (pred[k] && (nper[w] < 1 || nper[w] > SURFDISP_NPER_MAX || pred_stride[k] < nper[w])) ok = false;
+        }
+    }
+    if (ok && !pred[0] && !pred[2]) ok = false;
+    if (ok && pred[4]) {                                                    // chi [B][nper[0]] of the Rayleigh solve
+        a.pred[4] = pred[4];
+        a.pstride[4] = pred_stride[4];
+        if (!pred[0] || pred_stride[4] < nper[0]) ok = false;
+    }
+    for (int k = 0; ok && k < 5; ++k) {                                     // a source's partials need its predictions
+        bool any = part_h[k] != nullptr;
+        a.part_h[k] = part_h[k];
+        for (int q = 0; q < 3; ++q) { a.part[3 * k + q] = part[3 * k + q]; any = any || part[3 * k + q]; }
+        if (any && !pred[k]) ok = false;
+    }
+    if (!ok) {
+        set_err("surfdisp_lsq_step_params_device: bad argument (B >= 1, 1 <= Lmax <= 200, 1 <= N <= 800, 1 <= Nu <= min(64, Np), "
+                "required pointers - jac, part, part_h, scale, params among them -, prior_ref with prior_w, every given prediction array "
+                "with 1 <= nper <= stride, partials only of sources with predictions)");
+        return SURFDISP_ERR_INVALID;
+    }
+    a.B = B; a.Lmax = Lmax; a.N = N; a.Nu = Nu; a.Np = Np;
+    a.nlay = nlay; a.jac = jac;
+    a.cols = cols; a.weights = weights; a.obs = obs; a.uncer = uncer; a.mask = mask; a.obs_per_stack = obs_per_stack ? 1 : 0;
+    a.free_mask = free_mask; a.free_per_stack = free_per_stack ? 1 : 0;
+    a.scale = scale; a.prior_w = prior_w; a.prior_ref = prior_ref; a.params = params; a.lam = lam;
+    a.delta = delta; a.stats = stats; a.info = info; a.cov = cov; a.sigma = sigma; a.logdet = logdet;
+    SD_HIP(sd::launch_lsq_step_params(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Measurement variants that do NOT synchronise: the caller owns four events per call
 // (surfdisp_events_create) which are recorded on the launch stream before prep, between the
 // kernels and after finish; durations are read later with surfdisp_events_elapsed_ms, after the

@@ -367,6 +367,44 @@ struct LsqArgs {
     double *delta_y;        // [B][K] (the step kernel)
     double *sigma_post_y, *sigma_data_y, *rdiag_y;   // [B][K] (the resolution kernel)
 };
+// Jacobian of the params -> stack map and the least-squares step in parameter space (csrc/surfdisp_lsq_params.hip; include/surfdisp.h
+// section (6i))
+constexpr int SD_PLSQ_MAX_UNKNOWNS = 64;   // unknowns per stack: the packed triangle of 65 x 65 doubles is 17 KB of LDS
+constexpr int SD_PLSQ_CHUNK = 64;          // layers of the staged rows' partial arrays held in LDS at a time
+struct ParamsJacArgs {
+    int C, N, Nu, L;
+    const double *params;   // [C][N]
+    const int *idesc;       // see surfdisp_layers.hip
+    const double *fdesc;
+    double *layer;          // [C][4][L] or nullptr
+    double *jac;            // [C][4][L][Nu]
+};
+struct ParamLsqArgs {
+    int B, Lmax, N, Nu, Np; // stacks, layers per row, data rows, unknowns, doubles between the rows of params
+    const int *nlay;        // [B] or nullptr
+    const double *jac;      // [B][4][Lmax][Nu]: d(vp, vs, rho, h of layer i) / d(unknown j)
+    const float *part[15];  // as LsqArgs
+    const float *part_h[5];
+    const float *pred[5];
+    long pstride[5];
+    int nper[2];
+    const int *cols;        // [N][2]
+    const double *weights;  // [N]
+    const double *obs, *uncer;        // [N], or [B][N] when obs_per_stack
+    const unsigned char *mask;
+    int obs_per_stack;
+    const unsigned char *free_mask;   // [Nu] or [B][Nu] (free_per_stack), nullptr: every unknown
+    int free_per_stack;
+    const double *scale, *prior_w, *prior_ref;   // [Nu]; prior_w nullptr: 0 (prior_ref is then not read)
+    const double *params;   // [B][Np]: the current point, read for the prior term
+    const double *lam;      // [B]
+    double *delta;          // [B][Nu]
+    double *stats;          // [B][3]: data misfit, prior term at p, predicted objective at p + delta
+    int *info;              // [B][3]: rows used, rows dropped, flag
+    double *cov, *sigma, *logdet;     // [B][Nu][Nu], [B][Nu], [B], each or nullptr
+};
+hipError_t launch_params_jacobian(hipStream_t s, const ParamsJacArgs &a);
+hipError_t launch_lsq_step_params(hipStream_t s, const ParamLsqArgs &a);
 // posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; include/surfdisp.h section (6f)).  The descriptor's
 // integer part and the depths travel in the kernel arguments: the entry has checked them on the host.
 constexpr int SD_POST_SLAB = SURFDISP_POST_SLAB_ROWS;   // rows of one point a workgroup walks: the unit of the per-slab partials

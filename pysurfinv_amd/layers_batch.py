@@ -759,6 +759,14 @@ class Model1DBatch:
         _lib.check(rc)
         return model, None
 
+    def jacobian(self, params, rows=None):
+        """(layer [C, 4, L], jac [C, 4, L, Nu]) float64 device tensors: vp, vs, rho, h of the output layers of ``to_model_native``
+        before their rounding to float32, and their exact partial derivatives with respect to the random-walk parameters
+        (``surfdisp_params_jacobian_device``; ``pysurfinv_amd.paramlsq.model_jacobian``).  SurfdispError without a static native
+        descriptor, ValueError for a thermal layer."""
+        from .paramlsq import model_jacobian
+        return model_jacobian(self, params, rows)
+
     def to_model(self, params, rows=None):
         """model float32 [B, 5, Lmax] rows (vp, vs, rho, h, 1/Qs) + nlay - what ``_calForward``
         hands to ``fast_surf`` (models.py:20-27).  On a HIP device with a static layer structure this

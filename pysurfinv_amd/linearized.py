@@ -144,7 +144,7 @@ class _System:
     def __init__(self, G, Gy, r, w_over_sigma2, x0, alpha, Q, lam, mode_scale=None, mode_prior=None, mode_y=None):
         self.x0 = x0 = np.asarray(x0, np.float64).ravel()
         self.n = n = x0.size
-        self.G = G = np.asarray(G, np.float64).reshape(-1, n)
+        self.G = G = np.asarray(G, np.float64).reshape(np.shape(G)[0] if n == 0 else -1, n)   # (n = 0: modes only, paramlsq)
         N = G.shape[0]
         if Gy is not None and np.ndim(Gy) != 2:
             raise ValueError("Gy: a [N, K] array expected")
