@@ -499,6 +499,41 @@ int surfdisp_mcmc_propose_prior_device(void *stream, int C, int N, int K, int L,
                                        int gauss_tries, int uniform_tries,
                                        unsigned long long seed, unsigned long long counter, long chain0,
                                        double *out, unsigned short *tries, int *exhausted);
+/* Proposals shaped by a covariance (csrc/surfdisp_mcmc_cov.hip; added within ABI 4): surfdisp_mcmc_propose_cov_device is the entry
+ * above with the axis-aligned `step` replaced by a lower-triangular factor per point, cand = x + L z.  factor_t [F][N][N] holds the
+ * TRANSPOSED factors, factor_t[f][k][n] = L_f[n][k] (the 64 lanes read a column's entries side by side); chain c takes factor
+ * f = (chain0 + c) / chains_per_factor (chains_per_factor > 0, and (chain0 + C - 1) / chains_per_factor < F).  1 <= N <=
+ * SURFDISP_MCMC_COV_N_MAX: one lane per scalar.  out, depth, the tree's states, tries and *exhausted: as above.
+ * Whole-proposal retry r = 0 .. gauss_tries + uniform_tries - 1 of node k:
+ *   r < gauss_tries: z_n = sqrt(-2 log u1) cospi(2 u2) of ONE Philox call per (chain, scalar, node, retry): word 0 the counter's low
+ *   half, word 1 its high half XOR (node << 20) (the tag of Gaussian try 0), words 2, 3 the stream index gidx + (r << 48), gidx =
+ *   (chain0 + c) * N + n - the counter words of surfdisp_mcmc_propose_device's first candidate, with the retry where the prior entry
+ *   puts it ((chain0 + C) * N < 2^48); cand_n = x_n + sum_{k <= n} L[n][k] z_k, summed with k ascending;
+ *   r >= gauss_tries: the uniform draw vmin + (vmax - vmin) u of the prior entry's uniform phase, bit for bit.
+ * A candidate is good when every scalar lies strictly inside (vmin_n, vmax_n) and, with flags, the rules of surfdisp_prior_device hold
+ * on the row [N scalars | aux[c][0..K)]; the first good candidate is out[c][k][:] and tries[c][k] = r; none: the state the node drew
+ * from, tries[c][k] = gauss_tries + uniform_tries, *exhausted grows by one.  This is the reference's perturb (models.py:192-205: the
+ * whole proposal again while it is refused).  Redrawing into the box makes the proposal density slightly asymmetric near the walls,
+ * exactly as the reference's per-scalar redraw does (brownian.py:20-27); like the reference, no entry corrects for it.
+ * flags may be NULL, with idesc, fdesc and aux NULL and K = L = 0: no rules, only the box, and no descriptor is touched (a thermal
+ * model, whose rules the device cannot evaluate).  With flags: K, L, idesc, fdesc, aux, vs_max as above (N + K <=
+ * SURFDISP_MCMC_PRIOR_ROW_MAX).  LDS: (2 N + K + L + 11) doubles per chain.  A sampler split into chain groups (chain0) draws what one
+ * call draws.  Bad arguments: SURFDISP_ERR_INVALID before any device call.  Stream-ordered, no host synchronisation, graph-capturable.
+ * surfdisp_mcmc_cov_factor_device makes the factors: cov [P][N][N] symmetric with the rows and columns of fixed parameters all zero
+ * (what surfdisp_lsq_step_params_device returns), factor_t [P][N][N] in the layout above = the Cholesky factor of scale^2 cov over the
+ * rows with a non-zero diagonal (a fixed parameter gets a zero row and column: it never moves), flag [P] = 0.  A pivot that is not
+ * positive and finite: flag[p] = 1 and the point gets diag(fallback_step [N]) - the reference's step, never a half-factored matrix.
+ * One wavefront per point, the matrix in LDS (N N doubles); meant to run once per run, outside the lock step. */
+#define SURFDISP_MCMC_COV_N_MAX 64
+int surfdisp_mcmc_propose_cov_device(void *stream, int C, int N, int K, int L, int depth,
+                                     const double *p, const double *aux, const double *vmin, const double *vmax,
+                                     const double *factor_t, long chains_per_factor, int F,
+                                     const int *idesc, const double *fdesc, const int *flags, double vs_max,
+                                     int gauss_tries, int uniform_tries,
+                                     unsigned long long seed, unsigned long long counter, long chain0,
+                                     double *out, unsigned short *tries, int *exhausted);
+int surfdisp_mcmc_cov_factor_device(void *stream, int P, int N, const double *cov, double scale, const double *fallback_step,
+                                    double *factor_t, int *flag);
 /* The SPECULATIVE lock step for few chains (a lock step of 100 chains leaves the chip idle, so it costs no more to solve
  * several proposals per chain): propose_tree draws the binary tree of the next `depth` (1..4) accept / reject outcomes -
  * node k's proposal from the state its branch would be in (node 0: the chain's state; child 2k+1 "accepted": proposal k;

@@ -980,6 +980,71 @@ int surfdisp_mcmc_propose_prior_device(void *stream, int C, int N, int K, int L,
     return SURFDISP_SUCCESS;
 }
 
+// The same tree with proposals shaped by a per-point factor, and the factor from a covariance (csrc/surfdisp_mcmc_cov.hip; header
+// section (6c)).  Every argument is judged on the host before anything touches the device.
+int surfdisp_mcmc_propose_cov_device(void *stream, int C, int N, int K, int L, int depth,
+                                     const double *p, const double *aux, const double *vmin, const double *vmax,
+                                     const double *factor_t, long chains_per_factor, int F,
+                                     const int *idesc, const double *fdesc, const int *flags, double vs_max,
+                                     int gauss_tries, int uniform_tries,
+                                     unsigned long long seed, unsigned long long counter, long chain0,
+                                     double *out, unsigned short *tries, int *exhausted)
+{
+    const char *name = "surfdisp_mcmc_propose_cov_device";
+    if (C < 1 || N < 1 || N > sd::SD_MCMC_COV_MAX_N || K < 0 || depth < 1 || depth > sd::SD_MCMC_MAX_DEPTH) {
+        set_err("%s: invalid size (C >= 1; 1 <= N <= SURFDISP_MCMC_COV_N_MAX = 64; K >= 0; 1 <= depth <= 4)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (flags) {
+        if (L < 1 || L > SURFDISP_NLAY_MAX || (long)N + (long)K > sd::SD_MCMC_PRIOR_ROW) {
+            set_err("%s: invalid size with flags (1 <= L <= SURFDISP_NLAY_MAX; N + K <= SURFDISP_MCMC_PRIOR_ROW_MAX = 256)", name);
+            return SURFDISP_ERR_INVALID;
+        }
+        if (!idesc || !fdesc || (K > 0 && !aux)) {
+            set_err("%s: invalid argument: flags without idesc / fdesc (or K > 0 without aux)", name); return SURFDISP_ERR_INVALID;
+        }
+    } else if (idesc || fdesc || aux || K != 0 || L != 0) {
+        set_err("%s: invalid argument: without flags there are no rules: idesc, fdesc and aux NULL, K = L = 0", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (gauss_tries < 0 || uniform_tries < 0 || (long)gauss_tries + uniform_tries < 1 ||
+        (long)gauss_tries + uniform_tries > sd::SD_MCMC_PRIOR_TRIES) {
+        set_err("%s: invalid caps: gauss_tries >= 0, uniform_tries >= 0, 1 <= their sum <= 16384", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    // (chain0 + C) * N < 2^48: the retry index sits above bit 48 of the stream index
+    const long lim = 1L << 48;
+    if (chain0 < 0 || chain0 >= lim || chain0 + (long)C > (lim - 1) / N) {
+        set_err("%s: invalid chain0: (chain0 + C) * N must stay below 2^48", name); return SURFDISP_ERR_INVALID;
+    }
+    if (chains_per_factor < 1 || F < 1 || (chain0 + (long)C - 1) / chains_per_factor >= (long)F) {
+        set_err("%s: invalid factor index: chains_per_factor >= 1, F >= 1, (chain0 + C - 1) / chains_per_factor < F", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (!p || !vmin || !vmax || !factor_t || !out || !exhausted) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::McmcCovArgs a{C, N, K, L, depth, p, aux, vmin, vmax, factor_t, chains_per_factor, idesc, fdesc, flags, vs_max,
+                      gauss_tries, uniform_tries, seed, counter, chain0, out, tries, exhausted};
+    SD_HIP(sd::launch_mcmc_propose_cov(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
+int surfdisp_mcmc_cov_factor_device(void *stream, int P, int N, const double *cov, double scale, const double *fallback_step,
+                                    double *factor_t, int *flag)
+{
+    const char *name = "surfdisp_mcmc_cov_factor_device";
+    if (P < 1 || N < 1 || N > sd::SD_MCMC_COV_MAX_N) {
+        set_err("%s: invalid size (P >= 1; 1 <= N <= SURFDISP_MCMC_COV_N_MAX = 64)", name); return SURFDISP_ERR_INVALID;
+    }
+    if (!cov || !fallback_step || !factor_t || !flag) {
+        set_err("%s: invalid argument: a required pointer is NULL", name); return SURFDISP_ERR_INVALID;
+    }
+    sd::McmcCovFactorArgs a{P, N, cov, scale, fallback_step, factor_t, flag};
+    SD_HIP(sd::launch_mcmc_cov_factor(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; header section (6f)).  Workspace: the per-slab partials
 // [npoints][nslab][D + N][5] doubles, the slabs' smallest misfits [npoints][nslab] doubles, then four int arrays [npoints][nslab].
 static long post_slabs(int R) { return ((long)R + SURFDISP_POST_SLAB_ROWS - 1) / SURFDISP_POST_SLAB_ROWS; }

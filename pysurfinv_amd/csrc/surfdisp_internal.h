@@ -314,6 +314,37 @@ struct McmcPriorArgs {
     int *exhausted;         // [1], incremented per node without a good candidate
 };
 hipError_t launch_mcmc_propose_prior(hipStream_t s, const McmcPriorArgs &a);
+// the same tree with proposals x + F z, F the lower-triangular factor of the chain's point, and that factor from a covariance
+// (csrc/surfdisp_mcmc_cov.hip; include/surfdisp.h section (6c))
+constexpr int SD_MCMC_COV_MAX_N = SURFDISP_MCMC_COV_N_MAX;        // one lane per scalar
+struct McmcCovArgs {
+    int C, N, K, L, depth;
+    const double *p;        // [C][N] chain states
+    const double *aux;      // [C][K] per-chain local constants, nullptr when K == 0
+    const double *vmin, *vmax;   // [N]
+    const double *factor_t; // [F][N][N]: factor_t[f][k][n] = L_f[n][k]
+    long chains_per_factor; // chain chain0 + c takes factor (chain0 + c) / chains_per_factor
+    const int *idesc;       // the params -> stack descriptor, see surfdisp_layers.hip; nullptr without flags
+    const double *fdesc;
+    const int *flags;       // [L] the rules per output layer, see surfdisp_prior_kernel; nullptr: the box alone (K = L = 0)
+    double vs_max;          // < 0: no cap
+    int gauss_tries, uniform_tries;
+    unsigned long long seed, counter;
+    long chain0;
+    double *out;            // [C][2^depth - 1][N]
+    unsigned short *tries;  // [C][2^depth - 1] or nullptr
+    int *exhausted;         // [1], incremented per node without a good candidate
+};
+hipError_t launch_mcmc_propose_cov(hipStream_t s, const McmcCovArgs &a);
+struct McmcCovFactorArgs {
+    int P, N;
+    const double *cov;      // [P][N][N] symmetric; zero rows and columns at fixed parameters
+    double scale;
+    const double *fallback_step;   // [N]
+    double *factor_t;       // [P][N][N]
+    int *flag;              // [P]: 0 factored, 1 diag(fallback_step)
+};
+hipError_t launch_mcmc_cov_factor(hipStream_t s, const McmcCovFactorArgs &a);
 // joint data (Rayleigh / Love, phase / group, Rayleigh ellipticity): the accept kernel's arguments plus the solves' predictions and
 // the column table.  In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
 struct McmcJointArgs {

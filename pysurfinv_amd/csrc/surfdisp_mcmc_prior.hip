@@ -3,12 +3,14 @@
 // chain (models.py:192-219: the whole proposal again, up to 1000 times with the bounded Gaussian step, then up to 10 000
 // uniform prior draws), for every node of the speculative tree.  A translation unit of its own: the propose, accept, stack and
 // prior kernels of surfdisp_mcmc.hip and surfdisp_layers.hip keep their instruction streams (profiles/prior_redraw/isa_identity.txt);
-// the random streams and the grid points are theirs (surfdisp_mcmc_rng.h, surfdisp_layers_grid.h).
+// the random streams and the grid points are theirs (surfdisp_mcmc_rng.h, surfdisp_layers_grid.h).  The test of a candidate row
+// stands in surfdisp_mcmc_rules.h, shared with surfdisp_mcmc_cov.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "surfdisp_internal.h"
 #include "surfdisp_mcmc_rng.h"
 #include "surfdisp_layers_grid.h"
+#include "surfdisp_mcmc_rules.h"
 
 namespace sd {
 
@@ -34,30 +36,18 @@ __global__ __launch_bounds__(64) void surfdisp_mcmc_propose_prior_kernel(McmcPri
     const int lane = threadIdx.x;
     const size_t c = blockIdx.x;
     const int N = A.N, M = (1 << A.depth) - 1;
-    const int gcap = A.L + SD_MCMC_PRIOR_GRID_EXTRA;
     double *row = lds;                                 // the candidate: [N random-walk scalars | K local constants]
     double *vsg = lds + N + A.K;                       // Vs of the candidate at every grid point the rules look at: gcap doubles
     const int cap = A.gauss_tries + A.uniform_tries;
     const uint32_t k0 = (uint32_t)A.seed, k1 = (uint32_t)(A.seed >> 32);
     const long gidx0 = (A.chain0 + (long)c) * N;       // (chain, parameter 0) of the whole sampler: the random stream's index
     const LayersArgs G{A.C, N + A.K, nullptr, A.idesc, A.fdesc, nullptr, nullptr};
-    const int nin = A.idesc[0];
-    const int *top_i = A.idesc + 4 + 16 * nin;
-    const int L = A.L < A.idesc[2] ? A.L : A.idesc[2];
-    bool thermal = false;
-    for (int l = 0; l < nin; ++l) thermal = thermal || A.idesc[4 + 8 * l] == 6;
-    // grid points the flagged layers read: a layer's two points and the top of the next layer - the model's own ngrid points, and
-    // the ReferenceMantle's 21 behind them only where a flag reaches that far (PriorRules never sets one there)
-    const int ngrid = A.idesc[1];
-    bool far = false;
-    for (int i = lane; i < L; i += 64) {
-        const int f = A.flags[i];
-        if (f != 0) far = far || top_i[i] + 1 >= ngrid || ((f & 6) && i + 1 < L && top_i[i + 1] >= ngrid);
-    }
-    const int npts = __any(far) ? ngrid + 21 : ngrid;
-    const int ntry = (thermal || npts > gcap) ? 0 : cap;
+    const int *top_i;
+    int L, npts;
+    bool blocked;
+    prior_rule_setup(A.idesc, A.flags, A.L, lane, top_i, L, npts, blocked);
+    const int ntry = blocked ? 0 : cap;
     const bool capped = !(A.vs_max < 0.0);
-    const double eps = 2.220446049250313e-16;          // np.finfo(float).eps, models.py:8
     for (int k = lane; k < A.K; k += 64) row[N + k] = A.aux[c * A.K + k];
     for (int k = 0; k < M; ++k) {
         int j = k;                                     // the state of node k: the proposal of the last "accepted" edge above it
@@ -69,24 +59,7 @@ __global__ __launch_bounds__(64) void surfdisp_mcmc_propose_prior_kernel(McmcPri
                 row[n] = draw_bounded(src[n], A.vmin[n], A.vmax[n], A.step[n], k0, k1, A.counter, (uint32_t)k,
                                       gidx0 + n + ((long)r << 48), r >= A.gauss_tries);
             __syncthreads();
-            // every grid point once (surfdisp_prior_kernel evaluates a layer's three points per thread: the same values)
-            for (int g = lane; g < npts; g += 64) vsg[g] = grid_value(G, 0, row, g).vs;
-            __syncthreads();
-            bool ok = true;
-            for (int i = lane; i < L; i += 64) {
-                const int f = A.flags[i];
-                if (f == 0) continue;
-                const int g = top_i[i];
-                const double a = vsg[g], b = vsg[g + 1];
-                if ((f & 8) && capped) ok = ok && !(a > A.vs_max) && !(b > A.vs_max);
-                if (f & 1) ok = ok && (b - a >= eps);
-                if ((f & 6) && i + 1 < L) {
-                    const double n = vsg[top_i[i + 1]];
-                    if (f & 2) ok = ok && (n - b >= eps);
-                    if (f & 4) ok = ok && !(n < b);
-                }
-            }
-            const bool good = __all(ok) != 0;          // the same on every lane
+            const bool good = prior_rules_hold(G, A.flags, A.vs_max, capped, top_i, L, npts, row, vsg, lane);
             if (good) { found = r; break; }
             __syncthreads();                           // the next candidate overwrites the row
         }

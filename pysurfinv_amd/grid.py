@@ -33,7 +33,7 @@ def summary_columns(n_params, n_periods):
 def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, chainL, outdir=None,
              rank=0, world=1, device="cuda:0", seed=0, forward=None, isgood=None, fast_scan=False,
              writer_threads=4, keep_tracks=True, local_info=None, chain_groups=None, spec_depth=None,
-             profile_depths=None):
+             profile_depths=None, proposal=None, lsq_iters=8):
     """Invert the points owned by ``rank``.
 
     model_batch : layers_batch.Model1DBatch (one setting for the grid)
@@ -51,6 +51,13 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
                   numpy statement ``posterior_reference`` otherwise), formed from the tracks before they leave the device, inside
                   ``elapsed``, and gathered like the summaries: the result then carries ``profiles = dict(zdeps, count, mean, std,
                   min, max)``, [n_points, D] each, on every rank.
+    proposal    : None (the reference's proposal: independent steps ``spec.step``, chain 0 of a point starts at ``v0``) or "laplace":
+                  every point of the rank is first fitted by ``paramlsq.ParamLsqBatch`` (``lsq_iters`` iterations on the same data, with
+                  the ``PriorRules`` when ``isgood`` is one; a thermal model: its ValueError), chain 0 of the point starts at the fitted
+                  row and all chains of the point propose with the factor of its Laplace covariance (``proposal_factor`` ->
+                  ``MetropolisBatch.set_proposal``).  The report then carries ``lsq_rms_median`` (the fits' rms misfit, median over this
+                  rank's points) and ``factor_fallbacks`` (points, summed over ranks, that kept the reference's steps because their
+                  covariance could not be factored); inside ``elapsed``.
     Returns dict(points=(lo, hi), mcTrack=[n_local, chains*chainL, 3+N] or None, summaries=[n_points, 6+2N+P]
     (every rank holds all rows, point order), columns, elapsed (sampling + summaries + gather, this rank),
     elapsed_write, report).  ``report`` carries the MAX over ranks of ``elapsed`` and the summed counters; among them
@@ -69,6 +76,9 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     t0 = time.perf_counter()
     n_forward = 0
     mc = None
+    if proposal not in (None, "laplace"):
+        raise ValueError("run_grid: proposal must be None or 'laplace'")
+    lsq_rms_median, factor_fallbacks = None, 0
     tracks_dev = torch.zeros((n_local, chains_per_point * chainL, 3 + N), dtype=torch.float64, device=dev)
     summ = torch.zeros((n_local, 6 + 2 * N + P), dtype=torch.float64, device=dev)
     if model_batch.n_aux and local_info is None:
@@ -86,7 +96,20 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
         mc = MetropolisBatch(model_batch.spec, model_batch.to_model, periods, rep(c_obs), rep(uncer),
                              device=device, seed=seed + 7919 * rank, forward=forward, isgood=isgood, fast_scan=fast_scan,
                              local_rows=local_rows)
-        tracks_dev = mc.run_points(n_local, chains_per_point, chainL, on_device=True, groups=chain_groups, spec_depth=spec_depth).reshape(n_local, chains_per_point * chainL, -1)
+        start = None
+        if proposal == "laplace":
+            from .mcmc import PriorRules
+            from .obsdata import DispersionData
+            from .paramlsq import ParamLsqBatch
+            fit = ParamLsqBatch(model_batch, [DispersionData("R", "c", periods, c_obs[lo:hi], uncer[lo:hi])],
+                                rules=isgood if isinstance(isgood, PriorRules) else None,
+                                rows=None if local_rows is None else torch.arange(n_local, device=dev), device=device)
+            start = fit.run(lsq_iters)["params"].contiguous()
+            pf = fit.proposal_factor()
+            mc.set_proposal(pf["factor"], chains_per_point)
+            lsq_rms_median, factor_fallbacks = float(fit.rms.median()), int(pf["flag"].sum())
+        tracks_dev = mc.run_points(n_local, chains_per_point, chainL, on_device=True, groups=chain_groups, spec_depth=spec_depth,
+                                   start=start).reshape(n_local, chains_per_point * chainL, -1)
         first_chain = torch.arange(n_local, device=dev) * chains_per_point     # observation row of each point
         summ = mc.summarise_points(tracks_dev, first_chain)
         n_forward = mc.n_forward
@@ -127,12 +150,14 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
         with ThreadPoolExecutor(max_workers=max(1, int(writer_threads))) as ex:
             list(ex.map(write, range(n_local)))
     elapsed_write = time.perf_counter() - t1
-    max_elapsed, (tot_forward, tot_points, tot_exhausted) = shard.reduce_report(elapsed, [n_forward, n_local, prior_exhausted], device=cdev)
+    max_elapsed, (tot_forward, tot_points, tot_exhausted, tot_fallbacks) = shard.reduce_report(
+        elapsed, [n_forward, n_local, prior_exhausted, factor_fallbacks], device=cdev)
     steps = tot_points * chains_per_point * chainL
     res = dict(points=(lo, hi), mcTrack=tracks if keep_tracks else None, summaries=summaries,
                columns=summary_columns(N, P), elapsed=elapsed, elapsed_write=elapsed_write,
                report=dict(elapsed_max=max_elapsed, forward_solves=tot_forward, points=tot_points,
                            prior_exhausted=tot_exhausted, prior_exhausted_rank=prior_exhausted,
+                           proposal=proposal, lsq_rms_median=lsq_rms_median, factor_fallbacks=tot_fallbacks,
                            metropolis_steps=steps,
                            steps_per_s=steps / max_elapsed if max_elapsed > 0 else 0.0,
                            solves_per_s=tot_forward / max_elapsed if max_elapsed > 0 else 0.0))

@@ -20,6 +20,8 @@ Semantics kept from the reference:
   (``point.py:47-57``); ``mcTrack`` rows are ``[misfit, L, accepted, *params]`` of the PROPOSED
   model (``models.py:254-256``, ``point.py:58,73-76``); output ``.npz`` keys ``mcTrack, setting,
   obs, invMeta`` (``point.py:82-85``) so ``PostPoint`` / ``Model3D.loadInvDir`` can read it.
+Opt-in, beyond the reference: ``set_proposal`` replaces the independent steps by ``x + F z`` with a lower-triangular factor per grid
+point (e.g. ``paramlsq.ParamLsqBatch.proposal_factor``), ``run(start=)`` starts chains at given rows (e.g. the fitted ones).
 RNG: CPython's Mersenne Twister cannot be reproduced on the device; the production path uses a
 torch Philox generator (statistical parity), and ``PythonRandomProposer`` replays the reference's
 exact stream for one chain (trace parity, ``tests/test_mcmc.py``).
@@ -59,6 +61,64 @@ def _accept_rule(torch, chi0, chi1, u):
 def _put_row(track, i, mis, L, acc, p):
     """mcTrack row ``i`` of every chain: [misfit, L, accepted, *params] of the proposed model (models.py:254-256)."""
     track[:, i, 0] = mis; track[:, i, 1] = L; track[:, i, 2] = acc; track[:, i, 3:] = p
+
+
+COV_MAX_N = 64             # scalars per chain of the covariance-shaped proposal: one lane each (SURFDISP_MCMC_COV_N_MAX)
+
+
+def cov_factor_reference(cov, scale, fallback_step):
+    """``surfdisp_mcmc_cov_factor_device`` in numpy float64: cov [P, N, N] (symmetric; zero rows and columns at fixed parameters) ->
+    (L [P, N, N] lower triangular with L L^T = scale^2 cov over the rows whose diagonal is not zero and zero rows and columns
+    elsewhere, flag [P]).  Right-looking Cholesky, the kernel's order of operations; a pivot that is not positive and finite: flag 1
+    and L = diag(fallback_step)."""
+    cov = np.asarray(cov, np.float64)
+    P, N, _ = cov.shape
+    fb = np.asarray(fallback_step, np.float64)
+    out, flag = np.zeros((P, N, N)), np.zeros(P, np.int32)
+    for p in range(P):
+        live = np.flatnonzero(np.diagonal(cov[p]) != 0.0)
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+            A = (float(scale) * float(scale)) * np.triu(cov[p]).T          # the kernel reads cov[k][n], k <= n, as A[n][k]
+            Lp, bad = np.zeros((N, N)), False
+            for a, j in enumerate(live):
+                d = A[j, j]
+                if not (d > 0.0 and np.isfinite(d)):
+                    bad = True
+                    break
+                s = np.sqrt(d)
+                below = live[a + 1:]
+                l = A[below, j] / s
+                Lp[j, j], Lp[below, j] = s, l
+                for b, n in enumerate(below):
+                    ks = below[:b + 1]
+                    A[n, ks] -= l[b] * l[:b + 1]
+        out[p], flag[p] = (np.diag(fb), 1) if bad else (Lp, 0)
+    return out, flag
+
+
+def cov_factor(cov, scale, fallback_step):
+    """The proposal factors of P covariances on the device (``surfdisp_mcmc_cov_factor_device``: one launch, no host
+    synchronisation): cov float64 [P, N, N] on a HIP device, ``scale`` a float, ``fallback_step`` [N] -> dict(factor [P, N, N] lower
+    triangular - a view of the kernel's transposed layout, what ``MetropolisBatch.set_proposal`` takes -, flag [P] int32: 1 where the
+    matrix could not be factored and the point got diag(fallback_step))."""
+    import torch
+    if cov.dtype != torch.float64 or cov.ndim != 3 or cov.shape[1] != cov.shape[2] or not 1 <= cov.shape[1] <= COV_MAX_N:
+        raise ValueError(f"cov_factor: float64 [P, N, N] with 1 <= N <= {COV_MAX_N} expected, got {cov.dtype} {tuple(cov.shape)}")
+    if cov.device.type != "cuda":
+        raise _lib.SurfdispError("cov_factor needs a HIP device")
+    P, N, _ = cov.shape
+    cov = cov.contiguous()
+    fb = torch.as_tensor(np.asarray(fallback_step, np.float64) if not torch.is_tensor(fallback_step) else fallback_step,
+                         dtype=torch.float64, device=cov.device).contiguous()
+    if tuple(fb.shape) != (N,):
+        raise ValueError(f"cov_factor: fallback_step ({N},) expected, got {tuple(fb.shape)}")
+    factor_t = torch.empty_like(cov)
+    flag = torch.empty(P, dtype=torch.int32, device=cov.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(cov.device).cuda_stream)
+    with torch.cuda.device(cov.device):
+        _lib.check(_lib.lib().surfdisp_mcmc_cov_factor_device(stream, P, N, _ptr(cov), ctypes.c_double(float(scale)), _ptr(fb),
+                                                              _ptr(factor_t), _ptr(flag)))
+    return dict(factor=factor_t.transpose(1, 2), flag=flag)
 
 
 class PriorRules:
@@ -144,7 +204,8 @@ class ChainGroups:
             ch.independent, ch.fast_scan, ch.isgood = mc.independent, mc.fast_scan, mc.isgood
             ch.joint, ch.periods = mc.joint, mc.periods
             ch._chain0 = mc._chain0 + lo
-            ch._exh = mc._exhausted_counter() if mc._kernel_rules() is not None else None   # one counter for all groups
+            ch._prop = mc._prop                                 # (the factors are indexed by the chain's index in the whole sampler)
+            ch._exh = mc._exhausted_counter() if mc._redraws_in_kernel() else None          # one counter for all groups
             if ch._fz is not None and (ch._fz["c_obs"].data_ptr() != ch.c_obs.contiguous().data_ptr()):
                 ch._fz = None                                   # (the fused buffers hold contiguous copies of the observations)
 
@@ -239,7 +300,8 @@ class MetropolisBatch:
         self._counter = 0                                       # calls of the fused kernels so far: the Philox counter of the next one
         self._pipelined = False                                 # a chain group: another group's solve is in flight beside this one
         self._chain0 = 0                                        # index of this object's chain 0 in the whole sampler (chain groups)
-        self._exh = None                                        # PriorRules(redraw="kernel"): one device int, shared with the chain groups
+        self._exh = None                                        # PriorRules(redraw="kernel") / set_proposal: one device int, shared with the chain groups
+        self._prop = None                                       # set_proposal: dict(factor_t [F, N, N], cpf, F)
         self._last_groups = None                                # the ChainGroups of the last run (last_prior_tries)
 
     def _fresh_state(self):
@@ -351,7 +413,7 @@ class MetropolisBatch:
             st = dict(C=C, data=self.joint, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
                       chi=torch.zeros(C, dtype=torch.float64, device=self.device),
                       mask8=self.mask.to(torch.uint8).contiguous(), c_obs=self.c_obs.contiguous(), uncer=self.uncer.contiguous())
-            if self._kernel_rules() is not None:
+            if self._redraws_in_kernel():
                 self._exhausted_counter()                         # (made and zeroed here, once: no memset per step)
             self._fz = st
         return st
@@ -362,8 +424,13 @@ class MetropolisBatch:
         rules = self.isgood
         return rules if isinstance(rules, PriorRules) and rules.redraw == "kernel" else None
 
+    def _redraws_in_kernel(self):
+        """Whether the proposal kernel of this sampler redraws until the candidate is good and counts the nodes that found none
+        (``PriorRules(redraw="kernel")``, or a proposal factor: ``set_proposal``)."""
+        return self._kernel_rules() is not None or self._prop is not None
+
     def _exhausted_counter(self):
-        """The device int the prior-redraw kernel counts exhausted nodes in: one per sampler, shared by its chain groups."""
+        """The device int the redrawing propose kernels count exhausted nodes in: one per sampler, shared by its chain groups."""
         if self._exh is None:
             self._exh = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
         return self._exh
@@ -371,7 +438,8 @@ class MetropolisBatch:
     def prior_exhausted(self):
         """How many proposals of this sampler (tree nodes of all fused lock steps so far) found no model the prior accepts within
         ``gauss_tries + uniform_tries`` redraws and proposed the state they drew from - where the reference raises
-        ``RuntimeError`` (models.py:219).  0 for every other redraw mode.  Synchronises once; ``run()`` itself never does."""
+        ``RuntimeError`` (models.py:219) - with a proposal factor (``set_proposal``): within the caps of ``_propose_cov``, box
+        included.  0 for every other redraw mode.  Synchronises once; ``run()`` itself never does."""
         return 0 if self._exh is None else int(self._exh.item())
 
     def last_prior_tries(self):
@@ -402,6 +470,76 @@ class MetropolisBatch:
             stream, C, N, int(mb.n_aux), int(Lout), int(depth), _ptr(p), _ptr(aux), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
             _ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()), ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max),
             rules.gauss_tries, rules.uniform_tries, pr.seed_int, counter, self._chain0, _ptr(out), _ptr(tries), _ptr(self._exhausted_counter())))
+
+    # ------------------------------------------------------------------ covariance-shaped proposals
+    COV_TRIES = (1000, 10000)       # whole-proposal Gaussian / uniform redraws of a sampler with a factor and no PriorRules (the reference's caps)
+
+    def set_proposal(self, factor, chains_per_point=1):
+        """Proposals ``x + F z`` (z standard normal) in place of the reference's independent steps ``spec.step``: ``factor`` is a
+        float64 device tensor, lower triangular (the strict upper triangle is not read), [N, N] for every chain or [n_points, N, N]
+        with chain c taking ``factor[c // chains_per_point]`` (the chain order of ``run_points``) - e.g. the Cholesky factor of a
+        scaled Laplace covariance, ``ParamLsqBatch.proposal_factor``.  It is transposed once into the kernel's layout
+        (``surfdisp_mcmc_propose_cov_device``).  ``None`` returns to the reference's proposal: the sampler then launches the kernels
+        and draws the numbers of one that was never given a factor.
+
+        The whole proposal is redrawn inside the kernel while it leaves the open prior box or breaks the rules of a ``PriorRules``
+        (either ``redraw`` mode; its ``gauss_tries`` / ``uniform_tries``, 1000 / 10000 without rules), at every node of the
+        speculative tree; ``prior_exhausted()`` and ``last_prior_tries()`` report for this kernel too.  Like the reference's
+        per-scalar redraw, redrawing into the box makes the proposal slightly asymmetric near the walls; no correction is applied.
+        Needs the fused path: ValueError otherwise."""
+        torch = self.torch
+        if factor is None:
+            self._prop = None
+            return
+        N = self.spec.n
+        if not torch.is_tensor(factor) or factor.dtype != torch.float64 or factor.ndim not in (2, 3) or tuple(factor.shape[-2:]) != (N, N):
+            raise ValueError(f"set_proposal: a float64 tensor [{N}, {N}] or [n_points, {N}, {N}] expected, got "
+                             f"{getattr(factor, 'dtype', type(factor).__name__)} {tuple(getattr(factor, 'shape', ()))}")
+        if N > COV_MAX_N:
+            raise ValueError(f"set_proposal: {N} random-walk parameters, the kernel takes at most {COV_MAX_N}")
+        if int(chains_per_point) < 1:
+            raise ValueError("set_proposal: chains_per_point >= 1 expected")
+        if self.isgood is not None and not (isinstance(self.isgood, PriorRules) and self.isgood.device_flags() is not None):
+            raise ValueError("set_proposal: isgood must be None or a PriorRules the device can evaluate (an arbitrary callback cannot "
+                             "run inside the propose kernel)")
+        if self.isgood is not None and self.local_rows is not None:
+            raise ValueError("set_proposal: PriorRules together with local_rows are not evaluated inside the propose kernel")
+        if not self.fused_available():
+            raise ValueError("set_proposal needs the fused device path: a HIP device, the device proposer and the HIP forward path")
+        if factor.device != self.device:
+            raise ValueError(f"set_proposal: the factor lives on {factor.device}, the sampler on {self.device}")
+        ft = torch.tril(factor).transpose(-1, -2).contiguous()     # factor_t[f][k][n] = L_f[n][k]
+        if factor.ndim == 2:
+            self._prop = dict(factor_t=ft[None], cpf=1 << 62, F=1)
+        else:
+            self._prop = dict(factor_t=ft, cpf=int(chains_per_point), F=int(ft.shape[0]))
+
+    def _propose_cov(self, stream, p, out, depth, counter, st):
+        """The proposal tree ``out`` [C, 2^depth - 1, N] (depth 1: [C, N]) of the states ``p`` with the factors of ``set_proposal``,
+        every row redrawn inside the kernel until it lies in the box and the ``PriorRules`` (if any) hold
+        (``surfdisp_mcmc_propose_cov_device``: one launch) - a sibling of ``_propose_prior``."""
+        torch = self.torch
+        rules = self.isgood if isinstance(self.isgood, PriorRules) else None
+        C, N = p.shape
+        M = (1 << int(depth)) - 1
+        tries = st.get("tries")
+        if tries is None or tries.shape != (C, M):
+            tries = st["tries"] = torch.zeros((C, M), dtype=torch.int16, device=self.device).view(torch.uint16)
+        pr, pp = self.proposer, self._prop
+        if rules is not None:
+            mb = rules.model
+            idesc, fdesc, Lout = mb.native_descriptor()
+            aux = mb._full(p)[:, N:].contiguous() if mb.n_aux else None
+            desc = (int(mb.n_aux), int(Lout)), (_ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()),
+                                                  ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max))
+            caps = (rules.gauss_tries, rules.uniform_tries)
+        else:
+            aux = None
+            desc = (0, 0), (None, None, None, ctypes.c_double(-1.0))
+            caps = self.COV_TRIES
+        _lib.check(_lib.lib().surfdisp_mcmc_propose_cov_device(
+            stream, C, N, *desc[0], int(depth), _ptr(p), _ptr(aux), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pp["factor_t"]), pp["cpf"], pp["F"],
+            *desc[1], *caps, pr.seed_int, counter, self._chain0, _ptr(out), _ptr(tries), _ptr(self._exhausted_counter())))
 
     def _solve_raw(self, params, rows=None):
         """The solver's own fp32 output tensors (no copies) for the stacks of ``params``: (c[C, P], status[C]), or with joint
@@ -547,7 +685,9 @@ class MetropolisBatch:
                 p1 = p
             else:
                 p1 = st["p1"]
-                if self._kernel_rules() is not None:           # proposal and the prior's redraw loop in one kernel
+                if self._prop is not None:                     # x + F z, box and rules inside the kernel
+                    self._propose_cov(stream, p, p1, 1, counter, st)
+                elif self._kernel_rules() is not None:         # proposal and the prior's redraw loop in one kernel
                     self._propose_prior(stream, p, p1, 1, counter, st)
                 else:
                     _lib.check(_lib.lib().surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
@@ -597,11 +737,11 @@ class MetropolisBatch:
         (100 chains x 96 layers: 0.96 ms per step plain, 0.345 with d = 3, 0.31 with d = 4 at 4.1 forward solves per step;
         scripts/time_speculative.py): 4 up to 136 chains, 3 up to 292, 2 up to 682, 1 from 683 chains on, and 1 where the (stack, period) decomposition fills the chip
         instead (``independent``: 0.24 ms per step plain, 0.29 with d = 3).  A ``PriorRules`` in its default ``redraw="rounds"`` mode
-        keeps depth 1 (the rounds know no tree); with ``redraw="kernel"`` every node is redrawn until the rules hold and the depth
-        is the one above."""
+        keeps depth 1 (the rounds know no tree); with ``redraw="kernel"``, or with a proposal factor (``set_proposal``), every node
+        is redrawn until the rules hold and the depth is the one above."""
         if self._indep(C):
             return 1
-        if self.isgood is not None and self._kernel_rules() is None:
+        if self.isgood is not None and not self._redraws_in_kernel():
             return 1                                               # (prior rules: the redraw rounds belong to the plain lock step)
         for d in (4, 3, 2):
             if C * ((1 << d) - 1) <= self.SPEC_MAX_STACKS:
@@ -625,7 +765,9 @@ class MetropolisBatch:
             st["qrows"] = torch.arange(C, device=self.device).repeat_interleave(M) if self.local_rows is not None else None
         pr = self.proposer
         with torch.cuda.device(self.device):
-            if self._kernel_rules() is not None:                   # every node redrawn until the prior's rules hold
+            if self._prop is not None:                             # every node x + F z, redrawn until box and rules hold
+                self._propose_cov(stream, p, st["q"], depth, counter, st)
+            elif self._kernel_rules() is not None:                 # every node redrawn until the prior's rules hold
                 self._propose_prior(stream, p, st["q"], depth, counter, st)
             else:
                 _lib.check(_lib.lib().surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax),
@@ -702,7 +844,8 @@ class MetropolisBatch:
         return new
 
     # ------------------------------------------------------------------ the sampler
-    def run(self, n_chains, chainL, init_first=True, priori=False, _init_mask=None, spec_depth=None, fused=None, groups=None):
+    def run(self, n_chains, chainL, init_first=True, priori=False, _init_mask=None, spec_depth=None, fused=None, groups=None,
+            start=None, _start_mask=None):
         """Advance ``n_chains`` chains for ``chainL`` steps each (= MCinvMP with runN = n_chains*chainL).
 
         Returns mcTrack float64 [n_chains, chainL, 3+N]; chain 0 starts at the initial model when
@@ -720,25 +863,32 @@ class MetropolisBatch:
 
         ``fused`` (default: whenever ``fused_available()``): the lock step as device kernels around the solver
         (``fused_step``: Philox random numbers keyed by the proposer's seed; same proposal and accept distributions).
-        ``groups``: chain groups of the fused path (``chain_groups``; every chain's random numbers do not depend on it)."""
+        ``groups``: chain groups of the fused path (``chain_groups``; every chain's random numbers do not depend on it).
+        ``start``: a float64 tensor [n_chains, N] of rows the chains start from instead of ``v0`` / prior draws - row 0 of every
+        chain is that model, accepted, as today (e.g. the fitted rows of ``ParamLsqBatch``).  Rows outside the open prior box or
+        breaking ``isgood`` raise ValueError before anything is launched (one host synchronisation, outside the stepping loop)."""
         torch = self.torch
         C, N = int(n_chains), self.spec.n
+        if start is not None:
+            start = self._checked_start(start, C, _start_mask)
         if fused is None:
             fused = self.fused_available()
         fused = bool(fused) and not priori                         # a priori run evaluates nothing: the torch loop below
         if fused and not self.fused_available():
             raise ValueError("fused=True needs the device proposer, no isgood callback (or a PriorRules one) and the HIP forward path")
+        if self._prop is not None and not fused:
+            raise ValueError("run: a proposal factor (set_proposal) is drawn by the fused path only; set_proposal(None) for the torch loop")
         if spec_depth is None:
             spec_depth = self.auto_spec_depth(C) if (fused and groups in (None, 1)) else 1
         spec_depth = int(spec_depth)
         if spec_depth > 1 and groups not in (None, 1):
             raise ValueError("run: chain groups and speculative lock steps (spec_depth > 1) cannot be combined")
         if spec_depth > 1 and not priori and not fused:
-            return self._run_speculative(n_chains, chainL, init_first, _init_mask, spec_depth)
+            return self._run_speculative(n_chains, chainL, init_first, _init_mask, spec_depth, start, _start_mask)
         track = torch.zeros((C, chainL, 3 + N), dtype=torch.float64, device=self.device)
         if fused:
             # propose / accept kernels around the solver: mcTrack rows are written by the accept kernel itself
-            p = self._start(C, init_first, _init_mask).contiguous().clone()
+            p = self._start(C, init_first, _init_mask, start, _start_mask).contiguous().clone()
             stride = chainL * (3 + N)
             cg = self.chain_groups(C, groups) if spec_depth <= 1 else None
             self._last_groups = cg
@@ -768,7 +918,7 @@ class MetropolisBatch:
                 cg.join()
             self._counter = base + chainL
             return track
-        p0 = self._start(C, init_first, _init_mask)
+        p0 = self._start(C, init_first, _init_mask, start, _start_mask)
         chi0 = self._first_row(track, p0)
         for i in range(1, chainL):
             p1 = self.perturb(p0)
@@ -785,8 +935,35 @@ class MetropolisBatch:
             chi0 = torch.where(acc, chi1, chi0)
         return track
 
-    def _start(self, C, init_first, _init_mask):
+    def _checked_start(self, start, C, mask=None):
+        """``start`` [C, N] as a float64 tensor on the sampler's device; ValueError for a wrong shape or type, and for a row (of the
+        chains in ``mask``; None: all) outside the open prior box or refused by ``isgood``.  Synchronises once."""
         torch = self.torch
+        N = self.spec.n
+        if not torch.is_tensor(start) or start.dtype != torch.float64 or tuple(start.shape) != (C, N):
+            raise ValueError(f"start: a float64 tensor [{C}, {N}] expected, got {getattr(start, 'dtype', type(start).__name__)} "
+                             f"{tuple(getattr(start, 'shape', ()))}")
+        start = start.to(self.device)
+        lo = torch.as_tensor(np.asarray(self.spec.vmin, np.float64), device=self.device)
+        hi = torch.as_tensor(np.asarray(self.spec.vmax, np.float64), device=self.device)
+        used = torch.ones(C, dtype=torch.bool, device=self.device) if mask is None else mask
+        inside = ((start > lo) & (start < hi)).all(dim=1) | ~used
+        if not bool(inside.all()):
+            raise ValueError(f"start: {int((~inside).sum())} of {C} rows lie outside the open prior box (vmin, vmax)")
+        if self.isgood is not None:
+            rows = start[used]                                     # (rows of chains that start elsewhere are never looked at)
+            if isinstance(self.isgood, PriorRules) and self.local_rows is not None:
+                good = self.isgood(rows, rows=self.local_rows[used])
+            else:
+                good = self.isgood(rows)
+            if not bool(good.all()):
+                raise ValueError(f"start: {int((~good).sum())} rows break the prior's rules (isgood)")
+        return start
+
+    def _start(self, C, init_first, _init_mask, start=None, _start_mask=None):
+        torch = self.torch
+        if start is not None and _start_mask is None:
+            return start
         p0 = self.reset(C) if not (init_first and C == 1) else None
         if init_first or _init_mask is not None:
             v0 = torch.as_tensor(self.spec.v0, dtype=torch.float64, device=self.device)[None, :]
@@ -796,6 +973,8 @@ class MetropolisBatch:
                 p0 = torch.where(_init_mask[:, None], v0.expand_as(p0), p0)
             else:
                 p0 = v0 if p0 is None else torch.cat([v0, p0[1:]], dim=0)
+        if start is not None:                                      # (run_points: the chains of the mask start at their rows)
+            p0 = torch.where(_start_mask[:, None], start, p0)
         return p0
 
     def _first_row(self, track, p):
@@ -804,12 +983,12 @@ class MetropolisBatch:
         _put_row(track, 0, mis, L, 1.0, p)
         return chi
 
-    def _run_speculative(self, n_chains, chainL, init_first, _init_mask, d):
+    def _run_speculative(self, n_chains, chainL, init_first, _init_mask, d, start=None, _start_mask=None):
         torch = self.torch
         C, N = int(n_chains), self.spec.n
         M = (1 << d) - 1                                           # proposals per chain per lock step
         track = torch.zeros((C, chainL, 3 + N), dtype=torch.float64, device=self.device)
-        p = self._start(C, init_first, _init_mask)
+        p = self._start(C, init_first, _init_mask, start, _start_mask)
         chi = self._first_row(track, p)
         ar = torch.arange(C, device=self.device)
         i = 1
@@ -840,13 +1019,28 @@ class MetropolisBatch:
                 i += 1
         return track
 
-    def run_points(self, n_points, chains_per_point, chainL, on_device=False, groups=None, spec_depth=None):
+    def run_points(self, n_points, chains_per_point, chainL, on_device=False, groups=None, spec_depth=None, start=None):
         """MCinvMP for n_points at once: chain index = point * chains_per_point + k; chain k = 0 of
         every point starts at the initial model, the others at prior draws (point.py:95-99).
+        ``start``: float64 [n_points, N] - chain k = 0 of a point starts at its row instead, the others at prior draws as now - or
+        [n_points, chains_per_point, N] for all chains (checked as ``run(start=)`` checks its rows).
         Returns float64 [n_points, chains_per_point, chainL, 3+N] (numpy, or the device tensor)."""
         torch = self.torch
         C = n_points * chains_per_point
         first = (torch.arange(C, device=self.device) % chains_per_point) == 0
+        if start is not None:
+            N = self.spec.n
+            if not torch.is_tensor(start) or start.dtype != torch.float64 or \
+                    tuple(start.shape) not in ((n_points, N), (n_points, chains_per_point, N)):
+                raise ValueError(f"start: a float64 tensor [{n_points}, {N}] or [{n_points}, {chains_per_point}, {N}] expected, got "
+                                 f"{getattr(start, 'dtype', type(start).__name__)} {tuple(getattr(start, 'shape', ()))}")
+            if start.ndim == 2:
+                rows, kw = start.repeat_interleave(chains_per_point, dim=0), dict(_start_mask=first)
+            else:
+                rows, kw = start.reshape(C, N), {}
+            tr = self.run(C, chainL, init_first=False, groups=groups, spec_depth=spec_depth, start=rows, **kw)
+            tr = tr.reshape(n_points, chains_per_point, chainL, -1)
+            return tr if on_device else tr.cpu().numpy()
         tr = self.run(C, chainL, init_first=False, _init_mask=first, groups=groups, spec_depth=spec_depth).reshape(n_points, chains_per_point, chainL, -1)
         return tr if on_device else tr.cpu().numpy()
 

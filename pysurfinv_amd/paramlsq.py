@@ -4,7 +4,8 @@
 reference's model parameters - the ``setting`` dictionaries of ``models.py``: B-spline Vs coefficients per group, group
 thicknesses, ``BottomDepth`` - as ``ParamSpec`` rows through ``Model1DBatch``.  This module is the Gauss-Newton /
 Levenberg-Marquardt fit of those rows: a maximum a posteriori point to start chains from, a ``toYML``-able model comparable with the
-sampler's ``avgMod``, and a Gaussian (Laplace) covariance of the parameters to size proposal steps with.
+sampler's ``avgMod``, and a Gaussian (Laplace) covariance of the parameters to size proposal steps with -
+``ParamLsqBatch.proposal_factor`` hands its Cholesky factor to ``MetropolisBatch.set_proposal``, the fitted rows to ``run(start=)``.
 
 The map parameters -> stack is smooth and analytic for every layer class but the thermal mantle, so its Jacobian is exact
 (``surfdisp_params_jacobian_device``, one thread per (chain, layer, unknown) carrying a dual number), and the chain rule through
@@ -290,6 +291,7 @@ class ParamLsqBatch:
         t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
         self.params = t(p0)
         self.free, self.free8 = t(np.broadcast_to(fr, (M, Nu))), t(fr.astype(np.uint8))
+        self.n_free = fr.sum(axis=-1)                                      # free parameters: an integer, or [M] with per-point masks
         self.scale, self.prior_w, self.prior_ref = t(sc), t(beta), t(ref)
         self.has_prior = bool((beta > 0).any())
         w = hi - lo
@@ -385,6 +387,37 @@ class ParamLsqBatch:
             lam_t = lam_t.contiguous()
         st = self._step(lam_t, want_cov=True)
         return {k: st[k] for k in ("cov", "sigma", "logdet", "flag")}
+
+    def proposal_factor(self, scale=None, box_prior=True):
+        """The proposal of a Metropolis sampler from the Laplace approximation at the CURRENT point: dict(factor [M, Nu, Nu] lower
+        triangular, flag [M] int32) on the device, no host synchronisation - ``MetropolisBatch.set_proposal(factor,
+        chains_per_point)`` then proposes x + factor z at every chain of point m.  factor factor^T = scale^2 cov, cov = A^-1 of
+        ``plan.step(..., want_cov=True)`` at lam = 0 (``surfdisp_mcmc_cov_factor_device``; a fixed parameter has a zero row and
+        column and never moves).  ``box_prior``: the variance of the uniform prior box enters A as a Gaussian pull, prior_w_j + 12 /
+        (vmax_j - vmin_j)^2 - a parameter the data do not constrain then gets the box's own spread instead of an unbounded one
+        (without it such a parameter makes every Gaussian candidate leave the box).  ``scale``: None = 2.38 / sqrt(n_free), the
+        optimal random-walk scaling of Roberts, Gelman and Gilks (1997).  A point whose step has flag != 0, or whose
+        matrix cannot be factored, gets diag(spec.step) - the reference's proposal - and flag = 1."""
+        torch = self.torch
+        spec = self.model_batch.spec
+        pw = self.prior_w
+        if box_prior:
+            w = torch.as_tensor(np.asarray(spec.vmax, np.float64) - np.asarray(spec.vmin, np.float64), device=self.device)
+            pw = (pw + 12.0 / (w * w)).contiguous()
+        kw = dict(prior_w=pw, prior_ref=self.prior_ref) if (box_prior or self.has_prior) else {}
+        lam = torch.zeros(self.M, dtype=torch.float64, device=self.device)
+        st = self.plan.step(self.params, lam, self.scale, free=self.free8, rows=self.rows, want_cov=True, **kw)
+        cov = st["cov"]
+        if scale is None:
+            s = 2.38 / np.sqrt(np.maximum(self.n_free, 1))
+            if np.ndim(s):                                                 # per-point masks: scaled here, the kernel takes one scalar
+                cov, s = cov * torch.as_tensor(s * s, device=self.device)[:, None, None], 1.0
+        else:
+            s = float(scale)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=self.device)
+        cov = torch.where((st["flag"] != 0)[:, None, None], nan, cov)      # a flagged step left zeros: NaN takes the kernel's fallback
+        from .mcmc import cov_factor
+        return cov_factor(cov, float(s), np.asarray(spec.step, np.float64))
 
     def to_yml(self, point=None):
         """``Model1DBatch.to_yml`` of the current parameters: the dict of point ``point``, or the list over all points."""

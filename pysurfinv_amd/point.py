@@ -75,19 +75,37 @@ class Point:
         return float(mis[0]), float(chi[0]), float(L[0])
 
     def MCinvMP(self, outdir="MCtest", pid=None, runN=50000, chainL=1000, nprocess=None, seed=42,
-                priori=False, isgood=None, verbose=True, spec_depth=None, independent=False, fast_scan=False):
+                priori=False, isgood=None, verbose=True, spec_depth=None, independent=False, fast_scan=False, proposal=None):
         """``runN // chainL`` chains of ``chainL`` steps each, the first one started at the initial model
         (point.py:91-125); writes ``{outdir}/{pid}.npz`` and returns the mcTrack array [runN, 3 + N].
         ``independent="auto"``: the period-parallel root search while the chains are too few to fill the chip (3 x faster
         lock steps for 100 chains; see ``MetropolisBatch``) - opt-in, the default is the reference's period walk.
         ``spec_depth``: None = the sampler's default (speculative lock steps on the device path: four Metropolis steps per
-        batched solve for up to 136 chains, three up to 292, same chain distribution; ``MetropolisBatch.auto_spec_depth``), 1 = one step per solve."""
+        batched solve for up to 136 chains, three up to 292, same chain distribution; ``MetropolisBatch.auto_spec_depth``), 1 = one step per solve.
+        ``proposal="laplace"``: the point is first fitted by least squares (``paramlsq.ParamLsqBatch``, 8 iterations, on the same data
+        and with ``isgood`` when it is a ``PriorRules``; a thermal model: its ValueError), the first chain starts at the fitted model
+        and all chains propose with the factor of its Laplace covariance (``MetropolisBatch.set_proposal``)."""
+        if proposal not in (None, "laplace"):
+            raise ValueError("MCinvMP: proposal must be None or 'laplace'")
+        if proposal is not None and priori:
+            raise ValueError("MCinvMP: a priori run evaluates no data, so there is nothing to fit: proposal=None expected")
         if priori and outdir.split("_")[-1] != "priori":
             outdir = "_".join((outdir, "priori"))
         pid = self.pid if pid is None else pid
         mc = self._sampler(seed=seed, isgood=isgood, independent=independent, fast_scan=fast_scan)
-        track = mc.run(max(int(runN) // int(chainL), 1), int(chainL), init_first=True, priori=priori,
-                       spec_depth=spec_depth)
+        nch = max(int(runN) // int(chainL), 1)
+        if proposal == "laplace":
+            from .mcmc import PriorRules
+            from .obsdata import DispersionData
+            from .paramlsq import ParamLsqBatch
+            data = self.data if self.data is not None else [DispersionData("R", "c", self.obs["T"], self.obs["c"], self.obs["uncer"])]
+            v0 = np.array(self.initMod.spec.v0, np.float64)[None, :]
+            fit = ParamLsqBatch(self.initMod, data, params0=v0, rules=isgood if isinstance(isgood, PriorRules) else None)
+            row = fit.run(8)["params"]
+            mc.set_proposal(fit.proposal_factor()["factor"][0].contiguous())
+            track = mc.run_points(1, nch, int(chainL), on_device=True, spec_depth=spec_depth, start=row)[0]
+        else:
+            track = mc.run(nch, int(chainL), init_first=True, priori=priori, spec_depth=spec_depth)
         arr = track.cpu().numpy().reshape(-1, track.shape[-1])
         n_exhausted = mc.prior_exhausted()                         # PriorRules(redraw="kernel"); the track is on the host already
         if n_exhausted:

@@ -41,6 +41,10 @@ def main():
     ap.add_argument("--chain-groups", type=int, default=None, help="chain groups per rank (default: 2 from 4 096 chains on)")
     ap.add_argument("--spec-depth", type=int, default=None, help="Metropolis steps per batched solve (default: 4 / 3 / 2 for up to "
                                                                  "136 / 292 / 682 chains per rank, else 1)")
+    ap.add_argument("--proposal", choices=["laplace"], default=None,
+                    help="laplace: fit every point by least squares first (pysurfinv_amd.paramlsq), start chain 0 of the point at the fitted "
+                         "model and propose with the Cholesky factor of its Laplace covariance (default: the reference's independent steps)")
+    ap.add_argument("--lsq-iters", type=int, default=8, help="iterations of that fit")
     args = ap.parse_args()
 
     import torch
@@ -78,7 +82,8 @@ def main():
         lons, lats = 230.0 + 0.5 * (np.arange(n) % 64), 40.0 + 0.5 * (np.arange(n) // 64)
     r = grid.run_grid(mb, lons, lats, periods, c_obs, uncer, args.chains, args.chainL, outdir=args.outdir,
                       rank=rank, world=world, device=str(dev), seed=args.seed, fast_scan=args.fast_scan, keep_tracks=False,
-                      local_info=local_info, chain_groups=args.chain_groups, spec_depth=args.spec_depth)
+                      local_info=local_info, chain_groups=args.chain_groups, spec_depth=args.spec_depth,
+                      proposal=args.proposal, lsq_iters=args.lsq_iters)
     if rank == 0:
         os.makedirs(args.outdir, exist_ok=True)
         np.savez_compressed(os.path.join(args.outdir, "summaries.npz"), summaries=r["summaries"], columns=np.array(r["columns"]),
