@@ -534,6 +534,40 @@ int surfdisp_mcmc_propose_cov_device(void *stream, int C, int N, int K, int L, i
                                      double *out, unsigned short *tries, int *exhausted);
 int surfdisp_mcmc_cov_factor_device(void *stream, int P, int N, const double *cov, double scale, const double *fallback_step,
                                     double *factor_t, int *flag);
+/* Adaptive proposals (csrc/surfdisp_mcmc_adapt.hip; added within ABI 4): adaptive Metropolis (Haario et al. 2001) pooled over the
+ * chains of a grid point, with a Robbins-Monro step scale.  surfdisp_mcmc_adapt_device is ONE update for F points, each with cpp
+ * chains of N <= SURFDISP_MCMC_COV_N_MAX scalars: p [F * cpp][N] the chains' current states (chain c belongs to point c / cpp), the
+ * accept flags of the rows [row_lo, row_hi) of a track - flag of chain c, row r: track[c * chain_stride + r * row_stride + 2],
+ * strides in doubles; counted as accepted when > 0.5 -, step [N] the reference's step, and per point a block of
+ * SURFDISP_MCMC_ADAPT_HEAD + N + N N doubles in `state`:
+ *   [0] W the weight  [1] ls the log scale  [2] k the update count of ls  [3] the fallback count  [4] 1 when this call wrote the point's
+ *   cov_out, else 0  [5..7] 0  [8 .. 8 + N) mean  [8 + N ...) the scatter S[k][n] at k * N + n, k <= n (the entries below the
+ *   diagonal are carried along, times forget, and never read as values).
+ * A block of zeros is the fresh state.  Per point, in this order, in float64:
+ *   1. W *= forget; S *= forget;
+ *   2. for the point's chains in ascending order, one Welford step each: W += 1; d = x - mean; mean += d / W;
+ *      S[k][n] += d_k * (x_n - mean_n) for k <= n (mean_n: the updated one);
+ *   3. with target_accept >= 0 and row_hi > row_lo: a = (number of accepted flags of the point's chains and the window's rows) /
+ *      (cpp * (row_hi - row_lo)), the count an integer (exact, order-free); k += 1; ls += (gain * k^(-decay)) * (a - target_accept),
+ *      every operation rounded on its own, then clamped to [ls_min, ls_max].  target_accept < 0 or an empty window: ls and k stay;
+ *   4. with W >= min_weight: cov_out[f][k][n] = c * B[k][n], symmetric, B = S / W + ridge diag(step^2) with the diagonal term formed
+ *      as (ridge * step_n) * step_n, c = exp(2 ls) * (2.38^2 / N_live), N_live the scalars with B[n][n] != 0; a scalar with B[n][n] == 0
+ *      gets a zero row and column (the "fixed parameter" convention of surfdisp_mcmc_cov_factor_device).  [4] = 1.  Below min_weight
+ *      cov_out is left untouched and [4] = 0.  cov_out may be NULL (nothing is written; [4] still answers W >= min_weight).
+ * [3] is carried unchanged: factoring stays with surfdisp_mcmc_cov_factor_device (scale = 1, fallback_step = step, straight into the
+ * sampler's factor_t), launched by the caller on all points once every point has reached min_weight - with equally many chains per
+ * point and blocks started together, W is the same number on every point and known on the host without a read-back -, and the caller
+ * adds that entry's flag to [3].  One wavefront per point, lane n = scalar n, the scatter in LDS (N N + 128 doubles), the chains one
+ * after the other: no atomics, and the result does not depend on the launch shape.  Bad arguments - F, cpp, N < 1, N >
+ * SURFDISP_MCMC_COV_N_MAX, forget outside (0, 1], row_lo < 0, row_hi < row_lo, ridge < 0, min_weight < 1, ls_min > ls_max,
+ * target_accept > 1, a value that is not a number, p, state or step NULL, track NULL with a window to read -: SURFDISP_ERR_INVALID
+ * before any device call.  Stream-ordered, no host synchronisation. */
+#define SURFDISP_MCMC_ADAPT_HEAD 8
+int surfdisp_mcmc_adapt_device(void *stream, int F, int cpp, int N, const double *p,
+                               const double *track, long chain_stride, long row_stride, int row_lo, int row_hi,
+                               const double *step, double forget, double target_accept, double gain, double decay,
+                               double ls_min, double ls_max, double min_weight, double ridge,
+                               double *state, double *cov_out);
 /* The SPECULATIVE lock step for few chains (a lock step of 100 chains leaves the chip idle, so it costs no more to solve
  * several proposals per chain): propose_tree draws the binary tree of the next `depth` (1..4) accept / reject outcomes -
  * node k's proposal from the state its branch would be in (node 0: the chain's state; child 2k+1 "accepted": proposal k;

@@ -32,7 +32,7 @@ EXPORTS = (
     "surfdisp_events_elapsed_ms", "surfdisp_stream_wait_event", "surfdisp_params_to_model_device",
     "surfdisp_params_to_model_thermal_device", "surfdisp_thermal_scratch_bytes",
     "surfdisp_mcmc_propose_device", "surfdisp_mcmc_accept_device", "surfdisp_prior_device", "surfdisp_mcmc_propose_masked_device", "surfdisp_mcmc_propose_tree_device", "surfdisp_mcmc_accept_tree_device",
-    "surfdisp_mcmc_propose_prior_device", "surfdisp_mcmc_propose_cov_device", "surfdisp_mcmc_cov_factor_device", "surfdisp_mcmc_accept_joint_device", "surfdisp_mcmc_accept_tree_joint_device",
+    "surfdisp_mcmc_propose_prior_device", "surfdisp_mcmc_propose_cov_device", "surfdisp_mcmc_cov_factor_device", "surfdisp_mcmc_adapt_device", "surfdisp_mcmc_accept_joint_device", "surfdisp_mcmc_accept_tree_joint_device",
     "surfdisp_mcmc_accept_joint5_device", "surfdisp_mcmc_accept_tree_joint5_device", "surfdisp_forward_batch_device2_events",
     "surfdisp_forward_kernels_device", "surfdisp_kernels_workspace_bytes",
     "surfdisp_forward_group_kernels_device", "surfdisp_group_kernels_workspace_bytes",
@@ -193,6 +193,12 @@ def lib() -> ctypes.CDLL:
         # (stream, P, N, cov, scale, fallback_step, factor_t, flag)
         L.surfdisp_mcmc_cov_factor_device.restype = ctypes.c_int
         L.surfdisp_mcmc_cov_factor_device.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_double, vp, vp, vp]
+    if hasattr(L, "surfdisp_mcmc_adapt_device"):               # (absent from an older build loaded through SURFDISP_LIB_PATH)
+        # (stream, F, cpp, N, p, track, chain_stride, row_stride, row_lo, row_hi, step, forget, target_accept, gain, decay, ls_min,
+        #  ls_max, min_weight, ridge, state, cov_out)
+        L.surfdisp_mcmc_adapt_device.restype = ctypes.c_int
+        L.surfdisp_mcmc_adapt_device.argtypes = ([vp] + [ctypes.c_int] * 3 + [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                 vp] + [ctypes.c_double] * 8 + [vp, vp])
     # the accept entries: (stream, C, N, [P,] [depth, nsteps,] predictions, c_obs, uncer, mask, obs_per_chain, p1, p0, chi0, row,
     # row_stride, [step_stride,] seed, counter, [first,] chain0) - P and the predictions differ between the Rayleigh-phase entries
     # and the joint ones, the tree entries take depth, nsteps and step_stride in place of first

@@ -1045,6 +1045,39 @@ int surfdisp_mcmc_cov_factor_device(void *stream, int P, int N, const double *co
     return SURFDISP_SUCCESS;
 }
 
+// One pooled adaptive-Metropolis update per point (csrc/surfdisp_mcmc_adapt.hip; header section (6c)).  Every argument is judged on
+// the host before anything touches the device; the comparisons are written so that a NaN fails them.
+int surfdisp_mcmc_adapt_device(void *stream, int F, int cpp, int N, const double *p,
+                               const double *track, long chain_stride, long row_stride, int row_lo, int row_hi,
+                               const double *step, double forget, double target_accept, double gain, double decay,
+                               double ls_min, double ls_max, double min_weight, double ridge,
+                               double *state, double *cov_out)
+{
+    const char *name = "surfdisp_mcmc_adapt_device";
+    if (F < 1 || cpp < 1 || N < 1 || N > sd::SD_MCMC_COV_MAX_N) {
+        set_err("%s: invalid size (F >= 1; cpp >= 1; 1 <= N <= SURFDISP_MCMC_COV_N_MAX = 64)", name); return SURFDISP_ERR_INVALID;
+    }
+    if (!(forget > 0.0 && forget <= 1.0)) {
+        set_err("%s: invalid forget: 0 < forget <= 1 expected", name); return SURFDISP_ERR_INVALID;
+    }
+    if (row_lo < 0 || row_hi < row_lo) {
+        set_err("%s: invalid window: 0 <= row_lo <= row_hi expected", name); return SURFDISP_ERR_INVALID;
+    }
+    if (!(ridge >= 0.0) || !(min_weight >= 1.0) || !(ls_min <= ls_max) || !(target_accept <= 1.0) || !(gain == gain) || !(decay == decay)) {
+        set_err("%s: invalid option: ridge >= 0, min_weight >= 1, ls_min <= ls_max, target_accept <= 1 and numbers for gain and decay expected",
+                name);
+        return SURFDISP_ERR_INVALID;
+    }
+    if (!p || !state || !step || (!track && target_accept >= 0.0 && row_hi > row_lo)) {
+        set_err("%s: invalid argument: a required pointer is NULL (p, state, step; track with a window to read)", name);
+        return SURFDISP_ERR_INVALID;
+    }
+    sd::McmcAdaptArgs a{F, cpp, N, p, track, chain_stride, row_stride, row_lo, row_hi, step, forget, target_accept, gain, decay,
+                        ls_min, ls_max, min_weight, ridge, state, cov_out};
+    SD_HIP(sd::launch_mcmc_adapt(static_cast<hipStream_t>(stream), a));
+    return SURFDISP_SUCCESS;
+}
+
 // Posterior Vs(z) profiles of a Metropolis track (csrc/surfdisp_post.hip; header section (6f)).  Workspace: the per-slab partials
 // [npoints][nslab][D + N][5] doubles, the slabs' smallest misfits [npoints][nslab] doubles, then four int arrays [npoints][nslab].
 static long post_slabs(int R) { return ((long)R + SURFDISP_POST_SLAB_ROWS - 1) / SURFDISP_POST_SLAB_ROWS; }

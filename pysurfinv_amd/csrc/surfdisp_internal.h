@@ -345,6 +345,21 @@ struct McmcCovFactorArgs {
     int *flag;              // [P]: 0 factored, 1 diag(fallback_step)
 };
 hipError_t launch_mcmc_cov_factor(hipStream_t s, const McmcCovFactorArgs &a);
+// adaptive proposals: one pooled update of every point's mean, scatter and log scale, and the covariance the factor kernel takes
+// (csrc/surfdisp_mcmc_adapt.hip; include/surfdisp.h section (6c))
+constexpr int SD_MCMC_ADAPT_HEAD = SURFDISP_MCMC_ADAPT_HEAD;
+struct McmcAdaptArgs {
+    int F, cpp, N;
+    const double *p;        // [F * cpp][N] the chains' current states
+    const double *track;    // the accept flags: track[chain * chain_stride + row * row_stride + 2]; nullptr without a window
+    long chain_stride, row_stride;
+    int row_lo, row_hi;     // the window's rows [row_lo, row_hi)
+    const double *step;     // [N]
+    double forget, target_accept, gain, decay, ls_min, ls_max, min_weight, ridge;
+    double *state;          // [F][SD_MCMC_ADAPT_HEAD + N + N N]
+    double *cov_out;        // [F][N][N] or nullptr
+};
+hipError_t launch_mcmc_adapt(hipStream_t s, const McmcAdaptArgs &a);
 // joint data (Rayleigh / Love, phase / group, Rayleigh ellipticity): the accept kernel's arguments plus the solves' predictions and
 // the column table.  In `a`, c and P are unused; c_obs / uncer / mask have Ptot columns (P of `a` = Ptot).
 struct McmcJointArgs {

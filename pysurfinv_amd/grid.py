@@ -33,7 +33,7 @@ def summary_columns(n_params, n_periods):
 def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, chainL, outdir=None,
              rank=0, world=1, device="cuda:0", seed=0, forward=None, isgood=None, fast_scan=False,
              writer_threads=4, keep_tracks=True, local_info=None, chain_groups=None, spec_depth=None,
-             profile_depths=None, proposal=None, lsq_iters=8):
+             profile_depths=None, proposal=None, lsq_iters=8, adaptive=None):
     """Invert the points owned by ``rank``.
 
     model_batch : layers_batch.Model1DBatch (one setting for the grid)
@@ -58,6 +58,11 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
                   ``MetropolisBatch.set_proposal``).  The report then carries ``lsq_rms_median`` (the fits' rms misfit, median over this
                   rank's points) and ``factor_fallbacks`` (points, summed over ranks, that kept the reference's steps because their
                   covariance could not be factored); inside ``elapsed``.
+                  "adaptive": adaptive Metropolis pooled over the chains of every point (``MetropolisBatch.set_adaptive(chains_per_point,
+                  **adaptive)``, ``adaptive`` a dict of its options or None for the defaults) - any model the sampler runs, a thermal one
+                  included; chains start as with None.  The rows before ``until`` (default: the first half of every chain) are
+                  adaptation, no valid samples.  The report then carries ``adapt_updates`` (updates per point, this rank) and
+                  ``adapt_fallbacks`` (refactorings, summed over points and ranks, that kept the reference's steps).
     Returns dict(points=(lo, hi), mcTrack=[n_local, chains*chainL, 3+N] or None, summaries=[n_points, 6+2N+P]
     (every rank holds all rows, point order), columns, elapsed (sampling + summaries + gather, this rank),
     elapsed_write, report).  ``report`` carries the MAX over ranks of ``elapsed`` and the summed counters; among them
@@ -76,9 +81,12 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     t0 = time.perf_counter()
     n_forward = 0
     mc = None
-    if proposal not in (None, "laplace"):
-        raise ValueError("run_grid: proposal must be None or 'laplace'")
+    if proposal not in (None, "laplace", "adaptive"):
+        raise ValueError("run_grid: proposal must be None, 'laplace' or 'adaptive'")
+    if adaptive is not None and proposal != "adaptive":
+        raise ValueError("run_grid: adaptive= holds the options of proposal='adaptive'")
     lsq_rms_median, factor_fallbacks = None, 0
+    adapt_updates, adapt_fallbacks = 0, 0
     tracks_dev = torch.zeros((n_local, chains_per_point * chainL, 3 + N), dtype=torch.float64, device=dev)
     summ = torch.zeros((n_local, 6 + 2 * N + P), dtype=torch.float64, device=dev)
     if model_batch.n_aux and local_info is None:
@@ -108,6 +116,8 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
             pf = fit.proposal_factor()
             mc.set_proposal(pf["factor"], chains_per_point)
             lsq_rms_median, factor_fallbacks = float(fit.rms.median()), int(pf["flag"].sum())
+        elif proposal == "adaptive":
+            mc.set_adaptive(chains_per_point, **(adaptive or {}))
         tracks_dev = mc.run_points(n_local, chains_per_point, chainL, on_device=True, groups=chain_groups, spec_depth=spec_depth,
                                    start=start).reshape(n_local, chains_per_point * chainL, -1)
         first_chain = torch.arange(n_local, device=dev) * chains_per_point     # observation row of each point
@@ -136,6 +146,9 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
     # PriorRules(redraw="kernel"): proposals that found no good model within the caps.  Reported, not raised: a rank that raised
     # here would leave the others waiting in the collectives below.
     prior_exhausted = mc.prior_exhausted() if mc is not None else 0
+    if proposal == "adaptive" and mc is not None:
+        ad = mc.adaptation()
+        adapt_updates, adapt_fallbacks = int(ad["n_updates"].max()), int(ad["fallbacks"].sum())
     # ---- outside the timed path: tracks to the host and {lon}_{lat}.npz files from writer threads
     t1 = time.perf_counter()
     tracks = tracks_dev.cpu().numpy() if (keep_tracks or outdir is not None) else None
@@ -150,15 +163,15 @@ def run_grid(model_batch, lons, lats, periods, c_obs, uncer, chains_per_point, c
         with ThreadPoolExecutor(max_workers=max(1, int(writer_threads))) as ex:
             list(ex.map(write, range(n_local)))
     elapsed_write = time.perf_counter() - t1
-    max_elapsed, (tot_forward, tot_points, tot_exhausted, tot_fallbacks) = shard.reduce_report(
-        elapsed, [n_forward, n_local, prior_exhausted, factor_fallbacks], device=cdev)
+    max_elapsed, (tot_forward, tot_points, tot_exhausted, tot_fallbacks, tot_adapt_fallbacks) = shard.reduce_report(
+        elapsed, [n_forward, n_local, prior_exhausted, factor_fallbacks, adapt_fallbacks], device=cdev)
     steps = tot_points * chains_per_point * chainL
     res = dict(points=(lo, hi), mcTrack=tracks if keep_tracks else None, summaries=summaries,
                columns=summary_columns(N, P), elapsed=elapsed, elapsed_write=elapsed_write,
                report=dict(elapsed_max=max_elapsed, forward_solves=tot_forward, points=tot_points,
                            prior_exhausted=tot_exhausted, prior_exhausted_rank=prior_exhausted,
                            proposal=proposal, lsq_rms_median=lsq_rms_median, factor_fallbacks=tot_fallbacks,
-                           metropolis_steps=steps,
+                           adapt_updates=adapt_updates, adapt_fallbacks=tot_adapt_fallbacks, metropolis_steps=steps,
                            steps_per_s=steps / max_elapsed if max_elapsed > 0 else 0.0,
                            solves_per_s=tot_forward / max_elapsed if max_elapsed > 0 else 0.0))
     if profiles is not None:

@@ -21,7 +21,9 @@ Semantics kept from the reference:
   model (``models.py:254-256``, ``point.py:58,73-76``); output ``.npz`` keys ``mcTrack, setting,
   obs, invMeta`` (``point.py:82-85``) so ``PostPoint`` / ``Model3D.loadInvDir`` can read it.
 Opt-in, beyond the reference: ``set_proposal`` replaces the independent steps by ``x + F z`` with a lower-triangular factor per grid
-point (e.g. ``paramlsq.ParamLsqBatch.proposal_factor``), ``run(start=)`` starts chains at given rows (e.g. the fitted ones).
+point (e.g. ``paramlsq.ParamLsqBatch.proposal_factor``), ``run(start=)`` starts chains at given rows (e.g. the fitted ones);
+``set_adaptive`` makes that factor inside the run from the pooled states of a point's chains (adaptive Metropolis with a
+Robbins-Monro scale, for any model the sampler runs; the rows before ``until`` are adaptation, no valid samples).
 RNG: CPython's Mersenne Twister cannot be reproduced on the device; the production path uses a
 torch Philox generator (statistical parity), and ``PythonRandomProposer`` replays the reference's
 exact stream for one chain (trace parity, ``tests/test_mcmc.py``).
@@ -119,6 +121,81 @@ def cov_factor(cov, scale, fallback_step):
         _lib.check(_lib.lib().surfdisp_mcmc_cov_factor_device(stream, P, N, _ptr(cov), ctypes.c_double(float(scale)), _ptr(fb),
                                                               _ptr(factor_t), _ptr(flag)))
     return dict(factor=factor_t.transpose(1, 2), flag=flag)
+
+
+ADAPT_HEAD = 8             # doubles before the mean in a point's adaptation block (SURFDISP_MCMC_ADAPT_HEAD)
+ADAPT_DEFAULTS = dict(every=10, start=20, until=None, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6, min_weight=None, ridge=1e-3,
+                      log_scale_bounds=(-3.0, 3.0))
+
+
+def adapt_state_len(N):
+    """Doubles per point of the adaptation state (include/surfdisp.h: [W, ls, k, fallbacks, wrote-cov, 0, 0, 0 | mean [N] | S [N][N]])."""
+    return ADAPT_HEAD + N + N * N
+
+
+def adapt_state_views(state, N):
+    """dict of views into a state array / tensor [F, adapt_state_len(N)]: weight, log_scale, n_updates, fallbacks, ready [F],
+    mean [F, N], scatter [F, N, N] (its upper triangle is the scatter)."""
+    F = state.shape[0]
+    return dict(weight=state[:, 0], log_scale=state[:, 1], n_updates=state[:, 2], fallbacks=state[:, 3], ready=state[:, 4],
+                mean=state[:, ADAPT_HEAD:ADAPT_HEAD + N], scatter=state[:, ADAPT_HEAD + N:].reshape(F, N, N))
+
+
+def adapt_reference(state, x, flags, step, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6, min_weight=None, ridge=1e-3,
+                    log_scale_bounds=(-3.0, 3.0), cov=None):
+    """``surfdisp_mcmc_adapt_device`` in numpy float64, in the kernel's order of operations: ``state`` [F, adapt_state_len(N)] (None:
+    the fresh state, zeros), ``x`` [F, cpp, N] the chains' states, ``flags`` [F, cpp, R] the accept flags of the window's R rows
+    (None or R = 0: an empty window), ``step`` [N] -> (state', cov): cov [F, N, N] with the points that reached ``min_weight``
+    (default 4 N) written and the others as in ``cov=`` (zeros without), or None when no point did."""
+    x = np.asarray(x, np.float64)
+    F, cpp, N = x.shape
+    step = np.asarray(step, np.float64)
+    min_weight = 4.0 * N if min_weight is None else float(min_weight)
+    st = np.zeros((F, adapt_state_len(N))) if state is None else np.array(state, np.float64)
+    v = adapt_state_views(st, N)
+    up = np.triu(np.ones((N, N), bool))
+    W = v["weight"] * float(forget)
+    S = v["scatter"] * float(forget)
+    mean = v["mean"].copy()
+    for j in range(cpp):                                               # one Welford step per chain, ascending
+        W = W + 1.0
+        d = x[:, j] - mean
+        mean = mean + d / W[:, None]
+        e = x[:, j] - mean
+        S = S + np.where(up, d[:, :, None] * e[:, None, :], 0.0)
+    ls, k = v["log_scale"].copy(), v["n_updates"].copy()
+    R = 0 if flags is None else np.asarray(flags).shape[2]
+    if target_accept >= 0.0 and R > 0:
+        cnt = (np.asarray(flags, np.float64) > 0.5).sum(axis=(1, 2))   # integers: exact, order-free
+        a = cnt.astype(np.float64) / float(cpp * R)
+        k = k + 1.0
+        g = float(gain) * np.power(k, -float(decay))
+        inc = g * (a - float(target_accept))
+        ls = np.minimum(np.maximum(ls + inc, float(log_scale_bounds[0])), float(log_scale_bounds[1]))
+    ready = W >= min_weight
+    v["weight"][:], v["log_scale"][:], v["n_updates"][:], v["ready"][:] = W, ls, k, ready
+    v["mean"][:], v["scatter"][:] = mean, S
+    if not ready.any():
+        return st, None
+    out = np.zeros((F, N, N)) if cov is None else np.array(cov, np.float64)
+    out[ready] = adapt_cov_formula(S[ready], W[ready], ls[ready], step, ridge)
+    return st, out
+
+
+def adapt_cov_formula(S, W, ls, step, ridge):
+    """Step 4 of ``surfdisp_mcmc_adapt_device``: cov [F, N, N] = exp(2 ls) (2.38^2 / N_live) (S / W + ridge diag(step^2)), symmetric from the
+    upper triangle of S [F, N, N]; a scalar whose diagonal is zero: a zero row and column, and not counted in N_live."""
+    S, W, ls, step = (np.asarray(a, np.float64) for a in (S, W, ls, step))
+    F, N, _ = S.shape
+    Su = np.triu(S)
+    B = (Su + np.transpose(np.triu(S, 1), (0, 2, 1))) / W[:, None, None]
+    i = np.arange(N)
+    B[:, i, i] = B[:, i, i] + (float(ridge) * step) * step
+    live = B[:, i, i] != 0.0
+    nlive = live.sum(axis=1)
+    with np.errstate(divide="ignore"):
+        c = np.where(nlive > 0, np.exp(2.0 * ls) * ((2.38 * 2.38) / nlive.astype(np.float64)), 0.0)
+    return np.where(live[:, :, None] & live[:, None, :], c[:, None, None] * B, 0.0)
 
 
 class PriorRules:
@@ -303,6 +380,9 @@ class MetropolisBatch:
         self._exh = None                                        # PriorRules(redraw="kernel") / set_proposal: one device int, shared with the chain groups
         self._prop = None                                       # set_proposal: dict(factor_t [F, N, N], cpf, F)
         self._last_groups = None                                # the ChainGroups of the last run (last_prior_tries)
+        self._adapt = None                                      # set_adaptive: the options
+        self._adapt_run = None                                  # the adaptation of the last run: state, cov, factor_t, flag (adaptation())
+        self._adapting = False                                  # inside a run that adapts
 
     def _fresh_state(self):
         """What a sampler owns and a chain group's child (a shallow copy of its parent) must not share with it."""
@@ -480,7 +560,7 @@ class MetropolisBatch:
         with chain c taking ``factor[c // chains_per_point]`` (the chain order of ``run_points``) - e.g. the Cholesky factor of a
         scaled Laplace covariance, ``ParamLsqBatch.proposal_factor``.  It is transposed once into the kernel's layout
         (``surfdisp_mcmc_propose_cov_device``).  ``None`` returns to the reference's proposal: the sampler then launches the kernels
-        and draws the numbers of one that was never given a factor.
+        and draws the numbers of one that was never given a factor (and turns ``set_adaptive`` off, which proposes with a factor too).
 
         The whole proposal is redrawn inside the kernel while it leaves the open prior box or breaks the rules of a ``PriorRules``
         (either ``redraw`` mode; its ``gauss_tries`` / ``uniform_tries``, 1000 / 10000 without rules), at every node of the
@@ -490,6 +570,7 @@ class MetropolisBatch:
         torch = self.torch
         if factor is None:
             self._prop = None
+            self._adapt = None                                     # (adaptation proposes with a factor: off with it)
             return
         N = self.spec.n
         if not torch.is_tensor(factor) or factor.dtype != torch.float64 or factor.ndim not in (2, 3) or tuple(factor.shape[-2:]) != (N, N):
@@ -499,13 +580,7 @@ class MetropolisBatch:
             raise ValueError(f"set_proposal: {N} random-walk parameters, the kernel takes at most {COV_MAX_N}")
         if int(chains_per_point) < 1:
             raise ValueError("set_proposal: chains_per_point >= 1 expected")
-        if self.isgood is not None and not (isinstance(self.isgood, PriorRules) and self.isgood.device_flags() is not None):
-            raise ValueError("set_proposal: isgood must be None or a PriorRules the device can evaluate (an arbitrary callback cannot "
-                             "run inside the propose kernel)")
-        if self.isgood is not None and self.local_rows is not None:
-            raise ValueError("set_proposal: PriorRules together with local_rows are not evaluated inside the propose kernel")
-        if not self.fused_available():
-            raise ValueError("set_proposal needs the fused device path: a HIP device, the device proposer and the HIP forward path")
+        self._require_cov_path("set_proposal")
         if factor.device != self.device:
             raise ValueError(f"set_proposal: the factor lives on {factor.device}, the sampler on {self.device}")
         ft = torch.tril(factor).transpose(-1, -2).contiguous()     # factor_t[f][k][n] = L_f[n][k]
@@ -513,6 +588,140 @@ class MetropolisBatch:
             self._prop = dict(factor_t=ft[None], cpf=1 << 62, F=1)
         else:
             self._prop = dict(factor_t=ft, cpf=int(chains_per_point), F=int(ft.shape[0]))
+
+    def _require_cov_path(self, who):
+        """ValueError unless the propose kernel of ``set_proposal`` / ``set_adaptive`` can serve this sampler."""
+        if self.isgood is not None and not (isinstance(self.isgood, PriorRules) and self.isgood.device_flags() is not None):
+            raise ValueError(f"{who}: isgood must be None or a PriorRules the device can evaluate (an arbitrary callback cannot "
+                             "run inside the propose kernel)")
+        if self.isgood is not None and self.local_rows is not None:
+            raise ValueError(f"{who}: PriorRules together with local_rows are not evaluated inside the propose kernel")
+        if not self.fused_available():
+            raise ValueError(f"{who} needs the fused device path: a HIP device, the device proposer and the HIP forward path")
+
+    # ------------------------------------------------------------------ adaptive proposals
+    def set_adaptive(self, chains_per_point, every=10, start=20, until=None, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6,
+                     min_weight=None, ridge=1e-3, log_scale_bounds=(-3.0, 3.0)):
+        """Adaptive Metropolis (Haario et al. 2001) pooled over the ``chains_per_point`` chains of every grid point (the chain order
+        of ``run_points``), inside ``run()`` / ``run_points()`` and without a host synchronisation: after step i with ``start <= i <
+        until`` and ``(i - start) % every == 0`` the chains' current states update the point's running mean and scatter (weights
+        times ``forget`` per update), the accept rate a of the rows since the previous update moves the log scale by
+        ``gain k^-decay (a - target_accept)`` (k-th update; kept within ``log_scale_bounds``; ``target_accept < 0``: the scale stays
+        1), and once the weight has reached ``min_weight`` (None: 4 N) the point proposes ``x + F z`` with F F^T = scale^2 2.38^2 / N
+        (S / W + ridge diag(step^2)) (``surfdisp_mcmc_adapt_device`` -> ``surfdisp_mcmc_cov_factor_device``; a matrix that cannot be
+        factored: the reference's steps, counted).  Until a point first refactors it proposes with the factor given by
+        ``set_proposal`` before this call, or with diag(spec.step) through the same kernel.  ``until=None``: ``chainL // 2``.
+        On the speculative path an update that falls due inside a tree call happens once, at the call's end; with chain groups the
+        groups join for the update and fork again.
+
+        WHAT IS A SAMPLE.  While the proposal adapts the chain is not a Markov chain with the posterior as its fixed distribution:
+        the rows before ``until`` are adaptation (burn-in) and no valid sample.  From row ``until`` on the factor is frozen, and the
+        rows come from a fixed Metropolis kernel as with ``set_proposal``.
+
+        Needs the fused path and the ``isgood`` conditions of ``set_proposal`` (ValueError otherwise, and in ``run_graphed``).  Any
+        model the sampler runs qualifies - a thermal layer, H/V data, models without rules.  ``set_adaptive(None)`` and
+        ``set_proposal(None)`` turn it off: the sampler then launches the kernels and draws the numbers it did before.
+        ``adaptation()`` reports; the state is reset at the start of every run."""
+        if chains_per_point is None:
+            self._adapt = None
+            return
+        N = self.spec.n
+        if N > COV_MAX_N:
+            raise ValueError(f"set_adaptive: {N} random-walk parameters, the kernel takes at most {COV_MAX_N}")
+        if int(chains_per_point) < 1:
+            raise ValueError("set_adaptive: chains_per_point >= 1 expected")
+        if int(every) < 1 or int(start) < 0:
+            raise ValueError("set_adaptive: every >= 1 and start >= 0 expected")
+        if until is not None and int(until) <= int(start):
+            raise ValueError("set_adaptive: until > start expected (None: half of the chain)")
+        lo, hi = (float(b) for b in log_scale_bounds)
+        if not (0.0 < float(forget) <= 1.0) or not float(ridge) >= 0.0 or not lo <= hi or not float(target_accept) <= 1.0:
+            raise ValueError("set_adaptive: 0 < forget <= 1, ridge >= 0, log_scale_bounds (lo <= hi) and target_accept <= 1 expected")
+        mw = 4.0 * N if min_weight is None else float(min_weight)
+        if not mw >= 1.0:
+            raise ValueError("set_adaptive: min_weight >= 1 expected")
+        self._require_cov_path("set_adaptive")
+        self._adapt = dict(cpp=int(chains_per_point), every=int(every), start=int(start), until=None if until is None else int(until),
+                           forget=float(forget), target_accept=float(target_accept), gain=float(gain), decay=float(decay),
+                           min_weight=mw, ridge=float(ridge), ls_min=lo, ls_max=hi)
+
+    def adaptation(self):
+        """The adaptation of the last run, device tensors (None before the first): weight [F], mean [F, N], cov [F, N, N] (S / W,
+        symmetric), scale [F] (exp of the log scale), n_updates [F], fallbacks [F] (refactorings that kept the reference's steps),
+        factor [F, N, N] (lower triangular: the view ``cov_factor`` returns, of the factors the chains proposed with last)."""
+        torch = self.torch
+        run = self._adapt_run
+        if run is None:
+            return None
+        v = adapt_state_views(run["state"], self.spec.n)
+        S = torch.triu(v["scatter"])
+        S = S + torch.triu(S, 1).transpose(1, 2)
+        return dict(weight=v["weight"], mean=v["mean"], cov=S / v["weight"][:, None, None], scale=torch.exp(v["log_scale"]),
+                    n_updates=v["n_updates"].to(torch.int64), fallbacks=v["fallbacks"].to(torch.int64),
+                    factor=run["factor_t"].transpose(1, 2))
+
+    def _adapt_begin(self, C, chainL):
+        """The fresh adaptation of a run of C chains x chainL rows: state, covariance and flag buffers, and the working factors - a
+        copy of ``set_proposal``'s, or diag(spec.step) - which take the place of ``_prop`` until ``_adapt_end``."""
+        torch = self.torch
+        ad, N = self._adapt, self.spec.n
+        if C % ad["cpp"]:
+            raise ValueError(f"run: {C} chains are no whole number of points of {ad['cpp']} chains (set_adaptive)")
+        F = C // ad["cpp"]
+        given = self._prop
+        if given is None:
+            ft = torch.diag(self.proposer.step.to(torch.float64)).expand(F, N, N).contiguous()
+        elif given["F"] == 1:
+            ft = given["factor_t"].expand(F, N, N).contiguous()
+        elif given["F"] == F and given["cpf"] == ad["cpp"]:
+            ft = given["factor_t"].clone()
+        else:
+            raise ValueError(f"run: set_proposal gave {given['F']} factors for {given['cpf']} chains each, set_adaptive expects "
+                             f"{F} points of {ad['cpp']} chains")
+        until = chainL // 2 if ad["until"] is None else ad["until"]
+        self._adapt_run = dict(state=torch.zeros((F, adapt_state_len(N)), dtype=torch.float64, device=self.device),
+                               cov=torch.zeros((F, N, N), dtype=torch.float64, device=self.device),
+                               flag=torch.zeros(F, dtype=torch.int32, device=self.device), factor_t=ft, F=F, until=until,
+                               weight=0.0, prev=None, given=given, refactors=0)
+        self._prop = dict(factor_t=ft, cpf=ad["cpp"], F=F)
+
+    def _adapt_end(self):
+        if self._adapt_run is not None and "given" in self._adapt_run:
+            self._prop = self._adapt_run.pop("given")
+
+    def _adapt_due(self, lo, hi):
+        """Whether an update instant lies among the steps lo .. hi - 1."""
+        ad, run = self._adapt, self._adapt_run
+        a, b = max(lo, ad["start"]), min(hi, run["until"])
+        if a >= b:
+            return False
+        first = a + (-(a - ad["start"])) % ad["every"]             # the first instant >= a
+        return first < b
+
+    def _adapt_update(self, p, track, chain_stride, row_stride, i):
+        """The update after step i (the current stream; every group joined): the window is the rows since the previous update - at
+        the first one max(1, i - every + 1) .. i, so that row 0, accepted by construction, never counts -, then the factors of all
+        points once their weight - the same on every point, followed on the host - has reached ``min_weight``."""
+        torch = self.torch
+        ad, run, N = self._adapt, self._adapt_run, self.spec.n
+        lo = max(1, i - ad["every"] + 1) if run["prev"] is None else run["prev"] + 1
+        run["prev"] = i
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        step = self.proposer.step
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().surfdisp_mcmc_adapt_device(
+                stream, run["F"], ad["cpp"], N, _ptr(p), _ptr(track), int(chain_stride), int(row_stride), int(lo), int(i) + 1, _ptr(step),
+                ad["forget"], ad["target_accept"], ad["gain"], ad["decay"], ad["ls_min"], ad["ls_max"], ad["min_weight"], ad["ridge"],
+                _ptr(run["state"]), _ptr(run["cov"])))
+            w = run["weight"] * ad["forget"]                       # the kernel's own arithmetic: W is this number on every point
+            for _ in range(ad["cpp"]):
+                w += 1.0
+            run["weight"] = w
+            if w >= ad["min_weight"]:
+                _lib.check(_lib.lib().surfdisp_mcmc_cov_factor_device(stream, run["F"], N, _ptr(run["cov"]), ctypes.c_double(1.0), _ptr(step),
+                                                                      _ptr(run["factor_t"]), _ptr(run["flag"])))
+                run["state"][:, 3] += run["flag"]
+                run["refactors"] += 1
 
     def _propose_cov(self, stream, p, out, depth, counter, st):
         """The proposal tree ``out`` [C, 2^depth - 1, N] (depth 1: [C, N]) of the states ``p`` with the factors of ``set_proposal``,
@@ -866,9 +1075,22 @@ class MetropolisBatch:
         ``groups``: chain groups of the fused path (``chain_groups``; every chain's random numbers do not depend on it).
         ``start``: a float64 tensor [n_chains, N] of rows the chains start from instead of ``v0`` / prior draws - row 0 of every
         chain is that model, accepted, as today (e.g. the fitted rows of ``ParamLsqBatch``).  Rows outside the open prior box or
-        breaking ``isgood`` raise ValueError before anything is launched (one host synchronisation, outside the stepping loop)."""
+        breaking ``isgood`` raise ValueError before anything is launched (one host synchronisation, outside the stepping loop).
+        With ``set_adaptive`` the run carries the adaptation (fused path only; ``n_chains`` a whole number of points): its rows
+        before ``until`` are adaptation and no valid samples, the rows from ``until`` on come from a fixed Metropolis kernel."""
         torch = self.torch
         C, N = int(n_chains), self.spec.n
+        if self._adapt is not None and not self._adapting:
+            # adaptive proposals: the run itself, between _adapt_begin (the working factors stand in for _prop) and _adapt_end
+            if priori or fused is False or not self.fused_available():
+                raise ValueError("run: adaptive proposals (set_adaptive) are drawn by the fused path only; set_adaptive(None) for the torch loop")
+            self._adapt_begin(C, int(chainL))
+            self._adapting = True
+            try:
+                return self.run(n_chains, chainL, init_first, priori, _init_mask, spec_depth, fused, groups, start, _start_mask)
+            finally:
+                self._adapting = False
+                self._adapt_end()
         if start is not None:
             start = self._checked_start(start, C, _start_mask)
         if fused is None:
@@ -878,6 +1100,7 @@ class MetropolisBatch:
             raise ValueError("fused=True needs the device proposer, no isgood callback (or a PriorRules one) and the HIP forward path")
         if self._prop is not None and not fused:
             raise ValueError("run: a proposal factor (set_proposal) is drawn by the fused path only; set_proposal(None) for the torch loop")
+        adapting = self._adapt is not None and self._adapting
         if spec_depth is None:
             spec_depth = self.auto_spec_depth(C) if (fused and groups in (None, 1)) else 1
         spec_depth = int(spec_depth)
@@ -898,12 +1121,16 @@ class MetropolisBatch:
                 if spec_depth > 4:
                     raise ValueError("spec_depth of the fused path is at most 4")
                 self.fused_step(p, row=track, row_stride=stride, row_offset=0, first=True, counter=base + 1)
+                if adapting and self._adapt_due(0, 1):
+                    self._adapt_update(p, track, stride, 3 + N, 0)
                 i, n = 1, 1
                 while i < chainL:
                     ns = min(spec_depth, chainL - i)
                     n += 1
                     self.fused_tree_step(p, spec_depth, ns, row=track, row_stride=stride, row_offset=i * (3 + N),
                                          step_stride=3 + N, counter=base + n)
+                    if adapting and self._adapt_due(i, i + ns):    # once, at the call's end, with the window up to its last row
+                        self._adapt_update(p, track, stride, 3 + N, i + ns - 1)
                     i += ns
                 self._counter = base + n
                 return track
@@ -914,6 +1141,12 @@ class MetropolisBatch:
                     cg.step(p, row=track, row_stride=stride, row_offset=i * (3 + N), first=(i == 0), counter=base + i + 1)
                 else:
                     self.fused_step(p, row=track, row_stride=stride, row_offset=i * (3 + N), first=(i == 0), counter=base + i + 1)
+                if adapting and self._adapt_due(i, i + 1):
+                    if cg is not None:                             # the chains of a point may straddle two groups
+                        cg.join()
+                    self._adapt_update(p, track, stride, 3 + N, i)
+                    if cg is not None:
+                        cg.fork()
             if cg is not None:
                 cg.join()
             self._counter = base + chainL
@@ -1024,8 +1257,12 @@ class MetropolisBatch:
         every point starts at the initial model, the others at prior draws (point.py:95-99).
         ``start``: float64 [n_points, N] - chain k = 0 of a point starts at its row instead, the others at prior draws as now - or
         [n_points, chains_per_point, N] for all chains (checked as ``run(start=)`` checks its rows).
+        With ``set_adaptive`` the chains of a point pool their states (``chains_per_point`` must be the one given there: ValueError);
+        every chain's rows before ``until`` are adaptation and no valid samples.
         Returns float64 [n_points, chains_per_point, chainL, 3+N] (numpy, or the device tensor)."""
         torch = self.torch
+        if self._adapt is not None and int(chains_per_point) != self._adapt["cpp"]:
+            raise ValueError(f"run_points: {chains_per_point} chains per point, set_adaptive was given chains_per_point = {self._adapt['cpp']}")
         C = n_points * chains_per_point
         first = (torch.arange(C, device=self.device) % chains_per_point) == 0
         if start is not None:
@@ -1086,6 +1323,8 @@ class MetropolisBatch:
         for all practical purposes.  Random numbers come from torch's default device generator
         (graph-safe Philox)."""
         torch = self.torch
+        if self._adapt is not None:
+            raise ValueError("run_graphed: adaptive proposals (set_adaptive) are not supported: the update instants are placed by run()")
         if self.joint is not None:
             raise ValueError("run_graphed: joint data (data=) are not supported; use run()")
         if self.isgood is not None or not self.fused_available():

@@ -75,7 +75,8 @@ class Point:
         return float(mis[0]), float(chi[0]), float(L[0])
 
     def MCinvMP(self, outdir="MCtest", pid=None, runN=50000, chainL=1000, nprocess=None, seed=42,
-                priori=False, isgood=None, verbose=True, spec_depth=None, independent=False, fast_scan=False, proposal=None):
+                priori=False, isgood=None, verbose=True, spec_depth=None, independent=False, fast_scan=False, proposal=None,
+                adaptive=None):
         """``runN // chainL`` chains of ``chainL`` steps each, the first one started at the initial model
         (point.py:91-125); writes ``{outdir}/{pid}.npz`` and returns the mcTrack array [runN, 3 + N].
         ``independent="auto"``: the period-parallel root search while the chains are too few to fill the chip (3 x faster
@@ -84,9 +85,14 @@ class Point:
         batched solve for up to 136 chains, three up to 292, same chain distribution; ``MetropolisBatch.auto_spec_depth``), 1 = one step per solve.
         ``proposal="laplace"``: the point is first fitted by least squares (``paramlsq.ParamLsqBatch``, 8 iterations, on the same data
         and with ``isgood`` when it is a ``PriorRules``; a thermal model: its ValueError), the first chain starts at the fitted model
-        and all chains propose with the factor of its Laplace covariance (``MetropolisBatch.set_proposal``)."""
-        if proposal not in (None, "laplace"):
-            raise ValueError("MCinvMP: proposal must be None or 'laplace'")
+        and all chains propose with the factor of its Laplace covariance (``MetropolisBatch.set_proposal``).
+        ``proposal="adaptive"``: adaptive Metropolis pooled over the point's chains (``MetropolisBatch.set_adaptive``; ``adaptive``: a
+        dict of its options) - any model, a thermal one included; the rows of every chain before ``until`` (default: its first half)
+        are adaptation, no valid samples."""
+        if proposal not in (None, "laplace", "adaptive"):
+            raise ValueError("MCinvMP: proposal must be None, 'laplace' or 'adaptive'")
+        if adaptive is not None and proposal != "adaptive":
+            raise ValueError("MCinvMP: adaptive= holds the options of proposal='adaptive'")
         if proposal is not None and priori:
             raise ValueError("MCinvMP: a priori run evaluates no data, so there is nothing to fit: proposal=None expected")
         if priori and outdir.split("_")[-1] != "priori":
@@ -104,6 +110,9 @@ class Point:
             row = fit.run(8)["params"]
             mc.set_proposal(fit.proposal_factor()["factor"][0].contiguous())
             track = mc.run_points(1, nch, int(chainL), on_device=True, spec_depth=spec_depth, start=row)[0]
+        elif proposal == "adaptive":
+            mc.set_adaptive(nch, **(adaptive or {}))
+            track = mc.run_points(1, nch, int(chainL), on_device=True, spec_depth=spec_depth)[0]
         else:
             track = mc.run(nch, int(chainL), init_first=True, priori=priori, spec_depth=spec_depth)
         arr = track.cpu().numpy().reshape(-1, track.shape[-1])

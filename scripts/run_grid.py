@@ -41,9 +41,14 @@ def main():
     ap.add_argument("--chain-groups", type=int, default=None, help="chain groups per rank (default: 2 from 4 096 chains on)")
     ap.add_argument("--spec-depth", type=int, default=None, help="Metropolis steps per batched solve (default: 4 / 3 / 2 for up to "
                                                                  "136 / 292 / 682 chains per rank, else 1)")
-    ap.add_argument("--proposal", choices=["laplace"], default=None,
+    ap.add_argument("--proposal", choices=["laplace", "adaptive"], default=None,
                     help="laplace: fit every point by least squares first (pysurfinv_amd.paramlsq), start chain 0 of the point at the fitted "
-                         "model and propose with the Cholesky factor of its Laplace covariance (default: the reference's independent steps)")
+                         "model and propose with the Cholesky factor of its Laplace covariance; adaptive: adaptive Metropolis pooled over "
+                         "the chains of every point (MetropolisBatch.set_adaptive: any model, a thermal one included; the rows before "
+                         "'until', by default the first half of every chain, are adaptation and no valid samples) "
+                         "(default: the reference's independent steps)")
+    ap.add_argument("--adaptive", default=None, help="JSON object of set_adaptive's options for --proposal adaptive, "
+                                                     "e.g. '{\"every\": 10, \"start\": 20}'")
     ap.add_argument("--lsq-iters", type=int, default=8, help="iterations of that fit")
     args = ap.parse_args()
 
@@ -83,7 +88,8 @@ def main():
     r = grid.run_grid(mb, lons, lats, periods, c_obs, uncer, args.chains, args.chainL, outdir=args.outdir,
                       rank=rank, world=world, device=str(dev), seed=args.seed, fast_scan=args.fast_scan, keep_tracks=False,
                       local_info=local_info, chain_groups=args.chain_groups, spec_depth=args.spec_depth,
-                      proposal=args.proposal, lsq_iters=args.lsq_iters)
+                      proposal=args.proposal, lsq_iters=args.lsq_iters,
+                      adaptive=json.loads(args.adaptive) if args.adaptive else None)
     if rank == 0:
         os.makedirs(args.outdir, exist_ok=True)
         np.savez_compressed(os.path.join(args.outdir, "summaries.npz"), summaries=r["summaries"], columns=np.array(r["columns"]),

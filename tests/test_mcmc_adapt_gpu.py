@@ -1,0 +1,326 @@
+"""Adaptive proposals on the device: surfdisp_mcmc_adapt_device against its numpy statement (``mcmc.adapt_reference``), the update
+instants, windows and chain groups of ``MetropolisBatch.set_adaptive`` against the same statement fed from the tracks, the factor
+the chains propose with against the host replay of the propose kernel (tests/mcmc_cov_replay.py), a thermal model, the off
+switches, and the public routes ``run_grid(proposal="adaptive")`` / ``Point.MCinvMP(proposal="adaptive")``."""
+import ctypes
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mcmc_cov_replay as CR                         # noqa: E402
+from test_mcmc_replay import _bits, _dev, _ptr       # noqa: E402
+from test_prior_redraw import _cpu_model             # noqa: E402
+
+from pysurfinv_amd import _lib, settings             # noqa: E402
+from pysurfinv_amd.mcmc import (MetropolisBatch, PriorRules, adapt_cov_formula, adapt_reference, adapt_state_len,   # noqa: E402
+                                adapt_state_views, cov_factor, cov_factor_reference)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+U53 = 2.0 ** -53
+
+
+def _full(S):
+    S = np.triu(S)
+    return S + np.transpose(np.triu(S, 1), (0, 2, 1))
+
+
+def _moment_bars(dev_state, ref_state, N, n, xmax, what):
+    """The bars of the entry's moments after n samples per point: |S_dev - S_ref|[k][n] <= 8 n 2^-53 sqrt(S_kk S_nn) + 1e-300 (4
+    roundings per sample per entry, doubled for FMA contraction), the mean the same against max |x|; W and k exactly; ls exactly."""
+    d, r = adapt_state_views(dev_state, N), adapt_state_views(ref_state, N)
+    dg = np.einsum("fii->fi", r["scatter"])
+    bar = 8 * n * U53 * np.sqrt(dg[:, :, None] * dg[:, None, :]) + 1e-300
+    errS = np.abs(np.triu(d["scatter"]) - np.triu(r["scatter"]))
+    errm = np.abs(d["mean"] - r["mean"])
+    ulp_ls = np.abs(d["log_scale"] - r["log_scale"]) / (2 * U53 * np.maximum(np.abs(r["log_scale"]), 1e-300))
+    print(f"{what}: S worst {float((errS / bar).max()):.3f} of its bar, mean worst {float(errm.max() / (8 * n * U53 * xmax)):.3f} of its bar, "
+          f"ls differs by {float(ulp_ls.max()):.1f} ulp")
+    assert (errS <= bar).all(), what
+    assert (errm <= 8 * n * U53 * xmax).all(), what
+    assert np.array_equal(d["weight"], r["weight"]) and np.array_equal(d["n_updates"], r["n_updates"]), what
+    assert np.array_equal(d["ready"], r["ready"]) and np.array_equal(d["fallbacks"], r["fallbacks"]), what
+    assert np.array_equal(_bits(d["log_scale"]), _bits(r["log_scale"])), what
+
+
+# ------------------------------------------------------------------------------------------------------ the entry
+@pytest.mark.parametrize("F,cpp,N", [(1, 1, 1), (3, 2, 13), (5, 7, 5), (2, 100, 64)])
+def test_entry_is_the_numpy_statement(F, cpp, N):
+    """Three consecutive updates carrying the state, forget = 0.9, states in a box of width 1 around 3.5; one scalar constant with
+    step 0 (N > 1), the last point's chains identical; accept windows of 0, 1 and 6 rows in a track whose strides are not the
+    packed ones; min_weight = 1.5 cpp: the first update is below it (cov_out untouched), the others write."""
+    rng = np.random.default_rng(100 * F + N)
+    rows, width = 8, 3 + N
+    chain_stride, row_stride = rows * (width + 2) + 3, width + 2
+    track = rng.uniform(2.0, 3.0, F * cpp * chain_stride + 8)          # (column 2 is set below; the rest is never read)
+    flags = (rng.uniform(size=(F, cpp, rows)) < 0.4).astype(np.float64)
+    for c in range(F * cpp):
+        track[c * chain_stride + np.arange(rows) * row_stride + 2] = flags[c // cpp, c % cpp]
+    step = rng.uniform(0.01, 0.1, N)
+    const = 1 if N > 1 else None
+    if const is not None:
+        step[const] = 0.0
+    opts = dict(forget=0.9, target_accept=0.25, gain=1.0, decay=0.6, min_weight=1.5 * cpp, ridge=1e-3, log_scale_bounds=(-3.0, 3.0))
+    windows = [(2, 2), (3, 4), (1, 7)]
+    L = _lib.lib()
+    dstate = torch.zeros((F, adapt_state_len(N)), dtype=torch.float64, device=DEV)
+    dcov = torch.full((F, N, N), float("nan"), dtype=torch.float64, device=DEV)
+    dtrack, dstep = _dev(track), _dev(step)
+    ref, same = None, None
+    for t, (lo, hi) in enumerate(windows):
+        x = 3.5 + rng.uniform(-0.5, 0.5, (F, cpp, N))
+        if const is not None:
+            x[:, :, const] = 3.25
+        same = x[F - 1, 0].copy() if t == 0 else same                  # the last point: every chain at one state, in every update
+        x[F - 1] = same
+        dp = _dev(x.reshape(F * cpp, N))
+        _lib.check(L.surfdisp_mcmc_adapt_device(None, F, cpp, N, _ptr(dp), _ptr(dtrack), chain_stride, row_stride, lo, hi, _ptr(dstep),
+                                                opts["forget"], opts["target_accept"], opts["gain"], opts["decay"], -3.0, 3.0,
+                                                opts["min_weight"], opts["ridge"], _ptr(dstate), _ptr(dcov)))
+        torch.cuda.synchronize()
+        ref, rc = adapt_reference(ref, x, flags[:, :, lo:hi], step, **opts)
+        st, cov = dstate.cpu().numpy(), dcov.cpu().numpy()
+        what = f"F {F} cpp {cpp} N {N} update {t}"
+        _moment_bars(st, ref, N, (t + 1) * cpp, 4.0, what)
+        v = adapt_state_views(st, N)
+        if t == 0:
+            assert rc is None and np.isnan(cov).all() and (v["ready"] == 0).all() and (v["n_updates"] == 0).all(), what
+            continue
+        assert rc is not None and (v["ready"] == 1).all() and (v["n_updates"] == t).all(), what
+        want = adapt_cov_formula(v["scatter"], v["weight"], v["log_scale"], step, opts["ridge"])   # on the DEVICE's S, W and ls
+        assert (np.abs(cov - want) <= 4 * 2 * U53 * np.abs(want)).all(), what
+        assert np.array_equal(_bits(cov), _bits(np.transpose(cov, (0, 2, 1)))), what
+        if const is not None:
+            assert not cov[:, const, :].any() and not cov[:, :, const].any(), what
+        assert not np.tril(cov[F - 1], -1).any() and (np.diagonal(cov[F - 1])[step > 0] > 0).all(), what   # identical chains: the ridge alone
+        r = cov_factor(dcov, 1.0, step)
+        torch.cuda.synchronize()
+        Lf, flag = r["factor"].cpu().numpy(), r["flag"].cpu().numpy()
+        Lr, rflag = cov_factor_reference(cov, 1.0, step)
+        assert not flag.any() and not rflag.any(), what
+        for p in range(F):
+            assert np.abs(Lf[p] - Lr[p]).max() <= 64 * CR.EPS * N * np.abs(Lr[p]).max(), what
+            assert np.abs(Lf[p] @ Lf[p].T - cov[p]).max() <= 64 * CR.EPS * N * np.abs(cov[p]).max(), what
+
+
+# ------------------------------------------------------------------------------------------------------ the sampler
+NPTS, CPP, CHAINL = 3, 5, 40
+OPTS = dict(every=5, start=10, until=30, min_weight=10.0)              # 5 chains: the weight reaches 10 at the second update
+TEAM = 4                                                               # lanes per stack, fixed: a stack's result does not depend on its place in the batch
+
+
+@functools.lru_cache(maxsize=None)
+def _data():
+    mb, c_obs, unc = settings.synthetic_observations(NPTS, torch.device(DEV))
+    return mb, c_obs, unc, PriorRules(mb)
+
+
+def _sampler(seed=3):
+    mb, c_obs, unc, rules = _data()
+    return MetropolisBatch(mb.spec, mb.to_model, settings.MCMC_PERIODS, np.repeat(c_obs, CPP, axis=0), np.repeat(unc, CPP, axis=0),
+                           device=torch.device(DEV), seed=seed, isgood=rules)
+
+
+@functools.lru_cache(maxsize=None)
+def _run(groups=1, spec_depth=1, until=30, adaptive=True, proposal=None):
+    """One run under the fixed team size -> (track [NPTS, CPP, CHAINL, 3 + N] numpy, adaptation as numpy, the raw state, seed)."""
+    L = _lib.lib()
+    mc = _sampler()
+    if proposal == "diag":
+        mc.set_proposal(torch.diag(mc.proposer.step))
+    if adaptive:
+        mc.set_adaptive(CPP, **dict(OPTS, until=until))
+    assert L.surfdisp_set_team(TEAM) == 0
+    try:
+        tr = mc.run_points(NPTS, CPP, CHAINL, on_device=True, groups=groups, spec_depth=spec_depth)
+        torch.cuda.synchronize()
+    finally:
+        L.surfdisp_set_team(0)
+    assert (mc._last_groups is not None) == (groups == 2)
+    ad = mc.adaptation()
+    ad = None if ad is None else {k: v.cpu().numpy() for k, v in ad.items()}
+    state = None if ad is None else mc._adapt_run["state"].cpu().numpy()
+    assert mc.prior_exhausted() == 0 and (not adaptive or mc._prop is None)      # (the working factors left with the run)
+    return tr.cpu().numpy(), ad, state, mc.proposer.seed_int
+
+
+def _states(tr, i):
+    """The chains' states after step i, [NPTS, CPP, N]: the parameters of the last accepted row up to i (row 0 is accepted)."""
+    acc = tr[:, :, :i + 1, 2] > 0.5
+    assert acc[:, :, 0].all()
+    last = np.where(acc, np.arange(i + 1), 0).max(axis=2)
+    return np.take_along_axis(tr[..., 3:], last[:, :, None, None], axis=2)[:, :, 0]
+
+
+def _instants(spec_depth, until=30):
+    """[(row whose states are fed, window lo, window hi)] of the run: the instants start, start + every, ... < until; on the
+    speculative path (row 0, then spec_depth rows per call) an update happens once at the end of the call it falls in."""
+    due = [i for i in range(CHAINL) if OPTS["start"] <= i < until and (i - OPTS["start"]) % OPTS["every"] == 0]
+    if spec_depth > 1:
+        ends = []
+        for i in due:
+            end = min(((i - 1) // spec_depth) * spec_depth + spec_depth, CHAINL - 1) if i > 0 else 0
+            if end not in ends:
+                ends.append(end)
+        due = ends
+    out, prev = [], None
+    for i in due:
+        out.append((i, max(1, i - OPTS["every"] + 1) if prev is None else prev + 1, i + 1))
+        prev = i
+    return out
+
+
+def _replayed_state(tr, spec_depth, until=30):
+    mb = _data()[0]
+    ref = None
+    for i, lo, hi in _instants(spec_depth, until):
+        ref, _ = adapt_reference(ref, _states(tr, i), tr[:, :, lo:hi, 2], mb.spec.step, min_weight=OPTS["min_weight"])
+    return ref
+
+
+@pytest.mark.parametrize("groups,spec_depth", [(1, 1), (2, 1), (1, 3)])
+def test_updates_follow_the_tracks(groups, spec_depth):
+    """The device's adaptation at the end of the run against adapt_reference fed with the states and accept windows rebuilt from the
+    track at the update instants.  C = 15 in two groups: the bound at 7 splits point 1."""
+    tr, ad, state, _ = _run(groups, spec_depth)
+    N = tr.shape[-1] - 3
+    inst = _instants(spec_depth)
+    assert len(inst) == 4 and (ad["n_updates"] == 4).all() and np.isfinite(tr).all()
+    if spec_depth == 3:
+        assert [i for i, _, _ in inst] == [12, 15, 21, 27] and inst[0][1:] == (8, 13) and inst[2][1:] == (16, 22)
+    else:
+        assert [i for i, _, _ in inst] == [10, 15, 20, 25] and inst[0][1:] == (6, 11) and inst[1][1:] == (11, 16)
+    ref = _replayed_state(tr, spec_depth)
+    _moment_bars(state, ref, N, 4 * CPP, float(np.abs(tr[..., 3:]).max()), f"groups {groups} depth {spec_depth}")
+    r = adapt_state_views(ref, N)
+    assert np.array_equal(ad["weight"], r["weight"]) and (ad["weight"] == 4 * CPP).all() and (ad["fallbacks"] == 0).all()
+    assert np.abs(ad["scale"] - np.exp(r["log_scale"])).max() <= 4 * 2 * U53 * np.exp(r["log_scale"]).max()
+    cov_ref = _full(r["scatter"]) / r["weight"][:, None, None]
+    dg = np.einsum("fii->fi", cov_ref)
+    assert (np.abs(ad["cov"] - cov_ref) <= (8 * 4 * CPP + 2) * U53 * np.sqrt(dg[:, :, None] * dg[:, None, :]) + 1e-300).all()
+    assert not np.triu(ad["factor"], 1).any() and (np.einsum("fii->fi", ad["factor"]) > 0).all()
+    acc = tr[:, :, 1:, 2]
+    assert 0 < acc.mean() < 1
+
+
+def test_chain_groups_do_not_change_the_adapted_tracks():
+    """Under the fixed team size one and two chain groups write the same tracks and reach the same adaptation."""
+    one, two = _run(1, 1), _run(2, 1)
+    assert np.array_equal(_bits(one[0]), _bits(two[0])) and np.array_equal(_bits(one[2]), _bits(two[2]))
+    assert np.array_equal(_bits(one[1]["factor"]), _bits(two[1]["factor"]))
+
+
+def test_the_factor_is_the_one_used():
+    """The rows between the first refactoring (after step 15) and the next update (after step 20): a run frozen at until = 16 ends
+    with that factor and writes the same rows; replayed on the host from the states rebuilt from the track, with the device's
+    factor, the proposed parameters are the track's - the comparison of tests/test_mcmc_cov_gpu.py::_compare, whose `tries` the track
+    does not carry (a different try is another draw, far outside the bound); at most CR.MAX_EXCLUDED of the cases doubtful."""
+    tr, _, _, seed = _run(1, 1)
+    frozen, ad, state, _ = _run(1, 1, until=16)
+    assert (ad["n_updates"] == 2).all() and np.array_equal(_bits(tr[:, :, :21]), _bits(frozen[:, :, :21]))
+    assert not np.array_equal(_bits(tr[:, :, 21:]), _bits(frozen[:, :, 21:]))                   # (the main run refactors again)
+    mb = _data()[0]
+    N = mb.spec.n
+    diag = np.broadcast_to(np.diag(mb.spec.step), (NPTS, N, N))
+    assert np.abs(ad["factor"] - diag).max() > 0.1 * mb.spec.step.min()                          # not the start's diag(step)
+    rules = PriorRules(_cpu_model())
+    n_doubt, n_all, worst = 0, 0, 0.0
+    for i in range(16, 21):
+        p = _states(tr, i - 1).reshape(NPTS * CPP, N)
+        out, tries, margin, tol, slack = CR.propose_cov(p, mb.spec.vmin, mb.spec.vmax, ad["factor"], CPP, rules, seed, i + 1, 1,
+                                                        rules.gauss_tries, rules.uniform_tries)
+        keep = ~CR.doubtful(margin, slack)
+        err = np.abs(tr[:, :, i, 3:].reshape(NPTS * CPP, 1, N) - out)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = np.where(tol > 0, err / tol, np.where(err == 0, 0.0, np.inf))
+        n_doubt, n_all = n_doubt + int((~keep).sum()), n_all + keep.size
+        worst = max(worst, float(rel[keep].max()))
+    print(f"rows 16 .. 20: worst difference {worst:.4f} of the bound, {n_doubt} of {n_all} (chain, row) doubtful")
+    assert n_doubt <= CR.MAX_EXCLUDED * n_all
+    assert worst <= 1.0
+    # before the first refactoring the chains propose with diag(step) through the same kernel
+    p = _states(tr, 11).reshape(NPTS * CPP, N)
+    out, tries, margin, tol, slack = CR.propose_cov(p, mb.spec.vmin, mb.spec.vmax, diag, CPP, rules, seed, 13, 1, rules.gauss_tries,
+                                                    rules.uniform_tries)
+    keep = ~CR.doubtful(margin, slack)
+    assert int((~keep).sum()) <= CR.MAX_EXCLUDED * keep.size
+    assert (np.abs(tr[:, :, 12, 3:].reshape(NPTS * CPP, 1, N) - out)[keep] <= tol[keep]).all()
+
+
+def test_off_means_off():
+    """After set_adaptive(None) the tracks are, bit for bit, those of a sampler never given adaptation; with until at the first
+    refactoring's instant no point ever refactors and the tracks are those of set_proposal(diag(step))."""
+    plain = _run(adaptive=False)[0]
+    mc = _sampler()
+    mc.set_adaptive(CPP, **OPTS)
+    mc.set_adaptive(None)
+    L = _lib.lib()
+    assert L.surfdisp_set_team(TEAM) == 0
+    try:
+        again = mc.run_points(NPTS, CPP, CHAINL, on_device=True).cpu().numpy()
+    finally:
+        L.surfdisp_set_team(0)
+    assert mc._adapt is None and mc.adaptation() is None and np.array_equal(_bits(again), _bits(plain))
+    never, ad, _, _ = _run(until=15)                                    # updates after steps 10 only: weight 5 < min_weight
+    assert (ad["n_updates"] == 1).all() and (ad["weight"] == CPP).all()
+    diag = _run(adaptive=False, proposal="diag")[0]
+    assert np.array_equal(_bits(never), _bits(diag)) and not np.array_equal(_bits(never), _bits(plain))
+
+
+def test_thermal_model():
+    """C5_SETTING (an OceanMantleHybrid layer, which the Laplace route refuses): the run completes, every update happens, every
+    proposed row lies strictly inside the box, no refactoring falls back, the tracks are finite.  8 chains without rules take the
+    speculative path at depth 4 (row 0, then the calls 1-4, 5-8, ...): the instants 6 | 9, 12 | 15 | 18 fall into four calls."""
+    dev = torch.device(DEV)
+    mb, c_obs, unc = settings.synthetic_observations(2, dev, setting=settings.C5_SETTING)
+    assert mb._native_thermal
+    cpp, chainL = 4, 30
+    mc = MetropolisBatch(mb.spec, mb.to_model, settings.MCMC_PERIODS, np.repeat(c_obs, cpp, axis=0), np.repeat(unc, cpp, axis=0),
+                         device=dev, seed=3)
+    mc.set_adaptive(cpp, every=3, start=6, until=20, min_weight=8.0)
+    tr = mc.run_points(2, cpp, chainL, on_device=True)
+    torch.cuda.synchronize()
+    ad = mc.adaptation()
+    assert mc.auto_spec_depth(2 * cpp) == 4
+    assert ad["n_updates"].cpu().tolist() == [4, 4] and ad["fallbacks"].cpu().tolist() == [0, 0]     # at the rows 8, 12, 16, 20
+    tr = tr.cpu().numpy()
+    par = tr[..., 3:]
+    assert np.isfinite(tr).all() and ((par > mb.spec.vmin) & (par < mb.spec.vmax)).all() and mc.prior_exhausted() == 0
+    assert np.isfinite(ad["factor"].cpu().numpy()).all() and float(ad["weight"].min()) == 4 * cpp
+
+
+# ------------------------------------------------------------------------------------------------------ the public routes
+def test_run_grid_with_the_adaptive_proposal(tmp_path):
+    from pysurfinv_amd import grid
+    from pysurfinv_amd.point import PostPoint
+    mb, c_obs, unc, rules = _data()
+    lons, lats = 230.0 + np.arange(NPTS), np.full(NPTS, 45.0)
+    r = grid.run_grid(mb, lons, lats, settings.MCMC_PERIODS, c_obs, unc, CPP, CHAINL, outdir=str(tmp_path), device=DEV, seed=1,
+                      isgood=rules, proposal="adaptive", adaptive=OPTS)
+    rep = r["report"]
+    assert rep["proposal"] == "adaptive" and rep["adapt_updates"] == 4 and rep["adapt_fallbacks"] == 0 and rep["prior_exhausted"] == 0
+    assert r["mcTrack"].shape == (NPTS, CPP * CHAINL, 3 + mb.spec.n)
+    plain = grid.run_grid(mb, lons[:1], lats[:1], settings.MCMC_PERIODS, c_obs[:1], unc[:1], 2, 3, device=DEV)["report"]
+    assert plain["proposal"] is None and plain["adapt_updates"] == 0 and plain["adapt_fallbacks"] == 0
+    pp = PostPoint(str(tmp_path / f"{lons[0]}_{lats[0]}.npz"), device=DEV)
+    acc = r["mcTrack"][0][:, 2] > 0.5
+    assert pp.MC.shape == (CPP * CHAINL, 3 + mb.spec.n) and np.array_equal(pp.MC[:, :3], r["mcTrack"][0][:, :3])
+    assert np.array_equal(pp.MC[acc], r["mcTrack"][0][acc]) and np.isfinite(pp.avgMod.misfit)
+
+
+def test_point_with_the_adaptive_proposal(tmp_path):
+    from pysurfinv_amd.point import Point, PostPoint
+    mb, c_obs, unc, rules = _data()
+    pt = Point(settings.MCMC_SETTING, periods=list(settings.MCMC_PERIODS), vels=list(c_obs[0]), uncers=list(unc[0]), device=DEV)
+    arr = pt.MCinvMP(outdir=str(tmp_path / "mc"), runN=8 * 30, chainL=30, seed=5, isgood=PriorRules(pt.initMod), proposal="adaptive",
+                     adaptive=dict(every=4, start=4, min_weight=16.0))
+    N = mb.spec.n
+    assert arr.shape == (8 * 30, 3 + N) and arr[0, 2] == 1
+    assert ((arr[:, 3:] > mb.spec.vmin) & (arr[:, 3:] < mb.spec.vmax)).all() and 0 < arr[:, 2].mean() < 1
+    pp = PostPoint(str(tmp_path / "mc" / "test.npz"), device=DEV)
+    assert pp.MC.shape == arr.shape and np.isfinite(pp.minMod.misfit)
