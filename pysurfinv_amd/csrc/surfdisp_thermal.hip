@@ -1,8 +1,11 @@
 // surfdisp_thermal.hip -- the thermal mantle layer of a parameters -> layer stack evaluation on the
 // device: OceanMantleHybrid (layers.py:297-363) over HSCM, OceanSeisRitz and
 // OceanSeisRuan (ThermSeis.py:56-173, 325-448).  One 64-lane workgroup per chain, lane j = grid
-// point j of the layer (at most 61 points); the result (vs, qs per grid point) goes to a scratch
-// array that surfdisp_layers_kernel reads for layers of kind 6.
+// point j of the layer; the result (vs, qs per grid point) goes to a scratch array that
+// surfdisp_layers_kernel reads for layers of kind 6.  At most 64 points: one lane, one bit of the
+// 64-bit knot ballot, one of the 64 LDS slots and one of the 64 scratch rows per point, which is what
+// Model1DBatch.native_descriptor admits (npts <= 64).  The layer rule itself (_n_fine_mantle: 5, 10,
+// 15, 30 or 60 fine layers) only ever gives 6, 11, 16, 31 or 61.
 //
 // Arithmetic is fp64 with contraction off and the operation order of pysurfinv_amd/thermseis.py
 // (the torch host mirror, itself pinned to the reference at 1e-14), so the two agree to the last
@@ -198,11 +201,17 @@ __global__ __launch_bounds__(64) void surfdisp_thermal_kernel(LayersArgs A)
     const bool keep = on && (upper || lower);
     const double yj = upper ? vs_th : pert + vs_th;
 
-    // knots to the front (merge2, layers.py:321-325)
+    // knots to the front, then the other grid points in grid order (merge2, layers.py:321-325; the stable
+    // argsort of thermseis.cubic_spline_through).  A row with fewer than two knots is the line through the
+    // first two entries of that order, so every one of the npts slots is written: nothing read below is
+    // left over from another workgroup.
     const unsigned long long mask = __ballot(keep);
-    const int n = max(__popcll(mask), 2);
-    const int ki = __popcll(mask & ((1ull << j) - 1ull));
-    if (keep) { xk[ki] = zj; yk[ki] = yj; }
+    const unsigned long long rest = __ballot(on && !keep);
+    const unsigned long long before = (1ull << j) - 1ull;
+    const int nkeep = __popcll(mask);
+    const int n = max(nkeep, 2);
+    const int ki = keep ? __popcll(mask & before) : nkeep + __popcll(rest & before);
+    if (on) { xk[ki] = zj; yk[ki] = yj; }
     __syncthreads();
 
     // knot derivatives of the not-a-knot cubic spline (thermseis.cubic_spline_through), solved by

@@ -284,13 +284,20 @@ def tridiagonal_solve(lo, di, up, rhs):
 def cubic_spline_through(x, y, keep):
     """Row-wise ``scipy.interpolate.CubicSpline(x[keep], y[keep])(x)`` (not-a-knot ends; extrapolating
     with the end pieces) - ``merge2`` of ``OceanMantleHybrid._calVs`` (layers.py:321-325).
-    x, y [B, N] (x ascending), keep bool [B, N] with at least 2 knots per row.  No host
-    synchronisation anywhere (HIP-graph capturable)."""
+    x, y [B, N] (x ascending), keep bool [B, N].  No host synchronisation anywhere (HIP-graph
+    capturable).
+
+    Rows with fewer than two knots do occur in merge2: a thin thermal layer whose top lies below the
+    melt depth and whose bottom lies above 1.7 x that depth keeps no grid point, or one.  The reference
+    raises there (``CubicSpline`` wants two points); this project continues, and its rule is: order the
+    grid points as "kept points, then the others in grid order" (the stable argsort below) and take
+    the line through the first two entries of that order.  surfdisp_thermal_kernel follows the same
+    rule (tests/test_thermal_cases_host.py, tests/test_thermal_cases_gpu.py)."""
     B, N = x.shape
     dev = x.device
     order = torch.argsort((~keep).to(torch.int8), dim=1, stable=True)
     n = keep.sum(dim=1)                                      # knots per row
-    n = n.clamp(min=2)                                       # fewer than two knots cannot occur in merge2
+    n = n.clamp(min=2)                                       # fewer than two: the first two entries of `order` (see above)
     xk = torch.gather(x, 1, order)
     yk = torch.gather(y, 1, order)
     idx = torch.arange(N, device=dev)[None, :]
