@@ -65,137 +65,10 @@ def _put_row(track, i, mis, L, acc, p):
     track[:, i, 0] = mis; track[:, i, 1] = L; track[:, i, 2] = acc; track[:, i, 3:] = p
 
 
-COV_MAX_N = 64             # scalars per chain of the covariance-shaped proposal: one lane each (SURFDISP_MCMC_COV_N_MAX)
-
-
-def cov_factor_reference(cov, scale, fallback_step):
-    """``surfdisp_mcmc_cov_factor_device`` in numpy float64: cov [P, N, N] (symmetric; zero rows and columns at fixed parameters) ->
-    (L [P, N, N] lower triangular with L L^T = scale^2 cov over the rows whose diagonal is not zero and zero rows and columns
-    elsewhere, flag [P]).  Right-looking Cholesky, the kernel's order of operations; a pivot that is not positive and finite: flag 1
-    and L = diag(fallback_step)."""
-    cov = np.asarray(cov, np.float64)
-    P, N, _ = cov.shape
-    fb = np.asarray(fallback_step, np.float64)
-    out, flag = np.zeros((P, N, N)), np.zeros(P, np.int32)
-    for p in range(P):
-        live = np.flatnonzero(np.diagonal(cov[p]) != 0.0)
-        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-            A = (float(scale) * float(scale)) * np.triu(cov[p]).T          # the kernel reads cov[k][n], k <= n, as A[n][k]
-            Lp, bad = np.zeros((N, N)), False
-            for a, j in enumerate(live):
-                d = A[j, j]
-                if not (d > 0.0 and np.isfinite(d)):
-                    bad = True
-                    break
-                s = np.sqrt(d)
-                below = live[a + 1:]
-                l = A[below, j] / s
-                Lp[j, j], Lp[below, j] = s, l
-                for b, n in enumerate(below):
-                    ks = below[:b + 1]
-                    A[n, ks] -= l[b] * l[:b + 1]
-        out[p], flag[p] = (np.diag(fb), 1) if bad else (Lp, 0)
-    return out, flag
-
-
-def cov_factor(cov, scale, fallback_step):
-    """The proposal factors of P covariances on the device (``surfdisp_mcmc_cov_factor_device``: one launch, no host
-    synchronisation): cov float64 [P, N, N] on a HIP device, ``scale`` a float, ``fallback_step`` [N] -> dict(factor [P, N, N] lower
-    triangular - a view of the kernel's transposed layout, what ``MetropolisBatch.set_proposal`` takes -, flag [P] int32: 1 where the
-    matrix could not be factored and the point got diag(fallback_step))."""
-    import torch
-    if cov.dtype != torch.float64 or cov.ndim != 3 or cov.shape[1] != cov.shape[2] or not 1 <= cov.shape[1] <= COV_MAX_N:
-        raise ValueError(f"cov_factor: float64 [P, N, N] with 1 <= N <= {COV_MAX_N} expected, got {cov.dtype} {tuple(cov.shape)}")
-    if cov.device.type != "cuda":
-        raise _lib.SurfdispError("cov_factor needs a HIP device")
-    P, N, _ = cov.shape
-    cov = cov.contiguous()
-    fb = torch.as_tensor(np.asarray(fallback_step, np.float64) if not torch.is_tensor(fallback_step) else fallback_step,
-                         dtype=torch.float64, device=cov.device).contiguous()
-    if tuple(fb.shape) != (N,):
-        raise ValueError(f"cov_factor: fallback_step ({N},) expected, got {tuple(fb.shape)}")
-    factor_t = torch.empty_like(cov)
-    flag = torch.empty(P, dtype=torch.int32, device=cov.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(cov.device).cuda_stream)
-    with torch.cuda.device(cov.device):
-        _lib.check(_lib.lib().surfdisp_mcmc_cov_factor_device(stream, P, N, _ptr(cov), ctypes.c_double(float(scale)), _ptr(fb),
-                                                              _ptr(factor_t), _ptr(flag)))
-    return dict(factor=factor_t.transpose(1, 2), flag=flag)
-
-
-ADAPT_HEAD = 8             # doubles before the mean in a point's adaptation block (SURFDISP_MCMC_ADAPT_HEAD)
-ADAPT_DEFAULTS = dict(every=10, start=20, until=None, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6, min_weight=None, ridge=1e-3,
-                      log_scale_bounds=(-3.0, 3.0))
-
-
-def adapt_state_len(N):
-    """Doubles per point of the adaptation state (include/surfdisp.h: [W, ls, k, fallbacks, wrote-cov, 0, 0, 0 | mean [N] | S [N][N]])."""
-    return ADAPT_HEAD + N + N * N
-
-
-def adapt_state_views(state, N):
-    """dict of views into a state array / tensor [F, adapt_state_len(N)]: weight, log_scale, n_updates, fallbacks, ready [F],
-    mean [F, N], scatter [F, N, N] (its upper triangle is the scatter)."""
-    F = state.shape[0]
-    return dict(weight=state[:, 0], log_scale=state[:, 1], n_updates=state[:, 2], fallbacks=state[:, 3], ready=state[:, 4],
-                mean=state[:, ADAPT_HEAD:ADAPT_HEAD + N], scatter=state[:, ADAPT_HEAD + N:].reshape(F, N, N))
-
-
-def adapt_reference(state, x, flags, step, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6, min_weight=None, ridge=1e-3,
-                    log_scale_bounds=(-3.0, 3.0), cov=None):
-    """``surfdisp_mcmc_adapt_device`` in numpy float64, in the kernel's order of operations: ``state`` [F, adapt_state_len(N)] (None:
-    the fresh state, zeros), ``x`` [F, cpp, N] the chains' states, ``flags`` [F, cpp, R] the accept flags of the window's R rows
-    (None or R = 0: an empty window), ``step`` [N] -> (state', cov): cov [F, N, N] with the points that reached ``min_weight``
-    (default 4 N) written and the others as in ``cov=`` (zeros without), or None when no point did."""
-    x = np.asarray(x, np.float64)
-    F, cpp, N = x.shape
-    step = np.asarray(step, np.float64)
-    min_weight = 4.0 * N if min_weight is None else float(min_weight)
-    st = np.zeros((F, adapt_state_len(N))) if state is None else np.array(state, np.float64)
-    v = adapt_state_views(st, N)
-    up = np.triu(np.ones((N, N), bool))
-    W = v["weight"] * float(forget)
-    S = v["scatter"] * float(forget)
-    mean = v["mean"].copy()
-    for j in range(cpp):                                               # one Welford step per chain, ascending
-        W = W + 1.0
-        d = x[:, j] - mean
-        mean = mean + d / W[:, None]
-        e = x[:, j] - mean
-        S = S + np.where(up, d[:, :, None] * e[:, None, :], 0.0)
-    ls, k = v["log_scale"].copy(), v["n_updates"].copy()
-    R = 0 if flags is None else np.asarray(flags).shape[2]
-    if target_accept >= 0.0 and R > 0:
-        cnt = (np.asarray(flags, np.float64) > 0.5).sum(axis=(1, 2))   # integers: exact, order-free
-        a = cnt.astype(np.float64) / float(cpp * R)
-        k = k + 1.0
-        g = float(gain) * np.power(k, -float(decay))
-        inc = g * (a - float(target_accept))
-        ls = np.minimum(np.maximum(ls + inc, float(log_scale_bounds[0])), float(log_scale_bounds[1]))
-    ready = W >= min_weight
-    v["weight"][:], v["log_scale"][:], v["n_updates"][:], v["ready"][:] = W, ls, k, ready
-    v["mean"][:], v["scatter"][:] = mean, S
-    if not ready.any():
-        return st, None
-    out = np.zeros((F, N, N)) if cov is None else np.array(cov, np.float64)
-    out[ready] = adapt_cov_formula(S[ready], W[ready], ls[ready], step, ridge)
-    return st, out
-
-
-def adapt_cov_formula(S, W, ls, step, ridge):
-    """Step 4 of ``surfdisp_mcmc_adapt_device``: cov [F, N, N] = exp(2 ls) (2.38^2 / N_live) (S / W + ridge diag(step^2)), symmetric from the
-    upper triangle of S [F, N, N]; a scalar whose diagonal is zero: a zero row and column, and not counted in N_live."""
-    S, W, ls, step = (np.asarray(a, np.float64) for a in (S, W, ls, step))
-    F, N, _ = S.shape
-    Su = np.triu(S)
-    B = (Su + np.transpose(np.triu(S, 1), (0, 2, 1))) / W[:, None, None]
-    i = np.arange(N)
-    B[:, i, i] = B[:, i, i] + (float(ridge) * step) * step
-    live = B[:, i, i] != 0.0
-    nlive = live.sum(axis=1)
-    with np.errstate(divide="ignore"):
-        c = np.where(nlive > 0, np.exp(2.0 * ls) * ((2.38 * 2.38) / nlive.astype(np.float64)), 0.0)
-    return np.where(live[:, :, None] & live[:, None, :], c[:, None, None] * B, 0.0)
+# (the proposals, the adaptation and their numpy statements live in .proposal; every public name is re-exported here)
+from .proposal import (ADAPT_DEFAULTS, ADAPT_HEAD, COV_MAX_N, COV_TRIES, MAX_DEPTH, Adaptation, ExhaustedCounter, Factor,    # noqa: F401
+                       KernelRedraw, ReferenceSteps, adapt_cov_formula, adapt_reference, adapt_state_len, adapt_state_views,
+                       cov_factor, cov_factor_reference, fused_schedule, rules_args)
 
 
 class PriorRules:
@@ -256,7 +129,7 @@ class ChainGroups:
         self.mc, self.C, self.G = mc, int(C), int(G)
         self.bounds = [self.C * g // self.G for g in range(self.G + 1)]
         self.streams = [torch.cuda.Stream(device=mc.device) for _ in range(self.G)]
-        self.children = []
+        self.children, self._obs = [], None
         for g in range(self.G):
             ch = copy.copy(mc)                                  # shares spec, proposer (bounds, steps, seed), periods, to_model
             ch._fresh_state()                                   # (its own plans, fused buffers, counters, Love stream)
@@ -269,22 +142,23 @@ class ChainGroups:
         afresh at every fork: a parent whose observations or ``local_rows`` were replaced, or whose ``independent`` / ``fast_scan`` changed after
         a first grouped run, must not advance on the first run's copies."""
         mc = self.mc
+        obs = (mc.c_obs, mc.uncer, mc.mask)
+        sliced = self._obs is not None and all(a is b for a, b in zip(obs, self._obs))     # the children hold slices of these already
+        self._obs = obs
+        pr = mc.proposal()                                      # one object for all groups, its factors indexed by the chain's
+        if pr.redraws_in_kernel:                                # index in the whole sampler, and one counter, zeroed before the fork
+            pr.exhausted.tensor()
         for g, ch in enumerate(self.children):
             lo, hi = self.bounds[g], self.bounds[g + 1]
-            if mc.c_obs.ndim == 2:
-                if mc.c_obs.shape[0] != self.C:
-                    raise ValueError(f"{self.C} chains against {mc.c_obs.shape[0]} rows of observations")
-                ch.c_obs, ch.uncer, ch.mask = mc.c_obs[lo:hi], mc.uncer[lo:hi], mc.mask[lo:hi]
-            else:
-                ch.c_obs, ch.uncer, ch.mask = mc.c_obs, mc.uncer, mc.mask
+            if mc.c_obs.ndim == 2 and mc.c_obs.shape[0] != self.C:
+                raise ValueError(f"{self.C} chains against {mc.c_obs.shape[0]} rows of observations")
+            if not sliced:                                      # (new tensors: _fused_buffers then makes the child's buffers anew)
+                ch.c_obs, ch.uncer, ch.mask = (a[lo:hi] for a in obs) if mc.c_obs.ndim == 2 else obs
             ch.local_rows = None if mc.local_rows is None else mc.local_rows[lo:hi]
             ch.independent, ch.fast_scan, ch.isgood = mc.independent, mc.fast_scan, mc.isgood
             ch.joint, ch.periods = mc.joint, mc.periods
             ch._chain0 = mc._chain0 + lo
-            ch._prop = mc._prop                                 # (the factors are indexed by the chain's index in the whole sampler)
-            ch._exh = mc._exhausted_counter() if mc._redraws_in_kernel() else None          # one counter for all groups
-            if ch._fz is not None and (ch._fz["c_obs"].data_ptr() != ch.c_obs.contiguous().data_ptr()):
-                ch._fz = None                                   # (the fused buffers hold contiguous copies of the observations)
+            ch._shared = pr
 
     def fork(self):
         self._refresh()
@@ -377,12 +251,13 @@ class MetropolisBatch:
         self._counter = 0                                       # calls of the fused kernels so far: the Philox counter of the next one
         self._pipelined = False                                 # a chain group: another group's solve is in flight beside this one
         self._chain0 = 0                                        # index of this object's chain 0 in the whole sampler (chain groups)
-        self._exh = None                                        # PriorRules(redraw="kernel") / set_proposal: one device int, shared with the chain groups
-        self._prop = None                                       # set_proposal: dict(factor_t [F, N, N], cpf, F)
+        self._exh = ExhaustedCounter(self.device)               # what the redrawing propose kernels count in, shared with the chain groups
+        self._given = None                                      # set_proposal: a proposal.Factor
+        self._steps = None                                      # the proposal made from isgood (proposal())
+        self._shared = None                                     # a chain group's child: the proposal its parent had in force at the fork
         self._last_groups = None                                # the ChainGroups of the last run (last_prior_tries)
-        self._adapt = None                                      # set_adaptive: the options
-        self._adapt_run = None                                  # the adaptation of the last run: state, cov, factor_t, flag (adaptation())
-        self._adapting = False                                  # inside a run that adapts
+        self._adaptation = None                                 # set_adaptive: a proposal.Adaptation
+        self._adapted = None                                    # the Adaptation of the last run that adapted (adaptation())
 
     def _fresh_state(self):
         """What a sampler owns and a chain group's child (a shallow copy of its parent) must not share with it."""
@@ -479,48 +354,50 @@ class MetropolisBatch:
     def fused_available(self):
         """The lock step can run as propose kernel -> stacks -> solver -> accept kernel (no torch glue, no host
         synchronisation): device proposer, the HIP forward path, and no ``isgood`` callback - or a ``PriorRules`` one, whose
-        redraw loop runs on the device too (``_redraw_with_rules``, or ``_propose_prior`` with ``redraw="kernel"``)."""
+        redraw loop runs on the device too (``proposal.ReferenceSteps``, or ``proposal.KernelRedraw`` with ``redraw="kernel"``)."""
         dev_prior = self.isgood is None or (isinstance(self.isgood, PriorRules) and self.device.type == "cuda"
                                             and self.local_rows is None and self.isgood.device_flags() is not None)
         return (dev_prior and isinstance(self.proposer, TorchProposer) and self.device.type == "cuda"
                 and self._forward is None)
 
     def _fused_buffers(self, C):
+        """The fused path's buffers of C chains: made anew whenever C, the joint data or one of the ``c_obs`` / ``uncer`` / ``mask``
+        tensors is no longer the object they were made from (they hold contiguous copies of the three)."""
         torch = self.torch
         st = self._fz
-        if st is None or st["C"] != C or st.get("data") is not self.joint:
+        made = (self.joint, self.c_obs, self.uncer, self.mask)
+        if st is None or st["C"] != C or any(a is not b for a, b in zip(made, st["made"])):
             N = self.spec.n
-            st = dict(C=C, data=self.joint, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
+            st = dict(C=C, made=made, p1=torch.empty((C, N), dtype=torch.float64, device=self.device),
                       chi=torch.zeros(C, dtype=torch.float64, device=self.device),
                       mask8=self.mask.to(torch.uint8).contiguous(), c_obs=self.c_obs.contiguous(), uncer=self.uncer.contiguous())
-            if self._redraws_in_kernel():
-                self._exhausted_counter()                         # (made and zeroed here, once: no memset per step)
             self._fz = st
         return st
 
-    # ------------------------------------------------------------------ prior redraw inside the propose kernel
-    def _kernel_rules(self):
-        """The ``PriorRules`` of this sampler when its redraw loop runs inside the propose kernel (``redraw="kernel"``), else None."""
-        rules = self.isgood
-        return rules if isinstance(rules, PriorRules) and rules.redraw == "kernel" else None
-
-    def _redraws_in_kernel(self):
-        """Whether the proposal kernel of this sampler redraws until the candidate is good and counts the nodes that found none
-        (``PriorRules(redraw="kernel")``, or a proposal factor: ``set_proposal``)."""
-        return self._kernel_rules() is not None or self._prop is not None
-
-    def _exhausted_counter(self):
-        """The device int the redrawing propose kernels count exhausted nodes in: one per sampler, shared by its chain groups."""
-        if self._exh is None:
-            self._exh = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
-        return self._exh
+    # ------------------------------------------------------------------ the proposal in force
+    def proposal(self):
+        """The proposal in force now (``pysurfinv_amd.proposal``): the working factors of the adaptation while an adaptive run is in
+        progress, else ``set_proposal``'s factors, else the kernel redraw if ``isgood`` is a ``PriorRules(redraw="kernel")``, else
+        the reference's steps (with the redraw rounds of a ``PriorRules``).  A chain group's child: its parent's."""
+        if self._shared is not None:
+            return self._shared
+        ad, isgood = self._adaptation, self.isgood
+        pr = ad.working if ad is not None and ad.working is not None else self._given
+        if pr is not None:
+            pr.isgood = isgood                                     # (isgood may be assigned after set_proposal)
+            return pr
+        pr = self._steps
+        if pr is None or pr.isgood is not isgood:
+            kernel = isinstance(isgood, PriorRules) and isgood.redraw == "kernel"
+            pr = self._steps = KernelRedraw(self.proposer, isgood, self._exh) if kernel else ReferenceSteps(self.proposer, isgood)
+        return pr
 
     def prior_exhausted(self):
         """How many proposals of this sampler (tree nodes of all fused lock steps so far) found no model the prior accepts within
         ``gauss_tries + uniform_tries`` redraws and proposed the state they drew from - where the reference raises
-        ``RuntimeError`` (models.py:219) - with a proposal factor (``set_proposal``): within the caps of ``_propose_cov``, box
+        ``RuntimeError`` (models.py:219) - with a proposal factor (``set_proposal``): within the caps of ``proposal.Factor``, box
         included.  0 for every other redraw mode.  Synchronises once; ``run()`` itself never does."""
-        return 0 if self._exh is None else int(self._exh.item())
+        return self._exh.count()
 
     def last_prior_tries(self):
         """uint16 [C, M]: the retry index every proposal of the last fused lock step was accepted at by the prior (M = 2^depth - 1
@@ -532,28 +409,7 @@ class MetropolisBatch:
             return None
         return ts[0] if len(ts) == 1 else torch.cat([t.view(torch.int16) for t in ts], dim=0).view(torch.uint16)
 
-    def _propose_prior(self, stream, p, out, depth, counter, st):
-        """The proposal tree ``out`` [C, 2^depth - 1, N] (depth 1: [C, N]) of the states ``p``, every row redrawn inside the kernel
-        until the ``PriorRules`` hold (``surfdisp_mcmc_propose_prior_device``: one launch)."""
-        torch = self.torch
-        rules = self._kernel_rules()
-        C, N = p.shape
-        M = (1 << int(depth)) - 1
-        mb = rules.model
-        idesc, fdesc, Lout = mb.native_descriptor()
-        tries = st.get("tries")
-        if tries is None or tries.shape != (C, M):
-            tries = st["tries"] = torch.zeros((C, M), dtype=torch.int16, device=self.device).view(torch.uint16)
-        aux = mb._full(p)[:, N:].contiguous() if mb.n_aux else None
-        pr = self.proposer
-        _lib.check(_lib.lib().surfdisp_mcmc_propose_prior_device(
-            stream, C, N, int(mb.n_aux), int(Lout), int(depth), _ptr(p), _ptr(aux), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
-            _ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()), ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max),
-            rules.gauss_tries, rules.uniform_tries, pr.seed_int, counter, self._chain0, _ptr(out), _ptr(tries), _ptr(self._exhausted_counter())))
-
     # ------------------------------------------------------------------ covariance-shaped proposals
-    COV_TRIES = (1000, 10000)       # whole-proposal Gaussian / uniform redraws of a sampler with a factor and no PriorRules (the reference's caps)
-
     def set_proposal(self, factor, chains_per_point=1):
         """Proposals ``x + F z`` (z standard normal) in place of the reference's independent steps ``spec.step``: ``factor`` is a
         float64 device tensor, lower triangular (the strict upper triangle is not read), [N, N] for every chain or [n_points, N, N]
@@ -569,8 +425,8 @@ class MetropolisBatch:
         Needs the fused path: ValueError otherwise."""
         torch = self.torch
         if factor is None:
-            self._prop = None
-            self._adapt = None                                     # (adaptation proposes with a factor: off with it)
+            self._given = None
+            self._adaptation = None                                # (adaptation proposes with a factor: off with it)
             return
         N = self.spec.n
         if not torch.is_tensor(factor) or factor.dtype != torch.float64 or factor.ndim not in (2, 3) or tuple(factor.shape[-2:]) != (N, N):
@@ -584,10 +440,8 @@ class MetropolisBatch:
         if factor.device != self.device:
             raise ValueError(f"set_proposal: the factor lives on {factor.device}, the sampler on {self.device}")
         ft = torch.tril(factor).transpose(-1, -2).contiguous()     # factor_t[f][k][n] = L_f[n][k]
-        if factor.ndim == 2:
-            self._prop = dict(factor_t=ft[None], cpf=1 << 62, F=1)
-        else:
-            self._prop = dict(factor_t=ft, cpf=int(chains_per_point), F=int(ft.shape[0]))
+        ft, cpf = (ft[None], 1 << 62) if factor.ndim == 2 else (ft, chains_per_point)
+        self._given = Factor(self.proposer, self.isgood, self._exh, ft, cpf)
 
     def _require_cov_path(self, who):
         """ValueError unless the propose kernel of ``set_proposal`` / ``set_adaptive`` can serve this sampler."""
@@ -623,132 +477,18 @@ class MetropolisBatch:
         ``set_proposal(None)`` turn it off: the sampler then launches the kernels and draws the numbers it did before.
         ``adaptation()`` reports; the state is reset at the start of every run."""
         if chains_per_point is None:
-            self._adapt = None
+            self._adaptation = None
             return
-        N = self.spec.n
-        if N > COV_MAX_N:
-            raise ValueError(f"set_adaptive: {N} random-walk parameters, the kernel takes at most {COV_MAX_N}")
-        if int(chains_per_point) < 1:
-            raise ValueError("set_adaptive: chains_per_point >= 1 expected")
-        if int(every) < 1 or int(start) < 0:
-            raise ValueError("set_adaptive: every >= 1 and start >= 0 expected")
-        if until is not None and int(until) <= int(start):
-            raise ValueError("set_adaptive: until > start expected (None: half of the chain)")
-        lo, hi = (float(b) for b in log_scale_bounds)
-        if not (0.0 < float(forget) <= 1.0) or not float(ridge) >= 0.0 or not lo <= hi or not float(target_accept) <= 1.0:
-            raise ValueError("set_adaptive: 0 < forget <= 1, ridge >= 0, log_scale_bounds (lo <= hi) and target_accept <= 1 expected")
-        mw = 4.0 * N if min_weight is None else float(min_weight)
-        if not mw >= 1.0:
-            raise ValueError("set_adaptive: min_weight >= 1 expected")
+        ad = Adaptation(self.proposer, self.spec.n, self._exh, chains_per_point, every, start, until, forget, target_accept, gain, decay,
+                        min_weight, ridge, log_scale_bounds)
         self._require_cov_path("set_adaptive")
-        self._adapt = dict(cpp=int(chains_per_point), every=int(every), start=int(start), until=None if until is None else int(until),
-                           forget=float(forget), target_accept=float(target_accept), gain=float(gain), decay=float(decay),
-                           min_weight=mw, ridge=float(ridge), ls_min=lo, ls_max=hi)
+        self._adaptation = ad
 
     def adaptation(self):
         """The adaptation of the last run, device tensors (None before the first): weight [F], mean [F, N], cov [F, N, N] (S / W,
         symmetric), scale [F] (exp of the log scale), n_updates [F], fallbacks [F] (refactorings that kept the reference's steps),
         factor [F, N, N] (lower triangular: the view ``cov_factor`` returns, of the factors the chains proposed with last)."""
-        torch = self.torch
-        run = self._adapt_run
-        if run is None:
-            return None
-        v = adapt_state_views(run["state"], self.spec.n)
-        S = torch.triu(v["scatter"])
-        S = S + torch.triu(S, 1).transpose(1, 2)
-        return dict(weight=v["weight"], mean=v["mean"], cov=S / v["weight"][:, None, None], scale=torch.exp(v["log_scale"]),
-                    n_updates=v["n_updates"].to(torch.int64), fallbacks=v["fallbacks"].to(torch.int64),
-                    factor=run["factor_t"].transpose(1, 2))
-
-    def _adapt_begin(self, C, chainL):
-        """The fresh adaptation of a run of C chains x chainL rows: state, covariance and flag buffers, and the working factors - a
-        copy of ``set_proposal``'s, or diag(spec.step) - which take the place of ``_prop`` until ``_adapt_end``."""
-        torch = self.torch
-        ad, N = self._adapt, self.spec.n
-        if C % ad["cpp"]:
-            raise ValueError(f"run: {C} chains are no whole number of points of {ad['cpp']} chains (set_adaptive)")
-        F = C // ad["cpp"]
-        given = self._prop
-        if given is None:
-            ft = torch.diag(self.proposer.step.to(torch.float64)).expand(F, N, N).contiguous()
-        elif given["F"] == 1:
-            ft = given["factor_t"].expand(F, N, N).contiguous()
-        elif given["F"] == F and given["cpf"] == ad["cpp"]:
-            ft = given["factor_t"].clone()
-        else:
-            raise ValueError(f"run: set_proposal gave {given['F']} factors for {given['cpf']} chains each, set_adaptive expects "
-                             f"{F} points of {ad['cpp']} chains")
-        until = chainL // 2 if ad["until"] is None else ad["until"]
-        self._adapt_run = dict(state=torch.zeros((F, adapt_state_len(N)), dtype=torch.float64, device=self.device),
-                               cov=torch.zeros((F, N, N), dtype=torch.float64, device=self.device),
-                               flag=torch.zeros(F, dtype=torch.int32, device=self.device), factor_t=ft, F=F, until=until,
-                               weight=0.0, prev=None, given=given, refactors=0)
-        self._prop = dict(factor_t=ft, cpf=ad["cpp"], F=F)
-
-    def _adapt_end(self):
-        if self._adapt_run is not None and "given" in self._adapt_run:
-            self._prop = self._adapt_run.pop("given")
-
-    def _adapt_due(self, lo, hi):
-        """Whether an update instant lies among the steps lo .. hi - 1."""
-        ad, run = self._adapt, self._adapt_run
-        a, b = max(lo, ad["start"]), min(hi, run["until"])
-        if a >= b:
-            return False
-        first = a + (-(a - ad["start"])) % ad["every"]             # the first instant >= a
-        return first < b
-
-    def _adapt_update(self, p, track, chain_stride, row_stride, i):
-        """The update after step i (the current stream; every group joined): the window is the rows since the previous update - at
-        the first one max(1, i - every + 1) .. i, so that row 0, accepted by construction, never counts -, then the factors of all
-        points once their weight - the same on every point, followed on the host - has reached ``min_weight``."""
-        torch = self.torch
-        ad, run, N = self._adapt, self._adapt_run, self.spec.n
-        lo = max(1, i - ad["every"] + 1) if run["prev"] is None else run["prev"] + 1
-        run["prev"] = i
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        step = self.proposer.step
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().surfdisp_mcmc_adapt_device(
-                stream, run["F"], ad["cpp"], N, _ptr(p), _ptr(track), int(chain_stride), int(row_stride), int(lo), int(i) + 1, _ptr(step),
-                ad["forget"], ad["target_accept"], ad["gain"], ad["decay"], ad["ls_min"], ad["ls_max"], ad["min_weight"], ad["ridge"],
-                _ptr(run["state"]), _ptr(run["cov"])))
-            w = run["weight"] * ad["forget"]                       # the kernel's own arithmetic: W is this number on every point
-            for _ in range(ad["cpp"]):
-                w += 1.0
-            run["weight"] = w
-            if w >= ad["min_weight"]:
-                _lib.check(_lib.lib().surfdisp_mcmc_cov_factor_device(stream, run["F"], N, _ptr(run["cov"]), ctypes.c_double(1.0), _ptr(step),
-                                                                      _ptr(run["factor_t"]), _ptr(run["flag"])))
-                run["state"][:, 3] += run["flag"]
-                run["refactors"] += 1
-
-    def _propose_cov(self, stream, p, out, depth, counter, st):
-        """The proposal tree ``out`` [C, 2^depth - 1, N] (depth 1: [C, N]) of the states ``p`` with the factors of ``set_proposal``,
-        every row redrawn inside the kernel until it lies in the box and the ``PriorRules`` (if any) hold
-        (``surfdisp_mcmc_propose_cov_device``: one launch) - a sibling of ``_propose_prior``."""
-        torch = self.torch
-        rules = self.isgood if isinstance(self.isgood, PriorRules) else None
-        C, N = p.shape
-        M = (1 << int(depth)) - 1
-        tries = st.get("tries")
-        if tries is None or tries.shape != (C, M):
-            tries = st["tries"] = torch.zeros((C, M), dtype=torch.int16, device=self.device).view(torch.uint16)
-        pr, pp = self.proposer, self._prop
-        if rules is not None:
-            mb = rules.model
-            idesc, fdesc, Lout = mb.native_descriptor()
-            aux = mb._full(p)[:, N:].contiguous() if mb.n_aux else None
-            desc = (int(mb.n_aux), int(Lout)), (_ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()),
-                                                  ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max))
-            caps = (rules.gauss_tries, rules.uniform_tries)
-        else:
-            aux = None
-            desc = (0, 0), (None, None, None, ctypes.c_double(-1.0))
-            caps = self.COV_TRIES
-        _lib.check(_lib.lib().surfdisp_mcmc_propose_cov_device(
-            stream, C, N, *desc[0], int(depth), _ptr(p), _ptr(aux), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pp["factor_t"]), pp["cpf"], pp["F"],
-            *desc[1], *caps, pr.seed_int, counter, self._chain0, _ptr(out), _ptr(tries), _ptr(self._exhausted_counter())))
+        return None if self._adapted is None else self._adapted.report()
 
     def _solve_raw(self, params, rows=None):
         """The solver's own fp32 output tensors (no copies) for the stacks of ``params``: (c[C, P], status[C]), or with joint
@@ -888,54 +628,14 @@ class MetropolisBatch:
         than the last call's).  Everything stream-ordered on the current stream."""
         C, N = p.shape
         st, stream, counter, rowp = self._fused_call(C, row, row_offset, counter)
-        pr = self.proposer
         with self.torch.cuda.device(self.device):
             if first:
                 p1 = p
             else:
                 p1 = st["p1"]
-                if self._prop is not None:                     # x + F z, box and rules inside the kernel
-                    self._propose_cov(stream, p, p1, 1, counter, st)
-                elif self._kernel_rules() is not None:         # proposal and the prior's redraw loop in one kernel
-                    self._propose_prior(stream, p, p1, 1, counter, st)
-                else:
-                    _lib.check(_lib.lib().surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
-                                                                       pr.seed_int, counter, 0, _ptr(p1), self._chain0))
-                    if self.isgood is not None:
-                        self._redraw_with_rules(p, p1, counter, stream)
+                self.proposal().draw(stream, p, p1, 1, counter, st, self._chain0)
             self._accept(stream, self._solve_raw(p1), st, p1, p, rowp, row_stride, counter, False, first=first)
         return p
-
-    def _redraw_with_rules(self, p, p1, counter, stream):
-        """The redraw loop of ``MCinv.perturb`` / ``reset`` (models.py:192-219) for a ``PriorRules`` predicate, on the device and
-        without a host synchronisation: the prior kernel marks the chains whose proposal ``p1`` breaks a rule, the masked
-        proposal kernel draws those again - ``rounds`` Gaussian rounds, ``reset_rounds`` uniform ones, then the chain's own
-        state.  One tag per chain, rising from round to round (cleared once per step)."""
-        torch = self.torch
-        rules = self.isgood
-        C, N = p1.shape
-        mb = rules.model
-        idesc, fdesc, Lout = mb.native_descriptor()
-        flags = rules.device_flags()
-        st = self._fz
-        if st.get("tags") is None or st["tags"].numel() != C:
-            st["tags"] = torch.zeros(C, dtype=torch.uint8, device=self.device)
-        tags = st["tags"]
-        L = _lib.lib()
-        pr = self.proposer
-        vmax = -1.0 if rules.vs_max is None else rules.vs_max
-        pfull = lambda q: q if mb.n_aux == 0 else mb._full(q).contiguous()
-        total = rules.rounds + rules.reset_rounds + 1
-        tags.zero_()                                               # once per step: the rounds use rising tags 1, 2, ...
-        for r in range(total):
-            q = pfull(p1)
-            # round r: chains redrawn in round r - 1 carry tag r (all chains in round 0); the ones that break a rule get r + 1 ...
-            _lib.check(L.surfdisp_prior_device(stream, C, q.shape[1], int(Lout), _ptr(q), _ptr(idesc), _ptr(fdesc), _ptr(flags),
-                                               ctypes.c_double(vmax), r if r > 0 else -1, r + 1, _ptr(tags)))
-            # ... and draw again: Gaussian rounds, then uniform prior draws, last the chain's own state
-            mode = 0 if r < rules.rounds else (1 if r < rules.rounds + rules.reset_rounds else 2)
-            _lib.check(L.surfdisp_mcmc_propose_masked_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
-                                                             pr.seed_int, counter, r, mode, _ptr(tags), r + 1, _ptr(p1), self._chain0))
 
     SPEC_MAX_STACKS = 2048          # stacks per speculative lock step: a 64-lane team = one wavefront each, the chip holds 4 096
 
@@ -950,12 +650,19 @@ class MetropolisBatch:
         is redrawn until the rules hold and the depth is the one above."""
         if self._indep(C):
             return 1
-        if self.isgood is not None and not self._redraws_in_kernel():
-            return 1                                               # (prior rules: the redraw rounds belong to the plain lock step)
-        for d in (4, 3, 2):
+        for d in range(self.proposal().max_depth, 1, -1):         # (prior rules in rounds: those belong to the plain lock step)
             if C * ((1 << d) - 1) <= self.SPEC_MAX_STACKS:
                 return d
         return 1
+
+    def _check_depth(self, depth):
+        """ValueError for a speculative depth the fused path, or the proposal in force, cannot draw."""
+        if depth > MAX_DEPTH:
+            raise ValueError("spec_depth of the fused path is at most 4")
+        if depth > self.proposal().max_depth:
+            raise ValueError(f"spec_depth = {depth}: the redraw rounds of a PriorRules follow one proposal per chain, not a tree; "
+                             'pass spec_depth=1 (the default with these rules) or PriorRules(redraw="kernel"), whose kernel '
+                             "redraws every node of the tree")
 
     def fused_tree_step(self, p, depth, nsteps, row=None, row_stride=0, row_offset=0, step_stride=0, counter=None):
         """``nsteps`` <= ``depth`` Metropolis steps of every chain from ONE batched solve (speculative / "prefetching"
@@ -967,20 +674,16 @@ class MetropolisBatch:
         torch = self.torch
         C, N = p.shape
         M = (1 << int(depth)) - 1
+        pr = self.proposal()
+        if depth > pr.max_depth:
+            self._check_depth(int(depth))                          # (raises, before the call is counted)
         st, stream, counter, rowp = self._fused_call(C, row, row_offset, counter)
         if st.get("M") != M:
             st["M"] = M
             st["q"] = torch.empty((C, M, N), dtype=torch.float64, device=self.device)
             st["qrows"] = torch.arange(C, device=self.device).repeat_interleave(M) if self.local_rows is not None else None
-        pr = self.proposer
         with torch.cuda.device(self.device):
-            if self._prop is not None:                             # every node x + F z, redrawn until box and rules hold
-                self._propose_cov(stream, p, st["q"], depth, counter, st)
-            elif self._kernel_rules() is not None:                 # every node redrawn until the prior's rules hold
-                self._propose_prior(stream, p, st["q"], depth, counter, st)
-            else:
-                _lib.check(_lib.lib().surfdisp_mcmc_propose_tree_device(stream, C, N, int(depth), _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax),
-                                                                        _ptr(pr.step), pr.seed_int, counter, _ptr(st["q"]), self._chain0))
+            pr.draw(stream, p, st["q"], depth, counter, st, self._chain0)
             self._accept(stream, self._solve_raw(st["q"].view(C * M, N), rows=st["qrows"]), st, st["q"], p, rowp, row_stride, counter,
                          True, depth=depth, nsteps=nsteps, step_stride=step_stride)
         return p
@@ -1068,7 +771,9 @@ class MetropolisBatch:
         Every proposal is still drawn from q(current state, .) and tested against the current state,
         so the chain is distributed exactly as with d = 1; only the order in which random numbers are
         consumed differs (the exact-replay path of the reference trace uses d = 1).  Default (None): on the fused device
-        path ``auto_spec_depth`` (4 for up to 136 chains, 3 up to 292, 2 up to 682, else 1), on the torch path 1.
+        path ``auto_spec_depth`` (4 for up to 136 chains, 3 up to 292, 2 up to 682, else 1), on the torch path 1.  A depth the
+        proposal in force cannot draw on the fused path - any d > 1 under a ``PriorRules`` in its default ``redraw="rounds"`` mode,
+        whose rounds follow one proposal per chain - raises ValueError before anything is launched.
 
         ``fused`` (default: whenever ``fused_available()``): the lock step as device kernels around the solver
         (``fused_step``: Philox random numbers keyed by the proposer's seed; same proposal and accept distributions).
@@ -1080,17 +785,50 @@ class MetropolisBatch:
         before ``until`` are adaptation and no valid samples, the rows from ``until`` on come from a fixed Metropolis kernel."""
         torch = self.torch
         C, N = int(n_chains), self.spec.n
-        if self._adapt is not None and not self._adapting:
-            # adaptive proposals: the run itself, between _adapt_begin (the working factors stand in for _prop) and _adapt_end
-            if priori or fused is False or not self.fused_available():
-                raise ValueError("run: adaptive proposals (set_adaptive) are drawn by the fused path only; set_adaptive(None) for the torch loop")
-            self._adapt_begin(C, int(chainL))
-            self._adapting = True
-            try:
-                return self.run(n_chains, chainL, init_first, priori, _init_mask, spec_depth, fused, groups, start, _start_mask)
-            finally:
-                self._adapting = False
-                self._adapt_end()
+        ad = self._adaptation
+        if ad is None:
+            return self._run(C, chainL, init_first, priori, _init_mask, spec_depth, fused, groups, start, _start_mask)
+        if priori or fused is False or not self.fused_available():
+            raise ValueError("run: adaptive proposals (set_adaptive) are drawn by the fused path only; set_adaptive(None) for the torch loop")
+        ad.begin(C, int(chainL), self._given, self.isgood)         # its working factors are the proposal in force until end()
+        self._adapted = ad
+        try:
+            return self._run(C, chainL, init_first, priori, _init_mask, spec_depth, fused, groups, start, _start_mask)
+        finally:
+            ad.end()
+
+    def _walk(self, p, track, cg, depth, calls):
+        """The fused lock steps ``calls`` (items of ``fused_schedule``) of the chains ``p`` [C, N] into ``track`` [C, chainL, 3 + N]:
+        every call advances the chains - the chain groups ``cg``, else a speculative call at ``depth`` > 1, else the plain step -
+        under the next Philox counter, and where an update instant of a running adaptation falls among its rows the update follows,
+        once, with the window up to the call's last row (the groups join for it and fork again: the chains of a point may straddle
+        two groups)."""
+        N = self.spec.n
+        width, stride = 3 + N, track.shape[1] * (3 + N)
+        ad = self._adaptation if self._adaptation is not None and self._adaptation.working is not None else None
+        base, n = self._counter, 0
+        if cg is not None:
+            cg.fork()
+        for n, (i, ns, first) in enumerate(calls, 1):
+            if cg is not None:
+                cg.step(p, row=track, row_stride=stride, row_offset=i * width, first=first, counter=base + n)
+            elif depth > 1 and not first:
+                self.fused_tree_step(p, depth, ns, row=track, row_stride=stride, row_offset=i * width, step_stride=width, counter=base + n)
+            else:
+                self.fused_step(p, row=track, row_stride=stride, row_offset=i * width, first=first, counter=base + n)
+            if ad is not None and ad.due(i, i + ns):
+                if cg is not None:
+                    cg.join()
+                ad.update(p, track, stride, width, i + ns - 1)
+                if cg is not None:
+                    cg.fork()
+        if cg is not None:
+            cg.join()
+        self._counter = base + n
+
+    def _run(self, C, chainL, init_first, priori, _init_mask, spec_depth, fused, groups, start, _start_mask):
+        torch = self.torch
+        N = self.spec.n
         if start is not None:
             start = self._checked_start(start, C, _start_mask)
         if fused is None:
@@ -1098,58 +836,24 @@ class MetropolisBatch:
         fused = bool(fused) and not priori                         # a priori run evaluates nothing: the torch loop below
         if fused and not self.fused_available():
             raise ValueError("fused=True needs the device proposer, no isgood callback (or a PriorRules one) and the HIP forward path")
-        if self._prop is not None and not fused:
+        if self._given is not None and not fused:
             raise ValueError("run: a proposal factor (set_proposal) is drawn by the fused path only; set_proposal(None) for the torch loop")
-        adapting = self._adapt is not None and self._adapting
         if spec_depth is None:
             spec_depth = self.auto_spec_depth(C) if (fused and groups in (None, 1)) else 1
         spec_depth = int(spec_depth)
         if spec_depth > 1 and groups not in (None, 1):
             raise ValueError("run: chain groups and speculative lock steps (spec_depth > 1) cannot be combined")
         if spec_depth > 1 and not priori and not fused:
-            return self._run_speculative(n_chains, chainL, init_first, _init_mask, spec_depth, start, _start_mask)
+            return self._run_speculative(C, chainL, init_first, _init_mask, spec_depth, start, _start_mask)
+        if fused:
+            self._check_depth(spec_depth)                          # before anything is launched or counted
         track = torch.zeros((C, chainL, 3 + N), dtype=torch.float64, device=self.device)
         if fused:
             # propose / accept kernels around the solver: mcTrack rows are written by the accept kernel itself
             p = self._start(C, init_first, _init_mask, start, _start_mask).contiguous().clone()
-            stride = chainL * (3 + N)
             cg = self.chain_groups(C, groups) if spec_depth <= 1 else None
             self._last_groups = cg
-            base = self._counter
-            if cg is None and spec_depth > 1:
-                # speculative lock steps: the first row is the start model itself, then spec_depth steps per batched solve
-                if spec_depth > 4:
-                    raise ValueError("spec_depth of the fused path is at most 4")
-                self.fused_step(p, row=track, row_stride=stride, row_offset=0, first=True, counter=base + 1)
-                if adapting and self._adapt_due(0, 1):
-                    self._adapt_update(p, track, stride, 3 + N, 0)
-                i, n = 1, 1
-                while i < chainL:
-                    ns = min(spec_depth, chainL - i)
-                    n += 1
-                    self.fused_tree_step(p, spec_depth, ns, row=track, row_stride=stride, row_offset=i * (3 + N),
-                                         step_stride=3 + N, counter=base + n)
-                    if adapting and self._adapt_due(i, i + ns):    # once, at the call's end, with the window up to its last row
-                        self._adapt_update(p, track, stride, 3 + N, i + ns - 1)
-                    i += ns
-                self._counter = base + n
-                return track
-            if cg is not None:
-                cg.fork()
-            for i in range(chainL):
-                if cg is not None:
-                    cg.step(p, row=track, row_stride=stride, row_offset=i * (3 + N), first=(i == 0), counter=base + i + 1)
-                else:
-                    self.fused_step(p, row=track, row_stride=stride, row_offset=i * (3 + N), first=(i == 0), counter=base + i + 1)
-                if adapting and self._adapt_due(i, i + 1):
-                    if cg is not None:                             # the chains of a point may straddle two groups
-                        cg.join()
-                    self._adapt_update(p, track, stride, 3 + N, i)
-                    if cg is not None:
-                        cg.fork()
-            if cg is not None:
-                cg.join()
-            self._counter = base + chainL
+            self._walk(p, track, cg, spec_depth, fused_schedule(chainL, spec_depth))
             return track
         p0 = self._start(C, init_first, _init_mask, start, _start_mask)
         chi0 = self._first_row(track, p0)
@@ -1261,8 +965,8 @@ class MetropolisBatch:
         every chain's rows before ``until`` are adaptation and no valid samples.
         Returns float64 [n_points, chains_per_point, chainL, 3+N] (numpy, or the device tensor)."""
         torch = self.torch
-        if self._adapt is not None and int(chains_per_point) != self._adapt["cpp"]:
-            raise ValueError(f"run_points: {chains_per_point} chains per point, set_adaptive was given chains_per_point = {self._adapt['cpp']}")
+        if self._adaptation is not None and int(chains_per_point) != self._adaptation.cpp:
+            raise ValueError(f"run_points: {chains_per_point} chains per point, set_adaptive was given chains_per_point = {self._adaptation.cpp}")
         C = n_points * chains_per_point
         first = (torch.arange(C, device=self.device) % chains_per_point) == 0
         if start is not None:
@@ -1323,7 +1027,7 @@ class MetropolisBatch:
         for all practical purposes.  Random numbers come from torch's default device generator
         (graph-safe Philox)."""
         torch = self.torch
-        if self._adapt is not None:
+        if self._adaptation is not None:
             raise ValueError("run_graphed: adaptive proposals (set_adaptive) are not supported: the update instants are placed by run()")
         if self.joint is not None:
             raise ValueError("run_graphed: joint data (data=) are not supported; use run()")

@@ -109,7 +109,7 @@ def _timing_child():
     import numpy as np
     import torch
     from pysurfinv_amd import _lib, settings
-    from pysurfinv_amd.mcmc import MetropolisBatch, PriorRules
+    from pysurfinv_amd.mcmc import MetropolisBatch, PriorRules, fused_schedule
     REPS = int(os.environ.get("REPS", "4"))
     dev = torch.device("cuda:0")
     mb, c_obs, unc = settings.synthetic_observations(1, dev)
@@ -137,35 +137,29 @@ def _timing_child():
             mc.set_adaptive(CPP, every=EVERY, start=1, until=NSTEPS + 1, min_weight=CPP, log_scale_bounds=bounds)
 
     def window(mc, nsteps, rejoin=False):
-        """run()'s own loop (two chain groups) with events around the rows 1 .. nsteps; rejoin: the groups join and fork at the
-        adaptive variant's instants without an update between."""
+        """run()'s own loop (``_walk`` over ``fused_schedule``, two chain groups) with events around the rows 1 .. nsteps; rejoin:
+        the rows walked in pieces that end at the adaptive variant's instants, so that the groups join and fork there without an
+        update between."""
         p = mc._start(C, False, None).contiguous().clone()
         track = torch.zeros((C, nsteps + 1, 3 + N), dtype=torch.float64, device=dev)
-        stride = (nsteps + 1) * (3 + N)
-        adapting = mc._adapt is not None
-        if adapting:
-            mc._adapt_begin(C, nsteps + 1)
+        ad = mc._adaptation
+        if ad is not None:
+            ad.begin(C, nsteps + 1, mc._given, mc.isgood)
         cg = mc.chain_groups(C, 2)
         mc._last_groups = cg                            # (last_prior_tries reads the groups' buffers)
-        cg.fork(); cg.step(p, row=track, row_stride=stride, first=True); cg.join()
+        calls = list(fused_schedule(nsteps + 1, 1))
+        ends = [i + 1 for i in range(1, nsteps + 1) if (i - 1) % EVERY == 0] if rejoin else []
+        pieces = [calls[a:b] for a, b in zip([1] + ends, ends + [nsteps + 1]) if a < b]
+        mc._walk(p, track, cg, 1, calls[:1])
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
-        cg.fork()
-        for i in range(1, nsteps + 1):
-            cg.step(p, row=track, row_stride=stride, row_offset=i * (3 + N))
-            if adapting and mc._adapt_due(i, i + 1):
-                cg.join()
-                mc._adapt_update(p, track, stride, 3 + N, i)
-                cg.fork()
-            elif rejoin and (i - 1) % EVERY == 0:
-                cg.join()
-                cg.fork()
-        cg.join()
+        for piece in pieces:
+            mc._walk(p, track, cg, 1, piece)
         e1.record()
         torch.cuda.synchronize()
-        if adapting:
-            mc._adapt_end()
+        if ad is not None:
+            ad.end()
         return e0.elapsed_time(e1) / nsteps, float(track[:, 1:, 2].mean())
 
     kinds = ["plain", "factor", "factor rejoin"] + (["adaptive", "adaptive small"] if has_adapt else [])
@@ -190,17 +184,18 @@ def _timing_child():
         set_mode(mc, "adaptive", fac)
         p = mc._start(C, False, None).contiguous().clone()
         track = torch.zeros((C, 12, 3 + N), dtype=torch.float64, device=dev)
-        mc._adapt_begin(C, 24)
+        ad = mc._adaptation
+        ad.begin(C, 24, mc._given, mc.isgood)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        mc._adapt_update(p, track, 12 * (3 + N), 3 + N, 10)
+        ad.update(p, track, 12 * (3 + N), 3 + N, 10)
         torch.cuda.synchronize()
         e0.record()
         for _ in range(20):
-            mc._adapt_run["prev"] = 0
-            mc._adapt_update(p, track, 12 * (3 + N), 3 + N, 10)
+            ad.prev = 0
+            ad.update(p, track, 12 * (3 + N), 3 + N, 10)
         e1.record()
         torch.cuda.synchronize()
-        mc._adapt_end()
+        ad.end()
         res["update_kernels_ms"] = e0.elapsed_time(e1) / 20
     print("RESULT " + json.dumps(res), flush=True)
 

@@ -4,8 +4,8 @@ launches per lock step) against ``redraw="kernel"`` (the redraw loop inside the 
 process, alternating:
 
   * 25 600 chains x MCMC_SETTING (96 layers, 19 periods), the plain lock step in the sampler's default two chain groups;
-  * 100 chains with PriorRules(vs_max=4.9) at spec_depth 1, 3 and 4 (the rounds mode skips the rules at depth > 1: its
-    figures there are those of a sampler WITHOUT a prior, given for scale).
+  * 100 chains with PriorRules(vs_max=4.9) at spec_depth 1, 3 and 4 (the rounds mode draws no tree: its figures at depth > 1
+    are those of a sampler WITHOUT a prior, given for scale).
 
 Timed with device events around the lock steps after a warm-up of every shape; the best and the median of REPS windows.
 Then the propose stage ALONE on an otherwise idle chip, 50 calls between two events: the one call of the kernel mode against
@@ -19,16 +19,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from pysurfinv_amd import _lib, settings
-from pysurfinv_amd.mcmc import MetropolisBatch, PriorRules, _ptr
+from pysurfinv_amd import settings
+from pysurfinv_amd.mcmc import MetropolisBatch, PriorRules
 
 REPS = int(os.environ.get("REPS", "5"))
 dev = torch.device("cuda:0")
 mb, c_obs, unc = settings.synthetic_observations(1, dev)
 
 
-def sampler(mode):
-    rules = PriorRules(mb, vs_max=4.9, redraw=mode)
+def sampler(mode, d=1):
+    rules = PriorRules(mb, vs_max=4.9, redraw=mode) if (mode == "kernel" or d == 1) else None      # (the rounds draw no tree)
     return MetropolisBatch(mb.spec, mb.to_model, settings.MCMC_PERIODS, c_obs[0], unc[0], device=dev, seed=3, isgood=rules)
 
 
@@ -69,7 +69,7 @@ for what, C, nsteps, d, groups in (("25 600 chains, plain lock step (two chain g
                                    ("100 chains, spec_depth 3", 100, 600, 3, None),
                                    ("100 chains, spec_depth 4", 100, 600, 4, None),
                                    ("25 600 chains, plain lock step, ONE chain group", 25600, 40, 1, 1)):
-    mcs = {mode: sampler(mode) for mode in ("rounds", "kernel")}
+    mcs = {mode: sampler(mode, d) for mode in ("rounds", "kernel")}
     for mc in mcs.values():
         window(mc, C, max(nsteps // 10, 4), d, groups)                 # warm-up: plans, buffers, code objects
     ms = {mode: [] for mode in mcs}
@@ -80,7 +80,7 @@ for what, C, nsteps, d, groups in (("25 600 chains, plain lock step (two chain g
             ms[mode].append(t)
     print(what)
     for mode in mcs:
-        note = "  (rules skipped at this depth)" if mode == "rounds" and d > 1 else ""
+        note = "  (no rules at this depth)" if mode == "rounds" and d > 1 else ""
         print(f"    redraw={mode:7s}: best {min(ms[mode]):7.3f}  median {float(np.median(ms[mode])):7.3f} ms per lock step; "
               f"accept rate {acc[mode]:.3f}; exhausted {mcs[mode].prior_exhausted()}{note}", flush=True)
 
@@ -91,25 +91,15 @@ N = mb.spec.n
 for C, d in ((25600, 1), (12800, 1), (100, 1), (100, 4)):
     line = []
     for mode in ("rounds", "kernel"):
-        mc = sampler(mode)
-        pr, rules = mc.proposer, mc.isgood
-        q = pr.reset(5 * C)
-        p = q[rules(q)][:C].contiguous()                               # good start states
+        mc = sampler(mode, d)
+        q = mc.proposer.reset(5 * C)
+        p = q[PriorRules(mb, vs_max=4.9)(q)][:C].contiguous()          # good start states
         st = mc._fused_buffers(C)
         out = torch.empty((C, (1 << d) - 1, N), dtype=torch.float64, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L = _lib.lib()
 
-        def stage(counter):
-            if mode == "kernel":
-                mc._propose_prior(stream, p, out, d, counter, st)
-            elif d == 1:
-                _lib.check(L.surfdisp_mcmc_propose_device(stream, C, N, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step), pr.seed_int,
-                                                          counter, 0, _ptr(out), 0))
-                mc._redraw_with_rules(p, out.view(C, N), counter, stream)
-            else:                                                      # (no rules at this depth: the tree entry alone)
-                _lib.check(L.surfdisp_mcmc_propose_tree_device(stream, C, N, d, _ptr(p), _ptr(pr.vmin), _ptr(pr.vmax), _ptr(pr.step),
-                                                               pr.seed_int, counter, _ptr(out), 0))
+        def stage(counter):                                            # the sampler's own propose stage (rounds at depth > 1: the tree entry alone)
+            mc.proposal().draw(stream, p, out.view(C, N) if d == 1 else out, d, counter, st, mc._chain0)
         for i in range(5):
             stage(1 + i)
         torch.cuda.synchronize()
@@ -123,4 +113,4 @@ for C, d in ((25600, 1), (12800, 1), (100, 1), (100, 4)):
         if mode == "kernel":
             t = mc.last_prior_tries().cpu().view(torch.int16).float()
             line.append(f"(mean retries {float(t.mean()):.2f}, most {int(t.max())})")
-    print(f"    {C:6d} chains, depth {d}: " + "   ".join(line) + ("  (rounds: rules skipped at this depth)" if d > 1 else ""), flush=True)
+    print(f"    {C:6d} chains, depth {d}: " + "   ".join(line) + ("  (rounds: no rules at this depth)" if d > 1 else ""), flush=True)

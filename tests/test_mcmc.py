@@ -315,6 +315,47 @@ def test_fused_device_kernels_proposal_and_accept():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("groups", [1, 2])
+def test_fused_buffers_follow_a_replaced_uncer(groups):
+    """The fused path works on contiguous copies of c_obs / uncer / mask: a new ``uncer`` tensor alone (twice the old one) must reach
+    them, in a sampler and in the children of its chain groups.  Observations 0.4 % off the states' own curves at 1 % uncertainty:
+    chi-square about 19 x 0.16, below the fold at 50, so that doubling the uncertainty divides it by four (exactly, but for the
+    rounding of a sum: 1e-12 relative)."""
+    dev = torch.device("cuda:0")
+    mb = Model1DBatch(CONT, device=dev)
+    periods = G["trace/periods"]
+    C, P = 8, len(periods)
+    v0 = torch.as_tensor(mb.spec.v0, dtype=torch.float64, device=dev)[None, :]
+    lo, hi = (torch.as_tensor(np.asarray(a, np.float64), device=dev) for a in (mb.spec.vmin, mb.spec.vmax))
+    w = torch.as_tensor(np.random.default_rng(2).uniform(0.0, 0.1, (C, mb.spec.n)), device=dev)
+    start = (v0 + w * (0.5 * (lo + hi) - v0)).contiguous()
+    c, st = mb.forward(start, periods=periods)
+    assert bool((st == 0).all())
+    c = c.double().cpu().numpy()
+    mc = MetropolisBatch(mb.spec, mb.to_model, periods, c * (1 + 0.004 * (-1.0) ** np.arange(P)), 0.01 * c, device=dev, seed=5)
+
+    def first_chi():
+        p = start.clone()
+        if groups == 1:
+            mc.fused_step(p, first=True)
+            torch.cuda.synchronize()
+            return mc._fz["chi"].clone()
+        cg = mc.chain_groups(C, 2)
+        cg.fork(); cg.step(p, first=True); cg.join()
+        torch.cuda.synchronize()
+        return torch.cat([ch._fz["chi"] for ch in cg.children])
+
+    chi0 = first_chi()
+    print(f"groups {groups}: first chi-squares {chi0.min().item():.3f} .. {chi0.max().item():.3f}")
+    assert chi0.shape == (C,) and bool((chi0 > 0).all()) and bool((chi0 < 50).all())
+    c_obs, mask = mc.c_obs, mc.mask
+    mc.uncer = 2.0 * mc.uncer
+    chi1 = first_chi()
+    assert mc.c_obs is c_obs and mc.mask is mask
+    assert bool(((chi1 - chi0 / 4).abs() <= 1e-12 * chi0 / 4).all()), (chi0, chi1)
+
+
+@pytest.mark.gpu
 def test_fused_run_records_consistent_rows():
     """MetropolisBatch.run on the device path: every recorded row's misfit equals the eagerly recomputed misfit of its
     parameters, rows form a valid chain, acceptance comparable with the torch-glue path."""

@@ -19,6 +19,7 @@ from test_prior_redraw import _cpu_model             # noqa: E402
 from pysurfinv_amd import _lib, settings             # noqa: E402
 from pysurfinv_amd.mcmc import (MetropolisBatch, PriorRules, adapt_cov_formula, adapt_reference, adapt_state_len,   # noqa: E402
                                 adapt_state_views, cov_factor, cov_factor_reference)
+from pysurfinv_amd.proposal import Factor, ReferenceSteps   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -144,8 +145,9 @@ def _run(groups=1, spec_depth=1, until=30, adaptive=True, proposal=None):
     assert (mc._last_groups is not None) == (groups == 2)
     ad = mc.adaptation()
     ad = None if ad is None else {k: v.cpu().numpy() for k, v in ad.items()}
-    state = None if ad is None else mc._adapt_run["state"].cpu().numpy()
-    assert mc.prior_exhausted() == 0 and (not adaptive or mc._prop is None)      # (the working factors left with the run)
+    state = None if ad is None else mc._adapted.state.cpu().numpy()
+    assert mc.prior_exhausted() == 0                                   # (the working factors left with the run)
+    assert not adaptive or (mc._adaptation.working is None and type(mc.proposal()) is (Factor if proposal == "diag" else ReferenceSteps))
     return tr.cpu().numpy(), ad, state, mc.proposer.seed_int
 
 
@@ -265,7 +267,7 @@ def test_off_means_off():
         again = mc.run_points(NPTS, CPP, CHAINL, on_device=True).cpu().numpy()
     finally:
         L.surfdisp_set_team(0)
-    assert mc._adapt is None and mc.adaptation() is None and np.array_equal(_bits(again), _bits(plain))
+    assert mc._adaptation is None and mc.adaptation() is None and np.array_equal(_bits(again), _bits(plain))
     never, ad, _, _ = _run(until=15)                                    # updates after steps 10 only: weight 5 < min_weight
     assert (ad["n_updates"] == 1).all() and (ad["weight"] == CPP).all()
     diag = _run(adaptive=False, proposal="diag")[0]

@@ -16,6 +16,7 @@ from pysurfinv_amd import mcmc, settings             # noqa: E402
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd.mcmc import (MetropolisBatch, PriorRules, adapt_reference, adapt_state_len, adapt_state_views,   # noqa: E402
                                 cov_factor_reference)
+from pysurfinv_amd.proposal import Adaptation, Factor, ReferenceSteps, fused_schedule   # noqa: E402
 
 OFF = dict(target_accept=-1.0)
 
@@ -163,10 +164,13 @@ def _cpu_sampler(isgood=None, **kw):
     return MetropolisBatch(m.spec, m.to_model, settings.MCMC_PERIODS, np.full(P, 3.5), np.full(P, 0.05), device="cpu", isgood=isgood, **kw)
 
 
-def _options(cpp=4):
+def _options(mc, cpp=4):
     """What set_adaptive stores, made by hand: a sampler without a device cannot be given adaptation through the front door."""
-    return dict(cpp=cpp, every=10, start=20, until=None, forget=1.0, target_accept=0.25, gain=1.0, decay=0.6, min_weight=52.0, ridge=1e-3,
-                ls_min=-3.0, ls_max=3.0)
+    ad = Adaptation(mc.proposer, mc.spec.n, mc._exh, cpp, every=10, start=20, until=None, forget=1.0, target_accept=0.25, gain=1.0,
+                    decay=0.6, min_weight=52.0, ridge=1e-3, log_scale_bounds=(-3.0, 3.0))
+    assert (ad.cpp, ad.every, ad.start, ad.until, ad.forget, ad.target_accept, ad.gain, ad.decay, ad.min_weight, ad.ridge, ad.ls_min,
+            ad.ls_max) == (cpp, 10, 20, None, 1.0, 0.25, 1.0, 0.6, 52.0, 1e-3, -3.0, 3.0)
+    return ad
 
 
 def test_set_adaptive_refusals():
@@ -188,19 +192,33 @@ def test_set_adaptive_refusals():
     for kw in (dict(forget=0.0), dict(forget=1.5), dict(ridge=-1.0), dict(log_scale_bounds=(1.0, -1.0)), dict(min_weight=0.0)):
         with pytest.raises(ValueError, match="set_adaptive"):
             mc.set_adaptive(4, **kw)
-    assert mc._adapt is None and mc.adaptation() is None
+    assert mc._adaptation is None and mc.adaptation() is None
     # both switches turn it off
-    mc._adapt = _options()
+    mc._adaptation = _options(mc)
     mc.set_adaptive(None)
-    assert mc._adapt is None
-    mc._adapt = _options()
+    assert mc._adaptation is None
+    mc._adaptation = _options(mc)
     mc.set_proposal(None)
-    assert mc._adapt is None and mc._prop is None
+    assert mc._adaptation is None and mc._given is None
+    # ... and the proposal in force is the earlier one again; a run's working factors come before set_proposal's, and only while it lasts
+    plain = mc.proposal()
+    assert type(plain) is ReferenceSteps and plain.max_depth == 4
+    mc._adaptation = ad = _options(mc)
+    assert mc.proposal() is plain                                      # not inside a run: nothing of the adaptation is in force
+    ad.working = Factor(mc.proposer, None, mc._exh, torch.zeros(2, mc.spec.n, mc.spec.n, dtype=torch.float64), 4)
+    mc._given = Factor(mc.proposer, None, mc._exh, torch.zeros(1, mc.spec.n, mc.spec.n, dtype=torch.float64), 1 << 62)
+    assert mc.proposal() is ad.working and mc.proposal().max_depth == 4
+    ad.end()
+    assert mc.proposal() is mc._given
+    mc.set_adaptive(None)
+    assert mc.proposal() is mc._given
+    mc.set_proposal(None)
+    assert mc.proposal() is plain
 
 
 def test_run_points_run_and_run_graphed_refuse():
     mc = _cpu_sampler(forward=lambda *a: pytest.fail("nothing may be evaluated"))
-    mc._adapt = _options(cpp=4)
+    mc._adaptation = _options(mc, cpp=4)
     with pytest.raises(ValueError, match="chains_per_point"):
         mc.run_points(2, 3, 5)
     with pytest.raises(ValueError, match="set_adaptive"):
@@ -212,12 +230,40 @@ def test_run_points_run_and_run_graphed_refuse():
 
 
 def test_update_instants():
-    mc = object.__new__(MetropolisBatch)
-    mc._adapt, mc._adapt_run = dict(start=10, every=5), dict(until=30)
-    due = [i for i in range(60) if mc._adapt_due(i, i + 1)]
+    ad = Adaptation(None, 13, None, 4, start=10, every=5, until=30)
+    due = [i for i in range(60) if ad.due(i, i + 1)]
     assert due == [10, 15, 20, 25]
-    assert mc._adapt_due(11, 15) is False and mc._adapt_due(11, 16) and mc._adapt_due(26, 40) is False and mc._adapt_due(0, 11)
-    assert not mc._adapt_due(30, 31) and not mc._adapt_due(0, 10)
+    assert ad.due(11, 15) is False and ad.due(11, 16) and ad.due(26, 40) is False and ad.due(0, 11)
+    assert not ad.due(30, 31) and not ad.due(0, 10)
+
+
+@pytest.mark.parametrize("chainL", [1, 2, 5, 13])
+@pytest.mark.parametrize("d", [1, 2, 3, 4])
+def test_fused_schedule_covers_the_rows(chainL, d):
+    calls = list(fused_schedule(chainL, d))
+    assert calls[0] == (0, 1, True) and not any(first for _, _, first in calls[1:])
+    rows = [r for i, ns, _ in calls for r in range(i, i + ns)]
+    assert rows == list(range(chainL))                                 # every row once, in order
+    assert all(1 <= ns <= d for _, ns, _ in calls)
+    assert len(calls) == (chainL if d == 1 else 1 + -(-(chainL - 1) // d))
+    if d == 1:
+        assert calls == [(i, 1, i == 0) for i in range(chainL)]
+
+
+def test_fused_schedule_places_the_updates():
+    """start = 2, every = 3, until = 9: the instants 2, 5, 8.  An update follows the call among whose rows i .. i + ns - 1 an instant
+    lies, once, with the window up to the call's last row.  Written out from that rule: (call numbers from 1, window ends)."""
+    ad = Adaptation(None, 13, None, 4, start=2, every=3, until=9)
+    want = {(13, 1): ([3, 6, 9], [2, 5, 8]),          # one row per call: call n is row n - 1
+            (13, 2): ([2, 4, 5], [2, 6, 8]),          # calls 0 | 1-2 | 3-4 | 5-6 | 7-8 | 9-10 | 11-12
+            (13, 3): ([2, 3, 4], [3, 6, 9]),          # calls 0 | 1-3 | 4-6 | 7-9 | 10-12
+            (13, 4): ([2, 3], [4, 8]),                # calls 0 | 1-4 | 5-8 | 9-12: the instants 5 and 8 share a call
+            (5, 1): ([3], [2]), (5, 2): ([2], [2]),   # five rows: the instant 2 alone; calls 0 | 1-2 | 3-4
+            (5, 3): ([2], [3]), (5, 4): ([2], [4]),   # calls 0 | 1-3 | 4 and 0 | 1-4
+            (2, 1): ([], []), (2, 4): ([], [])}       # rows 0 and 1: no instant
+    for (chainL, d), (numbers, ends) in want.items():
+        got = [(n, i + ns - 1) for n, (i, ns, _) in enumerate(fused_schedule(chainL, d), 1) if ad.due(i, i + ns)]
+        assert got == list(zip(numbers, ends)), (chainL, d)
 
 
 def test_public_routes_reach_the_sampler_on_a_thermal_model():

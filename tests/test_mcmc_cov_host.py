@@ -31,6 +31,7 @@ from test_prior_redraw import CHAIN0_BIG, _cpu_model, _starts   # noqa: E402
 from pysurfinv_amd import mcmc, settings             # noqa: E402
 from pysurfinv_amd.layers_batch import Model1DBatch  # noqa: E402
 from pysurfinv_amd.mcmc import MetropolisBatch, PriorRules, cov_factor_reference   # noqa: E402
+from pysurfinv_amd.proposal import Factor, KernelRedraw, ReferenceSteps, rules_args   # noqa: E402
 
 # the stand-alone configurations of the entry, no rules: name -> (N, C, depth, chains_per_factor)
 CONFIGS = {"a": (1, 3, 1, 1), "b": (13, 67, 1, 8), "c": (13, 67, 4, 8), "d": (64, 5, 2, 2)}
@@ -214,7 +215,7 @@ def test_set_proposal_shapes_and_refusals():
     mc = _cpu_sampler()
     N = mc.spec.n
     eye = torch.eye(N, dtype=torch.float64)
-    assert mc._prop is None and not mc._redraws_in_kernel()
+    assert mc._given is None and not mc.proposal().redraws_in_kernel
     mc.set_proposal(None)                                              # always allowed: the reference's proposal
     for bad in (eye.float(), eye[:, :5], torch.zeros(2, 3, N, N, dtype=torch.float64), torch.zeros(4, N + 1, N + 1, dtype=torch.float64),
                 np.eye(N)):
@@ -229,14 +230,59 @@ def test_set_proposal_shapes_and_refusals():
     rules = PriorRules(_cpu_model())
     with pytest.raises(ValueError, match="local_rows"):
         _cpu_sampler(isgood=rules, local_rows=np.zeros(4, np.int64)).set_proposal(eye)
-    assert mc._prop is None
+    assert mc._given is None
     # the switches, asked without a device
-    mc2 = object.__new__(MetropolisBatch)
-    mc2.isgood, mc2._exh, mc2._prop, mc2.independent = rules, None, dict(factor_t=None, cpf=1, F=1), False
-    assert mc2._redraws_in_kernel() and mc2._kernel_rules() is None
+    mc2 = _cpu_sampler(isgood=rules)
+    mc2._given = Factor(mc2.proposer, rules, mc2._exh, torch.zeros(1, N, N, dtype=torch.float64), 1)
+    assert mc2.proposal().redraws_in_kernel and type(mc2.proposal()) is Factor
     assert mc2.auto_spec_depth(100) == 4 and mc2.auto_spec_depth(5000) == 1    # like redraw="kernel"
-    mc2._prop = None
+    mc2._given = None
     assert mc2.auto_spec_depth(100) == 1
+
+
+def test_proposal_in_force():
+    """Class and deepest tree of the proposal in force for every way of setting one; the off switches return to the earlier answer."""
+    m = _cpu_model()
+    N = m.spec.n
+    ft = torch.zeros(3, N, N, dtype=torch.float64)
+    rounds, kernel = PriorRules(m), PriorRules(m, redraw="kernel")
+    for isgood, cls, deepest in ((None, ReferenceSteps, 4), (rounds, ReferenceSteps, 1), (kernel, KernelRedraw, 4)):
+        mc = _cpu_sampler(isgood=isgood)
+        first = mc.proposal()
+        assert type(first) is cls and first.max_depth == deepest and first.redraws_in_kernel == (cls is KernelRedraw)
+        assert first.isgood is isgood and mc.proposal() is first
+        mc._given = Factor(mc.proposer, isgood, mc._exh, ft, 4)            # (set_proposal itself needs a device)
+        pr = mc.proposal()
+        assert pr is mc._given and pr.max_depth == 4 and pr.redraws_in_kernel and pr.isgood is isgood and (pr.F, pr.cpf) == (3, 4)
+        mc.set_proposal(None)
+        assert mc.proposal() is first
+        mc.set_adaptive(None)
+        assert mc.proposal() is first
+    # isgood is assignable after construction: the proposal follows it
+    mc = _cpu_sampler()
+    assert mc.proposal().max_depth == 4 and mc.auto_spec_depth(100) == 4
+    mc.isgood = rounds
+    assert type(mc.proposal()) is ReferenceSteps and mc.proposal().max_depth == 1 and mc.auto_spec_depth(100) == 1
+    mc.isgood = kernel
+    assert type(mc.proposal()) is KernelRedraw and mc.proposal().isgood is kernel and mc.auto_spec_depth(100) == 4
+    with pytest.raises(ValueError, match="spec_depth"):
+        _cpu_sampler(isgood=rounds)._check_depth(2)
+    with pytest.raises(ValueError, match="at most 4"):
+        _cpu_sampler()._check_depth(5)
+
+
+def test_rules_descriptor_is_marshalled_once():
+    """proposal.rules_args: the tensors of native_descriptor() / device_flags() by identity, vs_max = -1.0 for None.  The model of
+    this file has no per-point constants (K = 0): no aux columns."""
+    m = _cpu_model()
+    assert m.n_aux == 0
+    p = torch.as_tensor(np.array(_starts(4.5, 5)))
+    idesc, fdesc, L = m.native_descriptor()
+    for vs_max in (None, 4.5):
+        rules = PriorRules(m, vs_max=vs_max)
+        K, Lout, aux, i2, f2, flags, cap = rules_args(rules, p)
+        assert (K, Lout, aux) == (0, int(L), None) and i2 is idesc and f2 is fdesc and flags is rules.device_flags()
+        assert cap == (-1.0 if vs_max is None else 4.5) and isinstance(cap, float)
 
 
 def test_run_start_refusals():

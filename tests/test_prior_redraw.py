@@ -69,11 +69,11 @@ def test_prior_rules_interface():
     assert PriorRules(m, gauss_tries=0, uniform_tries=16384).uniform_tries == 16384
     assert PriorRules(m, gauss_tries=1, uniform_tries=0).gauss_tries == 1
     # the sampler's switches: no device needed to ask
-    mc = object.__new__(MetropolisBatch)
-    mc.isgood, mc._exh = k, None
-    assert mc._kernel_rules() is k and mc.prior_exhausted() == 0
+    P = len(MCMC_PERIODS)
+    mc = MetropolisBatch(m.spec, m.to_model, MCMC_PERIODS, np.full(P, 3.5), np.full(P, 0.05), device="cpu", isgood=k)
+    assert mc.proposal().redraws_in_kernel and mc.proposal().isgood is k and mc.prior_exhausted() == 0
     mc.isgood = r
-    assert mc._kernel_rules() is None
+    assert not mc.proposal().redraws_in_kernel and mc.proposal().isgood is r
 
 
 def test_retry_counter_layout():
@@ -401,3 +401,20 @@ def test_sampler_with_the_kernel_redraw_in_chain_groups():
     assert float((tr[:, 1:, 3:] != tr[:, :-1, 3:]).any(dim=2).float().mean()) > 0.9
     assert mc.prior_exhausted() == 0 and mc.last_prior_tries().shape == (4096, 1)
     assert _no_accepted_duplicate(tr)
+
+
+@pytest.mark.gpu
+def test_explicit_depth_with_the_redraw_rounds_is_refused():
+    """The redraw rounds cannot follow a tree: run(spec_depth=3) under PriorRules in its default mode raises before anything is
+    launched or counted (it used to take the tree kernels without any prior); the default depth runs, and every row obeys the rules."""
+    mb, make, _ = _sampler_case()
+    rules = PriorRules(mb, vs_max=4.9)
+    mc = make(rules)
+    before = (mc.n_forward, mc._counter)
+    with pytest.raises(ValueError, match='spec_depth.*redraw="kernel"'):
+        mc.run(16, 6, spec_depth=3)
+    assert (mc.n_forward, mc._counter) == before
+    tr = mc.run(16, 6)
+    torch.cuda.synchronize()
+    assert tr.shape == (16, 6, 3 + mb.spec.n) and mc._counter == 6
+    assert bool(rules(tr[:, :, 3:].reshape(-1, mb.spec.n)).all())
