@@ -607,6 +607,27 @@ int surfdisp_forward_kernels_device(void *stream, int B, int Lmax, const int *nl
     return forward_device_impl(stream, B, Lmax, nlay, model, P, per, kind, c, u, status, workspace, workspace_bytes, o);
 }
 
+// The thickness pass of the two thickness entries: the EIG instantiation of the group-velocity kernel (kb = nullptr: it writes
+// no partials; its U goes to the scratch plane) on the roots `tc` and ellipticities `tratio` at the periods `tper`, then K2e on
+// the eigen region it filled and the given KERN scratch (`tkscr`, factors `tksc`, deepest layers `tkhs`) with the group
+// velocities `tu` -> the rows dh, dz (dz may be nullptr).  n_nonfinite: nullptr, or where K2e counts the units that are not finite.
+static int thickness_pass(hipStream_t s, int B, int Lmax, int P, int wave, const float *model, const Layout &lay,
+                          const float *tper, const float *tc, const float *tratio, const float *tu, const float *tkscr,
+                          const float *tksc, const int *tkhs, float *dh, float *dz, int *n_nonfinite)
+{
+    const Carve &w = lay.w;
+    const EigCarve &e = lay.eig;
+    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, tper, tc, tratio, w.nsolved, lay.thick_us, nullptr, nullptr, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, 0, 0, 0, knobs().group_order};
+    ga.escr = e.escr; ga.ediv = e.ediv; ga.ehs = e.ehs; ga.esum = e.esum;
+    ga.stash = -1;
+    SD_HIP(sd::launch_group(s, wave, ga));
+    sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, tper, e.escr, e.ediv, e.ehs, e.esum, tkscr, tksc, tkhs,
+                     tc, tu, dh, dz, n_nonfinite};
+    SD_HIP(sd::launch_thickness(s, ta));
+    return SURFDISP_SUCCESS;
+}
+
 // What surfdisp_forward_group_thickness_kernels_device asks of group_launches beyond the group entry's outputs.
 struct GroupThickOuts {
     float *dcdh, *dcdz, *dudh, *dudz;     // the caller's [B][P][Lmax] rows (dcdz, dudz may be nullptr)
@@ -636,26 +657,13 @@ static int group_launches(void *stream, int B, int Lmax, const int *nlay, const 
     const Layout lay = layout(workspace, B, Lmax, P, ws);
     const Carve &w = lay.w;
     const GCarve &g = lay.g;
-    const EigCarve &e = lay.eig;
     const size_t PB = (size_t)P * B, rows = PB * Lmax;
     float *kscr = lay.k.kscr, *kscale0 = lay.k.kscale;                           // forward_device_impl's scratch and factors
-    // the EIG instantiation (kb = nullptr: it writes no partials) on the roots at `tper`, then K2e on its region and the given
-    // KERN scratch -> rows; a NaN row marks a unit that is not finite, the combination counts them
-    auto thickness_pass = [&](const float *tper, const float *tc, const float *tratio, const float *tu, const float *tkscr,
-                              const float *tksc, const int *tkhs, float *dh, float *dz) -> int {
-        sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, tper, tc, tratio, w.nsolved, lay.thick_us, nullptr, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, 0, 0, 0, kn.group_order};
-        ga.escr = e.escr; ga.ediv = e.ediv; ga.ehs = e.ehs; ga.esum = e.esum;
-        ga.stash = -1;
-        SD_HIP(sd::launch_group(s, wave, ga));
-        sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, tper, e.escr, e.ediv, e.ehs, e.esum, tkscr, tksc, tkhs,
-                         tc, tu, dh, dz, nullptr};
-        SD_HIP(sd::launch_thickness(s, ta));
-        return SURFDISP_SUCCESS;
-    };
     if (t) {
         if (t->n_nonfinite) SD_HIP(hipMemsetAsync(t->n_nonfinite, 0, sizeof(int), s));
-        rc = thickness_pass(per, w.ct, w.ratio, w.ut, kscr, kscale0, lay.k.khs, t->dcdh, t->dcdz);
+        // (a NaN row marks a unit that is not finite; the combination counts them)
+        rc = thickness_pass(s, B, Lmax, P, wave, model, lay, per, w.ct, w.ratio, w.ut, kscr, kscale0, lay.k.khs, t->dcdh, t->dcdz,
+                            nullptr);
         if (rc) return rc;
     }
     if (n_shift_failed) SD_HIP(hipMemsetAsync(n_shift_failed, 0, sizeof(int), s));
@@ -672,8 +680,9 @@ static int group_launches(void *stream, int B, int Lmax, const int *nlay, const 
                          sg ? g.kscr_p : kscr, g.ksc + sg * PB, g.khs + sg * PB, 0, 0, 0, kn.group_order};
         SD_HIP(sd::launch_group(s, wave, ga));
         if (t) {
-            rc = thickness_pass(g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB, g.us + sg * PB, sg ? g.kscr_p : kscr,
-                                g.ksc + sg * PB, g.khs + sg * PB, plane(sg, 0), t->dudz ? plane(sg, 1) : nullptr);
+            rc = thickness_pass(s, B, Lmax, P, wave, model, lay, g.pers + (size_t)sg * P, g.cs + sg * PB, g.ratio + sg * PB,
+                                g.us + sg * PB, sg ? g.kscr_p : kscr, g.ksc + sg * PB, g.khs + sg * PB, plane(sg, 0),
+                                t->dudz ? plane(sg, 1) : nullptr, nullptr);
             if (rc) return rc;
         }
     }
@@ -821,22 +830,11 @@ int surfdisp_forward_thickness_kernels_device(void *stream, int B, int Lmax, con
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int wave = kind & ~SD_KIND_FLAGS;
-    const EnvKnobs &kn = knobs();
     const Layout lay = layout(workspace, B, Lmax, P, WS_THICK);
     const Carve &w = lay.w;
     const KCarve &k = lay.k;                                                    // forward_device_impl's scratch, factors, layers
-    const EigCarve &e = lay.eig;
     if (n_nonfinite) SD_HIP(hipMemsetAsync(n_nonfinite, 0, sizeof(int), s));
-    // (kb = nullptr: the EIG instantiation, which writes no partials)
-    sd::GroupArgs ga{B, Lmax, P, w.mdl, w.nl, per, w.ct, w.ratio, w.nsolved, lay.thick_us, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, 0, 0, 0, kn.group_order};
-    ga.escr = e.escr; ga.ediv = e.ediv; ga.ehs = e.ehs; ga.esum = e.esum;
-    ga.stash = -1;
-    SD_HIP(sd::launch_group(s, wave, ga));
-    sd::ThickArgs ta{B, P, Lmax, wave, model, w.mdl, w.nl, per, e.escr, e.ediv, e.ehs, e.esum, k.kscr, k.kscale, k.khs,
-                     w.ct, w.ut, dcdh, dcdz, n_nonfinite};
-    SD_HIP(sd::launch_thickness(s, ta));
-    return SURFDISP_SUCCESS;
+    return thickness_pass(s, B, Lmax, P, wave, model, lay, per, w.ct, w.ratio, w.ut, k.kscr, k.kscale, k.khs, dcdh, dcdz, n_nonfinite);
 }
 
 // The launches of surfdisp_forward_group_kernels_device and of surfdisp_forward_thickness_kernels_device in one pass (c .. dcdr,

@@ -1,7 +1,9 @@
 // surfdisp_internal.h -- kernel argument blocks and launch prototypes shared by
 // surfdisp_kernels.hip and surfdisp_capi.hip.  Not part of the public ABI (include/surfdisp.h).
 // surfdisp_kernels.hip is one translation unit; its first stages are headers it includes: surfdisp_k_common.h,
-// surfdisp_k_prep.h (K0), surfdisp_k_secular.h.  The root search (K1) and what follows it stand in the .hip itself.
+// surfdisp_k_prep.h (K0), surfdisp_k_secular.h, and so is surfdisp_k_rows.h: the scratch-to-rows tile walk of K2b, K2d, K4c and
+// K5d and the unit part of Rodi's rule, which surfdisp_group_thick.hip (K4d) includes too.  The root search (K1) and what
+// follows it stand in the .hip itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -522,8 +524,7 @@ hipError_t launch_thermal(hipStream_t s, const LayersArgs &a);
 #ifndef SD_PHASE_BLOCK
 #define SD_PHASE_BLOCK 256
 #endif
-size_t phase_lds_bytes(int Lmax, int G, int kind);   // per workgroup of SD_PHASE_BLOCK lanes (kind: 1 Love, 2 Rayleigh)
-size_t phase_exact_lds_bytes(int Lmax, int G, int kind);
+size_t phase_lds_bytes(int Lmax, int G, int kind);   // per workgroup of SD_PHASE_BLOCK lanes (kind: 1 Love, 2 Rayleigh); the exact fallback's too
 int phase_exact_team(int Lmax, int kind);                // lanes per stack of the exact fallback kernel
 hipError_t launch_phase_exact(hipStream_t s, int kind, bool independent, const PhaseArgs &a);
 hipError_t launch_finish(hipStream_t s, const FinishArgs &a);

@@ -48,6 +48,7 @@
 #include "surfdisp_k_common.h"
 #include "surfdisp_k_prep.h"
 #include "surfdisp_k_secular.h"
+#include "surfdisp_k_rows.h"
 
 namespace sd {
 
@@ -2160,36 +2161,25 @@ __global__ __launch_bounds__(256) void surfdisp_finish_kernel(FinishArgs A)
     }
 }
 
-// K2b: the analytic partials from the layer-major scratch [3][Lmax][P*B] (unit index u = k*B + b) to the caller's
-// [B][P][Lmax] rows, 64 units x 64 layers per workgroup through an LDS tile: reads run along the units, writes along
-// the layers.  Applies the unit's factor 1 / (dL/dk) and writes zeros below the unit's deepest layer (entries the
-// group-velocity kernel never wrote are not read).  blockIdx.z: 0 dc/dVs, 1 dc/dVp, 2 dc/drho.
+// K2b: the analytic partials from the layer-major scratch [3][Lmax][P*B] to the caller's [B][P][Lmax] rows
+// (rows_through_tile, surfdisp_k_rows.h).  Applies the unit's factor 1 / (dL/dk) and writes zeros below the unit's deepest
+// layer (entries the group-velocity kernel never wrote are not read).  blockIdx.z: 0 dc/dVs, 1 dc/dVp, 2 dc/drho.
 __global__ __launch_bounds__(256) void surfdisp_kern_transpose_kernel(KernTransposeArgs A)
 {
-    __shared__ float tile[64][65];
     const int B = A.B, P = A.P, Lmax = A.Lmax;
     float *__restrict__ out = (blockIdx.z == 0) ? A.kb : ((blockIdx.z == 1) ? A.ka : A.kr);
     if (!out) return;                                        // (block-uniform)
-    const float *__restrict__ scr = A.kscr + (size_t)blockIdx.z * Lmax * P * B;
-    const bool zero_only = (blockIdx.z == 1) && (A.kind != 2);   // Love has no dc/dVp
-    const int nbb = (B + 63) / 64;
-    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
     const size_t PB = (size_t)P * B;
-    const int bl = threadIdx.x % 64;
+    const float *__restrict__ scr = A.kscr + (size_t)blockIdx.z * Lmax * PB;
+    const bool zero_only = (blockIdx.z == 1) && (A.kind != 2);   // Love has no dc/dVp
+    const RowTile t = row_tile(B);
     float sc = 0.0f; int hs = -1;
-    if (b0 + bl < B && !zero_only) { sc = A.kscale[(size_t)k * B + b0 + bl]; hs = A.khs[(size_t)k * B + b0 + bl]; }
-    for (int il = threadIdx.x / 64; il < 64; il += 4)
-        tile[il][bl] = (i0 + il <= hs) ? scr[(size_t)(i0 + il) * PB + (size_t)k * B + b0 + bl] * sc : 0.0f;
-    __syncthreads();
-    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
-        const int bq = t / 64, il = t % 64;
-        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
-    }
+    if (t.live && !zero_only) { sc = A.kscale[t.un]; hs = A.khs[t.un]; }
+    rows_through_tile(t, B, P, Lmax, out, [&](int i) { return (i <= hs) ? scr[(size_t)i * PB + t.un] * sc : 0.0f; });
 }
 
 // K2d: the eigenfunctions (surfdisp_forward_eigen_device) from the layer-major scratch [4][Lmax][P*B] the EIG group-velocity
-// kernel leaves (EOut / EUnit) to the caller's [B][P][Lmax] rows, through the 64 units x 64 layers LDS tile of K2b (row stride
-// 65 words: the stores run along a row, the loads down a column whose words fall into 64 different banks).  Divides by the
+// kernel leaves (EOut / EUnit) to the caller's [B][P][Lmax] rows (rows_through_tile, surfdisp_k_rows.h).  Divides by the
 // unit's divisor as the reference does (amp(l) / ut, surfa.f:580-581; Rayleigh: 1), writes zeros below the unit's deepest
 // layer and for units without one (unsolved periods, bad stacks, degenerate exits), and whole rows.  blockIdx.z: 0 ur (Love:
 // the transverse displacement), 1 uz, 2 tz, 3 tr (Love: the shear traction); Love's uz and tz are rows of zeros.
@@ -2200,7 +2190,6 @@ __global__ __launch_bounds__(256) void surfdisp_kern_transpose_kernel(KernTransp
 // 1e-15 / sqrt(6.28318): a constant factor away.
 __global__ __launch_bounds__(256) void surfdisp_eigen_transpose_kernel(EigenTransposeArgs A)
 {
-    __shared__ float tile[64][65];
     const int B = A.B, P = A.P, Lmax = A.Lmax;
     const int z = blockIdx.z;
     float *__restrict__ out = (z == 0) ? A.ur : ((z == 1) ? A.uz : ((z == 2) ? A.tz : A.tr));
@@ -2209,32 +2198,12 @@ __global__ __launch_bounds__(256) void surfdisp_eigen_transpose_kernel(EigenTran
     const bool zero_only = love && (z == 1 || z == 2);
     const size_t PB = (size_t)P * B;
     const float *__restrict__ scr = A.escr + (size_t)(love ? (z == 3 ? 1 : 0) : z) * Lmax * PB;
-    const int nbb = (B + 63) / 64;
-    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
-    const int bl = threadIdx.x % 64;
-    const bool live = b0 + bl < B;
-    const size_t un = (size_t)k * B + b0 + bl;               // (read only where live)
+    const RowTile t = row_tile(B);
+    const int k = t.k, b = t.b0 + t.bl;
+    const bool live = t.live;
+    const size_t un = t.un;
     float dv = 1.0f; int hs = -1;
     if (live && !zero_only) { dv = A.ediv[un]; hs = A.ehs[un]; }
-    for (int il = threadIdx.x / 64; il < 64; il += 4) {
-        const int i = i0 + il;
-        float v = 0.0f;
-        if (i <= hs) {
-            v = scr[(size_t)i * PB + un] / dv;
-            if (love) {
-                const float amp = (z == 0) ? v : A.escr[(size_t)i * PB + un] / dv;
-                if (fabsf(amp) < 1.0e-20f) {                 // (rare: only then are the two velocities formed)
-                    const float lnT = logf(1.0f / A.per[k]);
-                    const size_t fs = (size_t)Lmax * B;
-                    const int n = A.nl[b0 + bl];
-                    const float vb = layer_at(A.mdl, fs, (size_t)i * B + b0 + bl, lnT, i == n - 1).b;
-                    const float vh = layer_at(A.mdl, fs, (size_t)hs * B + b0 + bl, lnT, hs == n - 1).b;
-                    if (vb >= vh) v = 0.0f;
-                }
-            }
-        }
-        tile[il][bl] = v;
-    }
     if (z == 0 && blockIdx.y == 0 && A.energy && threadIdx.x < 64 && live) {
         float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f, amp = 0.0f;
         if (hs >= 0) {
@@ -2243,14 +2212,27 @@ __global__ __launch_bounds__(256) void surfdisp_eigen_transpose_kernel(EigenTran
             if (c > 0.0f) amp = (float)(1.0 / (2.0 * (double)c * (double)u * (double)e0));
             if (!fin(amp)) amp = 0.0f;
         }
-        float *e = A.energy + ((size_t)(b0 + bl) * P + k) * 4;
+        float *e = A.energy + ((size_t)b * P + k) * 4;
         e[0] = e0; e[1] = e1; e[2] = e2; e[3] = amp;
     }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
-        const int bq = t / 64, il = t % 64;
-        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
-    }
+    rows_through_tile(t, B, P, Lmax, out, [&](int i) {
+        float v = 0.0f;
+        if (i <= hs) {
+            v = scr[(size_t)i * PB + un] / dv;
+            if (love) {
+                const float amp = (z == 0) ? v : A.escr[(size_t)i * PB + un] / dv;
+                if (fabsf(amp) < 1.0e-20f) {                 // (rare: only then are the two velocities formed)
+                    const float lnT = logf(1.0f / A.per[k]);
+                    const size_t fs = (size_t)Lmax * B;
+                    const int n = A.nl[b];
+                    const float vb = layer_at(A.mdl, fs, (size_t)i * B + b, lnT, i == n - 1).b;
+                    const float vh = layer_at(A.mdl, fs, (size_t)hs * B + b, lnT, hs == n - 1).b;
+                    if (vb >= vh) v = 0.0f;
+                }
+            }
+        }
+        return v;
+    });
 }
 
 // K2c: the apparent attenuation of the mode from the same scratch (surfdisp_forward_atten_device).  After REIGEN / LEIGEN the
@@ -2764,60 +2746,42 @@ __global__ __launch_bounds__(256) void surfdisp_shift_kernel(ShiftArgs A)
     A.fail[idx] = bad;
 }
 
-// shaped as surfdisp_kern_transpose_kernel: 64 units x 64 layers per workgroup through an LDS tile.  A unit without phase
-// partials (factor 0 at T: unsolved) gets a row of zeros, a solved unit whose shifted pass failed a row of NaN.
+// K4c: Rodi's rule (rodi_unit, surfdisp_k_rows.h) on the two shifted scratches, to the caller's rows (rows_through_tile).  A
+// unit without phase partials (factor 0 at T: unsolved) gets a row of zeros, a solved unit whose shifted pass failed a row of
+// NaN and is counted.  blockIdx.z: 0 dU/dVs, 1 dU/dVp, 2 dU/drho.
 __global__ __launch_bounds__(256) void surfdisp_group_combine_kernel(GroupCombineArgs A)
 {
-    __shared__ float tile[64][65];
     const int B = A.B, P = A.P, Lmax = A.Lmax;
     float *__restrict__ out = (blockIdx.z == 0) ? A.ub : ((blockIdx.z == 1) ? A.ua : A.ur);
     if (!out) return;                                        // (block-uniform)
-    const size_t arr = (size_t)Lmax * P * B;
-    const float *__restrict__ sm = A.kscr_m + (size_t)blockIdx.z * arr;
-    const float *__restrict__ sp = A.kscr_p + (size_t)blockIdx.z * arr;
-    const bool zero_only = (blockIdx.z == 1) && (A.kind != 2);   // Love has no dU/dVp
-    const int nbb = (B + 63) / 64;
-    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
     const size_t PB = (size_t)P * B;
-    const int bl = threadIdx.x % 64;
-    int mode = 0;                                            // 0 zeros, 1 NaN, 2 the combination
-    float scm = 0.0f, scp = 0.0f, f1 = 0.0f, f2 = 0.0f;
+    const float *__restrict__ sm = A.kscr_m + (size_t)blockIdx.z * Lmax * PB;
+    const float *__restrict__ sp = A.kscr_p + (size_t)blockIdx.z * Lmax * PB;
+    const bool zero_only = (blockIdx.z == 1) && (A.kind != 2);   // Love has no dU/dVp
+    const RowTile t = row_tile(B);
+    RodiUnit r{RODI_ZEROS, 0.0f, 0.0f};
+    float scm = 0.0f, scp = 0.0f;
     int hsm = -1, hsp = -1;
-    if (b0 + bl < B && !zero_only) {
-        const size_t o = (size_t)k * B + b0 + bl;
-        if (A.ksc0[o] != 0.0f) {
-            scm = A.ksc_m[o]; scp = A.ksc_p[o];
-            hsm = A.khs_m[o]; hsp = A.khs_p[o];
-            const float c = A.c[o], u = A.u[o];
-            const bool ok = !A.fail[o] && !A.fail[PB + o] && scm != 0.0f && scp != 0.0f && c > 0.0f && u > 0.0f;
-            mode = ok ? 2 : 1;
-            if (ok) {
-                const float r = u / c;
-                f1 = 0.5f * r * (2.0f - r);                      // (U/c)(2 - U/c) x the mean
-                f2 = r * r * A.inv_dlnT;                         // (U/c)^2 / d ln T
-            } else if (A.n_failed && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) {
-                atomicAdd(A.n_failed, 1);
-            }
+    if (t.live && !zero_only) {
+        r = rodi_unit(A.ksc0, A.ksc_m, A.ksc_p, A.fail, A.c, A.u, A.inv_dlnT, t.un, PB);
+        if (r.state != RODI_ZEROS) {                         // (with the words rodi_unit reads, not behind its verdict)
+            scm = A.ksc_m[t.un]; scp = A.ksc_p[t.un];
+            hsm = A.khs_m[t.un]; hsp = A.khs_p[t.un];
         }
+        if (r.state == RODI_NAN && A.n_failed && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 64) atomicAdd(A.n_failed, 1);
     }
-    for (int il = threadIdx.x / 64; il < 64; il += 4) {
-        const int i = i0 + il;
+    rows_through_tile(t, B, P, Lmax, out, [&](int i) {
         float v = 0.0f;
-        if (mode == 1) {
+        if (r.state == RODI_NAN) {
             v = __builtin_nanf("");
-        } else if (mode == 2) {
-            const size_t q = (size_t)i * PB + (size_t)k * B + b0 + bl;
+        } else if (r.state == RODI_COMBINE) {
+            const size_t q = (size_t)i * PB + t.un;
             const float km = (i <= hsm) ? sm[q] * scm : 0.0f;
             const float kp = (i <= hsp) ? sp[q] * scp : 0.0f;
-            v = f1 * (km + kp) - f2 * (kp - km);
+            v = r.f1 * (km + kp) - r.f2 * (kp - km);
         }
-        tile[il][bl] = v;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
-        const int bq = t / 64, il = t % 64;
-        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
-    }
+        return v;
+    });
 }
 
 }  // namespace sd
@@ -2831,7 +2795,7 @@ template <int KIND, int G, bool INDEP, bool FAST = false, bool EXACT = false>
 hipError_t launch_phase_g(hipStream_t s, const sd::PhaseArgs &a)
 {
     constexpr int S = SD_PHASE_BLOCK / G;
-    const size_t lds = EXACT ? sd::phase_exact_lds_bytes(a.Lmax, G, KIND) : sd::phase_lds_bytes(a.Lmax, G, KIND);
+    const size_t lds = sd::phase_lds_bytes(a.Lmax, G, KIND);
     auto kern = sd::surfdisp_phase_kernel<KIND, G, INDEP, FAST, EXACT>;
     // raise the dynamic-LDS limit of this instantiation only when a launch needs more than any before it (per
     // device): the attribute call costs ~10 us, visible in launch-bound Metropolis loops
@@ -2890,14 +2854,12 @@ hipError_t launch_phase_k(hipStream_t s, const sd::PhaseArgs &a, int G)
 
 namespace sd {
 
-// one working stack per team + NEVILL's table x(12), y(12) behind the working stacks
+// one working stack per team + NEVILL's table x(12), y(12) behind the working stacks (the exact fallback: the same layout)
 size_t phase_lds_bytes(int Lmax, int G, int kind) { const int S = SD_PHASE_BLOCK / G; return ((size_t)lds_ls(S, kind == 1 ? NFW_LOVE : NFW) * Lmax + (size_t)24 * S) * sizeof(float); }
-// exact fallback: the same layout
-size_t phase_exact_lds_bytes(int Lmax, int G, int kind) { const int S = SD_PHASE_BLOCK / G; return ((size_t)lds_ls(S, kind == 1 ? NFW_LOVE : NFW) * Lmax + (size_t)24 * S) * sizeof(float); }
 int phase_exact_team(int Lmax, int kind)
 {
     int G = 16;
-    while (G < 64 && phase_exact_lds_bytes(Lmax, G, kind) > 64u * 1024u) G *= 2;
+    while (G < 64 && phase_lds_bytes(Lmax, G, kind) > 64u * 1024u) G *= 2;
     return G;
 }
 
@@ -2940,15 +2902,13 @@ hipError_t launch_phase(hipStream_t s, int kind, int G, bool independent, const 
 
 hipError_t launch_kern_transpose(hipStream_t s, const KernTransposeArgs &a)
 {
-    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 3u);
-    hipLaunchKernelGGL(surfdisp_kern_transpose_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(surfdisp_kern_transpose_kernel, rows_grid(a.B, a.P, a.Lmax, 3u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_eigen_transpose(hipStream_t s, const EigenTransposeArgs &a)
 {
-    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 4u);
-    hipLaunchKernelGGL(surfdisp_eigen_transpose_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(surfdisp_eigen_transpose_kernel, rows_grid(a.B, a.P, a.Lmax, 4u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -2979,8 +2939,7 @@ hipError_t launch_shift(hipStream_t s, const ShiftArgs &a)
 
 hipError_t launch_group_combine(hipStream_t s, const GroupCombineArgs &a)
 {
-    const dim3 grid((unsigned)(a.P * ((a.B + 63) / 64)), (unsigned)((a.Lmax + 63) / 64), 3u);
-    hipLaunchKernelGGL(surfdisp_group_combine_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(surfdisp_group_combine_kernel, rows_grid(a.B, a.P, a.Lmax, 3u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -3373,39 +3332,31 @@ __global__ __launch_bounds__(256) void surfdisp_ellip_kern_kernel(EllipKernArgs 
     if (top == -2 && A.n_nonfinite) atomicAdd(A.n_nonfinite, 1);
 }
 
-// K5d: share + gamma x F-share -> the caller's [B][P][Lmax] rows through an LDS tile (as surfdisp_kern_transpose_kernel);
-// zeros below the unit's half space and for units without partials, NaN for every entry of a non-finite unit
+// K5d: share + gamma x F-share -> the caller's [B][P][Lmax] rows (rows_through_tile, surfdisp_k_rows.h); zeros below the
+// unit's half space and for units without partials, NaN for every entry of a non-finite unit (khs == -2).  blockIdx.z: 0
+// dchi/dVs, 1 dchi/dVp, 2 dchi/drho.
 __global__ __launch_bounds__(256) void surfdisp_ellip_transpose_kernel(EllipTransposeArgs A)
 {
-    __shared__ float tile[64][65];
     const int B = A.B, P = A.P, Lmax = A.Lmax;
     float *__restrict__ out = (blockIdx.z == 0) ? A.eb : ((blockIdx.z == 1) ? A.ea : A.er);
     if (!out) return;                                        // (block-uniform)
     const size_t PB = (size_t)P * B;
     const float *__restrict__ xs = A.xscr + (size_t)blockIdx.z * Lmax * PB;
     const float *__restrict__ fsr = A.fscr + (size_t)blockIdx.z * Lmax * PB;
-    const int nbb = (B + 63) / 64;
-    const int k = blockIdx.x / nbb, b0 = (blockIdx.x % nbb) * 64, i0 = blockIdx.y * 64;
-    const int bl = threadIdx.x % 64;
+    const RowTile t = row_tile(B);
     float g = 0.0f; int hs = -1;
-    if (b0 + bl < B) { g = A.gam[(size_t)k * B + b0 + bl]; hs = A.khs[(size_t)k * B + b0 + bl]; }
-    for (int il = threadIdx.x / 64; il < 64; il += 4) {
-        const size_t o = (size_t)(i0 + il) * PB + (size_t)k * B + b0 + bl;
-        tile[il][bl] = (hs == -2) ? __int_as_float(0x7fc00000) : ((i0 + il <= hs) ? fmaf(g, fsr[o], xs[o]) : 0.0f);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 64 * 64; t += 256) {
-        const int bq = t / 64, il = t % 64;
-        if (i0 + il < Lmax && b0 + bq < B) out[((size_t)(b0 + bq) * P + k) * Lmax + i0 + il] = tile[il][bq];
-    }
+    if (t.live) { g = A.gam[t.un]; hs = A.khs[t.un]; }
+    rows_through_tile(t, B, P, Lmax, out, [&](int i) {
+        const size_t o = (size_t)i * PB + t.un;
+        return (hs == -2) ? __int_as_float(0x7fc00000) : ((i <= hs) ? fmaf(g, fsr[o], xs[o]) : 0.0f);
+    });
 }
 
 hipError_t launch_ellip_kern(hipStream_t s, const EllipKernArgs &a, const EllipTransposeArgs &t)
 {
     const size_t total = (size_t)a.B * a.P;
     hipLaunchKernelGGL(surfdisp_ellip_kern_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
-    const dim3 grid((unsigned)(t.P * ((t.B + 63) / 64)), (unsigned)((t.Lmax + 63) / 64), 3u);
-    hipLaunchKernelGGL(surfdisp_ellip_transpose_kernel, grid, dim3(256), 0, s, t);
+    hipLaunchKernelGGL(surfdisp_ellip_transpose_kernel, rows_grid(t.B, t.P, t.Lmax, 3u), dim3(256), 0, s, t);
     return hipGetLastError();
 }
 

@@ -8,9 +8,11 @@ surfdisp_last_error() text of one deliberately bad call per entry and kind of re
                                                  (part: device | host; the host part reads SURFDISP_HOST_CHUNK / _SLOTS)
 
 Device part: BatchPlan.run (plain, want_ratio, events, timed), run_kernels (both routes), run_group_kernels,
-run_ellip_kernels, run_atten, run_eigen, run_thickness_kernels on a ragged 3 x L6 x P4 batch, the sediment_R family of
-tests/golden/ref_families.npz, 256 x L10 x P20 and 64 x L64 x P19; both wave types; flags none / PHASE_ONLY / INDEPENDENT /
-PIPELINED / STRICT where the entry accepts them; forced teams 0, 2, 16, 64.  Host part: surfdisp_forward_batch on one stack
+run_ellip_kernels, run_atten, run_eigen, run_thickness_kernels, run_group_thickness_kernels on a ragged 3 x L6 x P4 batch, the
+sediment_R family of tests/golden/ref_families.npz, 256 x L10 x P20, 64 x L64 x P19 and the two batches of
+tests/kernel_rows_ref.py that cross the 64-unit and 64-layer tile edges of the rows kernels (deep 130 x L70, tall 66 x L129, periods
+10 / 30 / 100 s); both wave types; flags none / PHASE_ONLY / INDEPENDENT / PIPELINED / STRICT where the entry accepts them; forced
+teams 0, 2, 16, 64.  Host part: surfdisp_forward_batch on one stack
 (the arena path) and on 40 000 x L10 x P20 (chunked when SURFDISP_HOST_CHUNK=163840: three chunks)."""
 import ctypes
 import os
@@ -27,8 +29,12 @@ TEAMS = (0, 2, 16, 64)
 
 def shapes():
     from pysurfinv_amd import synth
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import kernel_rows_ref as kr
     z = np.load(os.path.join(ROOT, "tests", "golden", "ref_families.npz"))
-    return {"ragged3": (synth.synth_models(3, 6, seed=5), synth.default_periods(4), np.array([6, 4, 2], np.int32)),
+    tiles = np.array([10.0, 30.0, 100.0], np.float32)
+    return {"deep": kr.deep_batch()[:1] + (tiles,) + kr.deep_batch()[1:], "tall": kr.tall_batch()[:1] + (tiles,) + kr.tall_batch()[1:],
+            "ragged3": (synth.synth_models(3, 6, seed=5), synth.default_periods(4), np.array([6, 4, 2], np.int32)),
             "sediment": (z["sediment_R/model"], z["sediment_R/periods"].astype(np.float32), z["sediment_R/nlay"].astype(np.int32)),
             "b256": (synth.synth_models(256, 10, seed=11), synth.default_periods(20), None),
             "l64": (synth.synth_models(64, 64, seed=3), synth.default_periods(19), None)}
@@ -75,6 +81,7 @@ def dump_device(out):
                     keep(key + "/atten", plan.run_atten(dm, dp, kind=k, nlay=dn))
                     keep(key + "/eigen", plan.run_eigen(dm, dp, kind=k, nlay=dn))
                     keep(key + "/thickness", plan.run_thickness_kernels(dm, dp, kind=k, nlay=dn))
+                    keep(key + "/group_thickness", plan.run_group_thickness_kernels(dm, dp, kind=k, nlay=dn))
         L.surfdisp_set_team(0)
         torch.cuda.synchronize()
     res.update(bad_calls(L, _lib, torch))

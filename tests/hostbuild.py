@@ -15,8 +15,8 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 
 
 def sources(src):
-    """What a harness is built from: itself, every csrc/*.hip and *.h (surfdisp_kernels.hip includes its first stages as
-    surfdisp_k_*.h, and the argument blocks live in surfdisp_internal.h) and the public header."""
+    """What a harness is built from: itself, every csrc/*.hip and *.h (surfdisp_kernels.hip includes its first stages
+    and the rows walk of its last ones as surfdisp_k_*.h, and the argument blocks live in surfdisp_internal.h) and the public header."""
     return [src, *glob.glob(os.path.join(CSRC, "*.hip")), *glob.glob(os.path.join(CSRC, "*.h")), os.path.join(INCLUDE, "surfdisp.h")]
 
 

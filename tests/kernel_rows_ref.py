@@ -211,6 +211,27 @@ def deep_batch():
     return m.copy(), nlay.copy()
 
 
+TALL_PICKS = (0, 1, 63, 64, 65, 7, 20, 21)           # both sides of the 64-stack tile edge, of layers 64 and 128, a shallow stack
+
+
+@functools.lru_cache(maxsize=None)
+def _tall_batch():
+    """Three 64-layer tiles, the last with ONE row: B = 66 (a full 64-stack tile and one with two stacks), Lmax = 129 ->
+    (model [66, 5, 129], nlay int32 [66]).  Monotone stacks, nlay ragged in 3 .. 129 with stacks 0, 1, 63, 64, 65, 7, 20, 21
+    at 129, 128, 129, 65, 64, 3, 127, 66 layers."""
+    from pysurfinv_amd import synth
+    m = synth.synth_models(66, 129, seed=31, noise=0.03, monotone=True)
+    nlay = np.random.default_rng(9).integers(3, 130, 66).astype(np.int32)
+    for s, n in zip(TALL_PICKS, (129, 128, 129, 65, 64, 3, 127, 66)):
+        nlay[s] = n
+    return m, nlay
+
+
+def tall_batch():
+    m, nlay = _tall_batch()
+    return m.copy(), nlay.copy()
+
+
 CHAIN_PERIODS = (6.0, 10.0, 25.0, 60.0, 100.0)
 
 

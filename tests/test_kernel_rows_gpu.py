@@ -271,6 +271,88 @@ def test_deep_batch_atten_own_output_consistency(kind):
     assert eq < 1e-5 and eg < 1e-5 and ed < 1e-5
 
 
+# entry -> indices of (the rows with a 1e-5 bar, those with a 1e-3 bar, the rows compared bit for bit, the rows that may be NaN)
+TALL_ENTRIES = {"run_kernels": ((3, 4, 5), (), (), ()), "run_group_kernels": ((3, 4, 5, 6, 7, 8), (), (), (6, 7, 8)),
+                "run_eigen": ((), (), (3, 4, 5, 6), ()), "run_ellip_kernels": ((4, 5, 6), (7, 8, 9), (), (7, 8, 9))}
+TALL_KINDS = [(e, k) for e in TALL_ENTRIES for k in (2, 1) if not (e == "run_ellip_kernels" and k == 1)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry,kind", TALL_KINDS)
+def test_three_layer_tiles_with_a_one_row_last_tile(entry, kind):
+    """(3) past layer 127: B = 66, Lmax = 129, P = 3 (kernel_rows_ref.tall_batch: three 64-layer tiles, the last with one row;
+    a full 64-stack tile and one with two stacks).  For run_kernels, run_group_kernels, run_eigen (both wave types) and
+    run_ellip_kernels (Rayleigh) the rows of stacks 0, 1, 63, 64, 65, 7, 20, 21 (129, 128, 129, 65, 64, 3, 127, 66 layers) equal
+    BatchPlan(1, nlay[s], P) launches under the bars of the deep batch above - phase partials and dU to 1e-5 of the period's
+    peak, ellipticity rows to 1e-3 - and the eigenfunction rows and energy words under test_eigen_ragged_batch's: bit for bit,
+    at the batch's team size; everything at and beyond nlay[b] is exactly zero; NaN rows are whole rows; of the units of the
+    picked stacks with 128 layers or more at least 90 % are solved; some unit has a non-zero entry at layer index 128 (the
+    CPU oracle's partials of stacks 0 and 63 reach the last layer at 30 and 100 s, at 10 s they end near layer 75).
+    Measured on MI355X (profiles/row_tile/tall_batch.txt): every compared value equal (scalars and rows worst 0.0 for all seven
+    cases, the eigenfunction rows and energy words bit for bit); Rayleigh solves 198 of 198 units, Love 183 of 198, both 9 of 9
+    units of the picks with 128 layers or more; 4 units have a non-zero entry at layer 128 (as many as the oracle has: stacks
+    0 and 63 at 30 and 100 s)."""
+    from pysurfinv_amd import _lib, forward
+    m, nlay = kr.tall_batch()
+    per = np.asarray(DEEP_PERIODS, np.float32)
+    B, _, L = m.shape
+    assert (B, L) == (66, 129)
+    rows5, rows3, rowsb, nanable = TALL_ENTRIES[entry]
+    dm, dp, dn = _dev(m, per, nlay)
+    out = _np(*getattr(forward.BatchPlan(B, L, per.size), entry)(dm, dp, kind=kind, nlay=dn))
+    c = out[0]
+    for q in rows5 + rows3 + rowsb:
+        if out[q] is None:
+            assert kind == 1
+            continue
+        r = out[q]
+        assert r.shape == (B, per.size, L)
+        nanrow = np.isnan(r).any(axis=2)
+        assert np.array_equal(np.isnan(r).all(axis=2), nanrow), q      # NaN rows are whole rows
+        assert q in nanable or not nanrow.any(), q
+        for b in range(B):                                             # (a NaN row is masked out here: the line above has shown it whole)
+            assert not np.where(nanrow[b][:, None], 0.0, r[b])[:, nlay[b]:].any(), (q, b)
+    tall = [s for s in kr.TALL_PICKS if nlay[s] >= 128]
+    solved = int((c[tall] > 0).sum())
+    first = out[(rows5 + rowsb)[0]]
+    last_layer = int((np.nan_to_num(first[:, :, 128]) != 0).sum())
+    lib = _lib.lib()
+    team = lib.surfdisp_get_team2(B, L, per.size, kind) if rowsb else 0
+    worst5, worst3, worsts, nbits = 0.0, 0.0, 0.0, 0
+    assert lib.surfdisp_set_team(team) == 0
+    try:
+        for s in kr.TALL_PICKS:
+            n = int(nlay[s])
+            d1, _, _ = _dev(m[s:s + 1, :, :n], per, None)
+            one = _np(*getattr(forward.BatchPlan(1, n, per.size), entry)(d1, dp, kind=kind))
+            assert one[2][0] == out[2][s]
+            if rowsb:                                                   # (the eigen entry: c, u, rows and energy bit for bit)
+                for q in (0, 1) + rowsb:
+                    assert np.array_equal(out[q][s][..., :n] if q in rowsb else out[q][s], one[q][0]), (entry, kind, s, q)
+                assert np.array_equal(out[7][s], one[7][0]), (entry, kind, s, "energy")
+                nbits += 1
+                continue
+            for q in (0, 1):
+                assert np.array_equal(out[q][s] == 0, one[q][0] == 0), (s, q)
+                assert np.allclose(out[q][s], one[q][0], rtol=1e-5, atol=0), (s, q, out[q][s], one[q][0])
+                nzv = one[q][0] != 0
+                if nzv.any():
+                    worsts = max(worsts, float(np.abs(out[q][s][nzv] / one[q][0][nzv] - 1.0).max()))
+            for q in rows5:
+                if out[q] is not None:
+                    worst5 = max(worst5, _rows_vs_single(out[q][s][:, :n], one[q][0], 1e-5, (entry, kind, s, q)))
+            for q in rows3:
+                worst3 = max(worst3, _rows_vs_single(out[q][s][:, :n], one[q][0], 1e-3, (entry, kind, s, q)))
+    finally:
+        lib.surfdisp_set_team(0)
+    print(f"tall batch {entry} kind {kind}: solved {int((c > 0).sum())} of {c.size} units, {solved} of {3 * len(tall)} of the picks with >= 128 "
+          f"layers; units with a non-zero entry at layer 128: {last_layer}; batch vs one-stack launches: "
+          + (f"{nbits} stacks bit for bit" if rowsb else f"scalars {worsts:.2e} (rtol 1e-5), rows {worst5:.2e} of peak (bar 1e-5)")
+          + (f", ellipticity rows {worst3:.2e} (bar 1e-3)" if rows3 else ""))
+    assert solved >= 0.9 * 3 * len(tall), solved
+    assert last_layer > 0
+
+
 # ------------------------------------------------------------------------------------------------------- (4) NULL outputs
 @pytest.mark.gpu
 @pytest.mark.parametrize("entry,kind", [("run_kernels", 2), ("run_kernels", 1), ("run_kernels_direct", 2), ("run_kernels_direct", 1),
