@@ -48,6 +48,7 @@
 #include "surfdisp_k_common.h"
 #include "surfdisp_k_prep.h"
 #include "surfdisp_k_secular.h"
+#include "surfdisp_k_scan.h"
 #include "surfdisp_k_rows.h"
 
 namespace sd {
@@ -94,7 +95,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
     const unsigned long long wcyc0 = __builtin_readcyclecounter();
     unsigned long long wcyc_eval = 0, wcyc_build = 0, wcyc_pre = 0, wpasses = 0;
     // ... and inside the Rayleigh evaluation (head, layer loop, closure), the lean scan pass's decision block, lean passes
-    unsigned long long wsec[3] = {0, 0, 0}, wcyc_lean = 0, wn_lean = 0;
+    unsigned long long wsec[3] = {0, 0, 0}, wcyc_lean = 0, wn_lean = 0, wn_double = 0;   // (wn_double: lean passes of two rounds)
     // team-passes by state, layers stepped per pass (the wavefront's trip count = max over lanes) and summed over lanes
     unsigned long long wn_scan = 0, wn_refine = 0, wn_nevill = 0, wn_ellip = 0, wn_idle = 0, wtrip = 0, wlanelayers = 0, wlanes = 0;
 #endif
@@ -348,6 +349,20 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
 #else
     constexpr bool LEAN_BHS = LEAN && (KIND == 2);
 #endif
+    // LEAN2 (the same instantiation, lock step): a lean pass evaluates TWO grid points per lane, one after the other through
+    // the one copy of the evaluation - A, the point of a single pass, then B two grid steps further up - and the team
+    // decides once over its four points in grid order (lane 0 A, lane 1 A, lane 0 B, lane 1 B: scan_decide4,
+    // surfdisp_k_scan.h), with the outcome of two consecutive lean passes: the priority test, the state tests, the trial
+    // choice's selects and the bracket / carry bookkeeping are paid once per four grid points instead of once per two.
+    // Between the evaluations only A's events are formed (wavefront masks in scalar registers; a lane keeps A's value and
+    // mm): a team with a crossing, the guard, a non-finite value or a pending deferral at A sits B out as a waiting team
+    // does, and when no team is left to scan on, B is not run at all - the wavefront evaluates exactly the rounds it did.
+    // Without lock step a bracket starts refining in the very next pass: those launches take the general body.
+#ifdef SD_NO_DOUBLE_SCAN
+    constexpr bool LEAN2 = false;
+#else
+    constexpr bool LEAN2 = LEAN_BHS;
+#endif
     // NEVILL's prologue, surfa.f:12-16, from the scan's bracket (del1 is the scan's value, whatever layer dropping it was computed
     // with - as in the reference)
     auto nevill_start = [&]() {
@@ -379,7 +394,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
                 else __builtin_amdgcn_s_setprio(0);
             }
         }
-        const bool lean = LEAN && A.scan_general == 0 && __all(st == ST_SCAN || st == ST_WREF || st == ST_DONE);
+        const bool lean = LEAN && A.scan_general == 0 && (!LEAN2 || LOCK) && __all(st == ST_SCAN || st == ST_WREF || st == ST_DONE);
         // ---------------------------------------------------------------- choose the trial point
         float cj = 1.0f;
         int mmj = 2, start = 1;
@@ -432,10 +447,10 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         float val = 0.0f, phj = 0.0f;
         int kcj = 0; bool kuncj = false;                       // Sturm count of this lane's trial (CERT)
 #ifdef SD_WAVECLOCK
-        const unsigned long long we0 = __builtin_readcyclecounter();
+        unsigned long long we0 = __builtin_readcyclecounter();
         wcyc_pre += we0 - wp0;                                 // priority, trial velocities, layer dropping
         ++wpasses;
-        {
+        auto wcount = [&]() {                                  // (once per evaluation round: LEAN2 runs two in a pass)
             const unsigned long long lead = __ballot(j == 0);
             wn_scan += __popcll(__ballot(st == ST_SCAN) & lead); wn_refine += __popcll(__ballot(st == ST_REFINE) & lead);
             wn_nevill += __popcll(__ballot(st == ST_NEVILL) & lead); wn_ellip += __popcll(__ballot(st == ST_ELLIP) & lead);
@@ -443,10 +458,19 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             int mx = eval ? mmj : 0, sm = eval ? mmj : 0;
             for (int d = 32; d > 0; d >>= 1) { mx = max(mx, __shfl_xor(mx, d)); sm += __shfl_xor(sm, d); }
             wtrip += mx; wlanelayers += sm; wlanes += __popcll(__ballot(eval));
-        }
+        };
+        wcount();
 #endif
         float vmag = 0.0f;                                     // magnitude of the terms the value is the sum of (production recursion)
         [[maybe_unused]] float bhsj = 0.0f;                    // b of this lane's effective half space (LEAN_BHS)
+        // LEAN2: what a lane keeps of its point A while it evaluates point B - the value and mm in two registers, the raw guard
+        // test as a lane mask - and "second": this pass ran both rounds
+        [[maybe_unused]] float a_val = 0.0f;
+        [[maybe_unused]] int a_mm = 0;
+        [[maybe_unused]] bool a_g = false, second = false;
+        // (one code instance of the evaluation for both points: the loop stays rolled, so A and B run the same instructions)
+#pragma nounroll
+        for (;;) {
         if (eval) {
             const bool want_mag = want_ratio && st == ST_ELLIP;   // (the in-kernel ellipticity passes' cancellation test)
             if (KIND == 2) val = EXACT ? delta_rayleigh_ref(wq, LS, S, mmj, cj, T, start)
@@ -466,6 +490,39 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
             else           val = EXACT ? delta_love_ref(wq, LS, S, mmj, cj, T)
                                        : delta_love<CERT, (G <= 16)>(wq, LS, S, mmj, cj, T, phj, kcj, kuncj, coarse);   // counts only where they are compared: coarse passes
         }
+        if constexpr (LEAN2) {
+            if (lean && !second) {
+                // point A's events.  The teams that scan on: no crossing, no guard, every value finite, no deferral pending
+                // (entry_overflow_risk at the period's start, acted on at the end of its first pass)
+                const bool scan = (st == ST_SCAN);
+                const float od = pair_swap(val);
+                bool cr;
+                const bool g = (cj < 0.8f * b1top) || !(cj < bhsj + 0.3f);             // calcul.f:165-166
+                const bool ev = scan_event((j == 0) ? p0d : od, !(first && j == 0), val, g, &cr);
+                const int hit = (int)(scan && (ev || defer || !fin(val)));
+                const bool go = scan && ((hit | pair_swap(hit)) == 0);                 // (neither lane of the team)
+                if (__any(go)) {
+#ifdef SD_WAVECLOCK
+                    const unsigned long long wa0 = __builtin_readcyclecounter();
+                    wcyc_eval += wa0 - we0;
+#endif
+                    second = true;
+                    a_val = val; a_mm = mmj; a_g = g;
+                    eval = go;
+                    cj = cj + DC; cj = cj + DC;                // the grid of the next single pass: its p0c is lane 1's A
+                    mmj = nodrop ? (n < 2 ? 2 : n) : drop_layers(wq, LS, S, n, cj, T);
+                    val = 0.0f;
+#ifdef SD_WAVECLOCK
+                    we0 = __builtin_readcyclecounter();
+                    wcyc_pre += we0 - wa0; ++wn_double;
+                    wcount();
+#endif
+                    continue;
+                }
+            }
+        }
+        break;
+        }
         // The in-kernel ellipticity passes (two-lane teams): a closure that is the remainder of a cancellation - |value| below
         // A.ell_ambig of the terms it is the sum of - marks the (stack, period) for the ellipticity kernel, which evaluates both
         // passes with the reference's arithmetic on the replayed working stack (see there)
@@ -476,7 +533,72 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         const unsigned long long wl0 = __builtin_readcyclecounter();
         wcyc_eval += wl0 - we0;
 #endif
-        if (lean) {
+        if constexpr (LEAN2) if (lean) {
+            // ------------------------------------------------------------ lean scan pass of one or two rounds (see LEAN2)
+            // Every lane of a team gathers the team's points in grid order - values and mm from the other lane by DPP, the
+            // trial velocities by the grid's own additions from p0c - and takes the same decision.
+            const bool scan = (st == ST_SCAN);
+            const bool j0 = (j == 0);
+            const ScanPt p0 = {p0d, p0c, p0mm, false};
+            const float c0 = first ? p0c : p0c + DC, c1 = c0 + DC;
+            const float av = second ? a_val : val;
+            const int am = second ? a_mm : mmj;
+            const bool ag = second ? a_g : ((cj < 0.8f * b1top) || !(cj < bhsj + 0.3f));
+            const float oav = pair_swap(av);
+            const int oam = pair_swap(am);
+            const bool oag = pair_swap((int)ag) != 0;
+            ScanOut o;
+            bool allfin;
+            if (second) {
+                const float c2 = c1 + DC, c3 = c2 + DC;
+                const bool bg = (cj < 0.8f * b1top) || !(cj < bhsj + 0.3f);
+                const float obv = pair_swap(val);
+                const int obm = pair_swap(mmj);
+                const bool obg = pair_swap((int)bg) != 0;
+                const ScanPt pt[4] = {{j0 ? av : oav, c0, j0 ? am : oam, j0 ? ag : oag}, {j0 ? oav : av, c1, j0 ? oam : am, j0 ? oag : ag},
+                                      {j0 ? val : obv, c2, j0 ? mmj : obm, j0 ? bg : obg}, {j0 ? obv : val, c3, j0 ? obm : mmj, j0 ? obg : bg}};
+                o = scan_decide4(p0, first, pt);
+                allfin = fin(av) && fin(oav) && fin(val) && fin(obv);   // (a team with its event at A has not evaluated B: 0)
+            } else {
+                const ScanPt pt[2] = {{j0 ? av : oav, c0, j0 ? am : oam, j0 ? ag : oag}, {j0 ? oav : av, c1, j0 ? oam : am, j0 ? oag : ag}};
+                o = scan_decide2(p0, first, pt);
+                allfin = fin(av) && fin(oav);
+            }
+            if (scan && !allfin) defer = true;                 // -> exact fallback kernel
+            bool failed = false;
+            if (scan) {
+                if (o.e >= 0 && o.cross) {                     // bracket found -> refine (see the general body)
+                    p0c = o.lo.c; p0d = o.lo.v; cb = o.hi.c; db = o.hi.v; mm_frozen = o.hi.mm; p0mm = o.lo.mm;
+                    p0ok = (o.lo.mm == o.hi.mm);
+                    if (o.e >= 2) first = false;
+                    passes = 0;
+                    st = ST_WREF;                              // (LOCK: see lean)
+                } else if (o.e >= 0) {
+                    failed = true;                             // label 250
+                } else {
+                    p0c = o.lo.c; p0d = o.lo.v; p0mm = o.lo.mm; first = false;
+                    passes += second ? 2 : 1;
+                    if (passes > 100000) failed = true;
+                }
+            }
+            if (defer) {
+                if (j == 0) A.fb_list[atomicAdd(A.fb_count, 1)] = (int)tg;
+                defer = false; st = ST_DONE; failed = false;
+            }
+            if (failed) {
+                status = (k == 0) ? SURFDISP_NOROOT : SURFDISP_PARTIAL;
+                st = ST_DONE;
+            }
+            if (!__any(st == ST_SCAN) && st == ST_WREF) {      // (no team ends its period in a scan pass)
+                st = ST_REFINE;
+                if (bracket_phase(p0c, cb, mm_frozen) > A.phimulti) nevill_start();
+            }
+#ifdef SD_WAVECLOCK
+            wcyc_lean += __builtin_readcyclecounter() - wl0; ++wn_lean;
+#endif
+            continue;
+        }
+        if (!LEAN2 && lean) {
             // ------------------------------------------------------------ lean scan pass (see LEAN)
             // What the general body below does for ST_SCAN, ST_WREF and ST_DONE teams, and nothing else.  Per team, the lane q
             // whose trial is kept: the first one with a crossing or the guard (bracket: q and the trial before it), else the
@@ -945,7 +1067,7 @@ __device__ __forceinline__ void phase_body(const PhaseArgs &A)
         o[4] = wcyc_build; o[5] = wpasses; o[6] = wcyc_pre;
         o[7] = wn_scan; o[8] = wn_refine; o[9] = wn_nevill; o[10] = wn_ellip; o[11] = wn_idle;
         o[12] = wtrip; o[13] = wlanelayers; o[14] = wlanes; o[15] = wsec[0];
-        o[16] = wsec[1]; o[17] = wsec[2]; o[18] = wcyc_lean; o[19] = wn_lean;
+        o[16] = wsec[1]; o[17] = wsec[2]; o[18] = wcyc_lean; o[19] = wn_lean; o[20] = wn_double;
     }
 #endif
     if (INDEP) {
