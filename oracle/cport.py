@@ -49,8 +49,29 @@ def lib():
         L.surfdisp_oracle_partials.restype = ctypes.c_int
         L.surfdisp_oracle_partials.argtypes = [ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ctypes.c_float,
                                                dp, dp, dp, dp, ip, ip, fp, fp]
+        L.surfdisp_oracle_flatten.restype = ctypes.c_int
+        L.surfdisp_oracle_flatten.argtypes = [ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp]
         _lib = L
     return _lib
+
+
+def flatten(h, kind, nlay=None, variant=0):
+    """The factors the oracle's flat1 applies to the stacks with thicknesses h [B, L] (float32; nlay [B]: layers of each): dict of
+    dif, qqq, dfl, hsf, hsr float32 [B, L], zero beyond nlay (surfdisp_oracle_flatten).  variant: surfdisp_oracle_set_variant for the
+    duration of the call (2: log / pow in double precision rounded once)."""
+    h = np.ascontiguousarray(h, np.float32)
+    B, L = h.shape
+    n = np.full(B, L, np.int64) if nlay is None else np.asarray(nlay, np.int64)
+    out = {k: np.zeros((B, L), np.float32) for k in ("dif", "qqq", "dfl", "hsf", "hsr")}
+    lib().surfdisp_oracle_set_variant(int(variant))
+    try:
+        for b in range(B):
+            rc = lib().surfdisp_oracle_flatten(int(n[b]), int(kind), _fp(h[b]), *[_fp(out[k][b]) for k in ("dif", "qqq", "dfl", "hsf", "hsr")])
+            if rc != 0:
+                raise RuntimeError(f"surfdisp_oracle_flatten: stack {b} returned {rc}")
+    finally:
+        lib().surfdisp_oracle_set_variant(0)
+    return out
 
 
 def _f32(a):

@@ -116,6 +116,30 @@ static void flat1(float *h, float *ro, float *vp, float *vs, int n, int kind)
     h[n - 1] = 0.0f;
 }
 
+/* Test read-out (not the reference): the factors flat1 applies, for every prefix length n = 1 .. nlay of the thicknesses h.  flat1
+ * runs on unit vp and rho, so what it leaves IS the factor: dif, qqq and the new thickness dfl of the regular layers i < nlay - 1
+ * (from the full-length call), hsf and hsr of layer n - 1 used as the half space (from the call of length n).  Arrays of nlay floats;
+ * entries a call does not define are 0.  Returns the number of regular-layer factors a shorter call forms differently from the
+ * full-length one (0: they depend on the radii alone), or -1 for a bad nlay. */
+int surfdisp_oracle_flatten(int nlay, int kind, const float *h, float *dif, float *qqq, float *dfl, float *hsf, float *hsr)
+{
+    if (nlay < 1 || nlay > NSZ) return -1;
+    float d[NSZ], ro[NSZ], vp[NSZ], vs[NSZ];
+    int differ = 0;
+    for (int i = 0; i < nlay; ++i) dif[i] = qqq[i] = dfl[i] = hsf[i] = hsr[i] = 0.0f;
+    for (int n = nlay; n >= 1; --n) {
+        for (int i = 0; i < n; ++i) { d[i] = h[i]; ro[i] = vp[i] = vs[i] = 1.0f; }
+        flat1(d, ro, vp, vs, n, kind);
+        hsf[n - 1] = vp[n - 1];
+        hsr[n - 1] = ro[n - 1];
+        for (int i = 0; i < n - 1; ++i) {
+            if (n == nlay) { dif[i] = vp[i]; qqq[i] = ro[i]; dfl[i] = d[i]; }
+            else if (vp[i] != dif[i] || vs[i] != dif[i] || ro[i] != qqq[i] || d[i] != dfl[i]) ++differ;
+        }
+    }
+    return differ;
+}
+
 /* attenuation-dispersed model for period t1 over the first m layers
  * (calcul.f:112-131; phase 2 copies :239-249 and :325-335 are identical) */
 static void build_model(ctx_t *s, float t1, int m)

@@ -64,6 +64,11 @@ int surfdisp_oracle_partials(int nlay, int kind,
  * reference's arithmetic.  For scripts/soak.py's classification of mismatches only; never set by the tests that pin parity. */
 void surfdisp_oracle_set_variant(int v);
 
+/* Test read-out: the earth-flattening factors flat1 applies for every prefix length n = 1 .. nlay of the thicknesses h [nlay] -
+ * dif, qqq, dfl of the regular layers (from the full-length call), hsf, hsr of layer n - 1 as the half space of the call of length n;
+ * five arrays of nlay floats.  Returns how many regular factors a shorter call forms differently (0), or -1 for a bad nlay. */
+int surfdisp_oracle_flatten(int nlay, int kind, const float *h, float *dif, float *qqq, float *dfl, float *hsf, float *hsr);
+
 /* Same signature as the reference's Fortran symbol fast_surf_ (fast_surf.f:2-5). */
 void surfdisp_oracle_fast_surf_(const int *n_layer, const int *kind,
                                 const float *vp, const float *vs, const float *rho,

@@ -161,6 +161,8 @@ def lib() -> ctypes.CDLL:
                                                                        ctypes.c_float] + [vp] * 16 + [ctypes.c_size_t])
     L.surfdisp_group_kernels_shift_offset.restype = ctypes.c_size_t     # test read-out (not in include/surfdisp.h)
     L.surfdisp_group_kernels_shift_offset.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.surfdisp_workspace_prep_offsets.restype = ctypes.c_int           # test read-out (not in include/surfdisp.h)
+    L.surfdisp_workspace_prep_offsets.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
     L.surfdisp_thermal_scratch_bytes.restype = ctypes.c_size_t
     L.surfdisp_thermal_scratch_bytes.argtypes = [ctypes.c_int]
     L.surfdisp_params_to_model_thermal_device.restype = ctypes.c_int

@@ -403,6 +403,20 @@ size_t surfdisp_group_kernels_shift_offset(int B, int Lmax, int P)
     return (size_t)reinterpret_cast<uintptr_t>(layout(nullptr, B, Lmax, P, WS_GROUP).g.cs);   // (null base: the pointer is the offset)
 }
 
+// test read-out (not in include/surfdisp.h): byte offsets, inside a forward workspace, of what the prep kernel writes - the SoA copy
+// mdl [9][Lmax][B], the row copy rows [B][9][Lmax], nl [B], fsafe [B], ovf [3][B] (float / int words).  0 on success.
+int surfdisp_workspace_prep_offsets(int B, int Lmax, int P, size_t out[5])
+{
+    if (B < 1 || Lmax < 2 || P < 1 || !out) return SURFDISP_ERR_INVALID;
+    const Carve w = layout(nullptr, B, Lmax, P, WS_FORWARD).w;                  // (null base: a pointer is its offset)
+    out[0] = (size_t)reinterpret_cast<uintptr_t>(w.mdl);
+    out[1] = (size_t)reinterpret_cast<uintptr_t>(w.rows);
+    out[2] = (size_t)reinterpret_cast<uintptr_t>(w.nl);
+    out[3] = (size_t)reinterpret_cast<uintptr_t>(w.fsafe);
+    out[4] = (size_t)reinterpret_cast<uintptr_t>(w.ovf);
+    return SURFDISP_SUCCESS;
+}
+
 // introspection: n words from fb_count on of the last solve that used this workspace.  Waits for `stream`.
 static int read_counters(void *stream, const void *workspace, int B, int Lmax, int P, int *counts, int n)
 {

@@ -20,6 +20,21 @@ extern "C" int sd_hostcheck_prep_rows(int B, int Lmax, const int *nlay, const fl
     return 0;
 }
 
+// prep_stack's per-stack verdict and statistics: nl [B], fsafe [B], ovf [3][B]
+extern "C" int sd_hostcheck_prep_stats(int B, int Lmax, const int *nlay, const float *model, int kind, int *nl, float *fsafe, float *ovf)
+{
+    std::vector<float> rows((size_t)B * 9 * Lmax);
+    sd::PrepArgs pa{B, Lmax, nlay, model, nullptr, nl};
+    pa.rows = rows.data();
+    pa.write_soa = 0;
+    pa.fsafe = fsafe;
+    pa.ovf = ovf;
+    for (int b = 0; b < B; ++b) {
+        if (kind == 2) sd::prep_stack<2>(pa, b); else sd::prep_stack<1>(pa, b);
+    }
+    return 0;
+}
+
 extern "C" int sd_hostcheck_group(int B, int Lmax, const int *nlay, const float *model, int P,
                                   const float *per, int kind, const float *c, const float *ratio,
                                   float *u, double *dbg)

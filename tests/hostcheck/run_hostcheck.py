@@ -44,6 +44,17 @@ def host_prep_rows(model, kind, nlay=None):
     return rows, nl
 
 
+def host_prep_stats(model, kind, nlay=None):
+    """prep_stack compiled for the host: (nl int32 [B], fsafe float32 [B], ovf float32 [3, B])."""
+    model = np.ascontiguousarray(model, np.float32)
+    B, _, L = model.shape
+    nl, fsafe, ovf = np.zeros(B, np.int32), np.zeros(B, np.float32), np.zeros((3, B), np.float32)
+    ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    nlay = None if nlay is None else np.ascontiguousarray(nlay, np.int32)
+    H.sd_hostcheck_prep_stats(B, L, None if nlay is None else ip(nlay), fp(model), int(kind), ip(nl), fp(fsafe), fp(ovf))
+    return nl, fsafe, ovf
+
+
 def host_kernels(model, per, kind, c, ratio, nlay=None, refcoord=False):
     """The KERN instantiation of group_rayleigh / group_love compiled for the host, at the roots c and ellipticities ratio
     [B, P]: (u [B, P], dcdb, dcda, dcdr [B, P, L]; dcda None for Love).  ``refcoord``: unit chain factors."""

@@ -101,6 +101,64 @@ def prep_factors64(model, kind, nlay=None):
                 hsf=np.where(live, hsf, z), hsr=np.where(live, hsr, z))
 
 
+def prep_bounds(model, kind, nlay=None):
+    """(bound, sel): per field the relative bound [B, L] of an fp32 evaluation in the kernel's operation order against
+    prep_factors64 - derived in tests/test_kernel_rows_host.py::test_prep_factors32_within_the_cancellation_bound_of_float64 - and
+    the entries it holds for (regular layers for dif, qqq, dfl; live layers for hsf, hsr).  Regular layers must be thicker than
+    0.05 km: the bound is for layers far above the radii's ulp."""
+    m, n = _stacks(model, nlay)
+    B, _, L = m.shape
+    p = float(pwr_of(kind))
+    h = np.maximum(m[:, 3, :].astype(np.float64), 1e-30)            # (the half space's 0 is never selected)
+    reg = np.arange(L)[None, :] < n[:, None] - 1
+    live = np.arange(L)[None, :] < n[:, None]
+    assert (h[reg] > 0.05).all()
+    hl = np.where(live, m[:, 3, :].astype(np.float64), 0.0)
+    r_top = R0 - (np.cumsum(hl, axis=1) - hl)                       # radius of the layer's top
+    dr_top = 2.0 ** -12 + np.arange(L)[None, :] * 2.0 ** -17       # ... its fp32 error: i additions and the subtraction
+    dr = dr_top + 2.0 ** -17                                       # (a depth below layer i: one more addition)
+    e = 2.0 ** -24
+    bound = dict(dif=3 * e * R0 / h + 8 * e, qqq=3 * e * R0 / h + 8 * e,
+                 dfl=(2 * (R0 * e + 2.0 ** -17 + dr) + 2.0 ** -17) / h,
+                 hsf=dr_top / r_top + 2 * e, hsr=p * (dr_top / r_top + 2 * e) + 2 * e)
+    return bound, {k: (live if k in ("hsf", "hsr") else reg) for k in FIELDS}
+
+
+ACCUR = np.float32(1.0e-8)           # csrc/surfdisp_k_common.h
+
+
+def prep_stats(model, kind, nlay=None, factors=None):
+    """The per-stack verdict and statistics of ``prep_stack`` restated in numpy, fp32 in its operation order, on the factors of
+    ``prep_factors32``: dict of nl int32 [B] (0: a bad stack), fsafe float32 [B] (the thickest regular layer of a good, monotone
+    stack, else 1e30), hthick (ovf[0]: the thickest flattened layer, 1e30 with a liquid layer below the top), rhomax and bmax
+    (float32: the arguments of the two logarithms, ovf[1] = 2 logf(rhomax), ovf[2] = 4 logf(2 bmax^2)).  hthick, rhomax and bmax
+    are meaningful for good stacks only."""
+    m, n = _stacks(model, nlay)
+    B, _, L = m.shape
+    f32 = np.float32
+    f = prep_factors32(m, kind, np.clip(n, 0, L)) if factors is None else factors
+    idx = np.arange(L)[None, :]
+    ok_n = (n >= 2) & (n <= L)
+    live, reg = (idx < n[:, None]) & ok_n[:, None], (idx < n[:, None] - 1) & ok_n[:, None]
+    vp, vs, rho, h, qs = (m[:, k, :].astype(f32) for k in range(5))
+    with np.errstate(all="ignore"):
+        bad = ~(np.isfinite(vp) & np.isfinite(vs) & np.isfinite(rho) & np.isfinite(h) & np.isfinite(qs)) | ~(vp > 0) | ~(rho > 0) | (vs < 0) | (h < 0)
+        r_n = (f32(R0) - np.cumsum(h, axis=1, dtype=f32)).astype(f32)           # (numpy sums a row of fp32 in order)
+        bad_reg = ~(r_n > 0) | ~np.isfinite(f["dif"]) | ~np.isfinite(f["qqq"])
+        ok = ok_n & ~(bad & live).any(axis=1) & ~(bad_reg & reg).any(axis=1)
+        hmax = np.where(reg, h, f32(0)).max(axis=1).astype(f32)
+        drop = np.zeros((B, L), bool)
+        drop[:, 1:] = (vs[:, 1:] < vs[:, :-1]) | (vp[:, 1:] < vp[:, :-1])
+        mono = ~(drop & live).any(axis=1)
+        hthick = np.where(live, f["dfl"], f32(0)).max(axis=1).astype(f32)
+        liquid = (~(np.abs(vs) > ACCUR) & live & (idx > 0)).any(axis=1)
+        hthick = np.where(liquid, f32(1.0e30), hthick).astype(f32)
+        rhomax = np.where(live, rho * np.maximum(f["qqq"], f["hsr"]), f32(0)).max(axis=1).astype(f32)
+        bmax = np.where(live, (f32(1.06) * vs) * np.maximum(f["dif"], f["hsf"]), f32(0)).max(axis=1).astype(f32)
+    return dict(nl=np.where(ok, n, 0).astype(np.int32), fsafe=np.where(ok & mono, hmax, f32(1.0e30)).astype(f32),
+                hthick=hthick, rhomax=rhomax, bmax=bmax)
+
+
 def chain64(model, periods, kind, factors):
     """Chain factors float64 [B, P, L] per (stack, period, layer) from the fp32 inputs and the per-layer ``factors``
     (``prep_factors32`` for what the kernel multiplies with, ``prep_factors64`` for the exact ones): dbdb, dadb, dada,

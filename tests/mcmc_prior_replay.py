@@ -27,15 +27,16 @@ SLACK_BAND = 1e-9
 EPS_MONO = float(np.finfo(float).eps)                                 # monoIncrease, models.py:8
 
 
-def rule_margins(rules, params):
-    """(good bool [B], slack float [B]) of the PriorRules on the rows of `params` (numpy [B, N]): good is the torch
+def rule_margins(rules, params, rows=None):
+    """(good bool [B], slack float [B]) of the PriorRules on the rows of `params` (numpy [B, N]; `rows`: the local-info row of each,
+    for a model with per-point constants): good is the torch
     ``PriorRules.__call__`` on the CPU in float64; slack the smallest |lhs - rhs| over every inequality the rules test
     (models.py:302-320: jumps between groups, the cap at every grid point, diff >= eps inside a monotone group), restated here
     on the same grid points and checked to give the same verdict."""
     m = rules.model
     t = torch.from_numpy(np.array(params, dtype=np.float64))          # (a copy: the caller's rows may be read-only)
-    good = rules(t).numpy()
-    (z, vs, *_), grp, ngrid = m.seis_prop_grids(t, ref_layer=False)
+    good = rules(t, rows=rows).numpy()
+    (z, vs, *_), grp, ngrid = m.seis_prop_grids(t, rows=rows, ref_layer=False)
     nm = np.asarray([m.GROUP_NAMES[int(q)] for q in grp[0].tolist() if int(q) >= 0])
     vs = vs[:, :nm.size].numpy()
     slack = np.full(vs.shape[0], np.inf)
@@ -72,16 +73,21 @@ def candidate(x, vmin, vmax, step, seed, counter, node, r, G, gidx, exact=True):
     return R.draw_bounded(x, b(vmin), b(vmax), b(step), seed, counter, node, gidx, reset=r >= G, exact=exact)
 
 
-def propose_prior(p, aux, vmin, vmax, step, rules, seed, counter, depth, G, U, chain0=0, given=None):
+def propose_prior(p, aux, vmin, vmax, step, rules, seed, counter, depth, G, U, chain0=0, given=None, rows=None):
     """surfdisp_mcmc_propose_prior_device on the host: p [C, N] -> (out [C, M, N], tries [C, M], margin [C, M], tol [C, M, N],
-    slack [C, M]), M = 2^depth - 1.  aux: None (K = 0; per-chain constants are not replayed here).
+    slack [C, M]), M = 2^depth - 1.  aux: None (K = 0), or the per-chain constants [C, K] the device call is given - then `rows` [C]
+    names the row of the model's local-information table each chain reads, aux must be those rows of the table, and the rules are
+    evaluated with rows=; the draws do not depend on aux.
     given: the device's `out`, whose rows serve as the children's states, so that every node is compared on bit-equal input;
     None: the replay's own tree, and a child inherits the doubt (margin, slack) and the error bound of the state it starts from.
     margin / slack: the smallest over every candidate the node compared, up to and including the chosen one (see the module's
     text); tol: the bound on |device - out| of the chosen candidate (the state's own bound where the node is exhausted and
     proposes its state: 0 on the device's tree)."""
     if aux is not None and np.size(aux):
-        raise NotImplementedError("propose_prior: per-chain constants (K > 0) are not replayed")
+        rows = np.asarray(rows, np.int64)
+        assert np.array_equal(np.asarray(aux, np.float64), rules.model._aux.cpu().numpy()[rows]), "aux is not the table's rows"
+    else:
+        rows = None
     p = np.ascontiguousarray(p, np.float64)
     C, N = p.shape
     M = (1 << depth) - 1
@@ -100,7 +106,7 @@ def propose_prior(p, aux, vmin, vmax, step, rules, seed, counter, depth, G, U, c
             if act.size == 0:
                 break
             v, m, t, u = candidate(x[act], vmin, vmax, step, seed, counter, k, r, G, retry_index(C, N, chain0, r)[act])
-            good, s = rule_margins(rules, v)
+            good, s = rule_margins(rules, v, None if rows is None else rows[act])
             mg[act] = np.minimum(mg[act], m.min(axis=1))
             sl[act] = np.minimum(sl[act], s)
             hit = act[good]
@@ -122,14 +128,26 @@ def marginal(margin, slack):
     return (margin < 1.0) | (slack < SLACK_BAND)
 
 
-def good_starts(rules, spec, C, seed):
-    """C uniform prior draws that satisfy `rules` (the first C good ones of a seeded numpy stream)."""
+def good_starts(rules, spec, C, seed, rows=None):
+    """C uniform prior draws that satisfy `rules` (the first C good ones of a seeded numpy stream).  rows [C]: the local-info row of
+    each chain; chain c then takes the first unused draw that is good at ITS row."""
     rng = np.random.default_rng(seed)
-    keep = []
+    if rows is None:
+        keep = []
+        for _ in range(200):
+            q = spec.vmin + (spec.vmax - spec.vmin) * rng.random((max(4 * C, 256), spec.n))
+            g, _ = rule_margins(rules, q)
+            keep.extend(q[g])
+            if len(keep) >= C:
+                return np.ascontiguousarray(np.array(keep[:C]))
+        raise RuntimeError("good_starts: the prior accepts too few uniform draws")
+    rows = np.asarray(rows, np.int64)
+    out, todo = np.zeros((C, spec.n)), np.arange(C)
     for _ in range(200):
-        q = spec.vmin + (spec.vmax - spec.vmin) * rng.random((max(4 * C, 256), spec.n))
-        g, _ = rule_margins(rules, q)
-        keep.extend(q[g])
-        if len(keep) >= C:
-            return np.ascontiguousarray(np.array(keep[:C]))
+        q = spec.vmin + (spec.vmax - spec.vmin) * rng.random((todo.size, spec.n))
+        g, _ = rule_margins(rules, q, rows[todo])
+        out[todo[g]] = q[g]
+        todo = todo[~g]
+        if todo.size == 0:
+            return np.ascontiguousarray(out)
     raise RuntimeError("good_starts: the prior accepts too few uniform draws")

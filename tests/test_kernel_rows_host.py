@@ -39,24 +39,11 @@ def test_prep_factors32_within_the_cancellation_bound_of_float64(kind):
       hsf : |d r| / r + 2 e at the layer's own top radius r, |d r| <= 2^-12 + i 2^-17;   hsr = (1/hsf)^p: p times that + 2 e.
     Measured: dif 0.70, qqq 0.45 (Love 0.38), dfl 0.62, hsf 0.49, hsr 0.46 (Love 0.52) of these bounds at worst."""
     worst = {k: 0.0 for k in kr.FIELDS}
-    p = float(kr.pwr_of(kind))
     for name, m, nlay in _inputs():
         f32, f64 = kr.prep_factors32(m, kind, nlay), kr.prep_factors64(m, kind, nlay)
-        B, _, L = m.shape
-        n = np.full(B, L) if nlay is None else np.asarray(nlay)
-        h = np.maximum(m[:, 3, :].astype(np.float64), 1e-30)            # (the half space's 0 is never selected)
-        reg = np.arange(L)[None, :] < n[:, None] - 1
-        live = np.arange(L)[None, :] < n[:, None]
-        assert (h[reg] > 0.05).all()                                   # (the bound is for layers far above the radii's ulp)
-        hl = np.where(live, m[:, 3, :].astype(np.float64), 0.0)
-        r_top = kr.R0 - (np.cumsum(hl, axis=1) - hl)                    # radius of the layer's top
-        dr_top = 2.0 ** -12 + np.arange(L)[None, :] * 2.0 ** -17       # ... its fp32 error: i additions and the subtraction
-        dr = dr_top + 2.0 ** -17                                       # (a depth below layer i: one more addition)
-        bound = dict(dif=3 * EPS * kr.R0 / h + 8 * EPS, qqq=3 * EPS * kr.R0 / h + 8 * EPS,
-                     dfl=(2 * (kr.R0 * EPS + 2.0 ** -17 + dr) + 2.0 ** -17) / h,
-                     hsf=dr_top / r_top + 2 * EPS, hsr=p * (dr_top / r_top + 2 * EPS) + 2 * EPS)
+        bound, sels = kr.prep_bounds(m, kind, nlay)                    # (the formulas above, shared with the tests of the prep kernel)
         for k in kr.FIELDS:
-            sel = live if k in ("hsf", "hsr") else reg
+            sel = sels[k]
             assert not f32[k][~sel].any() and not f64[k][~sel].any(), (name, k)
             rel = np.abs(f32[k].astype(np.float64)[sel] / f64[k][sel] - 1.0) / bound[k][sel]
             worst[k] = max(worst[k], float(rel.max()))

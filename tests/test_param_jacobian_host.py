@@ -19,12 +19,16 @@ from pysurfinv_amd import paramlsq
 HC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_jaccheck():
     L = ctypes.CDLL(hostbuild.build(os.path.join(HC, "jaccheck.hip"), os.path.join(HC, "libjaccheck.so")))
     L.sd_jaccheck.restype = ctypes.c_int
     L.sd_jaccheck.argtypes = [ctypes.c_int] * 4 + [ctypes.c_void_p] * 5
     return L
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_jaccheck()
 
 
 def host_jacobian(lib, mb, idesc, fdesc, L, p_full, Nu):

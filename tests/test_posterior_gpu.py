@@ -188,7 +188,25 @@ def test_per_point_constants(name):
     _check(f"local {name}, rows = None", mb, mbc, tr, zd)                        # point p reads table row p
 
 
-# ------------------------------------------------------------------ 6. argument errors
+# ------------------------------------------------------------------ 5b. the descriptor zoo
+ZOO_HIST = (1.003, 5.003, 400)        # the zoo's constant velocities (2.4, 3.9, 4.05, ...) would sit on the edges of HIST
+ZOO_DEPTHS = [-0.7, 0.5, 1.2, 2.2, 2.7, 3.5, 4.6, 8.0, 15.0, 25.0, 31.0, 50.0, 100.0, 179.0, 185.0, 205.0]
+
+
+@pytest.mark.parametrize("name", ["ten", "pairs", "moho"])
+def test_descriptor_zoo_settings(name):
+    """tests/descriptor_zoo.py: the cap of ten input layers (SURFDISP_POST_MAX_LAYERS), two layers per group with an 8-slot mantle,
+    and a BottomDepth on a middle layer under a per-point topography.  The bars of _check."""
+    import descriptor_zoo as Z
+    mb, mbc = Z.zoo_model(name, DEV), Z.cpu_model(name)
+    assert mb.native_descriptor() is not None and not mb._native_thermal
+    npnt = 4 if name == "moho" else 3
+    tr = _random_track(mbc, npnt, 300, seed=16)
+    dev = _check(f"zoo {name}", mb, mbc, tr, ZOO_DEPTHS, hist=ZOO_HIST, rows=np.array([2, 0, 3, 1]) if name == "moho" else None)
+    assert int(dev["count"].max()) > 0 and bool((dev["count"][:, 0] == 0).all())   # -0.7 km lies above every stack
+
+
+
 def test_argument_errors_return_before_launch():
     mb = Model1DBatch(CONT, device=DEV)
     idesc, fdesc = posterior._host_descriptor(mb)

@@ -196,20 +196,23 @@ def _gpu_model():
     return Model1DBatch(MCMC_SETTING, device=torch.device("cuda:0"))
 
 
-def _call_prior(p, rules_kw, step, seed, counter, depth, G, U, chain0, exhausted=None):
-    """One call of the entry on the states p (numpy [C, N]) -> (out [C, M, N], tries [C, M], the exhausted counter after it)."""
+def _call_prior(p, rules_kw, step, seed, counter, depth, G, U, chain0, exhausted=None, mb=None, aux=None):
+    """One call of the entry on the states p (numpy [C, N]) -> (out [C, M, N], tries [C, M], the exhausted counter after it).
+    mb: the model on the device (default: MCMC_SETTING's); aux: its per-chain constants, numpy [C, K]."""
     from pysurfinv_amd import _lib
-    mb = _gpu_model()
+    mb = _gpu_model() if mb is None else mb
     rules = PriorRules(mb, **rules_kw)
     idesc, fdesc, L = mb.native_descriptor()
     C, N = p.shape
     M = (1 << depth) - 1
     dp, lo, hi, st = _dev(p), _dev(mb.spec.vmin), _dev(mb.spec.vmax), _dev(step)
+    K = 0 if aux is None else int(aux.shape[1])
+    daux = None if aux is None else _dev(np.ascontiguousarray(aux, np.float64))
     out = torch.full((C, M, N), float("nan"), dtype=torch.float64, device="cuda:0")
     tries = torch.full((C, M), -1, dtype=torch.int16, device="cuda:0").view(torch.uint16)       # (65535: never a valid count)
     exh = torch.zeros(1, dtype=torch.int32, device="cuda:0") if exhausted is None else exhausted
     _lib.check(_lib.lib().surfdisp_mcmc_propose_prior_device(
-        None, C, N, 0, int(L), depth, _ptr(dp), None, _ptr(lo), _ptr(hi), _ptr(st), _ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()),
+        None, C, N, K, int(L), depth, _ptr(dp), _ptr(daux), _ptr(lo), _ptr(hi), _ptr(st), _ptr(idesc), _ptr(fdesc), _ptr(rules.device_flags()),
         ctypes.c_double(-1.0 if rules.vs_max is None else rules.vs_max), G, U, seed, counter, chain0, _ptr(out), _ptr(tries), _ptr(exh)))
     torch.cuda.synchronize()
     return out.cpu().numpy(), tries.cpu().view(torch.int16).numpy().view(np.uint16).astype(np.int64), int(exh.item())
@@ -244,18 +247,25 @@ def test_accept_all_rules_give_the_plain_and_the_tree_entries_bits(C):
                     assert np.array_equal(_bits(out[:, 0]), _bits(one.cpu().numpy())), what
 
 
-def _against_replay(cfg, vs_max, C, depth, chain0, seed, counter, min_retried, what):
+def _against_replay(cfg, vs_max, C, depth, chain0, seed, counter, min_retried, what, model=None):
     """One device call in configuration `cfg` against the replay on the device's own tree: tries and values of every non-marginal
     (chain, node).  The replay's tries is its FIRST good retry, so equal tries say that every earlier retry is bad in the replay and
-    the chosen one good.  Returns (dev out, dev tries, replay out, replay tol, keep)."""
-    m = _cpu_model()
+    the chosen one good.  Returns (dev out, dev tries, replay out, replay tol, keep).
+    model: None (MCMC_SETTING, start states good under the cap `vs_max`), or (the model on the CPU, the same on the device, the
+    local-info row of each chain or None); the start states are then good under the rules of `cfg` themselves."""
+    if model is None:
+        m, mb, rows, aux = _cpu_model(), None, None, None
+        p = np.array(_starts(vs_max, C))
+    else:
+        m, mb, rows = model
+        aux = None if rows is None else m._aux.numpy()[np.asarray(rows)]
+        p = PR.good_starts(PriorRules(m, **cfg["kw"]), m.spec, C, seed=7, rows=rows)
     spec = m.spec
-    p = np.array(_starts(vs_max, C))
     step = spec.step * cfg["step"]
-    out, tries, exh = _call_prior(p, cfg["kw"], step, seed, counter, depth, cfg["G"], cfg["U"], chain0)
+    out, tries, exh = _call_prior(p, cfg["kw"], step, seed, counter, depth, cfg["G"], cfg["U"], chain0, mb=mb, aux=aux)
     rules = PriorRules(m, **cfg["kw"])
-    ref, rtries, margin, tol, slack = PR.propose_prior(p, None, spec.vmin, spec.vmax, step, rules, seed, counter, depth, cfg["G"], cfg["U"],
-                                                       chain0, given=out)
+    ref, rtries, margin, tol, slack = PR.propose_prior(p, aux, spec.vmin, spec.vmax, step, rules, seed, counter, depth, cfg["G"], cfg["U"],
+                                                       chain0, given=out, rows=rows)
     keep = ~PR.marginal(margin, slack)
     excluded = int((~keep).sum())
     err = np.abs(out - ref)
@@ -269,7 +279,8 @@ def _against_replay(cfg, vs_max, C, depth, chain0, seed, counter, min_retried, w
     assert excluded <= MAX_EXCLUDED * keep.size, what
     assert np.array_equal(tries[keep], rtries[keep]), what
     assert worst <= 1.0, what
-    assert bool(rules(torch.as_tensor(out.reshape(-1, spec.n))).all()), what
+    M = out.shape[1]
+    assert bool(rules(torch.as_tensor(out.reshape(-1, spec.n)), rows=None if rows is None else np.repeat(np.asarray(rows), M)).all()), what
     assert retried >= min_retried, what
     return out, tries, ref, tol, keep
 
